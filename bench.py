@@ -24,10 +24,18 @@ exchange after every iteration instead.  `--scaling weak` restores 16 views per 
 bit-exact one; both are parity-tested at this very size and launch shape
 (tests/test_hip_fullsize_parity.py).
 
-Prints ONE JSON line (rank 0) with the throughput in Mpixel-hypotheses/s, the HBM-roofline
-figure of the dominant kernel (pm_step[_fast]_kernel<7,4>, timed with HIP events on its own stream
-through amvs_get_timing), -- at N=1 -- the CPU oracle (same arithmetic mode) timed on the host
-cores on a bounded sample of the same workload, and a `planesweep` sub-record (BASELINE config 2).
+Prints ONE JSON line (rank 0) with the throughput in Mpixel-hypotheses/s, `ms_per_step` and the
+HBM-roofline figure of the dominant kernel (pm_step[_fast]_kernel<7,4>, timed with HIP events on its
+own stream through amvs_get_timing, inside the timed steps).  A plain run does only that: set up, warm
+up, time --steps steps, print.  `--full` adds what takes work of its own: `first_step_ms`, the dense
+points of the last step's maps, -- at N=1 -- the CPU oracle (same arithmetic mode) timed on the host
+cores on a bounded sample of the same workload, and the `planesweep` (BASELINE config 2), `exact` and
+`cli_defaults` sub-records.
+
+`--dump-outputs DIR` writes the maps of the last timed step (depth, normal, confidence; the plane sweep:
+depth, confidence) as DIR/<name>.npy in float32, one row per pixel, views in order.  Maps larger than
+DUMP_LIMIT_BYTES in all are written as the same fixed, seeded sample of pixels (DUMP_SAMPLE_SEED), so
+that two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import gc
@@ -42,6 +50,26 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all arrays together at most this (else a pixel sample)
+DUMP_SAMPLE_SEED = 2024
+
+
+def dump_outputs(path, maps):
+    """--dump-outputs: write `maps` ({name: tensor with one row per pixel, all with the same pixel count})
+    as path/<name>.npy in float32.  Above DUMP_LIMIT_BYTES in all, every map is written at the same sorted,
+    seeded sample of pixel rows: the sample depends only on the pixel count, i.e. on the arguments."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n_px = int(next(iter(maps.values())).shape[0])
+    bytes_per_px = sum(4 * (t[0].numel() if t.dim() > 1 else 1) for t in maps.values())
+    sel = None
+    if n_px * bytes_per_px > DUMP_LIMIT_BYTES - 4096:            # (headroom for the .npy headers)
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        sel = np.unique(rng.integers(0, n_px, size=DUMP_LIMIT_BYTES // (2 * bytes_per_px)))
+    for name, t in maps.items():
+        if sel is not None:
+            t = t.index_select(0, torch.from_numpy(sel).to(t.device))
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float32).cpu().numpy())
 
 
 def kernel_source_hash(kernel_key):
@@ -263,7 +291,14 @@ def main():
                          "--scene-views scene): the per-rank sweep time of an N-GPU run measured on one GPU")
     ap.add_argument("--config5", action="store_true",
                     help="BASELINE config 5 preset: 64 views of 3840x2160 over the ranks, fusion inside the step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: first_step_ms, the dense points of the last "
+                         "step, the CPU oracle baseline and the planesweep / exact / cli_defaults sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the maps of the last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # `python bench.py --gpus N` without a launcher (no WORLD_SIZE): start the N ranks here, as fresh child
     # processes, BEFORE anything in this process touches torch or the GPU; this process only waits and
     # relays rank 0's JSON line
@@ -275,7 +310,8 @@ def main():
         if args.gpus == 1:
             args.views_per_gpu = 64
     if args.workload == "planesweep":
-        print(json.dumps(run_planesweep(args, args.steps, args.warmup, not args.no_cpu_baseline)), flush=True)
+        print(json.dumps(run_planesweep(args, args.steps, args.warmup, args.full and not args.no_cpu_baseline,
+                                        dump=args.dump_outputs)), flush=True)
         return
 
     import torch
@@ -555,12 +591,25 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    # one step from an idle pipeline, its exchange (and fusion) inside: the latency of one reconstruct
-    t1 = time.perf_counter()
-    step()
-    fence()
-    first_step = time.perf_counter() - t1
     k_last = (state["step"] - 1) % nbuf
+    if args.dump_outputs and rank == 0:
+        # what a caller receives: every view's maps (the gathered ones when the ranks exchange), view order
+        if multi:
+            maps = {"depth": in_view_order(full[k_last]["d"]).reshape(-1),
+                    "normal": in_view_order(full[k_last]["n"]).reshape(-1, 3),
+                    "confidence": in_view_order(full[k_last]["c"]).reshape(-1)}
+        else:
+            maps = {"depth": depth[k_last].reshape(-1), "normal": normal[k_last].reshape(-1, 3),
+                    "confidence": conf[k_last].reshape(-1)}
+        dump_outputs(args.dump_outputs, maps)
+    first_step = 0.0
+    if args.full:
+        # one step from an idle pipeline, its exchange (and fusion) inside: the latency of one reconstruct
+        t1 = time.perf_counter()
+        step()
+        fence()
+        first_step = time.perf_counter() - t1
+        k_last = (state["step"] - 1) % nbuf
     if multi:
         tt = torch.tensor([elapsed, first_step], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -593,7 +642,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 2),
-            "first_step_ms": round(first_step * 1e3, 2),
+            **({"first_step_ms": round(first_step * 1e3, 2)} if args.full else {}),
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
             "vs_baseline": None,
@@ -622,15 +671,15 @@ def main():
                          "avg_launch_ms": round(launch_ms, 4), "launches_timed": launches},
             "confidence_ms_per_step": round(conf_ms / args.steps, 3),
         }
-        # "dense points/s": fuse + filter the maps of the last step (untimed above) on the device
-        # (amvs_fuse_filter = mvs_patchmatch.py:536-588, bit-identical to the NumPy path) and relate
-        # the cloud to sweep + fusion time
+        # "dense points/s" (--full, or the fusion inside the step): fuse + filter the maps of the last step
+        # (untimed above) on the device (amvs_fuse_filter = mvs_patchmatch.py:536-588, bit-identical to the
+        # NumPy path) and relate the cloud to sweep + fusion time
         if args.fusion and state["cloud"] is not None:
             pts, cols, raw = state["cloud"]
             out["dense_points"] = {"raw": raw, "final": int(len(pts)), "fusion_inside_step": True,
                                    "points_per_s": round(len(pts) / (elapsed / args.steps), 1),
                                    "device_fusion_s": round(state["fusion_s"] / args.steps, 4)}
-        elif not multi:
+        elif args.full and not multi:
             torch.cuda.synchronize()
             t_f = time.perf_counter()
             pts, cols, raw = eng.fuse_filter_views(refs, depth[k_last].data_ptr(), conf[k_last].data_ptr(),
@@ -640,7 +689,7 @@ def main():
             out["dense_points"] = {"raw": raw, "final": int(len(pts)), "fusion_inside_step": False,
                                    "points_per_s": round(len(pts) / (elapsed / args.steps + t_f), 1),
                                    "device_fusion_s": round(t_f, 4)}
-        elif multi:
+        elif args.full and multi:
             # several ranks: every rank holds all maps after the exchange; rank 0 fuses the gathered maps of
             # the last step (untimed above, like the one-GPU line) -- "dense points/s at 1/2/4/8 GPU"
             torch.cuda.synchronize()
@@ -656,7 +705,7 @@ def main():
             out["dense_points"] = {"raw": raw, "final": int(len(pts)), "fusion_inside_step": False,
                                    "points_per_s": round(len(pts) / (elapsed / args.steps + t_f), 1),
                                    "device_fusion_s": round(t_f, 4)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             sample_refs = [n_views // 2, n_views // 2 + 1][: max(1, min(2, n_views))]
             out["cpu_baseline"] = cpu_baseline(sc, args.patch, sources, sample_refs, sc.depth_min, sc.depth_max,
                                                args.iters, args.samples, args.mode)
@@ -665,7 +714,7 @@ def main():
     eng.close()
     del eng, depth, normal, conf, full
     if rank == 0:
-        if world == 1 and not args.no_planesweep:
+        if args.full and world == 1 and not args.no_planesweep:
             # BASELINE config 2 beside it: a few steps (about 10 ms each) and a short CPU leg
             torch.cuda.empty_cache()
             # a plane-sweep step is ~6.5 ms: 8 untimed steps (~55 ms, what ONE warm-up step of the main line
@@ -880,10 +929,10 @@ def run_cli_defaults(n_views=16, h=3024, w=4032):
     return rec
 
 
-def run_planesweep(args, steps, warmup, with_cpu, cpu_reps=8):
+def run_planesweep(args, steps, warmup, with_cpu, cpu_reps=8, dump=None):
     """BASELINE config 2: plane-sweep stereo (dense_stereo.py:222-316) over all views of a
     1280x720 8-view scene, 64 inverse-depth planes, 5x5 NCC, 6 nearest neighbours.  Returns the
-    record (same fields as the main line)."""
+    record (same fields as the main line); `dump`: --dump-outputs of the last timed step's maps."""
     import torch
 
     import amvs
@@ -943,6 +992,8 @@ def run_planesweep(args, steps, warmup, with_cpu, cpu_reps=8):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    if dump:
+        dump_outputs(dump, {"depth": dmap.reshape(-1), "confidence": conf.reshape(-1)})
     if os.environ.get("AMVS_BENCH_TRACE"):
         print("planesweep per step (step ms, timing() ms):", trace, file=sys.stderr)
     n_hyp = n_views * H * W * D

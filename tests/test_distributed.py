@@ -435,7 +435,7 @@ def test_bench_two_ranks_self_launched_on_one_gpu():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--scene-views", "16", "--height", "270", "--width", "480", "--no-cpu-baseline"],
+                          "--scene-views", "16", "--height", "270", "--width", "480", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -223,3 +223,48 @@ def test_strip_height_follows_wave_quantisation(scene_1080):
     for n in (4, 2, 1):
         for a, b, what in zip(maps[16], maps[n], ("depth", "normal", "confidence")):
             _eq(b, a, f"{what}, {n} views per launch")
+
+
+def test_plain_bench_run_dumps_what_its_timed_step_computes(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` (no --full) on a small scene: one result line with the
+    headline fields and none of the extra records, and DIR holds the maps of the timed path's last step -- equal,
+    bit for bit, to what the engine computes for the same views, sources, schedule and seed, and equal on a second run."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import amvs
+    from amvs.engine import make_pm_params
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, H, W = 4, 135, 240
+    recs = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                              "--views-per-gpu", str(n), "--height", str(H), "--width", str(W),
+                              "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        recs.append(json.loads(lines[0]))
+    r = recs[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in r, key
+    assert r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0
+    for key in ("first_step_ms", "dense_points", "cpu_baseline", "planesweep", "exact", "cli_defaults"):
+        assert key not in r, key
+    got = {name: np.load(tmp_path / "a" / (name + ".npy")) for name in ("depth", "normal", "confidence")}
+    for name, a in got.items():
+        assert a.dtype == np.float32
+        _eq(np.load(tmp_path / "b" / (name + ".npy")), a, f"second run, {name}")
+    sc = _u8_scene(n, H, W, 1234)
+    ids = sorted(sc.poses)
+    pm = amvs.PatchMatchMVS.__new__(amvs.PatchMatchMVS)
+    sources = [pm._select_source_views(v, ids, sc.poses, k=4) for v in ids]
+    with amvs.Engine(H, W, n, sc.camera.K.astype(np.float32), mode="fast") as eng:
+        for i in ids:
+            eng.set_view(i, sc.grays[i], sc.poses[i].R, sc.poses[i].t)
+        depth, normal, conf = eng.patchmatch(ids, sources, make_pm_params(7, 8, 8, sc.depth_min, sc.depth_max), 42)
+    _eq(got["depth"], np.asarray(depth).reshape(-1), "dumped depth")
+    _eq(got["normal"], np.asarray(normal).reshape(-1, 3), "dumped normals")
+    _eq(got["confidence"], np.asarray(conf).reshape(-1), "dumped confidence")

@@ -360,8 +360,9 @@ def test_stereo_subsample_draw_equals_numpy_choice():
 
 def test_committed_bench_line_keeps_the_contract():
     """The driver-shaped line of the final build (profiles/r04_logs/bench_default_line.json, written by
-    `python bench.py --steps 20 --warmup 5` on an MI355X) carries every field the bench contract names, the figures
-    agree with each other, and every replayed traffic figure names its profile."""
+    `python bench.py --steps 20 --warmup 5` on an MI355X, before its extra records moved behind `--full`) carries
+    every field the bench contract names, the figures agree with each other, and every replayed traffic figure names
+    its profile."""
     import json
     path = os.path.join(ROOT, "profiles", "r04_logs", "bench_default_line.json")
     lines = [ln for ln in open(path).read().splitlines() if ln.startswith("{")]
@@ -391,3 +392,31 @@ def test_committed_bench_line_keeps_the_contract():
     cli = r["cli_defaults"]
     assert len(cli["timed_calls_s"]) == 5 and min(cli["timed_calls_s"]) <= cli["end_to_end_s"] <= max(cli["timed_calls_s"])
     assert len(cli["stereo"]["timed_calls_s"]) == 5
+
+
+def test_bench_dump_outputs_writes_float32_within_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (bench.dump_outputs): maps within the limit are written whole; above it every map is
+    written at the same sorted, seeded sample of pixel rows, the same on every call, all files together within the
+    limit."""
+    import torch
+    import bench
+    n = 5000
+    maps = {"depth": torch.arange(n, dtype=torch.float32), "normal": torch.arange(3 * n, dtype=torch.float32).reshape(n, 3),
+            "confidence": -torch.arange(n, dtype=torch.float32)}
+    bench.dump_outputs(str(tmp_path / "whole"), maps)
+    for name, t in maps.items():
+        got = np.load(tmp_path / "whole" / (name + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, t.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 20 * n // 4)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), maps)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["confidence.npy", "depth.npy", "normal.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_LIMIT_BYTES
+    d = np.load(tmp_path / "a" / "depth.npy")
+    assert 0 < len(d) < n and np.all(np.diff(d) > 0)                    # sorted distinct pixels
+    idx = d.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "normal.npy"), maps["normal"].numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "confidence.npy"), -d)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

@@ -15,8 +15,9 @@ PROF_TAG=pm_exact BENCH_ARGS="--no-planesweep --mode exact"        tools/profile
 PROF_TAG=pm_cli   BENCH_ARGS="--no-planesweep --mode exact --patch 11 --iters 3 --height 756 --width 1008" tools/profile.sh > gpurun_out/profile_pm_cli.log 2>&1 || exit 1
 PROF_TAG=ps_fast  BENCH_ARGS="--workload planesweep --steps 10 --warmup 8"               tools/profile.sh > gpurun_out/profile_ps_fast.log 2>&1 || exit 1
 PROF_TAG=ps_exact BENCH_ARGS="--workload planesweep --mode exact --steps 10 --warmup 8"  tools/profile.sh > gpurun_out/profile_ps_exact.log 2>&1 || exit 1
-timeout -k 10 400 python bench.py > gpurun_out/bench_full.json 2> gpurun_out/bench_full.err || exit 1
-cut -c1-200 gpurun_out/bench_full.json
+BENCH_OUT=${BENCH_OUT:-$PWD/cycle_out}; mkdir -p "$BENCH_OUT"          # the full bench record (every sub-record)
+timeout -k 10 400 python bench.py --full > "$BENCH_OUT/bench_full.json" 2> "$BENCH_OUT/bench_full.err" || exit 1
+cut -c1-200 "$BENCH_OUT/bench_full.json"
 if [ -z "$SKIP_FUZZ" ]; then
 AMVS_BENCH_BACKEND=gloo AMVS_BENCH_ONE_DEVICE=1 timeout -k 10 600 python bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline > gpurun_out/rehearse.log 2>&1 || { tail -5 gpurun_out/rehearse.log; exit 1; }
 timeout -k 10 600 python tools/fuzz_parity.py --cases 80 > gpurun_out/fuzz_pm.log 2>&1 || { tail -3 gpurun_out/fuzz_pm.log; exit 1; }
