@@ -10,7 +10,7 @@ repository root.
 from .core.camera import Camera, CameraPose, load_calibration  # noqa: F401
 
 __all__ = ["Camera", "CameraPose", "load_calibration", "PatchMatchMVS", "DepthNormalMap",
-           "DenseStereoReconstructor", "Engine", "AmvsError"]
+           "DenseStereoReconstructor", "Engine", "AmvsError", "save_ply", "save_mesh_ply"]
 
 
 def __getattr__(name):
@@ -25,6 +25,9 @@ def __getattr__(name):
     if name == "Engine":
         from .engine import Engine
         return Engine
+    if name in ("save_ply", "save_mesh_ply"):
+        from .core import utils
+        return getattr(utils, name)
     if name == "AmvsError":
         from ._lib import AmvsError
         return AmvsError

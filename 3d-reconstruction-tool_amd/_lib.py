@@ -14,6 +14,7 @@ AMVS_MAX_SRC = 6
 MODES = {"default": 0, "exact": 1, "fast": 2}
 SCHEDULES = {"auto": 0, "view-major": 1, "band-major": 2, "split": 3, "paired": 4}
 SUPPORTED_PATCH_SIZES = tuple(range(3, 32, 2))        # compiled: 3 ... 29; 31 runs the run-time-k kernels
+TSDF_MAX_POINTS = 1 << 27                              # include/amvs.h AMVS_TSDF_MAX_POINTS
 
 f32p = C.POINTER(C.c_float)
 i32p = C.POINTER(C.c_int)
@@ -114,6 +115,11 @@ SIGNATURES = {
                                       C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "amvs_set_view_colors": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint8)]),
     "amvs_fetch_cloud": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8)]),
+    "amvs_tsdf_integrate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, i32p, C.POINTER(C.c_uint8),
+                                      f32p, f32p, C.c_float, f32p, C.c_float, i32p, C.c_float]),
+    "amvs_tsdf_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "amvs_fetch_mesh": (C.c_int, [C.c_void_p, f32p, i32p, C.POINTER(C.c_uint8)]),
+    "amvs_tsdf_fetch_volume": (C.c_int, [C.c_void_p, f32p, f32p, f32p]),
     "amvs_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "amvs_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "amvs_allgather_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),

@@ -126,6 +126,90 @@ class PatchMatchMVS:
     # ------------------------------------------------------------------ public ----
     def reconstruct(self, images: List[dict], poses: Dict[int, CameraPose],
                     sparse_points: np.ndarray = None) -> Tuple[np.ndarray, np.ndarray]:
+        points, colors, _ = self._reconstruct_maps(images, poses, sparse_points)
+        return points, colors
+
+    def reconstruct_mesh(self, images: List[dict], poses: Dict[int, CameraPose], sparse_points: np.ndarray = None, *,
+                         voxel_size: Optional[float] = None, bounds=None, trunc_voxels: float = 4.0,
+                         max_dim: int = 256) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Surface mesh of the scene: reconstruct()'s preparation, sweep and fusion, then the per-view depth maps
+        fused into a truncated signed distance volume and its zero level set extracted by marching tetrahedra on
+        the GPU (csrc/amvs_mesh.hip; no reference counterpart).  Returns (vertices (V,3) float32, faces (F,3) int32,
+        colors (V,3) uint8 RGB); face normals point toward the cameras.
+
+        bounds: ((xmin, ymin, zmin), (xmax, ymax, zmax)) of the volume; default the fused cloud's box padded by the
+        truncation distance.  voxel_size: default the longest side / (max_dim - 1).  The truncation distance is
+        trunc_voxels * voxel_size.  The volume holds at most AMVS_TSDF_MAX_POINTS grid points (include/amvs.h)."""
+        rank, world = _parallel.rank_world(self.process_group)
+        if world > 1:
+            raise NotImplementedError("reconstruct_mesh runs on one process: meshing with a process group of "
+                                      f"{world} ranks is not implemented (call it without a process group)")
+        if trunc_voxels <= 0:
+            raise ValueError("trunc_voxels must be positive")
+        points, _, maps = self._reconstruct_maps(images, poses, sparse_points)
+        empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), np.zeros((0, 3), np.uint8))
+        if maps is None or (bounds is None and len(points) == 0):
+            return empty
+        origin, voxel, dims, trunc = self._mesh_grid(points, bounds, voxel_size, trunc_voxels, max_dim)
+        print(f"\nMeshing: {dims[0]} x {dims[1]} x {dims[2]} TSDF grid, voxel {voxel:.4g}, truncation {trunc:.4g}")
+        t0 = time.time()
+        ids, src = self._mesh_inputs(maps)
+        if not ids:
+            return empty
+        verts, faces, colors = self._engine.tsdf_mesh(self.K_scaled, [(poses[i].R, poses[i].t) for i in ids], self.min_views,
+                                                      origin, voxel, dims, trunc, **src)
+        print(f"  Mesh: {len(verts):,} vertices, {len(faces):,} faces ({time.time() - t0:.2f}s)")
+        return verts, faces, colors
+
+    def _mesh_inputs(self, maps):
+        """(view indices, Engine.tsdf_integrate keyword arguments) of the maps _reconstruct_maps returned: the device
+        tensors or the host maps, and the resident colour images where the engine holds them."""
+        kind, data, proc_images = maps
+        if kind == "resident":
+            ids = list(data.ref_ids)
+            import torch
+            torch.cuda.synchronize(data.depth.device)
+            src = dict(device_ptrs=(data.depth.data_ptr(), data.confidence.data_ptr(), len(ids)))
+        else:
+            ids = list(data)
+            if not ids:
+                return ids, {}
+            src = dict(depth=np.stack([data[i].depth for i in ids]), conf=np.stack([data[i].confidence for i in ids]))
+        if getattr(self, "_resident_colors", False) and proc_images is self._engine_images:
+            src["view_ids"] = [self._slot[i] for i in ids]
+        else:
+            src["colors_bgr"] = np.stack([proc_images[i]["color"] for i in ids])
+        return ids, src
+
+    @staticmethod
+    def _mesh_grid(points, bounds, voxel_size, trunc_voxels, max_dim):
+        """(origin, voxel, dims (nx, ny, nz), trunc) of reconstruct_mesh's volume."""
+        tv = float(trunc_voxels)
+        if bounds is None:
+            lo, hi = points.min(axis=0).astype(np.float64), points.max(axis=0).astype(np.float64)
+            if voxel_size is None:
+                # the padded box's longest side (longest + 2 trunc) spans max_dim - 1 voxels
+                room = int(max_dim) - 1 - 2.0 * tv
+                if room <= 0:
+                    raise ValueError(f"max_dim {max_dim} leaves no room inside the {tv}-voxel truncation band")
+                voxel = float((hi - lo).max()) / room
+            else:
+                voxel = float(voxel_size)
+            lo, hi = lo - tv * voxel, hi + tv * voxel
+        else:
+            lo, hi = (np.asarray(b, np.float64).reshape(3) for b in bounds)
+            if not np.all(hi > lo):
+                raise ValueError("bounds must be ((xmin, ymin, zmin), (xmax, ymax, zmax)) with max > min")
+            voxel = float((hi - lo).max()) / (int(max_dim) - 1) if voxel_size is None else float(voxel_size)
+        if not (voxel > 0 and np.isfinite(voxel)):
+            raise ValueError(f"voxel size {voxel} must be positive (a cloud of one point needs voxel_size or bounds)")
+        dims = tuple(max(2, int(np.ceil((hi[a] - lo[a]) / voxel - 1e-6)) + 1) for a in range(3))
+        return lo, voxel, dims, tv * voxel
+
+    def _reconstruct_maps(self, images: List[dict], poses: Dict[int, CameraPose], sparse_points: np.ndarray = None):
+        """reconstruct(): preparation, sweep, fusion and its progress lines.  Returns (points, colors, maps) where maps
+        is None (fewer than 3 cameras, no views) or (kind, per-view maps, prepared images): kind "resident" with the
+        device tensors of _sweep_resident / _sweep_extended, or "host" with the DepthNormalMap dict of _sweep."""
         print("\n" + "=" * 60)
         print("PATCHMATCH MULTI-VIEW STEREO")
         print(f"  Scale: {self.scale}x, Patch: {self.patch_size}, Iters: {self.num_iterations}")
@@ -135,7 +219,7 @@ class PatchMatchMVS:
         n_cams = len(cam_indices)
         if n_cams < 3:                                   # reference :88-90
             print("Need at least 3 cameras")
-            return np.array([]), np.array([])
+            return np.array([]), np.array([]), None
 
         self._estimate_depth_range(poses, sparse_points)
         print(f"  Depth range: [{self.depth_min:.2f}, {self.depth_max:.2f}]")
@@ -165,7 +249,7 @@ class PatchMatchMVS:
             if raw > 0:
                 print(f"  After filtering: {len(points):,}")
             print(f"\nPatchMatch MVS completed in {time.time() - t0:.1f}s")
-            return points, colors
+            return points, colors, ("resident", resident, proc_images)
 
         torch = _torch_cuda() if self.device_fusion else None
         if torch is not None and jobs:
@@ -176,7 +260,7 @@ class PatchMatchMVS:
             if raw > 0:
                 print(f"  After filtering: {len(points):,}")
             print(f"\nPatchMatch MVS completed in {time.time() - t0:.1f}s")
-            return points, colors
+            return points, colors, ("resident", resident, proc_images)
 
         depth_maps = self._sweep(jobs, proc_images, poses, cam_indices)
 
@@ -193,7 +277,7 @@ class PatchMatchMVS:
                 points, colors = self._filter_points(points, colors)
                 print(f"  After filtering: {len(points):,}")
         print(f"\nPatchMatch MVS completed in {time.time() - t0:.1f}s")
-        return points, colors
+        return points, colors, ("host", depth_maps, proc_images)
 
     # ------------------------------------------------------------- host geometry --
     def _estimate_depth_range(self, poses: Dict[int, CameraPose], sparse_points: np.ndarray = None):

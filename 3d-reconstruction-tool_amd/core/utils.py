@@ -2,7 +2,8 @@
 
 `save_ply` has the reference's signature and writes the same bytes (utils.py:8-37); the per-point
 Python `f.write` loop there dominates wall time for multi-million-point clouds, so the formatting
-runs in the native library (`amvs_write_ply`, host-only).
+runs in the native library (`amvs_write_ply`, host-only).  `save_mesh_ply` writes the surface mesh of
+PatchMatchMVS.reconstruct_mesh as binary little-endian PLY (no reference counterpart).
 """
 import ctypes as C
 from pathlib import Path
@@ -25,6 +26,40 @@ def save_ply(points: np.ndarray, colors: np.ndarray, output_path: str):
     if rc != 0:
         raise _lib.AmvsError(f"amvs_write_ply failed ({rc}): {lib.amvs_last_error(None).decode()}")
     print(f"Saved {n:,} points to {output_path}")
+
+
+def save_mesh_ply(vertices: np.ndarray, faces: np.ndarray, colors: np.ndarray, output_path: str):
+    """Save a triangle mesh as binary little-endian PLY (read by MeshLab, Open3D and most tools): `element vertex`
+    with float x, y, z and uchar red, green, blue; `element face` with `property list uchar int vertex_indices`.
+    vertices (V,3), faces (F,3) vertex ids, colors (V,3) RGB in 0..255."""
+    output_path = Path(output_path)
+    output_path.parent.mkdir(parents=True, exist_ok=True)
+    verts = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
+    n_v = len(verts)
+    tris = np.asarray(faces).reshape(-1, 3)
+    cols = np.asarray(colors).reshape(n_v, 3)
+    if tris.size and (tris.min() < 0 or tris.max() >= n_v):
+        raise ValueError("face vertex ids out of range")
+    if cols.size and (cols.min() < 0 or cols.max() > 255):
+        raise ValueError("colours must lie in 0..255")
+    vrec = np.empty(n_v, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("r", "u1"), ("g", "u1"), ("b", "u1")])
+    vrec["x"], vrec["y"], vrec["z"] = verts[:, 0], verts[:, 1], verts[:, 2]
+    vrec["r"], vrec["g"], vrec["b"] = cols[:, 0], cols[:, 1], cols[:, 2]
+    frec = np.empty(len(tris), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    frec["n"] = 3
+    frec["v"] = tris.astype(np.int32)
+    header = ("ply\nformat binary_little_endian 1.0\n"
+              f"element vertex {n_v}\n"
+              "property float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+              f"element face {len(tris)}\n"
+              "property list uchar int vertex_indices\n"
+              "end_header\n")
+    with open(output_path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(vrec.tobytes())
+        f.write(frec.tobytes())
+    print(f"Saved mesh with {n_v:,} vertices and {len(tris):,} faces to {output_path}")
 
 
 def compute_scene_bounds(points: np.ndarray) -> dict:

@@ -33,6 +33,7 @@ void check_fetch_generic(unsigned long long out[4], bool reset);
 void check_fetch_extended(unsigned long long out[4], bool reset);
 void check_fetch_fusion(unsigned long long out[4], bool reset);
 void check_fetch_knn(unsigned long long out[4], bool reset);
+void check_fetch_mesh(unsigned long long out[4], bool reset);
 }  // namespace amvs
 #endif
 
@@ -42,7 +43,7 @@ std::string g_create_error;
 
 // Sum of the violations all kernels have counted since the last reset and the record of the first one found
 // (out[1] = translation unit << 32 | source line: 1 amvs_kernels, 2 amvs_kernels_fast, 3 amvs_sweep_fast,
-// 4 amvs_sweep_exact, 5 amvs_generic, 6 amvs_extended, 7 amvs_fusion, 8 amvs_knn; out[2] = the index, out[3] = the
+// 4 amvs_sweep_exact, 5 amvs_generic, 6 amvs_extended, 7 amvs_fusion, 8 amvs_knn, 9 amvs_mesh; out[2] = the index, out[3] = the
 // extent it was compared with).  Zeros in the shipped build.
 void index_report(uint64_t out[4], bool reset)
 {
@@ -51,7 +52,8 @@ void index_report(uint64_t out[4], bool reset)
     (void)hipDeviceSynchronize();
     void (*const fetch[])(unsigned long long[4], bool) = {
         amvs::check_fetch_kernels, amvs::check_fetch_kernels_fast, amvs::check_fetch_sweep_fast, amvs::check_fetch_sweep_exact,
-        amvs::check_fetch_generic, amvs::check_fetch_extended, amvs::check_fetch_fusion, amvs::check_fetch_knn};
+        amvs::check_fetch_generic, amvs::check_fetch_extended, amvs::check_fetch_fusion, amvs::check_fetch_knn,
+        amvs::check_fetch_mesh};
     for (auto f : fetch) {
         unsigned long long r[4] = {0, 0, 0, 0};
         f(r, reset);
@@ -120,6 +122,7 @@ struct amvs_ctx {
     double *d_cloud_pts = nullptr;       // result of the last amvs_fuse_filter
     unsigned char *d_cloud_rgb = nullptr;
     long long cloud_n = 0;
+    amvs::TsdfState *tsdf = nullptr;     // volume, scans and mesh of amvs_tsdf_* (amvs_mesh.hip), lazily created
     // split schedule (amvs_pm_params.schedule == AMVS_SCHEDULE_SPLIT): sample maps, one stream per
     // view group, the token events that serialise the sampling kernels across the groups
     float *d_samples = nullptr;
@@ -912,6 +915,7 @@ int amvs_destroy(amvs_ctx *c)
     if (c->d_sweep_conf) (void)hipFree(c->d_sweep_conf);
     if (c->d_cloud_pts) (void)hipFree(c->d_cloud_pts);
     if (c->d_cloud_rgb) (void)hipFree(c->d_cloud_rgb);
+    amvs::tsdf_state_free(c->tsdf);
     amvs::pool_trim();                  // the post-steps' cached scratch blocks (amvs_pool.hip)
     if (c->d_images) (void)hipFree(c->d_images);
     if (c->d_pairs) (void)hipFree(c->d_pairs);
@@ -1924,6 +1928,81 @@ int amvs_fetch_cloud(amvs_ctx *c, double *points, uint8_t *colors)
     HIPCHK(c, hipMemcpyAsync(points, c->d_cloud_pts, sizeof(double) * 3 * c->cloud_n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(colors, c->d_cloud_rgb, 3 * c->cloud_n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_tsdf_integrate(amvs_ctx *c, int n_maps, const void *depth, const void *conf, int maps_on_device,
+                        const int *view_ids, const uint8_t *colors_bgr_host, const float K[9], const float *poses,
+                        float min_views, const float origin[3], float voxel, const int32_t dims[3], float trunc)
+{
+    if (!c) return AMVS_EINVAL;
+    if (n_maps < 1 || !depth || !conf || !K || !poses || !origin || !dims)
+        return fail(c, AMVS_EINVAL, "tsdf_integrate: bad argument");
+    if ((view_ids != nullptr) == (colors_bgr_host != nullptr))
+        return fail(c, AMVS_EINVAL, "tsdf_integrate: give exactly one colour source (view_ids or colors_bgr_host)");
+    if (!(voxel > 0.0f) || !std::isfinite(voxel) || !(trunc > 0.0f) || !std::isfinite(trunc))
+        return fail(c, AMVS_EINVAL, "tsdf_integrate: voxel and trunc must be positive and finite");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(origin[a])) return fail(c, AMVS_EINVAL, "tsdf_integrate: origin must be finite");
+    if (dims[0] < 2 || dims[1] < 2 || dims[2] < 2) return fail(c, AMVS_EINVAL, "tsdf_integrate: every dimension must be >= 2");
+    const long long points = (long long)dims[0] * dims[1] * dims[2];
+    if (dims[0] > AMVS_TSDF_MAX_POINTS || dims[1] > AMVS_TSDF_MAX_POINTS || dims[2] > AMVS_TSDF_MAX_POINTS ||
+        points > AMVS_TSDF_MAX_POINTS)
+        return fail(c, AMVS_EINVAL, "tsdf_integrate: volume of " + std::to_string(dims[0]) + " x " + std::to_string(dims[1]) +
+                                        " x " + std::to_string(dims[2]) + " grid points is over the budget of " +
+                                        std::to_string((long long)AMVS_TSDF_MAX_POINTS) + " (AMVS_TSDF_MAX_POINTS)");
+    std::vector<int> slots(n_maps);
+    for (int j = 0; j < n_maps; ++j) {
+        if (view_ids) {
+            if (view_ids[j] < 0 || view_ids[j] >= c->n_views || !c->have_bgr[view_ids[j]])
+                return fail(c, AMVS_EINVAL, "view " + std::to_string(view_ids[j]) + " has no resident colour image (amvs_set_view_bgr8)");
+            slots[j] = view_ids[j];
+        } else {
+            slots[j] = j;
+        }
+    }
+    int rc = bind_device(c);
+    if (rc) return rc;
+    if (!c->tsdf) c->tsdf = amvs::tsdf_state_new();
+    const hipError_t e = amvs::tsdf_integrate(c->tsdf, (const float *)depth, (const float *)conf, maps_on_device != 0, n_maps,
+                                              c->H, c->W, view_ids ? c->d_bgr : colors_bgr_host, view_ids != nullptr,
+                                              view_ids ? c->n_views : n_maps, slots.data(), K, poses, min_views, origin, voxel,
+                                              dims, trunc, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("tsdf_integrate: ") + hipGetErrorString(e));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_tsdf_extract(amvs_ctx *c, int64_t *n_vertices, int64_t *n_faces)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!n_vertices || !n_faces) return fail(c, AMVS_EINVAL, "tsdf_extract: NULL output");
+    if (!amvs::tsdf_has_volume(c->tsdf)) return fail(c, AMVS_EINVAL, "tsdf_extract: no volume (amvs_tsdf_integrate)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    long long nv = 0, nf = 0;
+    const hipError_t e = amvs::tsdf_extract(c->tsdf, &nv, &nf, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("tsdf_extract: ") + hipGetErrorString(e));
+    *n_vertices = nv; *n_faces = nf;
+    return checked(c, AMVS_OK);
+}
+
+int amvs_fetch_mesh(amvs_ctx *c, float *vertices, int32_t *faces, uint8_t *colors_rgb)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::tsdf_has_mesh(c->tsdf)) return fail(c, AMVS_EINVAL, "fetch_mesh: no mesh (amvs_tsdf_extract)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    HIPCHK(c, amvs::tsdf_fetch_mesh(c->tsdf, vertices, faces, colors_rgb, c->stream));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_tsdf_fetch_volume(amvs_ctx *c, float *tsdf, float *weight, float *color_sum)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::tsdf_has_volume(c->tsdf)) return fail(c, AMVS_EINVAL, "tsdf_fetch_volume: no volume (amvs_tsdf_integrate)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    HIPCHK(c, amvs::tsdf_fetch_volume(c->tsdf, tsdf, weight, color_sum, c->stream));
     return checked(c, AMVS_OK);
 }
 

@@ -225,4 +225,22 @@ hipError_t cloud_take(const double *pts, const unsigned char *rgb, long long n, 
 hipError_t voxel_downsample(const double *pts, const unsigned char *rgb, long long m, const unsigned char *keep_h,
                             double voxel, double **pts_out, unsigned char **rgb_out, long long *m_out, hipStream_t st);
 
+
+// amvs_mesh.hip: TSDF fusion of the per-view maps and marching-tetrahedra extraction (include/amvs.h
+// amvs_tsdf_*).  The state (volume, scans, mesh) is owned by a context and freed with it.
+struct TsdfState;
+TsdfState *tsdf_state_new();
+void tsdf_state_free(TsdfState *s);
+// depth / conf: [n_maps][H*W] (host or device); bgr: [bgr_images][H*W][3] BGR (host or device), map j takes
+// its colours from image slots_h[j]; poses_h: [n_maps][12] float32 R row-major, t.  Synchronises.
+hipError_t tsdf_integrate(TsdfState *s, const float *depth, const float *conf, bool maps_on_device, int n_maps, int H, int W,
+                          const unsigned char *bgr, bool bgr_on_device, long long bgr_images, const int *slots_h,
+                          const float K[9], const float *poses_h, float min_views, const float origin[3], float voxel,
+                          const int dims[3], float trunc, hipStream_t st);
+hipError_t tsdf_extract(TsdfState *s, long long *n_vertices, long long *n_faces, hipStream_t st);
+bool tsdf_has_volume(const TsdfState *s);
+bool tsdf_has_mesh(const TsdfState *s);
+hipError_t tsdf_fetch_mesh(TsdfState *s, float *verts, int *faces, unsigned char *rgb, hipStream_t st);
+hipError_t tsdf_fetch_volume(TsdfState *s, float *tsdf, float *weight, float *color_sum, hipStream_t st);
+
 }  // namespace amvs

@@ -1,0 +1,527 @@
+// amvs_mesh.hip -- surface mesh from the per-view depth maps: TSDF fusion into a dense voxel grid, then
+// marching tetrahedra on the Kuhn subdivision of every cube (no reference counterpart: the reference stops at
+// the point cloud).  Judged against synthetic ground truth and tests/mesh_restatement.py, a NumPy statement of
+// the same float32 operations in the same order (bit-identical volume and mesh).
+//
+// Grid point (i, j, k) is origin + (i, j, k) * voxel and lives at index (k * ny + j) * nx + i.
+//
+// Integration: one thread per grid point, the maps in a fixed order, the sums in registers, every output
+// written once (no float atomics: their sums would depend on arrival order).  Per view, in float32 under
+// -ffp-contract=off:
+//   Xc = ((R0 X + R1 Y) + R2 Z) + t                 (row by row)
+//   p  = (K0 Xc + K1 Yc) + K2 Zc ...,  u = p0 / p2, v = p1 / p2
+//   skip unless Zc > 0; px = floorf(u + 0.5f), py = floorf(v + 0.5f) inside the image;
+//   skip unless depth > 0 and conf >= min_views;  sdf = depth - Zc, skip if sdf < -trunc;
+//   sum += fminf(1, sdf / trunc), weight += 1, colour sum += the pixel's RGB.
+// tsdf = sum / weight (1 where weight == 0: unobserved, never meshed).
+//
+// Extraction (three passes, hipCUB scans between them):
+//   (a) every grid point owns 7 lattice edges, to p + d for the direction masks d = 1 .. 7 (bit 0 = +x,
+//       bit 1 = +y, bit 2 = +z: the axes, the face diagonals and the main diagonal).  An edge crosses when both
+//       ends are observed and (f0 < 0) != (f1 < 0).  Vertex ids: exclusive scan of the per-point counts, then
+//       direction order within a point.  Position P0 + t (P1 - P0), colour c0 + t (c1 - c0) of the two corners'
+//       mean colours rounded with floorf(c + 0.5f), t = f0 / (f0 - f1).
+//   (b) triangles per cube (the cube whose lowest corner is the point), scanned;
+//   (c) faces in cube order, then tetrahedron order, then table order, wound so that the normal points toward
+//       increasing TSDF (free space, the cameras' side);
+//   (d) the vertices no face uses are dropped (keeping the order of the others) and the faces renumbered.
+// The cube splits into the 6 tetrahedra 0 -> a -> a+b -> (1,1,1) along the main diagonal, one per axis order
+// (x,y,z) (x,z,y) (y,x,z) (y,z,x) (z,x,y) (z,y,x).  Every tetrahedron edge then joins a corner to a corner that
+// has all of its bits (it is one of the 7 lattice edges of its lower end), and every cube face is cut along the
+// diagonal from its lowest corner, so neighbouring cubes agree and the mesh is watertight.  A tetrahedron is
+// meshed only if all 4 corners are observed, so a crossing edge that only tetrahedra with an unobserved corner
+// share has a vertex in (a) that (d) removes.
+#define AMVS_TU_ID 9
+#include "amvs_check.h"
+#include "amvs_kernels.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <cstdint>
+#include <utility>
+
+namespace amvs {
+
+namespace {
+
+#define MCHK(call)                                 \
+    do {                                           \
+        hipError_t e_ = (call);                    \
+        if (e_ != hipSuccess) return e_;           \
+    } while (0)
+
+// tetrahedron edges (local vertex pairs) 0:(0,1) 1:(0,2) 2:(0,3) 3:(1,2) 4:(1,3) 5:(2,3)
+__constant__ unsigned char k_edge_a[6] = {0, 0, 0, 1, 1, 2};
+__constant__ unsigned char k_edge_b[6] = {1, 2, 3, 2, 3, 3};
+// Triangles of the 16 sign cases (bit v set = local vertex v has f < 0), as tetrahedron edges, wound for a
+// positively oriented tetrahedron (det(v1-v0, v2-v0, v3-v0) > 0) so the normal points toward the f >= 0
+// vertices.  One vertex apart from the other three: one triangle on its 3 edges.  Two and two (inside p < q,
+// outside r < s): the quad (p,r) (p,s) (q,s) (q,r) as the triangles [(p,r) (p,s) (q,s)] and [(p,r) (q,s) (q,r)].
+// Cases 0 and 15 have none; a case's triangle count is 1 for an odd bit count, 2 for two bits.
+__constant__ unsigned char k_tri[16][2][3] = {
+    {{0, 0, 0}, {0, 0, 0}}, {{0, 1, 2}, {0, 0, 0}}, {{0, 4, 3}, {0, 0, 0}}, {{1, 2, 4}, {1, 4, 3}},
+    {{1, 3, 5}, {0, 0, 0}}, {{0, 5, 2}, {0, 3, 5}}, {{0, 4, 5}, {0, 5, 1}}, {{2, 4, 5}, {0, 0, 0}},
+    {{2, 5, 4}, {0, 0, 0}}, {{0, 1, 5}, {0, 5, 4}}, {{0, 5, 3}, {0, 2, 5}}, {{1, 5, 3}, {0, 0, 0}},
+    {{1, 3, 4}, {1, 4, 2}}, {{0, 3, 4}, {0, 0, 0}}, {{0, 2, 1}, {0, 0, 0}}, {{0, 0, 0}, {0, 0, 0}}};
+// Kuhn tetrahedra: cube corners (bit 0 = +x, 1 = +y, 2 = +z) of local vertices 1 and 2 (vertex 0 is corner 0,
+// vertex 3 corner 7).  Odd axis orders (1, 2, 5) are negatively oriented: their triangles are wound backwards.
+__constant__ unsigned char k_tet_c1[6] = {1, 1, 2, 2, 4, 4};
+__constant__ unsigned char k_tet_c2[6] = {3, 5, 3, 6, 5, 6};
+
+__device__ __forceinline__ int tri_count(unsigned c) { const int b = __popc(c); return b == 2 ? 2 : (b & 1); }
+
+struct Grid {
+    float ox, oy, oz, voxel;
+    int nx, ny, nz;
+};
+
+struct Kmat { float k[9]; };
+
+__global__ __launch_bounds__(256) void tsdf_integrate_kernel(const float *__restrict__ depth, const float *__restrict__ conf,
+                                                             long long map_elems, const unsigned char *__restrict__ bgr,
+                                                             long long bgr_pixels, const int *__restrict__ color_slot,
+                                                             const float *__restrict__ cams, Kmat K, int n_maps, int H, int W,
+                                                             float min_views, float trunc, Grid g, float *__restrict__ tsdf,
+                                                             float *__restrict__ weight, float *__restrict__ color_sum)
+{
+    const int n = g.nx * g.ny * g.nz;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int i = p % g.nx, j = (p / g.nx) % g.ny, k = p / (g.nx * g.ny);
+    const float X = g.ox + (float)i * g.voxel, Y = g.oy + (float)j * g.voxel, Z = g.oz + (float)k * g.voxel;
+    const long long HW = (long long)H * W;
+    const float fW = (float)W, fH = (float)H;
+    float s = 0.0f, w = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+    for (int m = 0; m < n_maps; ++m) {
+        const float *P = cams + 12 * m;          // R row-major, t
+        const float zc = ((P[6] * X + P[7] * Y) + P[8] * Z) + P[11];
+        if (!(zc > 0.0f)) continue;
+        const float xc = ((P[0] * X + P[1] * Y) + P[2] * Z) + P[9];
+        const float yc = ((P[3] * X + P[4] * Y) + P[5] * Z) + P[10];
+        const float pu = (K.k[0] * xc + K.k[1] * yc) + K.k[2] * zc;
+        const float pv = (K.k[3] * xc + K.k[4] * yc) + K.k[5] * zc;
+        const float pw = (K.k[6] * xc + K.k[7] * yc) + K.k[8] * zc;
+        const float fx = floorf(pu / pw + 0.5f), fy = floorf(pv / pw + 0.5f);
+        if (!(fx >= 0.0f && fx < fW && fy >= 0.0f && fy < fH)) continue;
+        const long long pix = (long long)(int)fy * W + (int)fx;
+        const long long g_idx = AMVS_IDX(m * HW + pix, map_elems);
+        const float d = depth[g_idx], cf = conf[g_idx];
+        if (!(d > 0.0f) || !(cf >= min_views)) continue;
+        const float sdf = d - zc;
+        if (sdf < -trunc) continue;
+        s += fminf(1.0f, sdf / trunc);
+        w += 1.0f;
+        const long long q = 3 * AMVS_IDX((long long)color_slot[m] * HW + pix, bgr_pixels);
+        cb += (float)bgr[q]; cg += (float)bgr[q + 1]; cr += (float)bgr[q + 2];
+    }
+    tsdf[p] = w > 0.0f ? s / w : 1.0f;
+    weight[p] = w;
+    color_sum[3 * p] = cr; color_sum[3 * p + 1] = cg; color_sum[3 * p + 2] = cb;
+}
+
+// (a) crossing edges of every point: 7-bit mask (bit d-1 = direction d) and its population count
+__global__ __launch_bounds__(256) void edge_mask_kernel(const float *__restrict__ tsdf, const float *__restrict__ weight, Grid g,
+                                                        unsigned char *__restrict__ mask, unsigned *__restrict__ count)
+{
+    const int n = g.nx * g.ny * g.nz;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int i = p % g.nx, j = (p / g.nx) % g.ny, k = p / (g.nx * g.ny);
+    unsigned bits = 0;
+    if (weight[p] > 0.0f) {
+        const bool in0 = tsdf[p] < 0.0f;
+#pragma unroll
+        for (int d = 1; d < 8; ++d) {
+            const int di = d & 1, dj = (d >> 1) & 1, dk = d >> 2;
+            if (i + di >= g.nx || j + dj >= g.ny || k + dk >= g.nz) continue;
+            const int q = p + di + g.nx * (dj + g.ny * dk);
+            if (weight[q] > 0.0f && (tsdf[q] < 0.0f) != in0) bits |= 1u << (d - 1);
+        }
+    }
+    mask[p] = (unsigned char)bits;
+    count[p] = __popc(bits);
+}
+
+__device__ __forceinline__ unsigned char round_u8(float c)
+{
+    return (unsigned char)fminf(255.0f, fmaxf(0.0f, floorf(c + 0.5f)));
+}
+
+// (a) the vertices of every point's crossing edges, at vbase[p] + rank of the direction among its set bits
+__global__ __launch_bounds__(256) void vertex_kernel(const float *__restrict__ tsdf, const float *__restrict__ weight,
+                                                     const float *__restrict__ color_sum, Grid g,
+                                                     const unsigned char *__restrict__ mask, const unsigned *__restrict__ vbase,
+                                                     long long n_vertices, float *__restrict__ verts, unsigned char *__restrict__ rgb)
+{
+    const int n = g.nx * g.ny * g.nz;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const unsigned bits = mask[p];
+    if (!bits) return;
+    const int i = p % g.nx, j = (p / g.nx) % g.ny, k = p / (g.nx * g.ny);
+    const float f0 = tsdf[p], w0 = weight[p];
+    const float x0 = g.ox + (float)i * g.voxel, y0 = g.oy + (float)j * g.voxel, z0 = g.oz + (float)k * g.voxel;
+    const float c0[3] = {color_sum[3 * p] / w0, color_sum[3 * p + 1] / w0, color_sum[3 * p + 2] / w0};
+    unsigned id = vbase[p];
+    for (int d = 1; d < 8; ++d) {
+        if (!((bits >> (d - 1)) & 1u)) continue;
+        const int di = d & 1, dj = (d >> 1) & 1, dk = d >> 2;
+        const int q = AMVS_IDX(p + di + g.nx * (dj + g.ny * dk), n);
+        const float f1 = tsdf[q], w1 = weight[q];
+        const float t = f0 / (f0 - f1);
+        const float x1 = g.ox + (float)(i + di) * g.voxel, y1 = g.oy + (float)(j + dj) * g.voxel,
+                    z1 = g.oz + (float)(k + dk) * g.voxel;
+        const long long v = AMVS_IDX((long long)id, n_vertices);
+        verts[3 * v] = x0 + t * (x1 - x0);
+        verts[3 * v + 1] = y0 + t * (y1 - y0);
+        verts[3 * v + 2] = z0 + t * (z1 - z0);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float c1 = color_sum[3 * q + ch] / w1;
+            rgb[3 * v + ch] = round_u8(c0[ch] + t * (c1 - c0[ch]));
+        }
+        ++id;
+    }
+}
+
+// corner c of the cube at p: the point index and the "inside" / "observed" bits of all 8 corners
+__device__ __forceinline__ void cube_corners(const float *__restrict__ tsdf, const float *__restrict__ weight, const Grid &g,
+                                             int p, unsigned &inside, unsigned &observed)
+{
+    inside = 0; observed = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int q = p + (c & 1) + g.nx * (((c >> 1) & 1) + g.ny * (c >> 2));
+        if (weight[q] > 0.0f) observed |= 1u << c;
+        if (tsdf[q] < 0.0f) inside |= 1u << c;
+    }
+}
+
+__device__ __forceinline__ bool interior_cube(const Grid &g, int p)
+{
+    const int i = p % g.nx, j = (p / g.nx) % g.ny, k = p / (g.nx * g.ny);
+    return i + 1 < g.nx && j + 1 < g.ny && k + 1 < g.nz;
+}
+
+// sign case of Kuhn tetrahedron t from the cube's corner bits, or -1 if a corner is unobserved
+__device__ __forceinline__ int tet_case(int t, unsigned inside, unsigned observed)
+{
+    const unsigned c1 = k_tet_c1[t], c2 = k_tet_c2[t];
+    const unsigned need = 1u | (1u << c1) | (1u << c2) | 0x80u;
+    if ((observed & need) != need) return -1;
+    return (int)((inside & 1u) | (((inside >> c1) & 1u) << 1) | (((inside >> c2) & 1u) << 2) | (((inside >> 7) & 1u) << 3));
+}
+
+// cube corner of local tetrahedron vertex v (0 -> corner 0, 1 -> c1, 2 -> c2, 3 -> corner 7)
+__device__ __forceinline__ unsigned tet_corner(unsigned v, unsigned c1, unsigned c2)
+{
+    return v == 0 ? 0u : v == 1 ? c1 : v == 2 ? c2 : 7u;
+}
+
+// (b) triangles of every cube
+__global__ __launch_bounds__(256) void tri_count_kernel(const float *__restrict__ tsdf, const float *__restrict__ weight, Grid g,
+                                                        unsigned *__restrict__ count)
+{
+    const int n = g.nx * g.ny * g.nz;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    unsigned total = 0;
+    if (interior_cube(g, p)) {
+        unsigned inside, observed;
+        cube_corners(tsdf, weight, g, p, inside, observed);
+        if (observed) {
+#pragma unroll
+            for (int t = 0; t < 6; ++t) {
+                const int cs = tet_case(t, inside, observed);
+                if (cs >= 0) total += tri_count((unsigned)cs);
+            }
+        }
+    }
+    count[p] = total;
+}
+
+// (c) faces: vertex ids of the crossing edges, in cube / tetrahedron / table order
+__global__ __launch_bounds__(256) void face_kernel(const float *__restrict__ tsdf, const float *__restrict__ weight, Grid g,
+                                                   const unsigned char *__restrict__ mask, const unsigned *__restrict__ vbase,
+                                                   long long n_vertices, const unsigned *__restrict__ tcount,
+                                                   const unsigned *__restrict__ tbase, long long n_faces, int *__restrict__ faces)
+{
+    const int n = g.nx * g.ny * g.nz;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n || tcount[p] == 0) return;
+    unsigned inside, observed;
+    cube_corners(tsdf, weight, g, p, inside, observed);
+    long long f = tbase[p];
+    for (int t = 0; t < 6; ++t) {
+        const int cs = tet_case(t, inside, observed);
+        if (cs < 0) continue;
+        const int nt = tri_count((unsigned)cs);
+        const unsigned c1 = k_tet_c1[t], c2 = k_tet_c2[t];
+        const bool flip = t == 1 || t == 2 || t == 5;
+        for (int r = 0; r < nt; ++r) {
+            int ids[3];
+            for (int e = 0; e < 3; ++e) {
+                const int te = k_tri[cs][r][e];
+                const unsigned ca = tet_corner(k_edge_a[te], c1, c2), cb = tet_corner(k_edge_b[te], c1, c2);
+                const unsigned dir = ca ^ cb;                 // ca's bits are a subset of cb's
+                const int q = AMVS_IDX(p + (int)(ca & 1u) + g.nx * (int)(((ca >> 1) & 1u) + g.ny * (ca >> 2)), n);
+                ids[e] = (int)AMVS_IDX((long long)vbase[q] + __popc(mask[q] & ((1u << (dir - 1)) - 1u)), n_vertices);
+            }
+            const long long o = 3 * AMVS_IDX(f, n_faces);
+            faces[o] = ids[0];
+            faces[o + 1] = flip ? ids[2] : ids[1];
+            faces[o + 2] = flip ? ids[1] : ids[2];
+            ++f;
+        }
+    }
+}
+
+// (d) drop the vertices no face uses (their edges are shared only by tetrahedra with an unobserved corner):
+// flag the used ones (every writer stores the same 1), scan, move the kept vertices down, renumber the faces
+__global__ __launch_bounds__(256) void vertex_used_kernel(const int *__restrict__ faces, long long n_ids, long long n_vertices,
+                                                          unsigned *__restrict__ used)
+{
+    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < n_ids) used[AMVS_IDX((long long)faces[f], n_vertices)] = 1u;
+}
+
+__global__ __launch_bounds__(256) void vertex_compact_kernel(const float *__restrict__ verts, const unsigned char *__restrict__ rgb,
+                                                             const unsigned *__restrict__ used, const unsigned *__restrict__ new_id,
+                                                             long long n_vertices, long long n_kept, float *__restrict__ verts_out,
+                                                             unsigned char *__restrict__ rgb_out)
+{
+    const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_vertices || !used[v]) return;
+    const long long o = AMVS_IDX((long long)new_id[v], n_kept);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { verts_out[3 * o + c] = verts[3 * v + c]; rgb_out[3 * o + c] = rgb[3 * v + c]; }
+}
+
+__global__ __launch_bounds__(256) void face_renumber_kernel(int *__restrict__ faces, long long n_ids, long long n_vertices,
+                                                            const unsigned *__restrict__ new_id)
+{
+    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < n_ids) faces[f] = (int)new_id[AMVS_IDX((long long)faces[f], n_vertices)];
+}
+
+inline dim3 grid_of(long long n) { return dim3((unsigned)((n + 255) / 256)); }
+
+}  // namespace
+
+struct TsdfState {
+    Grid g{};
+    long long n = 0, cap = 0;                     // grid points, allocated points
+    bool have_volume = false, have_mesh = false;
+    float *tsdf = nullptr, *weight = nullptr, *color = nullptr;
+    unsigned char *mask = nullptr;
+    unsigned *vcount = nullptr, *vbase = nullptr, *tcount = nullptr, *tbase = nullptr;
+    void *scan_tmp = nullptr;
+    size_t cap_scan = 0;
+    float *cams = nullptr;                        // [n_maps][12] R, t
+    int *slots = nullptr;                         // colour image of every map
+    int cap_maps = 0;
+    float *stage_depth = nullptr, *stage_conf = nullptr;   // host maps
+    unsigned char *stage_bgr = nullptr;                    // host colour images
+    size_t cap_stage_depth = 0, cap_stage_conf = 0, cap_stage_bgr = 0;
+    float *verts = nullptr, *verts2 = nullptr;
+    int *faces = nullptr;
+    unsigned char *rgb = nullptr, *rgb2 = nullptr;
+    unsigned *vused = nullptr, *vnew = nullptr;   // (d): used flags and new ids of the vertices
+    long long n_vertices = 0, n_faces = 0, cap_vertices = 0, cap_faces = 0;
+};
+
+namespace {
+
+template <class T> hipError_t grow(T **p, size_t need, size_t &cap)
+{
+    if (need <= cap && *p) return hipSuccess;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; cap = 0;
+    MCHK(hipMalloc((void **)p, need > 0 ? need : 1));
+    cap = need;
+    return hipSuccess;
+}
+
+hipError_t exclusive_scan(TsdfState *s, const unsigned *in, unsigned *out, long long n, hipStream_t st)
+{
+    size_t bytes = 0;
+    MCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, st));
+    MCHK(grow(&s->scan_tmp, bytes, s->cap_scan));
+    return hipcub::DeviceScan::ExclusiveSum(s->scan_tmp, bytes, in, out, (int)n, st);
+}
+
+// total of an exclusive scan: base[n-1] + count[n-1]
+hipError_t scan_total(const unsigned *count, const unsigned *base, long long n, long long *total, hipStream_t st)
+{
+    unsigned h[2] = {0, 0};
+    MCHK(hipMemcpyAsync(&h[0], count + n - 1, 4, hipMemcpyDeviceToHost, st));
+    MCHK(hipMemcpyAsync(&h[1], base + n - 1, 4, hipMemcpyDeviceToHost, st));
+    MCHK(hipStreamSynchronize(st));
+    *total = (long long)h[0] + (long long)h[1];
+    return hipSuccess;
+}
+
+}  // namespace
+
+TsdfState *tsdf_state_new() { return new TsdfState(); }
+
+void tsdf_state_free(TsdfState *s)
+{
+    if (!s) return;
+    void *bufs[] = {s->tsdf, s->weight, s->color, s->mask, s->vcount, s->vbase, s->tcount, s->tbase, s->scan_tmp, s->cams,
+                    s->slots, s->stage_depth, s->stage_conf, s->stage_bgr, s->verts, s->faces, s->rgb, s->verts2, s->rgb2,
+                    s->vused, s->vnew};
+    for (void *b : bufs)
+        if (b) (void)hipFree(b);
+    delete s;
+}
+
+hipError_t tsdf_integrate(TsdfState *s, const float *depth, const float *conf, bool maps_on_device, int n_maps, int H, int W,
+                          const unsigned char *bgr, bool bgr_on_device, long long bgr_images, const int *slots_h,
+                          const float K[9], const float *poses_h, float min_views, const float origin[3], float voxel,
+                          const int dims[3], float trunc, hipStream_t st)
+{
+    s->have_volume = s->have_mesh = false;
+    const long long n = (long long)dims[0] * dims[1] * dims[2];
+    const size_t hw = (size_t)H * W, nmap = hw * (size_t)n_maps;
+    if (n > s->cap) {
+        for (float **b : {&s->tsdf, &s->weight, &s->color}) { if (*b) (void)hipFree(*b); *b = nullptr; }
+        for (unsigned **b : {&s->vcount, &s->vbase, &s->tcount, &s->tbase}) { if (*b) (void)hipFree(*b); *b = nullptr; }
+        if (s->mask) (void)hipFree(s->mask);
+        s->mask = nullptr; s->cap = 0;
+        MCHK(hipMalloc(&s->tsdf, 4 * n)); MCHK(hipMalloc(&s->weight, 4 * n)); MCHK(hipMalloc(&s->color, 12 * n));
+        MCHK(hipMalloc(&s->mask, n));
+        MCHK(hipMalloc(&s->vcount, 4 * n)); MCHK(hipMalloc(&s->vbase, 4 * n));
+        MCHK(hipMalloc(&s->tcount, 4 * n)); MCHK(hipMalloc(&s->tbase, 4 * n));
+        s->cap = n;
+    }
+    if (n_maps > s->cap_maps) {
+        if (s->cams) (void)hipFree(s->cams);
+        if (s->slots) (void)hipFree(s->slots);
+        s->cams = nullptr; s->slots = nullptr; s->cap_maps = 0;
+        MCHK(hipMalloc(&s->cams, sizeof(float) * 12 * n_maps));
+        MCHK(hipMalloc(&s->slots, sizeof(int) * n_maps));
+        s->cap_maps = n_maps;
+    }
+    MCHK(hipMemcpyAsync(s->cams, poses_h, sizeof(float) * 12 * n_maps, hipMemcpyHostToDevice, st));
+    MCHK(hipMemcpyAsync(s->slots, slots_h, sizeof(int) * n_maps, hipMemcpyHostToDevice, st));
+    if (!maps_on_device) {
+        MCHK(grow(&s->stage_depth, 4 * nmap, s->cap_stage_depth));
+        MCHK(grow(&s->stage_conf, 4 * nmap, s->cap_stage_conf));
+        MCHK(hipMemcpyAsync(s->stage_depth, depth, 4 * nmap, hipMemcpyHostToDevice, st));
+        MCHK(hipMemcpyAsync(s->stage_conf, conf, 4 * nmap, hipMemcpyHostToDevice, st));
+        depth = s->stage_depth; conf = s->stage_conf;
+    }
+    if (!bgr_on_device) {
+        MCHK(grow(&s->stage_bgr, 3 * hw * (size_t)bgr_images, s->cap_stage_bgr));
+        MCHK(hipMemcpyAsync(s->stage_bgr, bgr, 3 * hw * (size_t)bgr_images, hipMemcpyHostToDevice, st));
+        bgr = s->stage_bgr;
+    }
+    s->g = Grid{origin[0], origin[1], origin[2], voxel, dims[0], dims[1], dims[2]};
+    s->n = n;
+    Kmat km;
+    for (int q = 0; q < 9; ++q) km.k[q] = K[q];
+    hipLaunchKernelGGL(tsdf_integrate_kernel, grid_of(n), dim3(256), 0, st, depth, conf, (long long)nmap, bgr,
+                       (long long)(hw * (size_t)bgr_images), (const int *)s->slots, (const float *)s->cams, km, n_maps, H, W,
+                       min_views, trunc, s->g, s->tsdf, s->weight, s->color);
+    MCHK(hipGetLastError());
+    MCHK(hipStreamSynchronize(st));
+    s->have_volume = true;
+    return hipSuccess;
+}
+
+hipError_t tsdf_extract(TsdfState *s, long long *n_vertices, long long *n_faces, hipStream_t st)
+{
+    s->have_mesh = false;
+    const long long n = s->n;
+    // (a) vertices
+    hipLaunchKernelGGL(edge_mask_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf, (const float *)s->weight, s->g,
+                       s->mask, s->vcount);
+    MCHK(hipGetLastError());
+    MCHK(exclusive_scan(s, s->vcount, s->vbase, n, st));
+    long long nv = 0;
+    MCHK(scan_total(s->vcount, s->vbase, n, &nv, st));
+    size_t cap = (size_t)s->cap_vertices;
+    if ((size_t)nv > cap || !s->verts) {
+        for (void **b : {(void **)&s->verts, (void **)&s->rgb, (void **)&s->verts2, (void **)&s->rgb2, (void **)&s->vused,
+                         (void **)&s->vnew}) {
+            if (*b) (void)hipFree(*b);
+            *b = nullptr;
+        }
+        s->cap_vertices = 0;
+        const size_t m = (size_t)(nv > 0 ? nv : 1);
+        MCHK(hipMalloc(&s->verts, 12 * m)); MCHK(hipMalloc(&s->rgb, 3 * m));
+        MCHK(hipMalloc(&s->verts2, 12 * m)); MCHK(hipMalloc(&s->rgb2, 3 * m));
+        MCHK(hipMalloc(&s->vused, 4 * m)); MCHK(hipMalloc(&s->vnew, 4 * m));
+        s->cap_vertices = nv;
+    }
+    hipLaunchKernelGGL(vertex_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf, (const float *)s->weight,
+                       (const float *)s->color, s->g, (const unsigned char *)s->mask, (const unsigned *)s->vbase, nv, s->verts, s->rgb);
+    MCHK(hipGetLastError());
+    // (b) triangle counts
+    hipLaunchKernelGGL(tri_count_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf, (const float *)s->weight, s->g,
+                       s->tcount);
+    MCHK(hipGetLastError());
+    MCHK(exclusive_scan(s, s->tcount, s->tbase, n, st));
+    long long nf = 0;
+    MCHK(scan_total(s->tcount, s->tbase, n, &nf, st));
+    size_t capf = (size_t)s->cap_faces;
+    if ((size_t)nf > capf || !s->faces) {
+        if (s->faces) (void)hipFree(s->faces);
+        s->faces = nullptr; s->cap_faces = 0;
+        MCHK(hipMalloc(&s->faces, 12 * (size_t)(nf > 0 ? nf : 1)));
+        s->cap_faces = nf;
+    }
+    // (c) faces
+    hipLaunchKernelGGL(face_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf, (const float *)s->weight, s->g,
+                       (const unsigned char *)s->mask, (const unsigned *)s->vbase, nv, (const unsigned *)s->tcount,
+                       (const unsigned *)s->tbase, nf, s->faces);
+    MCHK(hipGetLastError());
+    // (d) keep the vertices the faces use, in their order
+    long long kept = 0;
+    if (nv > 0 && nf > 0) {
+        MCHK(hipMemsetAsync(s->vused, 0, 4 * (size_t)nv, st));
+        hipLaunchKernelGGL(vertex_used_kernel, grid_of(3 * nf), dim3(256), 0, st, (const int *)s->faces, 3 * nf, nv, s->vused);
+        MCHK(hipGetLastError());
+        MCHK(exclusive_scan(s, s->vused, s->vnew, nv, st));
+        MCHK(scan_total(s->vused, s->vnew, nv, &kept, st));
+        hipLaunchKernelGGL(vertex_compact_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->verts,
+                           (const unsigned char *)s->rgb, (const unsigned *)s->vused, (const unsigned *)s->vnew, nv, kept,
+                           s->verts2, s->rgb2);
+        MCHK(hipGetLastError());
+        hipLaunchKernelGGL(face_renumber_kernel, grid_of(3 * nf), dim3(256), 0, st, s->faces, 3 * nf, nv, (const unsigned *)s->vnew);
+        MCHK(hipGetLastError());
+        std::swap(s->verts, s->verts2);
+        std::swap(s->rgb, s->rgb2);
+    }
+    nv = kept;
+    MCHK(hipStreamSynchronize(st));
+    s->n_vertices = nv; s->n_faces = nf; s->have_mesh = true;
+    *n_vertices = nv; *n_faces = nf;
+    return hipSuccess;
+}
+
+bool tsdf_has_volume(const TsdfState *s) { return s && s->have_volume; }
+bool tsdf_has_mesh(const TsdfState *s) { return s && s->have_mesh; }
+
+hipError_t tsdf_fetch_mesh(TsdfState *s, float *verts, int *faces, unsigned char *rgb, hipStream_t st)
+{
+    if (s->n_vertices > 0) {
+        if (verts) MCHK(hipMemcpyAsync(verts, s->verts, 12 * (size_t)s->n_vertices, hipMemcpyDeviceToHost, st));
+        if (rgb) MCHK(hipMemcpyAsync(rgb, s->rgb, 3 * (size_t)s->n_vertices, hipMemcpyDeviceToHost, st));
+    }
+    if (s->n_faces > 0 && faces) MCHK(hipMemcpyAsync(faces, s->faces, 12 * (size_t)s->n_faces, hipMemcpyDeviceToHost, st));
+    return hipStreamSynchronize(st);
+}
+
+hipError_t tsdf_fetch_volume(TsdfState *s, float *tsdf, float *weight, float *color_sum, hipStream_t st)
+{
+    if (tsdf) MCHK(hipMemcpyAsync(tsdf, s->tsdf, 4 * (size_t)s->n, hipMemcpyDeviceToHost, st));
+    if (weight) MCHK(hipMemcpyAsync(weight, s->weight, 4 * (size_t)s->n, hipMemcpyDeviceToHost, st));
+    if (color_sum) MCHK(hipMemcpyAsync(color_sum, s->color, 12 * (size_t)s->n, hipMemcpyDeviceToHost, st));
+    return hipStreamSynchronize(st);
+}
+
+}  // namespace amvs
+
+AMVS_CHECK_TU(mesh)

@@ -525,6 +525,75 @@ class Engine:
                                                  rgb.ctypes.data_as(C.POINTER(C.c_uint8))))
         return pts, rgb, int(counts[0])
 
+    # -- surface mesh (TSDF fusion + marching tetrahedra) -------------------
+    def tsdf_integrate(self, K, poses, min_views, origin, voxel, dims, trunc, depth=None, conf=None, device_ptrs=None,
+                       view_ids=None, colors_bgr=None):
+        """Fuse depth maps into the context's TSDF volume (include/amvs.h amvs_tsdf_integrate).  Maps: depth / conf
+        (n,H,W) float32 host arrays, or device_ptrs=(depth_ptr, conf_ptr, n) of maps resident on the GPU.  Colours:
+        view_ids (map j takes the resident colour image of view view_ids[j]) or colors_bgr (n,H,W,3) uint8 BGR.
+        K (3,3) and poses = list of (R, t) are used in float32; dims = (nx, ny, nz) grid points."""
+        if device_ptrs is None:
+            depth = _f32(depth)
+            conf = _f32(conf)
+            n = depth.shape[0]
+            if depth.shape != (n, self.H, self.W) or conf.shape != depth.shape:
+                raise ValueError(f"maps must be (n, {self.H}, {self.W})")
+            dptr, cptr, on_dev = depth.ctypes.data_as(C.c_void_p), conf.ctypes.data_as(C.c_void_p), 0
+        else:
+            dptr, cptr, n = C.c_void_p(device_ptrs[0]), C.c_void_p(device_ptrs[1]), int(device_ptrs[2])
+            on_dev = 1
+        if len(poses) != n:
+            raise ValueError(f"{len(poses)} poses for {n} maps")
+        ids, idp, cols, colp = None, None, None, None
+        if view_ids is not None:
+            ids, idp = _ids(view_ids)
+            if ids.shape != (n,):
+                raise ValueError(f"{ids.shape[0]} view ids for {n} maps")
+        if colors_bgr is not None:
+            cols = np.ascontiguousarray(colors_bgr, dtype=np.uint8).reshape(n, self.H, self.W, 3)
+            colp = cols.ctypes.data_as(C.POINTER(C.c_uint8))
+        Kf = _f32(np.asarray(K, np.float64).astype(np.float32).reshape(9))
+        pp = _f32(np.stack([np.concatenate([np.asarray(R, np.float64).reshape(9), np.asarray(t, np.float64).reshape(3)])
+                            for R, t in poses]).astype(np.float32))
+        org = _f32(np.asarray(origin, np.float64).astype(np.float32).reshape(3))
+        dims = [int(d) for d in np.asarray(dims).reshape(3)]
+        if any(d < 2 or d > 2 ** 31 - 1 for d in dims):
+            raise ValueError(f"TSDF dims {dims}: every dimension must be in [2, 2^31)")
+        dm, dmp = _ids(dims)
+        self._chk(self._lib.amvs_tsdf_integrate(self._h, n, dptr, cptr, on_dev, idp, colp, _p(Kf), _p(pp),
+                                                float(min_views), _p(org), float(np.float32(voxel)), dmp,
+                                                float(np.float32(trunc))))
+        self._tsdf_dims = tuple(int(d) for d in dm)
+
+    def tsdf_extract(self):
+        """Marching tetrahedra of the last integrated volume: (vertices (V,3) float32, faces (F,3) int32,
+        colors (V,3) uint8 RGB)."""
+        nv, nf = C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.amvs_tsdf_extract(self._h, C.byref(nv), C.byref(nf)))
+        verts = np.empty((nv.value, 3), np.float32)
+        faces = np.empty((nf.value, 3), np.int32)
+        rgb = np.empty((nv.value, 3), np.uint8)
+        self._chk(self._lib.amvs_fetch_mesh(self._h, _p(verts), faces.ctypes.data_as(i32p),
+                                            rgb.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return verts, faces, rgb
+
+    def tsdf_mesh(self, K, poses, min_views, origin, voxel, dims, trunc, **maps_and_colors):
+        """tsdf_integrate(...) then tsdf_extract(): (vertices, faces, colors)."""
+        self.tsdf_integrate(K, poses, min_views, origin, voxel, dims, trunc, **maps_and_colors)
+        return self.tsdf_extract()
+
+    def tsdf_volume(self):
+        """The last integrated volume: tsdf (nz,ny,nx), weight (nz,ny,nx), colour sums (nz,ny,nx,3) RGB, float32."""
+        dims = getattr(self, "_tsdf_dims", None)
+        if dims is None:
+            raise AmvsError("no TSDF volume: call tsdf_integrate first")
+        nx, ny, nz = dims
+        tsdf = np.empty((nz, ny, nx), np.float32)
+        weight = np.empty((nz, ny, nx), np.float32)
+        color = np.empty((nz, ny, nx, 3), np.float32)
+        self._chk(self._lib.amvs_tsdf_fetch_volume(self._h, _p(tsdf), _p(weight), _p(color)))
+        return tsdf, weight, color
+
     def knn_mean_distance(self, points, k=20):
         """Mean distance of every point to its k-1 nearest other points, bit-identical to
         np.mean(NearestNeighbors(n_neighbors=k).fit(p).kneighbors(p)[0][:, 1:], axis=1)."""

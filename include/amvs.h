@@ -267,6 +267,37 @@ int amvs_fuse_filter_views(amvs_ctx *ctx, int n_maps, const int *view_ids, const
                            int64_t counts[2]);
 int amvs_fetch_cloud(amvs_ctx *ctx, double *points_out, uint8_t *colors_out);
 
+/* ---- surface mesh: TSDF fusion + marching tetrahedra (csrc/amvs_mesh.hip) ------------------------
+ * The reference stops at the point cloud; no counterpart, hence no parity: judged against synthetic ground
+ * truth and a NumPy restatement of the same float32 operations (tests/mesh_restatement.py).
+ * The volume is a dense grid of dims[0] x dims[1] x dims[2] points (x fastest); point (i,j,k) sits at
+ * origin + (i,j,k) * voxel.  At most AMVS_TSDF_MAX_POINTS points (about 20 B each for the volume, 30 B with the
+ * extraction's scans; 512^3 = 2^27 fits); a larger request fails with AMVS_EINVAL before anything is allocated.
+ * The volume and the mesh belong to the context (freed by amvs_destroy) and are replaced by the next call.  */
+#define AMVS_TSDF_MAX_POINTS (1ll << 27)
+/* Truncated signed distance fusion of n_maps depth maps ([n_maps][H][W] float32 at the context's size, host
+ * arrays or, with maps_on_device, device pointers, like amvs_fuse_filter) with the float32 intrinsics K and
+ * poses (n_maps x 12 float32: R row-major, then t; world -> camera).  Per grid point and map, in map order: project
+ * with R X + t then K, skip the map if z <= 0, take the nearest pixel floorf(u + 0.5f), skip it if outside the
+ * image, if depth <= 0 or confidence < min_views, or if sdf = depth - z < -trunc; otherwise add min(1, sdf / trunc)
+ * with weight 1 and the pixel's colour.  tsdf = mean (weight 0: unobserved).  Colours come from the resident
+ * prepared images of views view_ids[j] (amvs_set_view_bgr8 / amvs_set_view_colors) or from colors_bgr_host
+ * ([n_maps][H][W][3] uint8 BGR): exactly one of the two is non-NULL.  Synchronises.                      */
+int amvs_tsdf_integrate(amvs_ctx *ctx, int n_maps, const void *depth, const void *conf, int maps_on_device,
+                        const int *view_ids, const uint8_t *colors_bgr_host, const float K[9], const float *poses,
+                        float min_views, const float origin[3], float voxel, const int32_t dims[3], float trunc);
+/* Zero level set of the last integrated volume by marching tetrahedra on the Kuhn subdivision (6 tetrahedra per
+ * cube around its main diagonal; a tetrahedron with an unobserved corner is skipped): one vertex per lattice edge
+ * whose observed ends change sign and that a face uses, ids in point order then edge direction order; faces in cube,
+ * tetrahedron and table order, wound so that normals point toward increasing TSDF (free space, toward the cameras). */
+int amvs_tsdf_extract(amvs_ctx *ctx, int64_t *n_vertices, int64_t *n_faces);
+/* The mesh of the last amvs_tsdf_extract: n_vertices x 3 float32 positions, n_faces x 3 int32 vertex ids,
+ * n_vertices x 3 uint8 RGB colours (the two edge ends' mean colours, interpolated).  NULL skips an output.  */
+int amvs_fetch_mesh(amvs_ctx *ctx, float *vertices, int32_t *faces, uint8_t *colors_rgb);
+/* Test hook: the last integrated volume, dims[2] x dims[1] x dims[0] float32 tsdf and weight (views counted) and
+ * x 3 float32 RGB colour sums.  NULL skips an output.                                                      */
+int amvs_tsdf_fetch_volume(amvs_ctx *ctx, float *tsdf, float *weight, float *color_sum);
+
 /* ---- extended mode: what the reference's docstring names but does not implement ----------------
  * (mvs_patchmatch.py:1-13 lists plane hypotheses with normals and VIEW propagation; its code ignores
  * the normal in the cost, :323-390, and has no view propagation.)  Slanted-plane homography cost,
@@ -382,11 +413,12 @@ int amvs_write_ply(const char *path, const double *points, const int64_t *colors
 
 /* Index-checked build (csrc/amvs_check.h, -DAMVS_CHECK_INDICES; amvs_version() then ends in "+index-checks"): the
  * GPU-side substitute for an address sanitizer, which this pool does not offer for device code.  Every
- * data-dependent global index of the sweep, plane-sweep, extended, fusion and neighbour-search kernels is compared
+ * data-dependent global index of the sweep, plane-sweep, extended, fusion, neighbour-search and mesh kernels is compared
  * with its buffer's extent before the access; a violation is counted, the first is recorded and the access
  * redirected to a safe index.  report[0] = violations since the last reset, report[1] = translation unit << 32 |
  * source line of the first, report[2] = its index, report[3] = the extent; amvs_sync, amvs_patchmatch,
- * amvs_plane_sweep and amvs_fetch_cloud return AMVS_EINDEX while a violation is on record.  The shipped build
+ * amvs_plane_sweep, amvs_fetch_cloud and the amvs_tsdf_* / amvs_fetch_mesh calls return AMVS_EINDEX while a
+ * violation is on record.  The shipped build
  * compiles the checks away: it reports zeros.  (The reference has no counterpart; test infrastructure of the
  * device code.)                                                                                             */
 int amvs_index_check(uint64_t report[4], int reset);
