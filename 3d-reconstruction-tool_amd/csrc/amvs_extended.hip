@@ -227,10 +227,18 @@ AMVS_DEV float xcost_t(const XArgs &a, JobCP job, const XRef<N> &R, int x, int y
                 // corner test + convexity: 0 <= x0f <= W-2 up to the rounding of the incremental chain, i.e.
                 // -1 .. W-1 at worst.  The packed maps carry a zero border of AMVS_PAIR_BORDER = 2 texels, so
                 // that range needs no clamp there (a footprint one texel outside reads zeros with a weight
-                // of ~1e-7); the float maps have no border and keep the clamp.
+                // of ~1e-7); the float maps have no border and keep the clamp, so their weights are taken
+                // from the clamped origin and clamped to [0, 1]: u = -1e-7 then reads column 0 (not 1) and
+                // u = W - 1 + 1e-6 reads column W - 1 (not W - 2).
                 const int xi = U8 ? (int)x0f : min(max((int)x0f, 0), a.W - 2);
                 const int yi = U8 ? (int)y0f : min(max((int)y0f, 0), a.H - 2);
-                const float fx = u - x0f, fy = v - y0f;
+                float fx, fy;
+                if constexpr (U8) {
+                    fx = u - x0f; fy = v - y0f;
+                } else {
+                    fx = __builtin_fminf(__builtin_fmaxf(u - (float)xi, 0.0f), 1.0f);
+                    fy = __builtin_fminf(__builtin_fmaxf(v - (float)yi, 0.0f), 1.0f);
+                }
                 float top, bot;
                 if constexpr (U8) {
                     const uint32_t wd = load_pair_word(pimg, AMVS_IDX((yi + PB) * ppitch + xi + PB, (a.H + 2 * PB) * ppitch - 1), 0);

@@ -10,6 +10,10 @@ written from the kernel's documented arithmetic, against which the HIP kernels a
 STATED TOLERANCE (the kernels use v_rcp_f32 / v_rsq_f32, exp / log of the device library and real
 FMAs; this file uses IEEE division / sqrt, NumPy's exp / log and FMAs emulated in float64).
 
+Ref64 (below) is the float64 reference of every extended-mode kernel -- window cost in both samplings and
+both window loops, half sweep, consistency, initial state -- with per-pixel decision margins
+(tests/test_extended_paths.py).
+
 Conventions: images are 8-bit codes (H, W) uint8; gray = code / 255 in float32; state maps depth
 (H, W), normal (H, W, 3), cost (H, W) float32; K, K_inv float32 3x3 (K_inv as the engine forms it:
 the float32 inverse); poses (R, t) world -> camera.
@@ -322,3 +326,338 @@ class View:
             Nn.reshape(-1, 3)[idx, c3] = bn[c3]
         C.ravel()[idx] = bc
         return D, Nn, C
+
+
+# =====================================================================================================
+# float64 reference with decision margins (tests/test_extended_paths.py)
+#
+# Written from the specification (the kernel header, DESIGN.md section 7 "Extended mode"), not from the
+# kernels' operation order: float64 throughout, IEEE division / sqrt, NumPy exp / log.  Its inputs are the
+# job table's float32 values (K, K^-1, poses, the composed M, b of `compose`) and the float32 state maps.
+#
+# Every kernel decision is a float comparison against a threshold; where the exact value lies close to
+# the threshold the kernel's float32 rounding may decide the other way.  Each function therefore also
+# returns a DECISION MARGIN per pixel: the distance of the closest decision from its threshold, in pixels
+# for the u / v bounds of the footprint (and the rint of the consistency projection), relative (to the
+# unit normal or to the threshold) for the depth tests, n.r < -1e-6 and the normal's facing test.  A
+# decision that holds is limited by its smallest margin; a test that fails is limited by the LARGEST
+# margin among the failing tests (one clear failure decides it).
+#
+# The window.  The taps run -half, -half + stride, ... and stop at or before +half on both axes (the
+# generic loop `xcost`); for the (patch, stride) pairs the product uses, (patch - 1) is a multiple of
+# stride and this is the centred N x N window of `xcost_t`.  For a pair that does not fit, e.g. (9, 3),
+# the window is -4, -1, +2: NOT centred -- this is the specification (only C-ABI callers can ask for it).
+# Every tap must pass every test (n.r_q < -1e-6 along its ray, source depth > 0.1, 0 <= u < W - 1,
+# 0 <= v < H - 1); `taps="corners"` tests the four window corners only (what the N x N path does --
+# equivalent in exact arithmetic because each test is affine or projective in the tap position).
+# =====================================================================================================
+D = np.float64
+EPS32 = 2.0 ** -24
+
+
+def _and_margin(oks, ms):
+    """Conjunction of tests over the last axis: ok = all; margin = min of all margins if ok, else the largest
+    margin among the failing tests."""
+    ok = oks.all(axis=-1)
+    m_ok = ms.min(axis=-1)
+    m_fail = np.where(~oks, ms, -np.inf).max(axis=-1)
+    return ok, np.where(ok, m_ok, m_fail)
+
+
+def _rel(a, thr):
+    return np.abs(a - thr) / abs(thr)
+
+
+def normalise_facing64(nx, ny, nz):
+    """xnormalise_facing in float64: (nx, ny, nz, margin of the facing test nz < -0.05, relative to 0.05)."""
+    nx, ny, nz = (np.asarray(v, D) for v in (nx, ny, nz))
+    l = np.sqrt(nx * nx + ny * ny + nz * nz)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        il = np.where(l > 1e-12, 1.0 / l, 0.0)
+    nx, ny, nz = nx * il, ny * il, nz * il
+    m = _rel(nz, -0.05)
+    bad = ~(nz < -0.05)
+    return np.where(bad, 0.0, nx), np.where(bad, 0.0, ny), np.where(bad, -1.0, nz), m
+
+
+def init_state(seed, view, H, W, log_scale, log_min, rng_fill):
+    """xpm_init_kernel: depth = exp(u * log_scale + log_min) (log-uniform over [depth_min, depth_max]),
+    normal = normalise_facing(0.3 g0, 0.3 g1, -1), cost = +inf, from draw 0 of the view's stream."""
+    u, g = rng_fill(seed, view, 0, H * W)
+    d = np.exp(u.astype(D) * D(np.float32(log_scale)) + D(np.float32(log_min)))
+    nx, ny, nz, _ = normalise_facing64(g[:, 0].astype(D) * 0.3, g[:, 1].astype(D) * 0.3, np.full(H * W, -1.0))
+    return d.reshape(H, W), np.stack([nx, ny, nz], -1).reshape(H, W, 3)
+
+
+class Ref64:
+    """One reference view with its sources, float64.  grays: list of (H, W) float images of all views (the
+    float maps; 8-bit views are code / 255, for which the packed 8-bit sampling is exact)."""
+
+    def __init__(self, K, K_inv, grays, poses, ref, srcs, patch, stride, taps="all"):
+        self.Kf = np.asarray(K, np.float32).reshape(9)
+        self.K = self.Kf.astype(D)
+        self.Ki = np.asarray(K_inv, np.float32).reshape(9).astype(D)
+        self.grays = [np.asarray(g, np.float32).astype(D) for g in grays]
+        self.poses32 = [(np.asarray(R, np.float64).astype(np.float32).reshape(9), np.asarray(t, np.float64).astype(np.float32).reshape(3))
+                        for R, t in poses]
+        self.ref, self.srcs = int(ref), [int(s) for s in srcs]
+        self.H, self.W = self.grays[0].shape
+        self.patch, self.stride = int(patch), int(stride)
+        half = self.patch // 2
+        self.offs = np.arange(-half, half + 1, self.stride)
+        assert taps in ("all", "corners")
+        self.taps = taps
+        Rr, tr = self.poses32[self.ref]
+        self.Mb = [tuple(v.astype(D) for v in compose(self.Kf, Rr, tr, *self.poses32[s])) for s in self.srcs]
+        ys, xs = np.meshgrid(np.arange(self.H), np.arange(self.W), indexing="ij")
+        self.xs, self.ys = xs.ravel(), ys.ravel()
+
+    def _ray(self, x, y):
+        k = self.Ki
+        return k[0] * x + k[1] * y + k[2], k[3] * x + k[4] * y + k[5]
+
+    @staticmethod
+    def _bilinear(img, u, v):
+        H, W = img.shape
+        with np.errstate(invalid="ignore"):
+            x0 = np.clip(np.nan_to_num(np.floor(u), nan=0.0), 0, W - 2).astype(np.int64)
+            y0 = np.clip(np.nan_to_num(np.floor(v), nan=0.0), 0, H - 2).astype(np.int64)
+        fx, fy = u - x0, v - y0
+        top = img[y0, x0] + fx * (img[y0, x0 + 1] - img[y0, x0])
+        bot = img[y0 + 1, x0] + fx * (img[y0 + 1, x0 + 1] - img[y0 + 1, x0])
+        return top + fy * (bot - top)
+
+    # ---------------------------------------------------------------- cost -----
+    def cost(self, x, y, d, nx, ny, nz, edge_tol=0.0):
+        """Window cost of hypotheses (d[i], n[i]) at pixels (x[i], y[i]): (cost, margin, kappa).  kappa is the
+        conditioning of the per-source NCC (max over the valid sources of sum r^2 / var r + sum v^2 / var v):
+        a float32 evaluation of the sums loses about kappa * 2^-24 of the cost.  edge_tol > 0 widens the
+        footprint bounds to -edge_tol <= u < W - 1 + edge_tol (same for v) -- the samples themselves stay
+        exact (u = W - 1 reads column W - 1) -- to value windows whose validity is a rounding decision."""
+        H, W, offs = self.H, self.W, self.offs
+        x, y = np.asarray(x, np.int64), np.asarray(y, np.int64)
+        d, nx, ny, nz = (np.asarray(v, D) for v in (d, nx, ny, nz))
+        P = x.shape[0]
+        cost = np.full(P, np.inf)
+        margin = np.full(P, np.inf)
+        kappa = np.zeros(P)
+        win = (x + offs[0] >= 0) & (y + offs[0] >= 0) & (x + offs[-1] < W) & (y + offs[-1] < H)
+        rpx, rpy = self._ray(x, y)
+        ndr_p = nx * rpx + ny * rpy + nz
+        idx = np.nonzero(win)[0]
+        if idx.size == 0:
+            return cost, margin, kappa
+        oy, ox = (a.ravel() for a in np.meshgrid(offs, offs, indexing="ij"))
+        if self.taps == "corners":
+            n = offs.size
+            sel = np.array([0, n - 1, n * (n - 1), n * n - 1])
+            oy_t, ox_t = oy[sel], ox[sel]
+        else:
+            oy_t, ox_t = oy, ox
+        xi, yi = x[idx], y[idx]
+        dd, ax, ay, az = d[idx], nx[idx], ny[idx], nz[idx]
+        ndp = ndr_p[idx]
+        delta = dd * ndp
+
+        def geom(oxs, oys):
+            qx, qy = (xi[:, None] + oxs[None]).astype(D), (yi[:, None] + oys[None]).astype(D)
+            rqx, rqy = self._ray(qx, qy)
+            ndr = ax[:, None] * rqx + ay[:, None] * rqy + az[:, None]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                t = delta[:, None] / ndr
+            return qx, qy, ndr, t
+
+        # the plane faces the camera at the pixel and along every tested ray (source independent)
+        qxt, qyt, ndr_t, tt = geom(ox_t, oy_t)
+        nd_all = np.concatenate([ndp[:, None], ndr_t], axis=1)
+        face_ok, face_m = _and_margin(nd_all < -1e-6, np.abs(nd_all + 1e-6))
+        qx, qy, _, t = geom(ox, oy)
+        rv = self.grays[self.ref][yi[:, None] + oy[None], xi[:, None] + ox[None]]
+        n_t = ox.size
+        sr, srr = rv.sum(1), (rv * rv).sum(1)
+        vr = srr - sr * sr / n_t
+        src_cost, src_ok, src_m, src_k = [], [], [], []
+        with np.errstate(all="ignore"):
+            for s, (M, b) in zip(self.srcs, self.Mb):
+                def project(qx_, qy_, t_):
+                    X = [t_ * (M[3 * r] * qx_ + M[3 * r + 1] * qy_ + M[3 * r + 2]) + b[r] for r in range(3)]
+                    return X[0] / X[2], X[1] / X[2], X[2]
+                u, v, p2 = project(qxt, qyt, tt)
+                e = edge_tol
+                oks = np.concatenate([p2 > 0.1, u >= -e, u < W - 1 + e, v >= -e, v < H - 1 + e], axis=1)
+                ms = np.concatenate([_rel(p2, 0.1), np.abs(u), np.abs(W - 1 - u), np.abs(v), np.abs(H - 1 - v)], axis=1)
+                ms = np.where(np.isfinite(ms), ms, np.inf)
+                ok, m = _and_margin(oks, ms)
+                u, v, _ = project(qx, qy, t)
+                sv = self._bilinear(self.grays[s], np.where(ok[:, None], u, 0.0), np.where(ok[:, None], v, 0.0))
+                ssv, svv, srv = sv.sum(1), (sv * sv).sum(1), (rv * sv).sum(1)
+                vs = svv - ssv * ssv / n_t
+                cov = srv - sr * ssv / n_t
+                den = vr * vs
+                ncc = np.where(den > 1e-12, cov / np.sqrt(np.where(den > 0, den, 1.0)), 0.0)
+                m = np.where(ok, np.minimum(m, _rel(den, 1e-12)), m)
+                src_cost.append(np.where(ok, 1.0 - ncc, np.inf))
+                src_ok.append(ok)
+                src_m.append(m)
+                src_k.append(np.where(ok & (den > 1e-12), srr / np.maximum(vr, 1e-300) + svv / np.maximum(vs, 1e-300), 0.0))
+        sc = np.sort(np.stack(src_cost, 1), axis=1)
+        n_valid = np.stack(src_ok, 1).sum(1)
+        keep = np.maximum((n_valid + 1) // 2, 2)
+        with np.errstate(invalid="ignore"):
+            tot = np.where(np.arange(sc.shape[1])[None] < keep[:, None], sc, 0.0).sum(1)
+            c = np.where(n_valid >= 2, tot / keep, np.inf)
+        c = np.where(face_ok, c, np.inf)
+        m = np.where(face_ok, np.minimum(face_m, np.stack(src_m, 1).min(1)), face_m)
+        cost[idx], margin[idx], kappa[idx] = c, m, np.where(face_ok, np.stack(src_k, 1).max(1), 0.0)
+        return cost, margin, kappa
+
+    def cost_map(self, depth, normal, edge_tol=0.0):
+        """(cost, margin, kappa) maps of every pixel's current plane (AMVS_XPM_PHASE_EVAL)."""
+        n = np.asarray(normal).reshape(-1, 3)
+        res = self.cost(self.xs, self.ys, np.asarray(depth).ravel(), n[:, 0], n[:, 1], n[:, 2], edge_tol)
+        return tuple(r.reshape(self.H, self.W) for r in res)
+
+    # ---------------------------------------------------------------- half sweep --
+    def half_sweep(self, depth, normal, cost, cand_d, cand_n, colour, iteration, seed, rng_fill, depth_min, depth_max,
+                   num_refine=2, view_propagation=True, cost_tol=None):
+        """One red (colour 0) or black (colour 1) half sweep from the float32 state (depth, normal, cost) of
+        this view and its view candidates.  Returns (depth, normal, cost, kappa, margin, gap): the new maps
+        (the swept colour changed), the conditioning of the winning cost, the smallest margin of any decision
+        taken for the pixel (hypothesis validity, range and facing tests, the validity of every cost
+        evaluated) and the smallest cost gap of any comparison `c < best` with a finite side between two
+        planes that differ by more than 5e-6 -- the gap between the winner and the runner-up when they met.  cost_tol(kappa): the error bound of a
+        cost; when given, each gap is divided by the sum of the bounds of its two sides (decided if > 1)."""
+        H, W = self.H, self.W
+        Dm, Nm, Cm = (np.asarray(a).astype(D).copy() for a in (depth, normal, cost))
+        sel = ((self.xs + self.ys + colour) & 1) == 0
+        x, y = self.xs[sel], self.ys[sel]
+        P = x.shape[0]
+        idx = y * W + x
+        bd = Dm.ravel()[idx].copy()
+        bn = [Nm.reshape(-1, 3)[idx, c].copy() for c in range(3)]
+        bc = Cm.ravel()[idx].copy()
+        bk = self.cost(x, y, bd, *bn)[2]                  # conditioning of the current plane's cost
+        margin = np.full(P, np.inf)
+        gap = np.full(P, np.inf)
+        rpx, rpy = self._ray(x.astype(D), y.astype(D))
+        shrink = 0.5 ** iteration
+        rel_range, nrm_range = D(np.float32(max(0.2 * shrink, 0.004))), D(np.float32(max(0.4 * shrink, 0.01)))
+        with_random = iteration < 2
+        draw = 1 + 2 * iteration + colour
+        n_ref = max(0, min(6, num_refine))
+        n_hyp = 6 + n_ref + (1 if with_random else 0)
+        dmin, dmax = D(np.float32(depth_min)), D(np.float32(depth_max))
+        d0, n0 = np.asarray(depth).astype(D), np.asarray(normal).astype(D).reshape(-1, 3)
+        for hyp in range(n_hyp):
+            d, nx, ny, nz = bd.copy(), bn[0].copy(), bn[1].copy(), bn[2].copy()
+            have = np.ones(P, bool)
+            hm = np.full(P, np.inf)
+            with np.errstate(all="ignore"):
+                if hyp == 0:
+                    have = ~(bc < np.inf)
+                elif hyp <= 4:
+                    k = hyp - 1
+                    xx = x + (-1 if k == 0 else (1 if k == 1 else 0))
+                    yy = y + (-1 if k == 2 else (1 if k == 3 else 0))
+                    have = (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H)
+                    j = np.where(have, yy * W + xx, 0)
+                    nx, ny, nz = (n0[j, c] for c in range(3))
+                    rqx, rqy = self._ray(np.where(have, xx, 0).astype(D), np.where(have, yy, 0).astype(D))
+                    dl = d0.ravel()[j] * (nx * rqx + ny * rqy + nz)
+                    ndr = nx * rpx + ny * rpy + nz
+                    hm = np.where(have, np.abs(ndr + 1e-6), np.inf)
+                    have = have & (ndr < -1e-6)
+                    d = dl / ndr
+                elif hyp == 5:
+                    d = np.asarray(cand_d).astype(D).ravel()[idx]
+                    have = np.full(P, bool(view_propagation)) & (d > 0)
+                    nx, ny, nz = (np.asarray(cand_n).astype(D).reshape(-1, 3)[idx, c] for c in range(3))
+                elif hyp < 6 + n_ref:
+                    r = hyp - 6
+                    u, g = rng_fill(seed, self.ref, draw * 8 + r, H * W)
+                    u, g = u[idx].astype(D), g[idx].astype(D)
+                    scale = 1.0 if r == 0 else 0.25
+                    d = bd * (1.0 + (u * 2.0 - 1.0) * rel_range * scale)
+                    nx, ny, nz, hm = normalise_facing64(bn[0] + g[:, 0] * nrm_range * scale, bn[1] + g[:, 1] * nrm_range * scale,
+                                                        bn[2] + g[:, 2] * nrm_range * scale)
+                else:
+                    u, g = rng_fill(seed, self.ref, draw * 8 + 7, H * W)
+                    u, g = u[idx].astype(D), g[idx].astype(D)
+                    nx, ny, nz, hm = normalise_facing64(g[:, 0] * 0.3, g[:, 1] * 0.3, np.full(P, -1.0))
+                    lmin, lmax = np.log(dmin), np.log(dmax)
+                    d = np.exp(lmin + u * (lmax - lmin))
+                if hyp > 0:
+                    hm = np.minimum(hm, np.where(have, np.minimum(_rel(d, dmin), _rel(d, dmax)), np.inf))
+                    have = have & (d >= dmin) & (d <= dmax)
+            c, cm, ck = self.cost(x, y, np.where(have, d, 1.0), np.where(have, nx, 0.0), np.where(have, ny, 0.0),
+                                  np.where(have, nz, -1.0))
+            margin = np.minimum(margin, hm)
+            margin = np.where(have, np.minimum(margin, cm), margin)
+            if hyp > 0:
+                with np.errstate(invalid="ignore"):
+                    # a near-tie between two planes that agree to 5e-6 decides nothing
+                    differ = (np.abs(d - bd) > 5e-6 * np.abs(bd)) | (np.abs(nx - bn[0]) > 5e-6) | (np.abs(ny - bn[1]) > 5e-6) \
+                        | (np.abs(nz - bn[2]) > 5e-6)
+                    g_ = np.where(have & differ & (np.isfinite(c) | np.isfinite(bc)), np.abs(c - bc), np.inf)
+                    if cost_tol is not None:
+                        g_ = g_ / (cost_tol(ck) + cost_tol(bk))
+                gap = np.minimum(gap, np.where(np.isnan(g_), np.inf, g_))
+            take = have & ((hyp == 0) | (c < bc))
+            bc = np.where(take, c, bc)
+            bd = np.where(take, d, bd)
+            bk = np.where(take, ck, bk)
+            bn = [np.where(take, v, o) for v, o in zip((nx, ny, nz), bn)]
+        out_k, out_m, out_g = np.zeros(H * W), np.full(H * W, np.inf), np.full(H * W, np.inf)
+        Dm.ravel()[idx] = bd
+        for c3 in range(3):
+            Nm.reshape(-1, 3)[idx, c3] = bn[c3]
+        Cm.ravel()[idx] = bc
+        out_k[idx], out_m[idx], out_g[idx] = bk, margin, gap
+        return Dm, Nm, Cm, out_k.reshape(H, W), out_m.reshape(H, W), out_g.reshape(H, W)
+
+    # ---------------------------------------------------------------- consistency --
+    def consistency(self, depth_all, cost_ref, consistency_px=1.0, consistency_rel=0.01):
+        """xpm_consistency_kernel: per pixel of the reference view whose cost is below 0.6, the number of
+        sources in which its point (depth d) lands in front of the source (depth > 0.1), on a pixel (rounded
+        to the nearest) inside the image whose own depth d2 lifts to a point that, seen from the reference,
+        is in front of it (> 0.1), re-projects within consistency_px of the pixel and has a depth within
+        consistency_rel * d of d.  Returns (count, margin): the margin is in pixels for the rounding and the
+        re-projection error, relative for the depth tests (to 0.1 and to consistency_rel * d)."""
+        H, W = self.H, self.W
+        K, Ki = self.K, self.Ki
+        Rr, tr = (v.astype(D) for v in self.poses32[self.ref])
+        x, y = self.xs.astype(D), self.ys.astype(D)
+        d = np.asarray(depth_all[self.ref], np.float32).astype(D).ravel()
+        live = np.asarray(cost_ref, np.float32).ravel() < np.float32(0.6)
+        cnt = np.zeros(H * W, np.int64)
+        margin = np.full(H * W, np.inf)
+        rx, ry = self._ray(x, y)
+        with np.errstate(all="ignore"):
+            for s, (M, b) in zip(self.srcs, self.Mb):
+                Rs, ts = (v.astype(D) for v in self.poses32[s])
+                X = [d * (M[3 * r] * x + M[3 * r + 1] * y + M[3 * r + 2]) + b[r] for r in range(3)]
+                p2 = X[2]
+                u, v = X[0] / p2, X[1] / p2
+                px, py = np.rint(u), np.rint(v)
+                m_round = np.minimum(np.abs(np.abs(u - np.floor(u)) - 0.5), np.abs(np.abs(v - np.floor(v)) - 0.5))
+                inb = (p2 > 0.1) & (px >= 0) & (px < W) & (py >= 0) & (py < H)
+                # the decisions up to here: in front of the source (margin relative), the rounding (pixels)
+                m1 = np.where(p2 > 0.1, np.minimum(_rel(p2, 0.1), m_round), _rel(p2, 0.1))
+                pxi, pyi = np.where(inb, px, 0).astype(np.int64), np.where(inb, py, 0).astype(np.int64)
+                d2 = np.asarray(depth_all[s], np.float32).astype(D)[pyi, pxi]
+                Y = np.stack([(Ki[0] * pxi + Ki[1] * pyi + Ki[2]) * d2, (Ki[3] * pxi + Ki[4] * pyi + Ki[5]) * d2, d2])
+                Xw = Rs.reshape(3, 3).T @ (Y - ts[:, None])
+                Xr = Rr.reshape(3, 3) @ Xw + tr[:, None]
+                uu = (K[0] * Xr[0] + K[1] * Xr[1]) / Xr[2] + K[2]
+                vv = (K[3] * Xr[0] + K[4] * Xr[1]) / Xr[2] + K[5]
+                e = np.sqrt((uu - x) ** 2 + (vv - y) ** 2)
+                rel_err = np.abs(Xr[2] - d) / d
+                tests = np.stack([Xr[2] > 0.1, e < consistency_px, rel_err < consistency_rel], 1)
+                ms = np.stack([_rel(Xr[2], 0.1), np.abs(e - consistency_px), _rel(rel_err, consistency_rel)], 1)
+                ms = np.where(np.isfinite(ms), ms, np.inf)
+                ok2, m2 = _and_margin(tests, ms)
+                agree = live & inb & ok2
+                cnt += agree
+                m = np.where(inb, np.minimum(m1, m2), m1)
+                margin = np.where(live, np.minimum(margin, m), margin)
+        return cnt.reshape(H, W), margin.reshape(H, W)

@@ -324,6 +324,103 @@ def test_extended_restatement_is_sane_on_the_cpu():
     assert got.mean() > 0.25 and np.median(np.abs(D[got] - gt[got]) / gt[got]) < 0.01
 
 
+def _ref64_scene(H=32, W=48, n_views=5):
+    from amvs.synthetic import make_scene
+    sc = make_scene(n_views, H, W, seed=17)
+    codes = [np.round(g * 255).clip(0, 255).astype(np.uint8) for g in sc.grays]
+    K = sc.camera.K.astype(np.float32)
+    poses = [(sc.poses[i].R, sc.poses[i].t) for i in range(n_views)]
+    return sc, codes, K, np.linalg.inv(K).astype(np.float32), poses
+
+
+def test_extended_float64_reference_agrees_with_the_restatement_on_the_cpu():
+    """oracle/xpm_oracle.Ref64 (float64, float sampling, per-tap window tests) against the float32 restatement
+    of the 8-bit N x N path on 8-bit views: the same +inf pattern and costs within the rounding of the float32
+    sums; the per-tap window tests equal the corner tests on fitting windows; kappa and the margins positive."""
+    from oracle import xpm_oracle
+    sc, codes, K, Ki, poses = _ref64_scene()
+    grays = [c.astype(np.float32) / np.float32(255) for c in codes]
+    rng = np.random.default_rng(0)
+    d = (sc.depths[2] * (1 + 0.002 * rng.standard_normal(sc.depths[2].shape))).astype(np.float32)
+    n = np.zeros(d.shape + (3,), np.float32)
+    n[..., :2] = 0.1 * rng.standard_normal(d.shape + (2,))
+    n[..., 2] = -1
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    for patch, stride in ((3, 1), (7, 2), (11, 2)):
+        want32 = xpm_oracle.View(K, Ki, codes, poses, 2, [1, 3, 0, 4], patch, stride).cost_map(d, n)
+        ref = xpm_oracle.Ref64(K, Ki, grays, poses, 2, [1, 3, 0, 4], patch, stride)
+        c, m, k = ref.cost_map(d, n)
+        cc, _, _ = xpm_oracle.Ref64(K, Ki, grays, poses, 2, [1, 3, 0, 4], patch, stride, taps="corners").cost_map(d, n)
+        fin = np.isfinite(c)
+        assert np.array_equal(np.isinf(c), np.isinf(want32)) and fin.mean() > 0.3
+        assert (np.abs(c[fin] - want32[fin]) <= 8 * k[fin] * 2.0 ** -24 + 1e-6).all()
+        assert np.array_equal(c, cc)
+        assert (m > 0).all() and (k[fin] > 1).all()
+
+
+def test_extended_float64_reference_window_and_margins_on_the_cpu():
+    """The generic window: taps -half, -half + stride, ... up to +half (for (9, 3): -4, -1, 2, not centred).
+    Margins: positive, and small exactly where a window corner is constructed to land on the edge of a source
+    (u = W - 1 - 1e-5) or the plane is constructed to graze the rays (n.r = -1e-6 - 1e-9)."""
+    from oracle import xpm_oracle
+    H, W, f = 24, 40, 32.0
+    K = np.array([[f, 0, W / 2], [0, f, H / 2], [0, 0, 1]], np.float32)
+    Ki = np.linalg.inv(K).astype(np.float32)
+    shift, d0 = 2.0, 4.0
+    tx = shift * d0 / f
+    poses = [(np.eye(3), np.zeros(3)), (np.eye(3), np.array([tx, 0, 0])), (np.eye(3), np.array([-tx, 0, 0]))]
+    rng = np.random.default_rng(1)
+    grays = [rng.random((H, W)).astype(np.float32) for _ in range(3)]
+    assert list(xpm_oracle.Ref64(K, Ki, grays, poses, 0, [1, 2], 9, 3).offs) == [-4, -1, 2]
+    assert list(xpm_oracle.Ref64(K, Ki, grays, poses, 0, [1, 2], 7, 2).offs) == [-3, -1, 1, 3]
+    ref = xpm_oracle.Ref64(K, Ki, grays, poses, 0, [1, 2], 5, 1)
+    # source 1 sees u = x + 2 at depth 4: the right-most tap of pixel x = W - 5 lands at u = W - 1 - 1e-5
+    # for the depth below (u = x + f tx / d)
+    d_edge = f * tx / (shift - 1e-5)
+    x = np.array([W - 5, W - 5, 10]); y = np.array([10, 10, 10])
+    d = np.array([d_edge, d_edge * (1 - 1e-3), 4.0])
+    one = np.ones(3)
+    c, m, _ = ref.cost(x, y, d, 0 * one, 0 * one, -one)
+    assert np.isfinite(c[0]) and 5e-6 < m[0] < 2e-5          # valid, 1e-5 px from the edge
+    assert np.isinf(c[1]) and m[1] > 1e-3                    # clearly past it: decided
+    assert np.isfinite(c[2]) and m[2] > 0.5
+    # a (not normalised) normal with n.r = -1e-6 - 1e-9 along every ray: passes the facing test by 1e-9
+    one = np.ones(1)
+    c, m, _ = ref.cost(np.array([10]), np.array([10]), 4.0 * one, 0 * one, 0 * one, (-1e-6 - 1e-9) * one)
+    assert np.isfinite(c[0]) and 0 < m[0] < 1e-8
+
+
+def test_extended_consistency_reference_on_the_cpu():
+    """Ref64.consistency on the scene's true depth maps counts every source that sees the point (all four
+    on most interior pixels); with the reference's map scaled by 1.05 the depths disagree by 5 % > 1 % and
+    nothing counts; a cost of 0.6 or more counts nothing; the count's margins are positive."""
+    from oracle import xpm_oracle
+    sc, codes, K, Ki, poses = _ref64_scene()
+    grays = [c.astype(np.float32) / np.float32(255) for c in codes]
+    ref = xpm_oracle.Ref64(K, Ki, grays, poses, 2, [1, 3, 0, 4], 7, 2)
+    depth = np.stack(sc.depths).astype(np.float32)
+    zero = np.zeros(depth.shape[1:], np.float32)
+    cnt, m = ref.consistency(depth, zero)
+    inner = (slice(6, -6), slice(10, -10))
+    assert (cnt[inner] == 4).mean() > 0.9 and (m > 0).all()
+    scaled = depth.copy()
+    scaled[2] *= np.float32(1.05)
+    cnt_s, _ = ref.consistency(scaled, zero)
+    assert (cnt_s == 0).all()
+    cnt_c, _ = ref.consistency(depth, zero + np.float32(0.6))
+    assert (cnt_c == 0).all()
+
+
+def test_extended_init_reference_on_the_cpu():
+    """xpm_oracle.init_state: depths inside [depth_min, depth_max], log-uniform; unit normals facing the camera."""
+    from oracle import oracle, xpm_oracle
+    lmin, lmax = np.log(3.0), np.log(8.0)
+    d, n = xpm_oracle.init_state(11, 2, 40, 50, np.float32(lmax - lmin), np.float32(lmin), oracle.rng_fill)
+    assert d.min() >= 3.0 * (1 - 1e-6) and d.max() <= 8.0 * (1 + 1e-6)
+    assert abs(np.median(np.log(d)) - 0.5 * (lmin + lmax)) < 0.05
+    assert np.allclose(np.linalg.norm(n, axis=-1), 1.0) and (n[..., 2] < -0.05).all()
+
+
 def test_native_exchange_without_rccl_is_unsupported_not_fatal():
     """ADVICE (round 3): when librccl cannot be opened, amvs_comm_unique_id / amvs_comm_init return
     AMVS_EUNSUPPORTED with a message, as include/amvs.h documents (the first version built the message from
