@@ -6,7 +6,7 @@
 // together, one kernel launch per cost-evaluation step over the whole batch.
 #include "../../include/amvs.h"
 #include "amvs_kernels.h"
-#include "amvs_pool.h"
+#include "amvs_buffer.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>          // types only: the library is resolved at run time (amvs_comm_*)
@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -66,13 +67,20 @@ void index_report(uint64_t out[4], bool reset)
 }
 
 struct Stats {
-    float *mean = nullptr, *var = nullptr;
-    std::vector<char> done;
+    amvs::DeviceBuffer<float> mean, var;
+    std::vector<char> done;             // empty until the maps are allocated
 };
 
 struct FastStats {
-    float2 *maps = nullptr;             // [n_views][H*W]
+    amvs::DeviceBuffer<float2> maps;    // [n_views][H*W]
     std::vector<char> done;
+};
+
+// a point cloud on the device: float64 xyz, uint8 rgb
+struct Cloud {
+    amvs::DeviceBuffer<double> pts;
+    amvs::DeviceBuffer<unsigned char> rgb;
+    long long n = 0;
 };
 
 }  // namespace
@@ -84,18 +92,19 @@ struct amvs_ctx {
     std::vector<std::array<float, 9>> R;
     std::vector<std::array<float, 3>> t;
     std::vector<char> have;
-    float *d_images = nullptr;
+    // every device allocation of the context goes through its cache (amvs_buffer.h), the post-steps' short-lived
+    // blocks come from it
+    amvs::ScratchCache cache;
+    amvs::DeviceBuffer<float> d_images;
     // packed 8-bit row-pair maps (sampling fast path), valid while every uploaded view is
     // exactly code/255 (n_inexact == 0); otherwise the sweep samples the float32 maps
-    uint16_t *d_pairs = nullptr;
+    amvs::DeviceBuffer<uint16_t> d_pairs;
     long long pstride = 0;              // ushorts between packed maps
-    unsigned char *d_bgr = nullptr;      // [n_views][H*W*3] prepared colour images (amvs_set_view_bgr8), lazily allocated
-    unsigned char *d_prep_src = nullptr; // staging of one uploaded source image + the resize tables (amvs_set_view_bgr8):
-    size_t cap_prep_src = 0;             // kept across calls -- a hipMalloc / hipFree pair per view cost more than the copy
-    int *d_prep_tab = nullptr;
-    size_t cap_prep_tab = 0;
+    amvs::DeviceBuffer<unsigned char> d_bgr;      // [n_views][H*W*3] prepared colour images (amvs_set_view_bgr8), lazily allocated
+    amvs::DeviceBuffer<unsigned char> d_prep_src; // staging of one uploaded source image + the resize tables (amvs_set_view_bgr8):
+    amvs::DeviceBuffer<int> d_prep_tab;           // kept across calls -- an allocation per view cost more than the copy
     std::vector<char> have_bgr;
-    int *d_flag = nullptr;               // [n_views] 1 = the view did not quantise to 8 bits losslessly
+    amvs::DeviceBuffer<int> d_flag;     // [n_views] 1 = the view did not quantise to 8 bits losslessly
     mutable std::vector<char> exact8;    // host copy of !d_flag, refreshed lazily (flags_dirty)
     mutable bool flags_dirty = false;
     bool force_f32 = false;             // amvs_set_sampling: A/B switch for tests
@@ -105,28 +114,21 @@ struct amvs_ctx {
     int sweep_key8 = 1;                         // strips above 32 rows with 8-bit keys where the plane chunks allow it
     std::map<int, Stats> stats;
     std::map<int, FastStats> fstats;    // fast mode: (mean1, var1) maps per patch size
-    int cap_slots = 0;
-    float *d_depth[2] = {nullptr, nullptr}, *d_cost[2] = {nullptr, nullptr},
-          *d_normal[2] = {nullptr, nullptr}, *d_aux = nullptr;
-    amvs::Job *d_jobs = nullptr;
-    int cap_jobs = 0;
-    float *d_planes = nullptr;
-    int cap_planes = 0;
-    unsigned *d_keys = nullptr;          // plane-sweep running best, [slot][H*W]
-    int cap_keys = 0;
-    float *d_xcand_d = nullptr, *d_xcand_n = nullptr;           // extended mode: view-propagation candidates
-    int *d_xsrc = nullptr;
-    int cap_x = 0, cap_xsrc = 0;
-    float *d_sweep_depth = nullptr, *d_sweep_conf = nullptr;   // maps of the last amvs_plane_sweep_batch
-    int cap_sweep = 0, n_sweep = 0;
-    double *d_cloud_pts = nullptr;       // result of the last amvs_fuse_filter
-    unsigned char *d_cloud_rgb = nullptr;
-    long long cloud_n = 0;
-    amvs::TsdfState *tsdf = nullptr;     // volume, scans and mesh of amvs_tsdf_* (amvs_mesh.hip), lazily created
+    // PatchMatch state of the batch slots (ensure_slots); the cost is updated in place, so it has one buffer
+    amvs::DeviceBuffer<float> d_depth[2], d_cost, d_normal[2], d_aux;
+    amvs::DeviceBuffer<amvs::Job> d_jobs;
+    amvs::DeviceBuffer<float> d_planes;
+    amvs::DeviceBuffer<unsigned> d_keys;          // plane-sweep running best, [slot][H*W]
+    amvs::DeviceBuffer<float> d_xcand_d, d_xcand_n;            // extended mode: view-propagation candidates
+    amvs::DeviceBuffer<int> d_xsrc;
+    amvs::DeviceBuffer<float> d_sweep_depth, d_sweep_conf;     // maps of the last amvs_plane_sweep_batch
+    int n_sweep = 0;
+    Cloud cloud;                         // result of the last fusion / back-projection and the steps after it
+    // volume, scans and mesh of amvs_tsdf_* (amvs_mesh.hip), lazily created
+    std::unique_ptr<amvs::TsdfState, void (*)(amvs::TsdfState *)> tsdf{nullptr, amvs::tsdf_state_free};
     // split schedule (amvs_pm_params.schedule == AMVS_SCHEDULE_SPLIT): sample maps, one stream per
     // view group, the token events that serialise the sampling kernels across the groups
-    float *d_samples = nullptr;
-    size_t cap_samples = 0;
+    amvs::DeviceBuffer<float> d_samples;
     std::vector<hipStream_t> split_streams;  // [0] sampling kernels, [1] window kernels
     std::vector<hipEvent_t> split_events;    // [0] fork, [1 + g] sampled(g), [9 + g] windowed(g)
     int split_groups = 0, split_sample_rows = 0, split_sample_lds = 0;
@@ -207,36 +209,19 @@ int check_patch_src(amvs_ctx *c, int patch, int n_src)
     return AMVS_OK;
 }
 
+// state buffers for n batch slots: the whole group is released before any of it is allocated again (d_aux,
+// allocated last, holds the number of slots)
 int ensure_slots(amvs_ctx *c, int n)
 {
-    if (n <= c->cap_slots) return AMVS_OK;
     const size_t hw = (size_t)c->H * c->W;
+    if (hw * n <= c->d_aux.capacity()) return AMVS_OK;
+    for (auto *b : {&c->d_depth[0], &c->d_cost, &c->d_normal[0], &c->d_depth[1], &c->d_normal[1], &c->d_aux}) b->release();
     for (int i = 0; i < 2; ++i) {
-        if (c->d_depth[i]) (void)hipFree(c->d_depth[i]);
-        if (c->d_cost[i]) (void)hipFree(c->d_cost[i]);
-        if (c->d_normal[i]) (void)hipFree(c->d_normal[i]);
-        c->d_depth[i] = c->d_cost[i] = c->d_normal[i] = nullptr;
+        HIPCHK(c, c->d_depth[i].reserve(hw * n, c->cache));
+        if (i == 0) HIPCHK(c, c->d_cost.reserve(hw * n, c->cache));
+        HIPCHK(c, c->d_normal[i].reserve(hw * n * 3, c->cache));
     }
-    if (c->d_aux) (void)hipFree(c->d_aux);
-    c->d_aux = nullptr;
-    c->cap_slots = 0;
-    for (int i = 0; i < 2; ++i) {
-        HIPCHK(c, hipMalloc(&c->d_depth[i], sizeof(float) * hw * n));
-        if (i == 0) HIPCHK(c, hipMalloc(&c->d_cost[i], sizeof(float) * hw * n));   // cost is updated in place
-        HIPCHK(c, hipMalloc(&c->d_normal[i], sizeof(float) * hw * n * 3));
-    }
-    HIPCHK(c, hipMalloc(&c->d_aux, sizeof(float) * hw * n));
-    c->cap_slots = n;
-    return AMVS_OK;
-}
-
-int ensure_jobs(amvs_ctx *c, int n)
-{
-    if (n <= c->cap_jobs) return AMVS_OK;
-    if (c->d_jobs) (void)hipFree(c->d_jobs);
-    c->d_jobs = nullptr; c->cap_jobs = 0;
-    HIPCHK(c, hipMalloc(&c->d_jobs, sizeof(amvs::Job) * n));
-    c->cap_jobs = n;
+    HIPCHK(c, c->d_aux.reserve(hw * n, c->cache));
     return AMVS_OK;
 }
 
@@ -244,15 +229,15 @@ int ensure_jobs(amvs_ctx *c, int n)
 int ensure_stats(amvs_ctx *c, int patch)
 {
     Stats &s = c->stats[patch];
-    if (!s.mean) {
-        HIPCHK(c, hipMalloc(&s.mean, sizeof(float) * c->stride * c->n_views));
-        HIPCHK(c, hipMalloc(&s.var, sizeof(float) * c->stride * c->n_views));
+    if (s.done.empty()) {
+        HIPCHK(c, s.mean.reserve(c->stride * c->n_views, c->cache));
+        HIPCHK(c, s.var.reserve(c->stride * c->n_views, c->cache));
         s.done.assign(c->n_views, 0);
     }
     for (int v = 0; v < c->n_views; ++v) {
         if (!c->have[v] || s.done[v]) continue;
-        HIPCHK(c, amvs::launch_box_stats(patch, c->d_images, c->stride, c->H, c->W, v, 1, s.mean,
-                                         s.var, c->stream));
+        HIPCHK(c, amvs::launch_box_stats(patch, c->d_images.get(), c->stride, c->H, c->W, v, 1, s.mean.get(),
+                                         s.var.get(), c->stream));
         s.done[v] = 1;
     }
     return AMVS_OK;
@@ -264,14 +249,14 @@ int ensure_fast_stats(amvs_ctx *c, int patch)
 {
     FastStats &s = c->fstats[patch];
     const size_t hw = (size_t)c->H * c->W;
-    if (!s.maps) {
-        HIPCHK(c, hipMalloc(&s.maps, sizeof(float2) * hw * c->n_views));
+    if (s.done.empty()) {
+        HIPCHK(c, s.maps.reserve(hw * c->n_views, c->cache));
         s.done.assign(c->n_views, 0);
     }
     for (int v = 0; v < c->n_views; ++v) {
         if (!c->have[v] || s.done[v]) continue;
-        HIPCHK(c, amvs::launch_fast_stats(patch, c->d_pairs + (long long)v * c->pstride, c->H, c->W,
-                                          s.maps + (size_t)v * hw, c->stream));
+        HIPCHK(c, amvs::launch_fast_stats(patch, c->d_pairs.get() + (long long)v * c->pstride, c->H, c->W,
+                                          s.maps.get() + (size_t)v * hw, c->stream));
         s.done[v] = 1;
     }
     return AMVS_OK;
@@ -287,7 +272,7 @@ int upload_jobs(amvs_ctx *c, int n_ref, const int *ref_ids, const int *src_ids, 
     if (fast_patch > 0) {
         int rc = ensure_fast_stats(c, fast_patch);
         if (rc) return rc;
-        fmaps = c->fstats[fast_patch].maps;
+        fmaps = c->fstats[fast_patch].maps.get();
     }
     std::vector<amvs::Job> jobs(n_ref);
     for (int i = 0; i < n_ref; ++i) {
@@ -301,7 +286,7 @@ int upload_jobs(amvs_ctx *c, int n_ref, const int *ref_ids, const int *src_ids, 
         std::memcpy(j.Rref, c->R[r].data(), 36);
         std::memcpy(j.tref, c->t[r].data(), 12);
         j.ref_img = r;
-        j.ref_pairs = (unsigned long long)(uintptr_t)(c->d_pairs + (long long)r * c->pstride) +
+        j.ref_pairs = (unsigned long long)(uintptr_t)(c->d_pairs.get() + (long long)r * c->pstride) +
                       (unsigned long long)(amvs::pair_map_origin(c->W) * amvs::pair_map_texel_bytes());
         j.ref_stats = fmaps ? (unsigned long long)(uintptr_t)(fmaps + (size_t)r * c->H * c->W) : 0ull;
         j.stream_view = (uint32_t)r;
@@ -311,8 +296,8 @@ int upload_jobs(amvs_ctx *c, int n_ref, const int *ref_ids, const int *src_ids, 
             const int v = src_ids[i * n_src + s];
             if (v < 0 || v >= c->n_views || !c->have[v])
                 return fail(c, AMVS_EINVAL, "source view " + std::to_string(v) + " not uploaded");
-            j.src[s].pairs = (unsigned long long)(uintptr_t)(c->d_pairs + (long long)v * c->pstride);
-            j.src[s].gray = (unsigned long long)(uintptr_t)(c->d_images + (long long)v * c->stride);
+            j.src[s].pairs = (unsigned long long)(uintptr_t)(c->d_pairs.get() + (long long)v * c->pstride);
+            j.src[s].gray = (unsigned long long)(uintptr_t)(c->d_images.get() + (long long)v * c->stride);
             std::memcpy(j.src[s].R, c->R[v].data(), 36);
             std::memcpy(j.src[s].t, c->t[v].data(), 12);
             if (fast_patch > 0 || compose_only) {
@@ -322,9 +307,8 @@ int upload_jobs(amvs_ctx *c, int n_ref, const int *ref_ids, const int *src_ids, 
             }
         }
     }
-    int rc = ensure_jobs(c, n_ref);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_jobs, jobs.data(), sizeof(amvs::Job) * n_ref,
+    HIPCHK(c, c->d_jobs.reserve(n_ref, c->cache));
+    HIPCHK(c, hipMemcpyAsync(c->d_jobs.get(), jobs.data(), sizeof(amvs::Job) * n_ref,
                              hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));   // `jobs` is a stack-lifetime staging buffer
     return AMVS_OK;
@@ -337,7 +321,7 @@ const uint16_t *usable_pairs(const amvs_ctx *c)
     if (c->flags_dirty) {
         // the uploads only queue the losslessness test; its results are read here, once
         std::vector<int> flags(c->n_views, 1);
-        if (hipMemcpyAsync(flags.data(), c->d_flag, sizeof(int) * c->n_views, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+        if (hipMemcpyAsync(flags.data(), c->d_flag.get(), sizeof(int) * c->n_views, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
             hipStreamSynchronize(c->stream) == hipSuccess) {
             for (int v = 0; v < c->n_views; ++v) c->exact8[v] = flags[v] ? 0 : 1;
             c->flags_dirty = false;
@@ -347,7 +331,7 @@ const uint16_t *usable_pairs(const amvs_ctx *c)
     }
     for (int v = 0; v < c->n_views; ++v)
         if (c->have[v] && !c->exact8[v]) return nullptr;
-    return c->d_pairs;
+    return c->d_pairs.get();
 }
 
 // 1 when the sweeps of this call run in the fast arithmetic; fails when fast was asked for but
@@ -457,24 +441,24 @@ amvs::StepArgs base_args(const amvs_ctx *c, int patch, int n_jobs, int TH)
     a.tiles_y = (c->H + TH - 1) / TH;
     a.n_jobs = n_jobs;
     a.img_stride = c->stride;
-    a.images = c->d_images;
+    a.images = c->d_images.get();
     a.pairs = usable_pairs(c);
     a.pair_stride = c->pstride;
-    a.jobs = c->d_jobs;
-    a.aux = c->d_aux;
+    a.jobs = c->d_jobs.get();
+    a.aux = c->d_aux.get();
     return a;
 }
 
-// depth buffer `cur_d` is read and cur_d^1 written on every step; cost lives in d_cost[0] and is
+// depth buffer `cur_d` is read and cur_d^1 written on every step; cost lives in d_cost and is
 // updated in place; normals: both buffers, the sign bit of the state depths names each pixel's
 // current one (StepArgs::nbuf).  `tagged`: d_in is a state map (its depths carry that bit).
 void set_io(amvs::StepArgs &a, const amvs_ctx *c, int cur_d, bool tagged = true)
 {
-    a.d_in = c->d_depth[cur_d];
-    a.d_out = c->d_depth[cur_d ^ 1];
-    a.cost = c->d_cost[0];
-    a.nbuf[0] = c->d_normal[0];
-    a.nbuf[1] = c->d_normal[1];
+    a.d_in = c->d_depth[cur_d].get();
+    a.d_out = c->d_depth[cur_d ^ 1].get();
+    a.cost = c->d_cost.get();
+    a.nbuf[0] = c->d_normal[0].get();
+    a.nbuf[1] = c->d_normal[1].get();
     a.depth_mask = tagged ? 0x7FFFFFFFu : 0xFFFFFFFFu;
 }
 
@@ -616,14 +600,14 @@ int run_fused_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
         a.fast = fast;
         a.band_major = band_major;
         a.paired = paired ? 1 : 0;
-        a.jobs = c->d_jobs + j0;                   // slots stay global: job.slot = index in the batch
+        a.jobs = c->d_jobs.get() + j0;                   // slots stay global: job.slot = index in the batch
         a.depth_min = p->depth_min; a.depth_max = p->depth_max;
         a.seed = seed;
         int cur = cur0;
         // initialisation (mvs_patchmatch.py:268-284); a continuation call resumes the context's state
         if (do_init)
             HIPCHK(c, amvs::launch_init(a.jobs, nj, (long long)hw, seed, p->log_depth_scale, p->log_depth_min,
-                                        c->d_depth[cur], c->d_normal[0], c->d_cost[0], c->stream));
+                                        c->d_depth[cur].get(), c->d_normal[0].get(), c->d_cost.get(), c->stream));
         HIPCHK(c, hipEventRecord(c->ev_groups[3 * g], c->stream));
         if (c->step_timing) HIPCHK(c, hipEventRecord(c->ev_steps[c->n_step_events++], c->stream));
         for (size_t i = 0; i < sched.size(); ++i) {
@@ -645,7 +629,7 @@ int run_fused_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
         if (do_conf) {
             a.mode = amvs::MODE_CONF;
             set_io(a, c, cur);
-            a.aux = conf_dev ? (float *)conf_dev : c->d_aux;
+            a.aux = conf_dev ? (float *)conf_dev : c->d_aux.get();
             HIPCHK(c, amvs::launch_step(p->patch_size, n_src, a, c->stream));
         }
         HIPCHK(c, hipEventRecord(c->ev_groups[3 * g + 2], c->stream));
@@ -676,13 +660,7 @@ int run_split_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
     if (G > MAXG) G = MAXG;
     const int vpl = (n_ref + G - 1) / G;
     G = (n_ref + vpl - 1) / vpl;
-    const size_t need = (size_t)n_ref * n_src * hw;
-    if (need > c->cap_samples) {
-        if (c->d_samples) (void)hipFree(c->d_samples);
-        c->d_samples = nullptr; c->cap_samples = 0;
-        HIPCHK(c, hipMalloc(&c->d_samples, 4 * need));
-        c->cap_samples = need;
-    }
+    HIPCHK(c, c->d_samples.reserve((size_t)n_ref * n_src * hw, c->cache));
     if (c->split_streams.empty()) {
         int lo = 0, hi = 0;
         HIPCHK(c, hipDeviceGetStreamPriorityRange(&lo, &hi));        // lo = least urgent
@@ -720,7 +698,7 @@ int run_split_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
     all.fast = 1;
     all.depth_min = p->depth_min; all.depth_max = p->depth_max;
     all.seed = seed;
-    all.samples = c->d_samples;
+    all.samples = c->d_samples.get();
     all.half = p->patch_size / 2;
     all.s_TH = s_TH;
     all.s_lds = c->split_sample_lds;
@@ -728,7 +706,7 @@ int run_split_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
     all.s_tiles_y = (c->H + s_TH - 1) / s_TH;
     int cur = 0;
     HIPCHK(c, amvs::launch_init(all.jobs, n_ref, (long long)hw, seed, p->log_depth_scale, p->log_depth_min,
-                                c->d_depth[cur], c->d_normal[0], c->d_cost[0], c->stream));
+                                c->d_depth[cur].get(), c->d_normal[0].get(), c->d_cost.get(), c->stream));
     HIPCHK(c, hipEventRecord(c->ev_groups[0], c->stream));
     HIPCHK(c, hipEventRecord(ev_fork, c->stream));
     HIPCHK(c, hipStreamWaitEvent(s_smp, ev_fork, 0));
@@ -739,7 +717,7 @@ int run_split_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
             const int j0 = g * vpl, nj = (n_ref - j0) < vpl ? (n_ref - j0) : vpl;
             amvs::StepArgs a = all;
             a.n_jobs = nj;
-            a.jobs = c->d_jobs + j0;
+            a.jobs = c->d_jobs.get() + j0;
             apply_step(a, st);
             set_io(a, c, cur);
             if (!first) HIPCHK(c, hipStreamWaitEvent(s_smp, ev_windowed[g], 0));
@@ -760,7 +738,7 @@ int run_split_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
     if ((p->flags & AMVS_PM_NO_CONFIDENCE) == 0) {
         all.mode = amvs::MODE_CONF;
         set_io(all, c, cur);
-        all.aux = conf_dev ? (float *)conf_dev : c->d_aux;
+        all.aux = conf_dev ? (float *)conf_dev : c->d_aux.get();
         HIPCHK(c, amvs::launch_step(p->patch_size, n_src, all, c->stream));
     }
     HIPCHK(c, hipEventRecord(c->ev_groups[2], c->stream));
@@ -798,21 +776,61 @@ int one_step_begin(amvs_ctx *c, int ref, const int *src_ids, int n_src, int patc
 
 int upload_state(amvs_ctx *c, size_t hw, const float *depth, const float *normal, const float *cost)
 {
-    if (depth) HIPCHK(c, hipMemcpyAsync(c->d_depth[0], depth, 4 * hw, hipMemcpyHostToDevice, c->stream));
-    if (normal) HIPCHK(c, hipMemcpyAsync(c->d_normal[0], normal, 12 * hw, hipMemcpyHostToDevice, c->stream));
-    if (cost) HIPCHK(c, hipMemcpyAsync(c->d_cost[0], cost, 4 * hw, hipMemcpyHostToDevice, c->stream));
+    if (depth) HIPCHK(c, hipMemcpyAsync(c->d_depth[0].get(), depth, 4 * hw, hipMemcpyHostToDevice, c->stream));
+    if (normal) HIPCHK(c, hipMemcpyAsync(c->d_normal[0].get(), normal, 12 * hw, hipMemcpyHostToDevice, c->stream));
+    if (cost) HIPCHK(c, hipMemcpyAsync(c->d_cost.get(), cost, 4 * hw, hipMemcpyHostToDevice, c->stream));
     return AMVS_OK;
 }
 
 // state of slot 0 after a single step (tagged depths in d_depth[dbuf]) -> plain host arrays
 int download_state(amvs_ctx *c, size_t hw, int dbuf, float *depth, float *normal, float *cost)
 {
-    HIPCHK(c, amvs::launch_resolve_state(c->d_jobs, 1, (long long)hw, c->d_depth[dbuf], c->d_normal[0], c->d_normal[1],
+    HIPCHK(c, amvs::launch_resolve_state(c->d_jobs.get(), 1, (long long)hw, c->d_depth[dbuf].get(), c->d_normal[0].get(), c->d_normal[1].get(),
                                          nullptr, nullptr, 0, c->stream));
-    HIPCHK(c, hipMemcpyAsync(depth, c->d_depth[dbuf], 4 * hw, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(normal, c->d_normal[0], 12 * hw, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cost, c->d_cost[0], 4 * hw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(depth, c->d_depth[dbuf].get(), 4 * hw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(normal, c->d_normal[0].get(), 12 * hw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cost, c->d_cost.get(), 4 * hw, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return AMVS_OK;
+}
+
+// every view id names a view with a resident colour image
+int check_colour_views(amvs_ctx *c, int n, const int *view_ids)
+{
+    for (int j = 0; j < n; ++j)
+        if (view_ids[j] < 0 || view_ids[j] >= c->n_views || !c->have_bgr[view_ids[j]])
+            return fail(c, AMVS_EINVAL, "view " + std::to_string(view_ids[j]) + " has no resident colour image (amvs_set_view_bgr8)");
+    return AMVS_OK;
+}
+
+// the resident colour images of `view_ids` in map order (device-to-device; the images of a scene are rarely in that
+// order already)
+int gather_colours(amvs_ctx *c, int n, const int *view_ids, amvs::DeviceBuffer<unsigned char> &out)
+{
+    const size_t bytes = 3 * (size_t)c->H * c->W;
+    HIPCHK(c, out.reserve(bytes * n, c->cache));
+    for (int j = 0; j < n; ++j)
+        HIPCHK(c, hipMemcpyAsync(out.get() + bytes * j, c->d_bgr.get() + bytes * view_ids[j], bytes, hipMemcpyDeviceToDevice,
+                                 c->stream));
+    return AMVS_OK;
+}
+
+// n elements of host memory into `out` (a post-step's inputs)
+template <class T>
+int upload(amvs_ctx *c, const T *host, size_t n, amvs::DeviceBuffer<T> &out)
+{
+    HIPCHK(c, out.reserve(n, c->cache));
+    HIPCHK(c, hipMemcpyAsync(out.get(), host, sizeof(T) * n, hipMemcpyHostToDevice, c->stream));
+    return AMVS_OK;
+}
+
+// host maps of a post-step (n floats each) staged on the device: `depth` / `conf` then point into the copies
+int stage_maps(amvs_ctx *c, size_t n, const float *&depth, const float *&conf, amvs::DeviceBuffer<float> (&copy)[2])
+{
+    int rc;
+    if ((rc = upload(c, depth, n, copy[0])) || (rc = upload(c, conf, n, copy[1]))) return rc;
+    depth = copy[0].get();
+    conf = copy[1].get();
     return AMVS_OK;
 }
 
@@ -849,7 +867,7 @@ int amvs_create(int device_id, int H, int W, int n_views, const float K[9], cons
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, AMVS_EHIP, "no HIP device available (this backend has no CPU fallback)");
     if (device_id < 0 || device_id >= ndev) return fail(nullptr, AMVS_EINVAL, "device_id out of range");
-    amvs_ctx *c = new amvs_ctx();
+    std::unique_ptr<amvs_ctx, int (*)(amvs_ctx *)> c(new amvs_ctx(), amvs_destroy);
     c->device = device_id; c->H = H; c->W = W; c->n_views = n_views;
     // rows of an image are W floats; one extra 256-byte line of tail padding per image
     c->stride = (((long long)H * W + 63) / 64) * 64 + 64;
@@ -859,34 +877,23 @@ int amvs_create(int device_id, int H, int W, int n_views, const float K[9], cons
     c->exact8.assign(n_views, 0);
     c->have_bgr.assign(n_views, 0);
     c->pstride = ((amvs::pair_map_elems(H, W) + 63) / 64) * 64 + 64;
-    auto bail = [&](const char *what, hipError_t e) {
-        std::string m = std::string(what) + ": " + hipGetErrorString(e);
-        amvs_destroy(c);
-        return fail(nullptr, AMVS_EHIP, m);
-    };
-    hipError_t e;
-    if ((e = hipSetDevice(device_id)) != hipSuccess) return bail("hipSetDevice", e);
+    // (a failure below destroys the partial context: amvs_destroy; its error goes to amvs_last_error(NULL))
+    HIPCHK(nullptr, hipSetDevice(device_id));
     {
         int ncu = 0;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && ncu > 0)
             c->n_cu = ncu;
     }
-    if ((e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess)
-        return bail("hipStreamCreate", e);
+    HIPCHK(nullptr, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
-    for (auto &ev : c->ev)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipMalloc(&c->d_images, sizeof(float) * c->stride * n_views)) != hipSuccess)
-        return bail("hipMalloc(images)", e);
-    if ((e = hipMemsetAsync(c->d_images, 0, sizeof(float) * c->stride * n_views, c->stream)) != hipSuccess)
-        return bail("hipMemset(images)", e);
-    if ((e = hipMalloc(&c->d_pairs, sizeof(uint16_t) * c->pstride * n_views)) != hipSuccess)
-        return bail("hipMalloc(pairs)", e);
-    if ((e = hipMemsetAsync(c->d_pairs, 0, sizeof(uint16_t) * c->pstride * n_views, c->stream)) != hipSuccess)
-        return bail("hipMemset(pairs)", e);
-    if ((e = hipMalloc(&c->d_flag, sizeof(int) * n_views)) != hipSuccess) return bail("hipMalloc(flag)", e);
-    if ((e = hipMemsetAsync(c->d_flag, 0, sizeof(int) * n_views, c->stream)) != hipSuccess) return bail("hipMemset(flag)", e);
-    *out = c;
+    for (auto &ev : c->ev) HIPCHK(nullptr, hipEventCreate(&ev));
+    HIPCHK(nullptr, c->d_images.reserve(c->stride * n_views, c->cache));
+    HIPCHK(nullptr, hipMemsetAsync(c->d_images.get(), 0, sizeof(float) * c->stride * n_views, c->stream));
+    HIPCHK(nullptr, c->d_pairs.reserve(c->pstride * n_views, c->cache));
+    HIPCHK(nullptr, hipMemsetAsync(c->d_pairs.get(), 0, sizeof(uint16_t) * c->pstride * n_views, c->stream));
+    HIPCHK(nullptr, c->d_flag.reserve(n_views, c->cache));
+    HIPCHK(nullptr, hipMemsetAsync(c->d_flag.get(), 0, sizeof(int) * n_views, c->stream));
+    *out = c.release();
     return AMVS_OK;
 }
 
@@ -896,44 +903,13 @@ int amvs_destroy(amvs_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)amvs_comm_destroy(c);
-    for (int i = 0; i < 2; ++i) {
-        if (c->d_depth[i]) (void)hipFree(c->d_depth[i]);
-        if (c->d_cost[i]) (void)hipFree(c->d_cost[i]);
-        if (c->d_normal[i]) (void)hipFree(c->d_normal[i]);
-    }
-    if (c->d_aux) (void)hipFree(c->d_aux);
-    if (c->d_jobs) (void)hipFree(c->d_jobs);
-    if (c->d_planes) (void)hipFree(c->d_planes);
-    if (c->d_keys) (void)hipFree(c->d_keys);
-    if (c->d_xcand_d) (void)hipFree(c->d_xcand_d);
-    if (c->d_xcand_n) (void)hipFree(c->d_xcand_n);
-    if (c->d_xsrc) (void)hipFree(c->d_xsrc);
-    if (c->d_samples) (void)hipFree(c->d_samples);
     for (auto &st : c->split_streams) (void)hipStreamDestroy(st);
     for (auto &ev : c->split_events) (void)hipEventDestroy(ev);
-    if (c->d_sweep_depth) (void)hipFree(c->d_sweep_depth);
-    if (c->d_sweep_conf) (void)hipFree(c->d_sweep_conf);
-    if (c->d_cloud_pts) (void)hipFree(c->d_cloud_pts);
-    if (c->d_cloud_rgb) (void)hipFree(c->d_cloud_rgb);
-    amvs::tsdf_state_free(c->tsdf);
-    amvs::pool_trim();                  // the post-steps' cached scratch blocks (amvs_pool.hip)
-    if (c->d_images) (void)hipFree(c->d_images);
-    if (c->d_pairs) (void)hipFree(c->d_pairs);
-    if (c->d_flag) (void)hipFree(c->d_flag);
-    if (c->d_bgr) (void)hipFree(c->d_bgr);
-    if (c->d_prep_src) (void)hipFree(c->d_prep_src);
-    if (c->d_prep_tab) (void)hipFree(c->d_prep_tab);
-    for (auto &kv : c->stats) {
-        if (kv.second.mean) (void)hipFree(kv.second.mean);
-        if (kv.second.var) (void)hipFree(kv.second.var);
-    }
-    for (auto &kv : c->fstats)
-        if (kv.second.maps) (void)hipFree(kv.second.maps);
     for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->ev_groups) (void)hipEventDestroy(ev);
     for (auto &ev : c->ev_steps) (void)hipEventDestroy(ev);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                           // the device buffers and the scratch cache free themselves
     return AMVS_OK;
 }
 
@@ -954,6 +930,24 @@ int amvs_sync(amvs_ctx *c)
     return checked(c, AMVS_OK);
 }
 
+// The end of every upload of a view's gray image (queued on the stream): its packed 8-bit map and losslessness test
+// (read back lazily, usable_pairs), its pose; its window statistics are stale.  `sync`: host buffers of the upload
+// are the caller's again on return (a device buffer is only ordered on the stream).
+static int view_uploaded(amvs_ctx *c, int view, const float R[9], const float t[3], bool sync)
+{
+    HIPCHK(c, hipMemsetAsync(c->d_flag.get() + view, 0, sizeof(int), c->stream));
+    HIPCHK(c, amvs::launch_pack_pairs(c->d_images.get() + view * c->stride, c->H, c->W,
+                                      c->d_pairs.get() + view * c->pstride, c->d_flag.get() + view, c->stream));
+    c->flags_dirty = true;
+    if (sync) HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(c->R[view].data(), R, 36);
+    std::memcpy(c->t[view].data(), t, 12);
+    c->have[view] = 1;
+    for (auto &kv : c->stats) if (!kv.second.done.empty()) kv.second.done[view] = 0;
+    for (auto &kv : c->fstats) if (!kv.second.done.empty()) kv.second.done[view] = 0;
+    return AMVS_OK;
+}
+
 static int set_view_common(amvs_ctx *c, int view, const void *gray, const float R[9], const float t[3],
                            hipMemcpyKind kind)
 {
@@ -962,22 +956,11 @@ static int set_view_common(amvs_ctx *c, int view, const void *gray, const float 
     if (view < 0 || view >= c->n_views || !gray || !R || !t) return fail(c, AMVS_EINVAL, "bad view argument");
     int rc = bind_device(c);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_images + view * c->stride, gray, sizeof(float) * c->H * c->W, kind,
+    HIPCHK(c, hipMemcpyAsync(c->d_images.get() + view * c->stride, gray, sizeof(float) * c->H * c->W, kind,
                              c->stream));
-    // packed 8-bit map + losslessness test of this view (read back lazily, usable_pairs)
-    HIPCHK(c, hipMemsetAsync(c->d_flag + view, 0, sizeof(int), c->stream));
-    HIPCHK(c, amvs::launch_pack_pairs(c->d_images + view * c->stride, c->H, c->W,
-                                      c->d_pairs + view * c->pstride, c->d_flag + view, c->stream));
-    c->flags_dirty = true;
     c->have_bgr[view] = 0;
-    // a host buffer is the caller's again on return; a device buffer is only ordered on the stream
-    if (kind == hipMemcpyHostToDevice) HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(c->R[view].data(), R, 36);
-    std::memcpy(c->t[view].data(), t, 12);
-    c->have[view] = 1;
-    for (auto &kv : c->stats) if (!kv.second.done.empty()) kv.second.done[view] = 0;
-    for (auto &kv : c->fstats) if (!kv.second.done.empty()) kv.second.done[view] = 0;
-    return AMVS_OK;
+    if ((rc = view_uploaded(c, view, R, t, kind == hipMemcpyHostToDevice))) return rc;
+    return checked(c, AMVS_OK);
 }
 
 // OpenCV's linear-resize tables for one axis (resize.cpp, resizeGeneric_ setup, ksize = 2): float32
@@ -1016,50 +999,26 @@ int amvs_set_view_bgr8(amvs_ctx *c, int view, const uint8_t *bgr_host, int src_h
     resize_axis_tables(c->W, src_w, xofs, ialpha, true);
     resize_axis_tables(c->H, src_h, yofs, ibeta, false);
     // the prepared colour image stays on the device (the fusion reads it there: amvs_fuse_filter_views)
-    if (!c->d_bgr) HIPCHK(c, hipMalloc(&c->d_bgr, 3 * n_dst * (size_t)c->n_views));
-    unsigned char *d_scaled = c->d_bgr + 3 * n_dst * (size_t)view;
+    HIPCHK(c, c->d_bgr.reserve(3 * n_dst * (size_t)c->n_views, c->cache));
+    unsigned char *d_scaled = c->d_bgr.get() + 3 * n_dst * (size_t)view;
+    // tables: xofs [W], yofs [H] ints, then ialpha [2W], ibeta [2H] shorts
     const size_t tab_ints = (size_t)c->W + c->H, tab_shorts = 2 * ((size_t)c->W + c->H);
-    hipError_t e = hipSuccess;
-    if (3 * n_src > c->cap_prep_src) {
-        if (c->d_prep_src) (void)hipFree(c->d_prep_src);
-        c->d_prep_src = nullptr; c->cap_prep_src = 0;
-        e = hipMalloc(&c->d_prep_src, 3 * n_src);
-        if (e == hipSuccess) c->cap_prep_src = 3 * n_src;
-    }
-    if (e == hipSuccess && 4 * tab_ints + 2 * tab_shorts > c->cap_prep_tab) {
-        if (c->d_prep_tab) (void)hipFree(c->d_prep_tab);
-        c->d_prep_tab = nullptr; c->cap_prep_tab = 0;
-        e = hipMalloc(&c->d_prep_tab, 4 * tab_ints + 2 * tab_shorts);
-        if (e == hipSuccess) c->cap_prep_tab = 4 * tab_ints + 2 * tab_shorts;
-    }
-    unsigned char *d_src = c->d_prep_src;
-    int *d_tab = c->d_prep_tab;
-    int *d_xofs = d_tab, *d_yofs = d_tab ? d_tab + c->W : nullptr;
-    short *d_ialpha = d_tab ? (short *)(d_tab + tab_ints) : nullptr, *d_ibeta = d_ialpha ? d_ialpha + 2 * c->W : nullptr;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_src, bgr_host, 3 * n_src, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_xofs, xofs.data(), 4 * (size_t)c->W, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_yofs, yofs.data(), 4 * (size_t)c->H, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ialpha, ialpha.data(), 4 * (size_t)c->W, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ibeta, ibeta.data(), 4 * (size_t)c->H, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = amvs::launch_prep_bgr8(d_src, src_h, src_w, c->H, c->W, d_xofs, d_ialpha, d_yofs, d_ibeta, d_scaled,
-                                   c->d_images + view * c->stride, c->stream);
-    if (e == hipSuccess && scaled_bgr_out)
-        e = hipMemcpyAsync(scaled_bgr_out, d_scaled, 3 * n_dst, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_flag + view, 0, sizeof(int), c->stream);
-    if (e == hipSuccess)
-        e = amvs::launch_pack_pairs(c->d_images + view * c->stride, c->H, c->W, c->d_pairs + view * c->pstride,
-                                    c->d_flag + view, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("set_view_bgr8: ") + hipGetErrorString(e));
-    c->flags_dirty = true;
+    HIPCHK(c, c->d_prep_src.reserve(3 * n_src, c->cache));
+    HIPCHK(c, c->d_prep_tab.reserve(tab_ints + tab_shorts / 2, c->cache));
+    unsigned char *d_src = c->d_prep_src.get();
+    int *d_xofs = c->d_prep_tab.get(), *d_yofs = d_xofs + c->W;
+    short *d_ialpha = (short *)(d_xofs + tab_ints), *d_ibeta = d_ialpha + 2 * c->W;
+    HIPCHK(c, hipMemcpyAsync(d_src, bgr_host, 3 * n_src, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_xofs, xofs.data(), 4 * (size_t)c->W, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_yofs, yofs.data(), 4 * (size_t)c->H, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_ialpha, ialpha.data(), 4 * (size_t)c->W, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_ibeta, ibeta.data(), 4 * (size_t)c->H, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, amvs::launch_prep_bgr8(d_src, src_h, src_w, c->H, c->W, d_xofs, d_ialpha, d_yofs, d_ibeta, d_scaled,
+                                     c->d_images.get() + view * c->stride, c->stream));
+    if (scaled_bgr_out) HIPCHK(c, hipMemcpyAsync(scaled_bgr_out, d_scaled, 3 * n_dst, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = view_uploaded(c, view, R, t, true))) return rc;
     c->have_bgr[view] = 1;
-    std::memcpy(c->R[view].data(), R, 36);
-    std::memcpy(c->t[view].data(), t, 12);
-    c->have[view] = 1;
-    for (auto &kv : c->stats) if (!kv.second.done.empty()) kv.second.done[view] = 0;
-    for (auto &kv : c->fstats) if (!kv.second.done.empty()) kv.second.done[view] = 0;
-    return AMVS_OK;
+    return checked(c, AMVS_OK);
 }
 
 int amvs_set_view_colors(amvs_ctx *c, int view, const uint8_t *bgr_host)
@@ -1069,11 +1028,11 @@ int amvs_set_view_colors(amvs_ctx *c, int view, const uint8_t *bgr_host)
     int rc = bind_device(c);
     if (rc) return rc;
     const size_t n = (size_t)c->H * c->W;
-    if (!c->d_bgr) HIPCHK(c, hipMalloc(&c->d_bgr, 3 * n * (size_t)c->n_views));
-    HIPCHK(c, hipMemcpyAsync(c->d_bgr + 3 * n * (size_t)view, bgr_host, 3 * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, c->d_bgr.reserve(3 * n * (size_t)c->n_views, c->cache));
+    HIPCHK(c, hipMemcpyAsync(c->d_bgr.get() + 3 * n * (size_t)view, bgr_host, 3 * n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_bgr[view] = 1;
-    return AMVS_OK;
+    return checked(c, AMVS_OK);
 }
 
 int amvs_set_view(amvs_ctx *c, int view, const float *gray_host, const float R[9], const float t[3])
@@ -1161,7 +1120,7 @@ int amvs_patchmatch_device(amvs_ctx *c, int n_ref, const int *ref_ids, const int
     if (rc) return rc;
     const size_t hw = (size_t)c->H * c->W;
     // untagged depths and the current normal of every pixel straight into the caller's arrays
-    HIPCHK(c, amvs::launch_resolve_state(c->d_jobs, n_ref, (long long)hw, c->d_depth[cur], c->d_normal[0], c->d_normal[1],
+    HIPCHK(c, amvs::launch_resolve_state(c->d_jobs.get(), n_ref, (long long)hw, c->d_depth[cur].get(), c->d_normal[0].get(), c->d_normal[1].get(),
                                          (float *)depth_dev, (float *)normal_dev, 0, c->stream));
     return AMVS_OK;
 }
@@ -1178,12 +1137,12 @@ int amvs_patchmatch(amvs_ctx *c, int n_ref, const int *ref_ids, const int *src_i
     int rc = patchmatch_core(c, n_ref, ref_ids, src_ids, n_src, p, seed, nullptr, &cur);
     if (rc) return rc;
     const size_t hw = (size_t)c->H * c->W;
-    HIPCHK(c, amvs::launch_resolve_state(c->d_jobs, n_ref, (long long)hw, c->d_depth[cur], c->d_normal[0], c->d_normal[1],
+    HIPCHK(c, amvs::launch_resolve_state(c->d_jobs.get(), n_ref, (long long)hw, c->d_depth[cur].get(), c->d_normal[0].get(), c->d_normal[1].get(),
                                          nullptr, nullptr, 0, c->stream));
-    HIPCHK(c, hipMemcpyAsync(depth_out, c->d_depth[cur], 4 * hw * n_ref, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(normal_out, c->d_normal[0], 12 * hw * n_ref, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(depth_out, c->d_depth[cur].get(), 4 * hw * n_ref, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(normal_out, c->d_normal[0].get(), 12 * hw * n_ref, hipMemcpyDeviceToHost, c->stream));
     if ((p->flags & AMVS_PM_NO_CONFIDENCE) == 0)
-        HIPCHK(c, hipMemcpyAsync(conf_out, c->d_aux, 4 * hw * n_ref, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(conf_out, c->d_aux.get(), 4 * hw * n_ref, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     resolve_timing(c);
     return checked(c, AMVS_OK);
@@ -1296,21 +1255,10 @@ int amvs_plane_sweep_device(amvs_ctx *c, int n_ref, const int *ref_ids, const in
     int fast = 0;
     if ((rc = resolve_fast(c, AMVS_MODE_DEFAULT, &fast))) return rc;
     if ((rc = upload_jobs(c, n_ref, ref_ids, nbr_ids, n_nbr, fast ? patch_size : 0))) return rc;
-    if (D > c->cap_planes) {
-        if (c->d_planes) (void)hipFree(c->d_planes);
-        c->d_planes = nullptr; c->cap_planes = 0;
-        HIPCHK(c, hipMalloc(&c->d_planes, sizeof(float) * D));
-        c->cap_planes = D;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_planes, depths, sizeof(float) * D, hipMemcpyHostToDevice, c->stream));
+    if ((rc = upload(c, depths, D, c->d_planes))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const size_t hw = (size_t)c->H * c->W;
-    if (n_ref > c->cap_keys) {
-        if (c->d_keys) (void)hipFree(c->d_keys);
-        c->d_keys = nullptr; c->cap_keys = 0;
-        HIPCHK(c, hipMalloc(&c->d_keys, sizeof(unsigned) * hw * n_ref));
-        c->cap_keys = n_ref;
-    }
+    HIPCHK(c, c->d_keys.reserve(hw * n_ref, c->cache));
     amvs::SweepArgs a{};
     a.H = c->H; a.W = c->W;
     // tall strips (little halo re-sampling); the planes are chunked so that the launch still has
@@ -1346,27 +1294,27 @@ int amvs_plane_sweep_device(amvs_ctx *c, int n_ref, const int *ref_ids, const in
     if (!a.key8) shape(AMVS_SWEEP_MAX_TH);
     c->last_tile_rows = a.TH;
     a.img_stride = c->stride;
-    a.images = c->d_images;
+    a.images = c->d_images.get();
     a.pairs = usable_pairs(c);
     a.pair_stride = c->pstride;
     a.fast = fast;
-    a.depths = c->d_planes;
+    a.depths = c->d_planes.get();
     a.thresh = thresh;
     if (!fast && amvs::patch_compiled(patch_size)) {
         // the exact sweep loads the reference views' window statistics (plane-invariant) from the resident maps
         if ((rc = ensure_stats(c, patch_size))) return rc;
-        a.ref_mean = c->stats[patch_size].mean;
-        a.ref_var = c->stats[patch_size].var;
+        a.ref_mean = c->stats[patch_size].mean.get();
+        a.ref_var = c->stats[patch_size].var.get();
     }
     a.depth_out = (float *)depth_dev; a.conf_out = (float *)conf_dev;
-    a.keys = c->d_keys;
-    a.jobs = c->d_jobs;
+    a.keys = c->d_keys.get();
+    a.jobs = c->d_jobs.get();
     resolve_timing(c);
     c->timing = amvs_timing{};
     c->timing_groups = 0;
     c->n_step_events = 0;
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_keys, 0, sizeof(unsigned) * hw * n_ref, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_keys.get(), 0, sizeof(unsigned) * hw * n_ref, c->stream));
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     HIPCHK(c, amvs::launch_sweep(patch_size, n_nbr, a, c->stream));
     HIPCHK(c, amvs::launch_sweep_finish(a, c->stream));
@@ -1389,10 +1337,10 @@ int amvs_plane_sweep(amvs_ctx *c, int ref, const int *nbr_ids, int n_nbr, const 
     c->pm_resumable = false;                    // the maps below land in slot 0 of the PatchMatch state
     const size_t hw = (size_t)c->H * c->W;
     rc = amvs_plane_sweep_device(c, 1, &ref, nbr_ids, n_nbr, depths, D, patch_size, thresh,
-                                 c->d_depth[0], c->d_aux);
+                                 c->d_depth[0].get(), c->d_aux.get());
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(depth_out, c->d_depth[0], 4 * hw, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(conf_out, c->d_aux, 4 * hw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(depth_out, c->d_depth[0].get(), 4 * hw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(conf_out, c->d_aux.get(), 4 * hw, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     resolve_timing(c);
     return checked(c, AMVS_OK);
@@ -1406,20 +1354,14 @@ int amvs_plane_sweep_batch(amvs_ctx *c, int n_ref, const int *ref_ids, const int
     int rc = bind_device(c);
     if (rc) return rc;
     const size_t hw = (size_t)c->H * c->W;
-    if (n_ref > c->cap_sweep) {
-        if (c->d_sweep_depth) (void)hipFree(c->d_sweep_depth);
-        if (c->d_sweep_conf) (void)hipFree(c->d_sweep_conf);
-        c->d_sweep_depth = c->d_sweep_conf = nullptr; c->cap_sweep = 0;
-        HIPCHK(c, hipMalloc(&c->d_sweep_depth, 4 * hw * n_ref));
-        HIPCHK(c, hipMalloc(&c->d_sweep_conf, 4 * hw * n_ref));
-        c->cap_sweep = n_ref;
-    }
     c->n_sweep = 0;
+    HIPCHK(c, c->d_sweep_depth.reserve(hw * n_ref, c->cache));
+    HIPCHK(c, c->d_sweep_conf.reserve(hw * n_ref, c->cache));
     rc = amvs_plane_sweep_device(c, n_ref, ref_ids, nbr_ids, n_nbr, depths, D, patch_size, thresh,
-                                 c->d_sweep_depth, c->d_sweep_conf);
+                                 c->d_sweep_depth.get(), c->d_sweep_conf.get());
     if (rc) return rc;
     c->n_sweep = n_ref;
-    return AMVS_OK;
+    return checked(c, AMVS_OK);
 }
 
 int amvs_fetch_sweep_maps(amvs_ctx *c, int first, int count, float *depth_out, float *conf_out)
@@ -1430,11 +1372,11 @@ int amvs_fetch_sweep_maps(amvs_ctx *c, int first, int count, float *depth_out, f
     int rc = bind_device(c);
     if (rc) return rc;
     const size_t hw = (size_t)c->H * c->W;
-    HIPCHK(c, hipMemcpyAsync(depth_out, c->d_sweep_depth + first * hw, 4 * hw * count, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(conf_out, c->d_sweep_conf + first * hw, 4 * hw * count, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(depth_out, c->d_sweep_depth.get() + first * hw, 4 * hw * count, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(conf_out, c->d_sweep_conf.get() + first * hw, 4 * hw * count, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     resolve_timing(c);
-    return AMVS_OK;
+    return checked(c, AMVS_OK);
 }
 
 int amvs_stereo_backproject(amvs_ctx *c, int n_maps, const void *depth, const void *conf, int maps_where,
@@ -1449,35 +1391,22 @@ int amvs_stereo_backproject(amvs_ctx *c, int n_maps, const void *depth, const vo
     int rc = bind_device(c);
     if (rc) return rc;
     const size_t hw = (size_t)c->H * c->W, n = hw * (size_t)n_maps;
-    if (c->d_cloud_pts) (void)hipFree(c->d_cloud_pts);
-    if (c->d_cloud_rgb) (void)hipFree(c->d_cloud_rgb);
-    c->d_cloud_pts = nullptr; c->d_cloud_rgb = nullptr; c->cloud_n = 0;
-    float *dd = nullptr, *dc = nullptr;
-    unsigned char *dbgr = nullptr;
-    hipError_t e = hipMalloc(&dbgr, 3 * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(dbgr, colors_bgr_host, 3 * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && maps_where == 0) {
-        e = hipMalloc(&dd, 4 * n);
-        if (e == hipSuccess) e = hipMalloc(&dc, 4 * n);
-        if (e == hipSuccess) e = hipMemcpyAsync(dd, depth, 4 * n, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dc, conf, 4 * n, hipMemcpyHostToDevice, c->stream);
-    } else if (e == hipSuccess) {
-        dd = maps_where == 2 ? c->d_sweep_depth : (float *)depth;
-        dc = maps_where == 2 ? c->d_sweep_conf : (float *)conf;
-    }
+    c->cloud = Cloud{};
+    amvs::DeviceBuffer<unsigned char> dbgr;
+    amvs::DeviceBuffer<float> copy[2];
+    const float *dd = maps_where == 2 ? c->d_sweep_depth.get() : (const float *)depth;
+    const float *dc = maps_where == 2 ? c->d_sweep_conf.get() : (const float *)conf;
+    if ((rc = upload(c, colors_bgr_host, 3 * n, dbgr))) return rc;
+    if (maps_where == 0 && (rc = stage_maps(c, n, dd, dc, copy))) return rc;
     long long tot = 0;
     std::vector<long long> per(n_maps, 0);
-    if (e == hipSuccess)
-        e = amvs::stereo_backproject(dd, dc, dbgr, n_maps, c->H, c->W, K_inv, poses, min_confidence, &c->d_cloud_pts,
-                                     &c->d_cloud_rgb, &tot, per.data(), c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    if (maps_where == 0) { if (dd) (void)hipFree(dd); if (dc) (void)hipFree(dc); }
-    if (dbgr) (void)hipFree(dbgr);
+    const hipError_t e = amvs::stereo_backproject(dd, dc, dbgr.get(), n_maps, c->H, c->W, K_inv, poses, min_confidence, c->cache,
+                                                  c->cloud.pts, c->cloud.rgb, &tot, per.data(), c->stream);
     if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("stereo_backproject: ") + hipGetErrorString(e));
-    c->cloud_n = tot;
+    c->cloud.n = tot;
     *total = tot;
     if (per_map_counts) for (int j = 0; j < n_maps; ++j) per_map_counts[j] = per[j];
-    return AMVS_OK;
+    return checked(c, AMVS_OK);
 }
 
 int amvs_stereo_backproject_views(amvs_ctx *c, int n_maps, const int *view_ids, const double K_inv[9], const double *poses,
@@ -1486,44 +1415,34 @@ int amvs_stereo_backproject_views(amvs_ctx *c, int n_maps, const int *view_ids, 
     if (!c) return AMVS_EINVAL;
     if (n_maps < 1 || !view_ids || !K_inv || !poses || !total) return fail(c, AMVS_EINVAL, "bad argument");
     if (n_maps != c->n_sweep) return fail(c, AMVS_EINVAL, "n_maps differs from the resident plane-sweep batch");
-    for (int j = 0; j < n_maps; ++j)
-        if (view_ids[j] < 0 || view_ids[j] >= c->n_views || !c->have_bgr[view_ids[j]])
-            return fail(c, AMVS_EINVAL, "view " + std::to_string(view_ids[j]) + " has no resident colour image (amvs_set_view_bgr8)");
-    int rc = bind_device(c);
+    int rc = check_colour_views(c, n_maps, view_ids);
     if (rc) return rc;
-    const size_t hw = (size_t)c->H * c->W;
-    if (c->d_cloud_pts) (void)hipFree(c->d_cloud_pts);
-    if (c->d_cloud_rgb) (void)hipFree(c->d_cloud_rgb);
-    c->d_cloud_pts = nullptr; c->d_cloud_rgb = nullptr; c->cloud_n = 0;
-    unsigned char *dbgr = nullptr;
-    hipError_t e = hipMalloc(&dbgr, 3 * hw * (size_t)n_maps);
-    for (int j = 0; j < n_maps && e == hipSuccess; ++j)
-        e = hipMemcpyAsync(dbgr + 3 * hw * (size_t)j, c->d_bgr + 3 * hw * (size_t)view_ids[j], 3 * hw,
-                           hipMemcpyDeviceToDevice, c->stream);
+    if ((rc = bind_device(c))) return rc;
+    c->cloud = Cloud{};
+    amvs::DeviceBuffer<unsigned char> dbgr;
+    if ((rc = gather_colours(c, n_maps, view_ids, dbgr))) return rc;
     long long tot = 0;
     std::vector<long long> per(n_maps, 0);
-    if (e == hipSuccess)
-        e = amvs::stereo_backproject(c->d_sweep_depth, c->d_sweep_conf, dbgr, n_maps, c->H, c->W, K_inv, poses, min_confidence,
-                                     &c->d_cloud_pts, &c->d_cloud_rgb, &tot, per.data(), c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    if (dbgr) (void)hipFree(dbgr);
+    const hipError_t e = amvs::stereo_backproject(c->d_sweep_depth.get(), c->d_sweep_conf.get(), dbgr.get(), n_maps, c->H, c->W,
+                                                  K_inv, poses, min_confidence, c->cache, c->cloud.pts, c->cloud.rgb, &tot,
+                                                  per.data(), c->stream);
     if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("stereo_backproject_views: ") + hipGetErrorString(e));
-    c->cloud_n = tot;
+    c->cloud.n = tot;
     *total = tot;
     if (per_map_counts) for (int j = 0; j < n_maps; ++j) per_map_counts[j] = per[j];
-    return AMVS_OK;
+    return checked(c, AMVS_OK);
 }
 
 int amvs_cloud_knn_mean_distance(amvs_ctx *c, int k, double *mean_out)
 {
     if (!c) return AMVS_EINVAL;
-    if (!mean_out || c->cloud_n < 1) return fail(c, AMVS_EINVAL, "no resident cloud / NULL output");
+    if (!mean_out || c->cloud.n < 1) return fail(c, AMVS_EINVAL, "no resident cloud / NULL output");
     if (!amvs::knn_supported(k)) return fail(c, AMVS_EUNSUPPORTED, "k not compiled in (8, 10, 16, 20, 32)");
-    if (c->cloud_n < k) return fail(c, AMVS_EINVAL, "fewer points than neighbours");
+    if (c->cloud.n < k) return fail(c, AMVS_EINVAL, "fewer points than neighbours");
     int rc = bind_device(c);
     if (rc) return rc;
-    HIPCHK(c, amvs::knn_mean_distance(c->d_cloud_pts, c->cloud_n, k, mean_out, c->stream, true));
-    return AMVS_OK;
+    HIPCHK(c, amvs::knn_mean_distance(c->cloud.pts.get(), c->cloud.n, k, mean_out, c->cache, c->stream, true));
+    return checked(c, AMVS_OK);
 }
 
 int amvs_cloud_voxel_downsample(amvs_ctx *c, const uint8_t *keep_mask, double voxel_size, int64_t *count)
@@ -1532,39 +1451,31 @@ int amvs_cloud_voxel_downsample(amvs_ctx *c, const uint8_t *keep_mask, double vo
     if (!count || !(voxel_size > 0.0)) return fail(c, AMVS_EINVAL, "bad argument");
     int rc = bind_device(c);
     if (rc) return rc;
-    double *p2 = nullptr;
-    unsigned char *r2 = nullptr;
-    long long m = 0;
-    if (c->cloud_n > 0) {
-        hipError_t e = amvs::voxel_downsample(c->d_cloud_pts, c->d_cloud_rgb, c->cloud_n, keep_mask, voxel_size, &p2, &r2,
-                                              &m, c->stream);
-        if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("voxel_downsample: ") + hipGetErrorString(e));
-        (void)hipFree(c->d_cloud_pts); (void)hipFree(c->d_cloud_rgb);
-    }
-    c->d_cloud_pts = p2; c->d_cloud_rgb = r2; c->cloud_n = m;
-    *count = m;
-    return AMVS_OK;
+    Cloud next;                         // (the resident cloud is the input: replaced once the new one is made)
+    const hipError_t e = amvs::voxel_downsample(c->cloud.pts.get(), c->cloud.rgb.get(), c->cloud.n, keep_mask, voxel_size,
+                                                c->cache, next.pts, next.rgb, &next.n, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("voxel_downsample: ") + hipGetErrorString(e));
+    c->cloud = std::move(next);
+    *count = c->cloud.n;
+    return checked(c, AMVS_OK);
 }
 
 int amvs_cloud_take(amvs_ctx *c, const int64_t *indices, int64_t m)
 {
     if (!c) return AMVS_EINVAL;
     if (m < 0 || (m > 0 && !indices)) return fail(c, AMVS_EINVAL, "bad argument");
-    if (c->cloud_n < 1 && m > 0) return fail(c, AMVS_EINVAL, "no resident cloud");
+    if (c->cloud.n < 1 && m > 0) return fail(c, AMVS_EINVAL, "no resident cloud");
     int rc = bind_device(c);
     if (rc) return rc;
     static_assert(sizeof(long long) == sizeof(int64_t), "index width");
-    double *p2 = nullptr;
-    unsigned char *r2 = nullptr;
-    if (m > 0) {
-        hipError_t e = amvs::cloud_take(c->d_cloud_pts, c->d_cloud_rgb, c->cloud_n, (const long long *)indices, m, &p2, &r2, c->stream);
-        if (e == hipErrorInvalidValue) return fail(c, AMVS_EINVAL, "cloud_take: index outside the resident cloud");
-        if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("cloud_take: ") + hipGetErrorString(e));
-    }
-    if (c->d_cloud_pts) (void)hipFree(c->d_cloud_pts);
-    if (c->d_cloud_rgb) (void)hipFree(c->d_cloud_rgb);
-    c->d_cloud_pts = p2; c->d_cloud_rgb = r2; c->cloud_n = m;
-    return AMVS_OK;
+    Cloud next;                         // (the resident cloud is the input: replaced once the new one is made)
+    const hipError_t e = amvs::cloud_take(c->cloud.pts.get(), c->cloud.rgb.get(), c->cloud.n, (const long long *)indices, m,
+                                          c->cache, next.pts, next.rgb, c->stream);
+    if (e == hipErrorInvalidValue) return fail(c, AMVS_EINVAL, "cloud_take: index outside the resident cloud");
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("cloud_take: ") + hipGetErrorString(e));
+    next.n = m;
+    c->cloud = std::move(next);
+    return checked(c, AMVS_OK);
 }
 
 int amvs_knn_supported(int k) { return amvs::knn_supported(k) ? 1 : 0; }
@@ -1582,29 +1493,17 @@ static int xpm_begin(amvs_ctx *c, int n_ref, const int *ref_ids, const int *src_
     if (rc) return rc;
     if ((rc = upload_jobs(c, n_ref, ref_ids, src_ids, n_src, 0, true))) return rc;
     const size_t hw = (size_t)c->H * c->W;
-    if (n_ref > c->cap_x) {
-        if (c->d_xcand_d) (void)hipFree(c->d_xcand_d);
-        if (c->d_xcand_n) (void)hipFree(c->d_xcand_n);
-        c->d_xcand_d = c->d_xcand_n = nullptr; c->cap_x = 0;
-        HIPCHK(c, hipMalloc(&c->d_xcand_d, 4 * hw * n_ref));
-        HIPCHK(c, hipMalloc(&c->d_xcand_n, 12 * hw * n_ref));
-        c->cap_x = n_ref;
-    }
-    if (n_ref * n_src > c->cap_xsrc) {
-        if (c->d_xsrc) (void)hipFree(c->d_xsrc);
-        c->d_xsrc = nullptr; c->cap_xsrc = 0;
-        HIPCHK(c, hipMalloc(&c->d_xsrc, sizeof(int) * n_ref * n_src));
-        c->cap_xsrc = n_ref * n_src;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_xsrc, src_ids, sizeof(int) * n_ref * n_src, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, c->d_xcand_d.reserve(hw * n_ref, c->cache));
+    HIPCHK(c, c->d_xcand_n.reserve(3 * hw * n_ref, c->cache));
+    if ((rc = upload(c, src_ids, (size_t)n_ref * n_src, c->d_xsrc))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     a = amvs::XArgs{};
     a.H = c->H; a.W = c->W; a.n_jobs = n_ref; a.n_src = n_src;
-    a.jobs = c->d_jobs; a.images = c->d_images; a.img_stride = c->stride;
+    a.jobs = c->d_jobs.get(); a.images = c->d_images.get(); a.img_stride = c->stride;
     a.pairs = usable_pairs(c); a.pair_stride = c->pstride;
     a.depth = (float *)depth_all; a.normal = (float *)normal_all; a.cost = (float *)cost_all;
     a.snap_depth = a.depth; a.snap_normal = a.normal;
-    a.cand_d = c->d_xcand_d; a.cand_n = c->d_xcand_n; a.src_view = c->d_xsrc;
+    a.cand_d = c->d_xcand_d.get(); a.cand_n = c->d_xcand_n.get(); a.src_view = c->d_xsrc.get();
     a.patch = p->patch_size; a.stride = p->window_stride;
     a.depth_min = p->depth_min; a.depth_max = p->depth_max;
     return AMVS_OK;
@@ -1691,14 +1590,16 @@ int amvs_xpm_iterate(amvs_ctx *c, int n_ref, const int *ref_ids, const int *src_
 int amvs_xpm_fetch_candidates(amvs_ctx *c, int n_ref, float *cand_depth_out, float *cand_normal_out)
 {
     if (!c) return AMVS_EINVAL;
-    if (!cand_depth_out || !cand_normal_out || n_ref < 1 || n_ref > c->cap_x) return fail(c, AMVS_EINVAL, "bad argument / no candidates");
+    const size_t hw = (size_t)c->H * c->W;
+    if (!cand_depth_out || !cand_normal_out || n_ref < 1 || hw * n_ref > c->d_xcand_d.capacity() ||
+        3 * hw * n_ref > c->d_xcand_n.capacity())
+        return fail(c, AMVS_EINVAL, "bad argument / no candidates");
     int rc = bind_device(c);
     if (rc) return rc;
-    const size_t hw = (size_t)c->H * c->W;
-    HIPCHK(c, hipMemcpyAsync(cand_depth_out, c->d_xcand_d, 4 * hw * n_ref, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cand_normal_out, c->d_xcand_n, 12 * hw * n_ref, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cand_depth_out, c->d_xcand_d.get(), 4 * hw * n_ref, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cand_normal_out, c->d_xcand_n.get(), 12 * hw * n_ref, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return AMVS_OK;
+    return checked(c, AMVS_OK);
 }
 
 int amvs_xpm_consistency(amvs_ctx *c, int n_ref, const int *ref_ids, const int *src_ids, int n_src,
@@ -1722,9 +1623,9 @@ int amvs_eval_cost(amvs_ctx *c, int ref, const int *src_ids, int n_src, int patc
     if ((rc = upload_state(c, o.hw, depth_in, nullptr, nullptr))) return rc;
     o.a.mode = amvs::MODE_EVAL;
     HIPCHK(c, amvs::launch_step(patch_size, n_src, o.a, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cost_out, c->d_aux, 4 * o.hw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cost_out, c->d_aux.get(), 4 * o.hw, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return AMVS_OK;
+    return checked(c, AMVS_OK);
 }
 
 int amvs_sample_sources(amvs_ctx *c, int ref, const int *src_ids, int n_src, int patch_size, int bounds,
@@ -1735,20 +1636,17 @@ int amvs_sample_sources(amvs_ctx *c, int ref, const int *src_ids, int n_src, int
     if (rc) return rc;
     if (!depth_in || !sampled_out || !valid_out || bounds < 0 || bounds > 2) return fail(c, AMVS_EINVAL, "bad argument");
     if ((rc = upload_state(c, o.hw, depth_in, nullptr, nullptr))) return rc;
-    float *ds = nullptr;
-    unsigned char *dv = nullptr;
-    HIPCHK(c, hipMalloc(&ds, 4 * o.hw * n_src));
-    hipError_t e = hipMalloc(&dv, o.hw);
+    amvs::DeviceBuffer<float> ds;
+    amvs::DeviceBuffer<unsigned char> dv;
+    HIPCHK(c, ds.reserve(o.hw * n_src, c->cache));
+    HIPCHK(c, dv.reserve(o.hw, c->cache));
     o.a.TH = patch_size / 2;
     o.a.mode = bounds == 0 ? amvs::MODE_EVAL : (bounds == 1 ? amvs::MODE_CONF : amvs::MODE_EVAL + 100);
-    if (e == hipSuccess) e = amvs::launch_sample_dump(n_src, o.a, ds, dv, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(sampled_out, ds, 4 * o.hw * n_src, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(valid_out, dv, o.hw, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(ds);
-    if (dv) (void)hipFree(dv);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("sample_sources: ") + hipGetErrorString(e));
-    return AMVS_OK;
+    HIPCHK(c, amvs::launch_sample_dump(n_src, o.a, ds.get(), dv.get(), c->stream));
+    HIPCHK(c, hipMemcpyAsync(sampled_out, ds.get(), 4 * o.hw * n_src, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(valid_out, dv.get(), o.hw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return checked(c, AMVS_OK);
 }
 
 int amvs_confidence(amvs_ctx *c, int ref, const int *src_ids, int n_src, int patch_size,
@@ -1762,9 +1660,9 @@ int amvs_confidence(amvs_ctx *c, int ref, const int *src_ids, int n_src, int pat
     o.a.mode = amvs::MODE_CONF;
     set_io(o.a, c, 0, false);
     HIPCHK(c, amvs::launch_step(patch_size, n_src, o.a, c->stream));
-    HIPCHK(c, hipMemcpyAsync(conf_out, c->d_aux, 4 * o.hw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(conf_out, c->d_aux.get(), 4 * o.hw, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return AMVS_OK;
+    return checked(c, AMVS_OK);
 }
 
 int amvs_propagate_step(amvs_ctx *c, int ref, const int *src_ids, int n_src, int patch_size, float *depth,
@@ -1779,7 +1677,7 @@ int amvs_propagate_step(amvs_ctx *c, int ref, const int *src_ids, int n_src, int
     set_io(o.a, c, 0);
     o.a.oy = oy; o.a.ox = ox; o.a.depth_min = depth_min;
     HIPCHK(c, amvs::launch_step(patch_size, n_src, o.a, c->stream));
-    return download_state(c, o.hw, 1, depth, normal, cost);
+    return checked(c, download_state(c, o.hw, 1, depth, normal, cost));
 }
 
 int amvs_refine_step(amvs_ctx *c, int ref, const int *src_ids, int n_src, int patch_size, float *depth,
@@ -1792,7 +1690,7 @@ int amvs_refine_step(amvs_ctx *c, int ref, const int *src_ids, int n_src, int pa
     if (!depth || !normal || !cost) return fail(c, AMVS_EINVAL, "NULL argument");
     if ((rc = upload_state(c, o.hw, depth, normal, cost))) return rc;
     // the job's RNG stream defaults to the reference view; tests may address another stream
-    HIPCHK(c, hipMemcpyAsync(&c->d_jobs[0].stream_view, &stream_view, sizeof(uint32_t),
+    HIPCHK(c, hipMemcpyAsync(&c->d_jobs.get()->stream_view, &stream_view, sizeof(uint32_t),
                              hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     o.a.mode = amvs::MODE_REFINE;
@@ -1801,7 +1699,7 @@ int amvs_refine_step(amvs_ctx *c, int ref, const int *src_ids, int n_src, int pa
     o.a.depth_range = depth_range; o.a.normal_range = normal_range;
     o.a.depth_min = depth_min; o.a.depth_max = depth_max;
     HIPCHK(c, amvs::launch_step(patch_size, n_src, o.a, c->stream));
-    return download_state(c, o.hw, 1, depth, normal, cost);
+    return checked(c, download_state(c, o.hw, 1, depth, normal, cost));
 }
 
 int amvs_init_state(amvs_ctx *c, uint64_t seed, uint32_t stream_view, float log_depth_scale,
@@ -1813,16 +1711,16 @@ int amvs_init_state(amvs_ctx *c, uint64_t seed, uint32_t stream_view, float log_
     if (rc) return rc;
     c->pm_resumable = false;
     if ((rc = ensure_slots(c, 1))) return rc;
-    if ((rc = ensure_jobs(c, 1))) return rc;
+    HIPCHK(c, c->d_jobs.reserve(1, c->cache));
     amvs::Job j;
     std::memset(&j, 0, sizeof(j));
     j.stream_view = stream_view;
-    HIPCHK(c, hipMemcpyAsync(c->d_jobs, &j, sizeof(j), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_jobs.get(), &j, sizeof(j), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const size_t hw = (size_t)c->H * c->W;
-    HIPCHK(c, amvs::launch_init(c->d_jobs, 1, (long long)hw, seed, log_depth_scale, log_depth_min,
-                                c->d_depth[0], c->d_normal[0], c->d_cost[0], c->stream));
-    return download_state(c, hw, 0, depth, normal, cost);
+    HIPCHK(c, amvs::launch_init(c->d_jobs.get(), 1, (long long)hw, seed, log_depth_scale, log_depth_min,
+                                c->d_depth[0].get(), c->d_normal[0].get(), c->d_cost.get(), c->stream));
+    return checked(c, download_state(c, hw, 0, depth, normal, cost));
 }
 
 int amvs_box_stats(amvs_ctx *c, int view, int patch_size, float *mean_out, float *var_out)
@@ -1836,10 +1734,10 @@ int amvs_box_stats(amvs_ctx *c, int view, int patch_size, float *mean_out, float
     if ((rc = ensure_stats(c, patch_size))) return rc;
     const Stats &s = c->stats.at(patch_size);
     const size_t hw = (size_t)c->H * c->W;
-    HIPCHK(c, hipMemcpyAsync(mean_out, s.mean + view * c->stride, 4 * hw, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(var_out, s.var + view * c->stride, 4 * hw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(mean_out, s.mean.get() + view * c->stride, 4 * hw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(var_out, s.var.get() + view * c->stride, 4 * hw, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return AMVS_OK;
+    return checked(c, AMVS_OK);
 }
 
 int amvs_fuse_filter(amvs_ctx *c, int n_maps, const void *depth, const void *conf, int maps_on_device,
@@ -1852,35 +1750,19 @@ int amvs_fuse_filter(amvs_ctx *c, int n_maps, const void *depth, const void *con
     int rc = bind_device(c);
     if (rc) return rc;
     const size_t hw = (size_t)c->H * c->W, n = hw * (size_t)n_maps;
-    if (c->d_cloud_pts) (void)hipFree(c->d_cloud_pts);
-    if (c->d_cloud_rgb) (void)hipFree(c->d_cloud_rgb);
-    c->d_cloud_pts = nullptr; c->d_cloud_rgb = nullptr; c->cloud_n = 0;
-    float *dd = nullptr, *dc = nullptr;
-    unsigned char *dbgr = nullptr;
-    auto cleanup = [&]() {
-        if (!maps_on_device) { if (dd) (void)hipFree(dd); if (dc) (void)hipFree(dc); }
-        if (dbgr) (void)hipFree(dbgr);
-    };
-    hipError_t e = hipMalloc(&dbgr, 3 * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(dbgr, colors_bgr_host, 3 * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && !maps_on_device) {
-        e = hipMalloc(&dd, 4 * n);
-        if (e == hipSuccess) e = hipMalloc(&dc, 4 * n);
-        if (e == hipSuccess) e = hipMemcpyAsync(dd, depth, 4 * n, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dc, conf, 4 * n, hipMemcpyHostToDevice, c->stream);
-    } else if (e == hipSuccess) {
-        dd = (float *)depth; dc = (float *)conf;
-    }
+    c->cloud = Cloud{};
+    amvs::DeviceBuffer<unsigned char> dbgr;
+    amvs::DeviceBuffer<float> copy[2];
+    const float *dd = (const float *)depth, *dc = (const float *)conf;
+    if ((rc = upload(c, colors_bgr_host, 3 * n, dbgr))) return rc;
+    if (!maps_on_device && (rc = stage_maps(c, n, dd, dc, copy))) return rc;
     long long cnt[2] = {0, 0};
-    if (e == hipSuccess)
-        e = amvs::fuse_filter(dd, dc, dbgr, n_maps, c->H, c->W, K_inv, poses, min_views, do_filter != 0,
-                              &c->d_cloud_pts, &c->d_cloud_rgb, cnt, c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    cleanup();
+    const hipError_t e = amvs::fuse_filter(dd, dc, dbgr.get(), n_maps, c->H, c->W, K_inv, poses, min_views, do_filter != 0,
+                                           c->cache, c->cloud.pts, c->cloud.rgb, cnt, c->stream);
     if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("fuse_filter: ") + hipGetErrorString(e));
     counts[0] = cnt[0]; counts[1] = cnt[1];
-    c->cloud_n = cnt[1];
-    return AMVS_OK;
+    c->cloud.n = cnt[1];
+    return checked(c, AMVS_OK);
 }
 
 int amvs_fuse_filter_views(amvs_ctx *c, int n_maps, const int *view_ids, const void *depth_dev, const void *conf_dev,
@@ -1890,43 +1772,30 @@ int amvs_fuse_filter_views(amvs_ctx *c, int n_maps, const int *view_ids, const v
     if (!c) return AMVS_EINVAL;
     if (n_maps < 1 || !view_ids || !depth_dev || !conf_dev || !K_inv || !poses || !counts)
         return fail(c, AMVS_EINVAL, "bad argument");
-    for (int j = 0; j < n_maps; ++j)
-        if (view_ids[j] < 0 || view_ids[j] >= c->n_views || !c->have_bgr[view_ids[j]])
-            return fail(c, AMVS_EINVAL, "view " + std::to_string(view_ids[j]) + " has no resident colour image (amvs_set_view_bgr8)");
-    int rc = bind_device(c);
+    int rc = check_colour_views(c, n_maps, view_ids);
     if (rc) return rc;
-    const size_t hw = (size_t)c->H * c->W;
-    if (c->d_cloud_pts) (void)hipFree(c->d_cloud_pts);
-    if (c->d_cloud_rgb) (void)hipFree(c->d_cloud_rgb);
-    c->d_cloud_pts = nullptr; c->d_cloud_rgb = nullptr; c->cloud_n = 0;
-    // the maps' colour images in map order (device-to-device; the images of a scene are rarely in
-    // that order already)
-    unsigned char *dbgr = nullptr;
-    hipError_t e = hipMalloc(&dbgr, 3 * hw * (size_t)n_maps);
-    for (int j = 0; j < n_maps && e == hipSuccess; ++j)
-        e = hipMemcpyAsync(dbgr + 3 * hw * (size_t)j, c->d_bgr + 3 * hw * (size_t)view_ids[j], 3 * hw,
-                           hipMemcpyDeviceToDevice, c->stream);
+    if ((rc = bind_device(c))) return rc;
+    c->cloud = Cloud{};
+    amvs::DeviceBuffer<unsigned char> dbgr;
+    if ((rc = gather_colours(c, n_maps, view_ids, dbgr))) return rc;
     long long cnt[2] = {0, 0};
-    if (e == hipSuccess)
-        e = amvs::fuse_filter((const float *)depth_dev, (const float *)conf_dev, dbgr, n_maps, c->H, c->W, K_inv, poses,
-                              min_views, do_filter != 0, &c->d_cloud_pts, &c->d_cloud_rgb, cnt, c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    if (dbgr) (void)hipFree(dbgr);
+    const hipError_t e = amvs::fuse_filter((const float *)depth_dev, (const float *)conf_dev, dbgr.get(), n_maps, c->H, c->W, K_inv,
+                                           poses, min_views, do_filter != 0, c->cache, c->cloud.pts, c->cloud.rgb, cnt, c->stream);
     if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("fuse_filter_views: ") + hipGetErrorString(e));
     counts[0] = cnt[0]; counts[1] = cnt[1];
-    c->cloud_n = cnt[1];
-    return AMVS_OK;
+    c->cloud.n = cnt[1];
+    return checked(c, AMVS_OK);
 }
 
 int amvs_fetch_cloud(amvs_ctx *c, double *points, uint8_t *colors)
 {
     if (!c) return AMVS_EINVAL;
-    if (c->cloud_n == 0) return AMVS_OK;
+    if (c->cloud.n == 0) return AMVS_OK;
     if (!points || !colors) return fail(c, AMVS_EINVAL, "NULL output");
     int rc = bind_device(c);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(points, c->d_cloud_pts, sizeof(double) * 3 * c->cloud_n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(colors, c->d_cloud_rgb, 3 * c->cloud_n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(points, c->cloud.pts.get(), sizeof(double) * 3 * c->cloud.n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(colors, c->cloud.rgb.get(), 3 * c->cloud.n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return checked(c, AMVS_OK);
 }
@@ -1952,20 +1821,13 @@ int amvs_tsdf_integrate(amvs_ctx *c, int n_maps, const void *depth, const void *
                                         " x " + std::to_string(dims[2]) + " grid points is over the budget of " +
                                         std::to_string((long long)AMVS_TSDF_MAX_POINTS) + " (AMVS_TSDF_MAX_POINTS)");
     std::vector<int> slots(n_maps);
-    for (int j = 0; j < n_maps; ++j) {
-        if (view_ids) {
-            if (view_ids[j] < 0 || view_ids[j] >= c->n_views || !c->have_bgr[view_ids[j]])
-                return fail(c, AMVS_EINVAL, "view " + std::to_string(view_ids[j]) + " has no resident colour image (amvs_set_view_bgr8)");
-            slots[j] = view_ids[j];
-        } else {
-            slots[j] = j;
-        }
-    }
-    int rc = bind_device(c);
-    if (rc) return rc;
-    if (!c->tsdf) c->tsdf = amvs::tsdf_state_new();
-    const hipError_t e = amvs::tsdf_integrate(c->tsdf, (const float *)depth, (const float *)conf, maps_on_device != 0, n_maps,
-                                              c->H, c->W, view_ids ? c->d_bgr : colors_bgr_host, view_ids != nullptr,
+    int rc = AMVS_OK;
+    if (view_ids && (rc = check_colour_views(c, n_maps, view_ids))) return rc;
+    for (int j = 0; j < n_maps; ++j) slots[j] = view_ids ? view_ids[j] : j;
+    if ((rc = bind_device(c))) return rc;
+    if (!c->tsdf) c->tsdf.reset(amvs::tsdf_state_new());
+    const hipError_t e = amvs::tsdf_integrate(c->tsdf.get(), c->cache, (const float *)depth, (const float *)conf, maps_on_device != 0,
+                                              n_maps, c->H, c->W, view_ids ? c->d_bgr.get() : colors_bgr_host, view_ids != nullptr,
                                               view_ids ? c->n_views : n_maps, slots.data(), K, poses, min_views, origin, voxel,
                                               dims, trunc, c->stream);
     if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("tsdf_integrate: ") + hipGetErrorString(e));
@@ -1976,11 +1838,11 @@ int amvs_tsdf_extract(amvs_ctx *c, int64_t *n_vertices, int64_t *n_faces)
 {
     if (!c) return AMVS_EINVAL;
     if (!n_vertices || !n_faces) return fail(c, AMVS_EINVAL, "tsdf_extract: NULL output");
-    if (!amvs::tsdf_has_volume(c->tsdf)) return fail(c, AMVS_EINVAL, "tsdf_extract: no volume (amvs_tsdf_integrate)");
+    if (!amvs::tsdf_has_volume(c->tsdf.get())) return fail(c, AMVS_EINVAL, "tsdf_extract: no volume (amvs_tsdf_integrate)");
     int rc = bind_device(c);
     if (rc) return rc;
     long long nv = 0, nf = 0;
-    const hipError_t e = amvs::tsdf_extract(c->tsdf, &nv, &nf, c->stream);
+    const hipError_t e = amvs::tsdf_extract(c->tsdf.get(), c->cache, &nv, &nf, c->stream);
     if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("tsdf_extract: ") + hipGetErrorString(e));
     *n_vertices = nv; *n_faces = nf;
     return checked(c, AMVS_OK);
@@ -1989,20 +1851,20 @@ int amvs_tsdf_extract(amvs_ctx *c, int64_t *n_vertices, int64_t *n_faces)
 int amvs_fetch_mesh(amvs_ctx *c, float *vertices, int32_t *faces, uint8_t *colors_rgb)
 {
     if (!c) return AMVS_EINVAL;
-    if (!amvs::tsdf_has_mesh(c->tsdf)) return fail(c, AMVS_EINVAL, "fetch_mesh: no mesh (amvs_tsdf_extract)");
+    if (!amvs::tsdf_has_mesh(c->tsdf.get())) return fail(c, AMVS_EINVAL, "fetch_mesh: no mesh (amvs_tsdf_extract)");
     int rc = bind_device(c);
     if (rc) return rc;
-    HIPCHK(c, amvs::tsdf_fetch_mesh(c->tsdf, vertices, faces, colors_rgb, c->stream));
+    HIPCHK(c, amvs::tsdf_fetch_mesh(c->tsdf.get(), vertices, faces, colors_rgb, c->stream));
     return checked(c, AMVS_OK);
 }
 
 int amvs_tsdf_fetch_volume(amvs_ctx *c, float *tsdf, float *weight, float *color_sum)
 {
     if (!c) return AMVS_EINVAL;
-    if (!amvs::tsdf_has_volume(c->tsdf)) return fail(c, AMVS_EINVAL, "tsdf_fetch_volume: no volume (amvs_tsdf_integrate)");
+    if (!amvs::tsdf_has_volume(c->tsdf.get())) return fail(c, AMVS_EINVAL, "tsdf_fetch_volume: no volume (amvs_tsdf_integrate)");
     int rc = bind_device(c);
     if (rc) return rc;
-    HIPCHK(c, amvs::tsdf_fetch_volume(c->tsdf, tsdf, weight, color_sum, c->stream));
+    HIPCHK(c, amvs::tsdf_fetch_volume(c->tsdf.get(), tsdf, weight, color_sum, c->stream));
     return checked(c, AMVS_OK);
 }
 
@@ -2017,8 +1879,8 @@ int amvs_knn_mean_distance(amvs_ctx *c, const double *points, int64_t n, int k, 
     if (n > (1ll << 30)) return fail(c, AMVS_EINVAL, "cloud too large (32-bit point indices)");
     int rc = bind_device(c);
     if (rc) return rc;
-    HIPCHK(c, amvs::knn_mean_distance(points, (long long)n, k, mean_out, c->stream));
-    return AMVS_OK;
+    HIPCHK(c, amvs::knn_mean_distance(points, (long long)n, k, mean_out, c->cache, c->stream));
+    return checked(c, AMVS_OK);
 }
 
 // ---- native exchange: RCCL through dlopen (no link-time dependency; with a PyTorch-ROCm wheel in the
@@ -2202,17 +2064,15 @@ int amvs_selftest_lean_math(amvs_ctx *c, uint64_t mismatches[2])
     if (!c || !mismatches) return AMVS_EINVAL;
     int rc = bind_device(c);
     if (rc) return rc;
-    unsigned long long *d = nullptr;
-    HIPCHK(c, hipMalloc(&d, 16));
-    hipError_t e = hipMemsetAsync(d, 0, 16, c->stream);
-    if (e == hipSuccess) e = amvs::launch_lean_math_check(d, c->stream);
+    amvs::DeviceBuffer<unsigned long long> d;
+    HIPCHK(c, d.reserve(2, c->cache));
+    HIPCHK(c, hipMemsetAsync(d.get(), 0, 16, c->stream));
+    HIPCHK(c, amvs::launch_lean_math_check(d.get(), c->stream));
     unsigned long long h[2] = {~0ull, ~0ull};
-    if (e == hipSuccess) e = hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("selftest: ") + hipGetErrorString(e));
+    HIPCHK(c, hipMemcpyAsync(h, d.get(), 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     mismatches[0] = h[0]; mismatches[1] = h[1];
-    return AMVS_OK;
+    return checked(c, AMVS_OK);
 }
 
 int amvs_rng_fill(amvs_ctx *c, uint64_t seed, uint32_t stream_view, uint32_t draw, int64_t n, float *u_out,
@@ -2222,20 +2082,14 @@ int amvs_rng_fill(amvs_ctx *c, uint64_t seed, uint32_t stream_view, uint32_t dra
     if (n < 0 || n > (1ll << 31)) return fail(c, AMVS_EINVAL, "bad n");
     int rc = bind_device(c);
     if (rc) return rc;
-    float *du = nullptr, *dn = nullptr;
-    if (u_out) HIPCHK(c, hipMalloc(&du, 4 * (size_t)(n ? n : 1)));
-    if (n_out && hipMalloc(&dn, 12 * (size_t)(n ? n : 1)) != hipSuccess) {
-        if (du) (void)hipFree(du);
-        return fail(c, AMVS_EHIP, "hipMalloc(rng) failed");
-    }
-    hipError_t e = amvs::launch_rng_fill(seed, stream_view, draw, n, du, dn, c->stream);
-    if (e == hipSuccess && du) e = hipMemcpyAsync(u_out, du, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && dn) e = hipMemcpyAsync(n_out, dn, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (du) (void)hipFree(du);
-    if (dn) (void)hipFree(dn);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("rng_fill: ") + hipGetErrorString(e));
-    return AMVS_OK;
+    amvs::DeviceBuffer<float> du, dn;
+    if (u_out) HIPCHK(c, du.reserve(n ? n : 1, c->cache));
+    if (n_out) HIPCHK(c, dn.reserve(3 * (size_t)(n ? n : 1), c->cache));
+    HIPCHK(c, amvs::launch_rng_fill(seed, stream_view, draw, n, du.get(), dn.get(), c->stream));
+    if (u_out) HIPCHK(c, hipMemcpyAsync(u_out, du.get(), 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (n_out) HIPCHK(c, hipMemcpyAsync(n_out, dn.get(), 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return checked(c, AMVS_OK);
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@
 #define AMVS_TU_ID 7
 #include "amvs_check.h"
 #include "amvs_kernels.h"
-#include "amvs_pool.h"
+#include "amvs_buffer.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -20,10 +20,11 @@ namespace amvs {
 
 namespace {
 
-#define FCHK(call)                                 \
-    do {                                           \
-        hipError_t e_ = (call);                    \
-        if (e_ != hipSuccess) return e_;           \
+// (a failure synchronises `st` first: the scratch leases go back to the cache with nothing in flight, amvs_buffer.h)
+#define FCHK(call)                                                  \
+    do {                                                            \
+        hipError_t e_ = (call);                                     \
+        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
     } while (0)
 
 // per-pixel flag: confidence >= min_views (mvs_patchmatch.py:545)
@@ -174,84 +175,69 @@ __global__ __launch_bounds__(256) void take_kernel(const double *__restrict__ pt
 
 inline dim3 grid_for(long long n) { long long b = (n + 255) / 256; return dim3((unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b))); }
 
-struct Scratch {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t n)
-    {
-        if (n <= cap) return hipSuccess;
-        if (p) pool_free(p);
-        p = nullptr; cap = 0;
-        hipError_t e = pool_malloc(&p, n);                  // (amvs_pool.hip: blocks cached between calls)
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    ~Scratch() { if (p) pool_free(p); }
-};
+using Lease = ScratchCache::Lease;
 
 // order-preserving selection of the indices [0,n) whose flag is set
 hipError_t select_indices(const unsigned char *flag, long long n, long long *out, long long *d_count,
-                          long long *h_count, Scratch &tmp, hipStream_t st)
+                          long long *h_count, ScratchCache &cache, Lease &tmp, hipStream_t st)
 {
     hipcub::CountingInputIterator<long long> iota(0);
     size_t bytes = 0;
     FCHK(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flag, out, d_count, (int)n, st));
-    FCHK(tmp.need(bytes));
-    FCHK(hipcub::DeviceSelect::Flagged(tmp.p, bytes, iota, flag, out, d_count, (int)n, st));
+    FCHK(cache.lease(tmp, bytes));
+    FCHK(hipcub::DeviceSelect::Flagged(tmp.get(), bytes, iota, flag, out, d_count, (int)n, st));
     FCHK(hipMemcpyAsync(h_count, d_count, sizeof(long long), hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
-hipError_t sort_keys(double *in, double *out, long long n, Scratch &tmp, hipStream_t st)
+hipError_t sort_keys(double *in, double *out, long long n, ScratchCache &cache, Lease &tmp, hipStream_t st)
 {
     size_t bytes = 0;
     FCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, in, out, (int)n, 0, 64, st));
-    FCHK(tmp.need(bytes));
-    return hipcub::DeviceRadixSort::SortKeys(tmp.p, bytes, in, out, (int)n, 0, 64, st);
+    FCHK(cache.lease(tmp, bytes));
+    return hipcub::DeviceRadixSort::SortKeys(tmp.get(), bytes, in, out, (int)n, 0, 64, st);
 }
 
 // First point of every voxel in key order (np.unique(keys, return_index=True)) among the points
 // sel[0 .. m2) of (pts, rgb): stable radix sort of the int64 keys, heads of the runs, gather.
 hipError_t voxel_first_of_key(const double *pts, const unsigned char *rgb, long long m_src, const long long *sel, long long m2,
-                              double voxel, Scratch &tmp, Scratch &flag, Scratch &cnt, double **pts2_out,
-                              unsigned char **rgb2_out, long long *m3_out, hipStream_t st)
+                              double voxel, ScratchCache &cache, Lease &tmp, Lease &flag, Lease &cnt,
+                              DeviceBuffer<double> &pts_out, DeviceBuffer<unsigned char> &rgb_out, long long *m3_out,
+                              hipStream_t st)
 {
-    *pts2_out = nullptr; *rgb2_out = nullptr; *m3_out = 0;
-    Scratch keysA, keysB, idxA, idxB, pick;
-    FCHK(keysA.need(8 * m2)); FCHK(keysB.need(8 * m2)); FCHK(idxA.need(8 * m2)); FCHK(idxB.need(8 * m2));
-    FCHK(pick.need(8 * m2));
-    FCHK(flag.need(m2));
-    hipLaunchKernelGGL(voxel_key_kernel, grid_for(m2), dim3(256), 0, st, pts, sel, m2, m_src, voxel, (long long *)keysA.p);
-    hipLaunchKernelGGL(iota_kernel, grid_for(m2), dim3(256), 0, st, (long long *)idxA.p, m2);
+    *m3_out = 0;
+    Lease keysA, keysB, idxA, idxB, pick;
+    FCHK(cache.lease(keysA, 8 * m2)); FCHK(cache.lease(keysB, 8 * m2)); FCHK(cache.lease(idxA, 8 * m2));
+    FCHK(cache.lease(idxB, 8 * m2)); FCHK(cache.lease(pick, 8 * m2));
+    FCHK(cache.lease(flag, m2));
+    hipLaunchKernelGGL(voxel_key_kernel, grid_for(m2), dim3(256), 0, st, pts, sel, m2, m_src, voxel, keysA.get<long long>());
+    hipLaunchKernelGGL(iota_kernel, grid_for(m2), dim3(256), 0, st, idxA.get<long long>(), m2);
     {
         size_t bytes = 0;
-        FCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (long long *)keysA.p, (long long *)keysB.p,
-                                                (long long *)idxA.p, (long long *)idxB.p, (int)m2, 0, 64, st));
-        FCHK(tmp.need(bytes));
-        FCHK(hipcub::DeviceRadixSort::SortPairs(tmp.p, bytes, (long long *)keysA.p, (long long *)keysB.p,
-                                                (long long *)idxA.p, (long long *)idxB.p, (int)m2, 0, 64, st));
+        FCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, keysA.get<long long>(), keysB.get<long long>(),
+                                                idxA.get<long long>(), idxB.get<long long>(), (int)m2, 0, 64, st));
+        FCHK(cache.lease(tmp, bytes));
+        FCHK(hipcub::DeviceRadixSort::SortPairs(tmp.get(), bytes, keysA.get<long long>(), keysB.get<long long>(),
+                                                idxA.get<long long>(), idxB.get<long long>(), (int)m2, 0, 64, st));
     }
-    hipLaunchKernelGGL(run_head_kernel, grid_for(m2), dim3(256), 0, st, (const long long *)keysB.p, m2, (unsigned char *)flag.p);
+    hipLaunchKernelGGL(run_head_kernel, grid_for(m2), dim3(256), 0, st, (const long long *)keysB.get(), m2, flag.get<unsigned char>());
     long long m3 = 0;
     {   // positions (in sorted order) of the run heads -> original indices idxB[pos]
         size_t bytes = 0;
-        FCHK(hipcub::DeviceSelect::Flagged(nullptr, bytes, (long long *)idxB.p, (unsigned char *)flag.p,
-                                           (long long *)pick.p, (long long *)cnt.p, (int)m2, st));
-        FCHK(tmp.need(bytes));
-        FCHK(hipcub::DeviceSelect::Flagged(tmp.p, bytes, (long long *)idxB.p, (unsigned char *)flag.p,
-                                           (long long *)pick.p, (long long *)cnt.p, (int)m2, st));
-        FCHK(hipMemcpyAsync(&m3, cnt.p, 8, hipMemcpyDeviceToHost, st));
+        FCHK(hipcub::DeviceSelect::Flagged(nullptr, bytes, idxB.get<long long>(), flag.get<unsigned char>(),
+                                           pick.get<long long>(), cnt.get<long long>(), (int)m2, st));
+        FCHK(cache.lease(tmp, bytes));
+        FCHK(hipcub::DeviceSelect::Flagged(tmp.get(), bytes, idxB.get<long long>(), flag.get<unsigned char>(),
+                                           pick.get<long long>(), cnt.get<long long>(), (int)m2, st));
+        FCHK(hipMemcpyAsync(&m3, cnt.get(), 8, hipMemcpyDeviceToHost, st));
         FCHK(hipStreamSynchronize(st));
     }
-    double *pts2 = nullptr;
-    unsigned char *rgb2 = nullptr;
-    FCHK(hipMalloc(&pts2, sizeof(double) * 3 * (m3 > 0 ? m3 : 1)));
-    hipError_t e = hipMalloc(&rgb2, 3 * (m3 > 0 ? m3 : 1));
-    if (e != hipSuccess) { (void)hipFree(pts2); return e; }
-    hipLaunchKernelGGL(gather_kernel, grid_for(m3), dim3(256), 0, st, pts, rgb, sel, (const long long *)pick.p, m3, m2, m_src, pts2, rgb2);
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipFree(pts2); (void)hipFree(rgb2); return e; }
-    *pts2_out = pts2; *rgb2_out = rgb2; *m3_out = m3;
+    FCHK(pts_out.reserve(3 * (size_t)(m3 > 0 ? m3 : 1), cache));
+    FCHK(rgb_out.reserve(3 * (size_t)(m3 > 0 ? m3 : 1), cache));
+    hipLaunchKernelGGL(gather_kernel, grid_for(m3), dim3(256), 0, st, pts, rgb, sel, (const long long *)pick.get(), m3, m2, m_src,
+                       pts_out.get(), rgb_out.get());
+    FCHK(hipStreamSynchronize(st));
+    *m3_out = m3;
     return hipSuccess;
 }
 
@@ -262,63 +248,58 @@ double median_sorted(const std::vector<double> &mid, long long n) { return n % 2
 
 // Fusion (+ optional filter).  depth/conf: [n_maps][H*W] float32 on the device; bgr: [n_maps][H*W][3]
 // uint8 on the device; Kinv: 9 doubles, poses: n_maps x 12 doubles (host).  Results stay on the
-// device in *pts_out / *rgb_out (hipMalloc'ed here, owned by the caller); counts[0] = raw points,
-// counts[1] = points after the filter.
+// device in pts_out / rgb_out; counts[0] = raw points, counts[1] = points after the filter.
 hipError_t fuse_filter(const float *depth, const float *conf, const unsigned char *bgr, int n_maps, int H, int W,
-                       const double *Kinv_h, const double *poses_h, float min_views, bool do_filter,
-                       double **pts_out, unsigned char **rgb_out, long long counts[2], hipStream_t st)
+                       const double *Kinv_h, const double *poses_h, float min_views, bool do_filter, ScratchCache &cache,
+                       DeviceBuffer<double> &pts_out, DeviceBuffer<unsigned char> &rgb_out, long long counts[2], hipStream_t st)
 {
-    *pts_out = nullptr; *rgb_out = nullptr; counts[0] = counts[1] = 0;
+    counts[0] = counts[1] = 0;
     const long long n = (long long)n_maps * H * W;
     if (n <= 0 || n > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    Scratch tmp, flag, sel, consts, cnt;
-    FCHK(flag.need(n));
-    FCHK(sel.need(sizeof(long long) * n));
-    FCHK(consts.need(sizeof(double) * (9 + 12 * n_maps)));
-    FCHK(cnt.need(sizeof(long long)));
-    double *d_Kinv = (double *)consts.p, *d_poses = d_Kinv + 9;
+    Lease tmp, flag, sel, consts, cnt;
+    FCHK(cache.lease(flag, n));
+    FCHK(cache.lease(sel, sizeof(long long) * n));
+    FCHK(cache.lease(consts, sizeof(double) * (9 + 12 * n_maps)));
+    FCHK(cache.lease(cnt, sizeof(long long)));
+    double *d_Kinv = consts.get<double>(), *d_poses = d_Kinv + 9;
     FCHK(hipMemcpyAsync(d_Kinv, Kinv_h, sizeof(double) * 9, hipMemcpyHostToDevice, st));
     FCHK(hipMemcpyAsync(d_poses, poses_h, sizeof(double) * 12 * n_maps, hipMemcpyHostToDevice, st));
 
     // ---- fusion: np.where(confidence >= min_views), view by view, row-major ----
-    hipLaunchKernelGGL(fuse_flag_kernel, grid_for(n), dim3(256), 0, st, conf, n, min_views, (unsigned char *)flag.p);
+    hipLaunchKernelGGL(fuse_flag_kernel, grid_for(n), dim3(256), 0, st, conf, n, min_views, flag.get<unsigned char>());
     long long m = 0;
-    FCHK(select_indices((unsigned char *)flag.p, n, (long long *)sel.p, (long long *)cnt.p, &m, tmp, st));
+    FCHK(select_indices(flag.get<unsigned char>(), n, sel.get<long long>(), cnt.get<long long>(), &m, cache, tmp, st));
     counts[0] = counts[1] = m;
     if (m == 0) return hipSuccess;
-    double *pts = nullptr;
-    unsigned char *rgb = nullptr;
-    FCHK(hipMalloc(&pts, sizeof(double) * 3 * m));
-    hipError_t e = hipMalloc(&rgb, 3 * m);
-    if (e != hipSuccess) { (void)hipFree(pts); return e; }
-    hipLaunchKernelGGL(fuse_project_kernel, grid_for(m), dim3(256), 0, st, (const long long *)sel.p, m, depth, bgr, H,
-                       W, d_Kinv, d_poses, n_maps, pts, rgb);
-    auto bail = [&](hipError_t err) { (void)hipFree(pts); (void)hipFree(rgb); return err; };
+    DeviceBuffer<double> pts;
+    DeviceBuffer<unsigned char> rgb;
+    FCHK(pts.reserve(3 * (size_t)m, cache));
+    FCHK(rgb.reserve(3 * (size_t)m, cache));
+    hipLaunchKernelGGL(fuse_project_kernel, grid_for(m), dim3(256), 0, st, (const long long *)sel.get(), m, depth, bgr, H,
+                       W, d_Kinv, d_poses, n_maps, pts.get(), rgb.get());
     if (!do_filter) {
-        e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return bail(e);
-        *pts_out = pts; *rgb_out = rgb;
+        FCHK(hipStreamSynchronize(st));
+        pts_out = std::move(pts); rgb_out = std::move(rgb);
         return hipSuccess;
     }
 
     // ---- filter: 95th-percentile radius around the per-axis median ----
-    Scratch colA, colB;
-    if ((e = colA.need(sizeof(double) * m)) != hipSuccess) return bail(e);
-    if ((e = colB.need(sizeof(double) * m)) != hipSuccess) return bail(e);
+    Lease colA, colB;
+    FCHK(cache.lease(colA, sizeof(double) * m));
+    FCHK(cache.lease(colB, sizeof(double) * m));
     double centroid[3];
     const long long lo = (m - 1) / 2;                         // middle element(s) of a sorted column
     for (int c = 0; c < 3; ++c) {
-        hipLaunchKernelGGL(column_kernel, grid_for(m), dim3(256), 0, st, pts, m, c, (double *)colA.p);
-        if ((e = sort_keys((double *)colA.p, (double *)colB.p, m, tmp, st)) != hipSuccess) return bail(e);
+        hipLaunchKernelGGL(column_kernel, grid_for(m), dim3(256), 0, st, pts.get(), m, c, colA.get<double>());
+        FCHK(sort_keys(colA.get<double>(), colB.get<double>(), m, cache, tmp, st));
         std::vector<double> mid(2, 0.0);
-        if ((e = hipMemcpyAsync(mid.data(), (double *)colB.p + lo, sizeof(double) * (m % 2 ? 1 : 2),
-                                hipMemcpyDeviceToHost, st)) != hipSuccess) return bail(e);
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return bail(e);
+        FCHK(hipMemcpyAsync(mid.data(), colB.get<double>() + lo, sizeof(double) * (m % 2 ? 1 : 2), hipMemcpyDeviceToHost, st));
+        FCHK(hipStreamSynchronize(st));
         centroid[c] = median_sorted(mid, m);
     }
-    hipLaunchKernelGGL(dist_kernel, grid_for(m), dim3(256), 0, st, pts, m, centroid[0], centroid[1], centroid[2],
-                       (double *)colA.p);
-    if ((e = sort_keys((double *)colA.p, (double *)colB.p, m, tmp, st)) != hipSuccess) return bail(e);
+    hipLaunchKernelGGL(dist_kernel, grid_for(m), dim3(256), 0, st, pts.get(), m, centroid[0], centroid[1], centroid[2],
+                       colA.get<double>());
+    FCHK(sort_keys(colA.get<double>(), colB.get<double>(), m, cache, tmp, st));
     // np.percentile(d, 95), method 'linear': virtual index 0.95*(m-1), numpy's _lerp
     double thr;
     {
@@ -328,25 +309,21 @@ hipError_t fuse_filter(const float *depth, const float *conf, const unsigned cha
         const long long next = prev + 1 < m ? prev + 1 : m - 1;
         const double t = vi - (double)prev;
         double ab[2];
-        if ((e = hipMemcpyAsync(&ab[0], (double *)colB.p + prev, sizeof(double), hipMemcpyDeviceToHost, st)) != hipSuccess) return bail(e);
-        if ((e = hipMemcpyAsync(&ab[1], (double *)colB.p + next, sizeof(double), hipMemcpyDeviceToHost, st)) != hipSuccess) return bail(e);
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return bail(e);
+        FCHK(hipMemcpyAsync(&ab[0], colB.get<double>() + prev, sizeof(double), hipMemcpyDeviceToHost, st));
+        FCHK(hipMemcpyAsync(&ab[1], colB.get<double>() + next, sizeof(double), hipMemcpyDeviceToHost, st));
+        FCHK(hipStreamSynchronize(st));
         const double diff = ab[1] - ab[0];
         thr = t >= 0.5 ? ab[1] - diff * (1.0 - t) : ab[0] + diff * t;
     }
-    hipLaunchKernelGGL(below_kernel, grid_for(m), dim3(256), 0, st, (const double *)colA.p, m, thr, (unsigned char *)flag.p);
+    hipLaunchKernelGGL(below_kernel, grid_for(m), dim3(256), 0, st, (const double *)colA.get(), m, thr, flag.get<unsigned char>());
     long long m2 = 0;
-    if ((e = select_indices((unsigned char *)flag.p, m, (long long *)sel.p, (long long *)cnt.p, &m2, tmp, st)) != hipSuccess) return bail(e);
-    if (m2 == 0) { (void)hipFree(pts); (void)hipFree(rgb); counts[1] = 0; return hipSuccess; }
+    FCHK(select_indices(flag.get<unsigned char>(), m, sel.get<long long>(), cnt.get<long long>(), &m2, cache, tmp, st));
+    if (m2 == 0) { counts[1] = 0; return hipSuccess; }
 
     // ---- voxel de-duplication: first point of every key, in key order ----
-    double *pts2 = nullptr;
-    unsigned char *rgb2 = nullptr;
     long long m3 = 0;
-    e = voxel_first_of_key(pts, rgb, m, (const long long *)sel.p, m2, 0.01, tmp, flag, cnt, &pts2, &rgb2, &m3, st);
-    (void)hipFree(pts); (void)hipFree(rgb);
-    if (e != hipSuccess) return e;
-    *pts_out = pts2; *rgb_out = rgb2;
+    FCHK(voxel_first_of_key(pts.get(), rgb.get(), m, (const long long *)sel.get(), m2, 0.01, cache, tmp, flag, cnt, pts_out,
+                            rgb_out, &m3, st));
     counts[1] = m3;
     return hipSuccess;
 }
@@ -356,70 +333,59 @@ hipError_t fuse_filter(const float *depth, const float *conf, const unsigned cha
 // the same float64 chain as fuse_project_kernel (float32 pixel coordinates convert exactly).
 // per_map_h[j] (host, optional) = points of map j -- the counts of the reference's progress lines.
 hipError_t stereo_backproject(const float *depth, const float *conf, const unsigned char *bgr, int n_maps, int H, int W,
-                              const double *Kinv_h, const double *poses_h, float min_confidence, double **pts_out,
-                              unsigned char **rgb_out, long long *total, long long *per_map_h, hipStream_t st)
+                              const double *Kinv_h, const double *poses_h, float min_confidence, ScratchCache &cache,
+                              DeviceBuffer<double> &pts_out, DeviceBuffer<unsigned char> &rgb_out, long long *total,
+                              long long *per_map_h, hipStream_t st)
 {
-    *pts_out = nullptr; *rgb_out = nullptr; *total = 0;
+    *total = 0;
     const long long HW = (long long)H * W, n = (long long)n_maps * HW;
     if (n <= 0 || n > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    Scratch tmp, flag, sel, consts, cnt, bounds;
-    FCHK(flag.need(n));
-    FCHK(sel.need(sizeof(long long) * n));
-    FCHK(consts.need(sizeof(double) * (9 + 12 * n_maps)));
-    FCHK(cnt.need(sizeof(long long)));
-    FCHK(bounds.need(sizeof(long long) * (n_maps + 1)));
-    double *d_Kinv = (double *)consts.p, *d_poses = d_Kinv + 9;
+    Lease tmp, flag, sel, consts, cnt, bounds;
+    FCHK(cache.lease(flag, n));
+    FCHK(cache.lease(sel, sizeof(long long) * n));
+    FCHK(cache.lease(consts, sizeof(double) * (9 + 12 * n_maps)));
+    FCHK(cache.lease(cnt, sizeof(long long)));
+    FCHK(cache.lease(bounds, sizeof(long long) * (n_maps + 1)));
+    double *d_Kinv = consts.get<double>(), *d_poses = d_Kinv + 9;
     FCHK(hipMemcpyAsync(d_Kinv, Kinv_h, sizeof(double) * 9, hipMemcpyHostToDevice, st));
     FCHK(hipMemcpyAsync(d_poses, poses_h, sizeof(double) * 12 * n_maps, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(stereo_flag_kernel, grid_for(n), dim3(256), 0, st, conf, depth, n, min_confidence,
-                       (unsigned char *)flag.p);
+                       flag.get<unsigned char>());
     long long m = 0;
-    FCHK(select_indices((unsigned char *)flag.p, n, (long long *)sel.p, (long long *)cnt.p, &m, tmp, st));
+    FCHK(select_indices(flag.get<unsigned char>(), n, sel.get<long long>(), cnt.get<long long>(), &m, cache, tmp, st));
     *total = m;
     if (per_map_h) {
         std::vector<long long> first(n_maps + 1, 0);
-        hipLaunchKernelGGL(map_bounds_kernel, dim3((n_maps + 1 + 63) / 64), dim3(64), 0, st, (const long long *)sel.p, m, HW,
-                           n_maps, (long long *)bounds.p);
-        FCHK(hipMemcpyAsync(first.data(), bounds.p, sizeof(long long) * (n_maps + 1), hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(map_bounds_kernel, dim3((n_maps + 1 + 63) / 64), dim3(64), 0, st, (const long long *)sel.get(), m, HW,
+                           n_maps, bounds.get<long long>());
+        FCHK(hipMemcpyAsync(first.data(), bounds.get(), sizeof(long long) * (n_maps + 1), hipMemcpyDeviceToHost, st));
         FCHK(hipStreamSynchronize(st));
         for (int j = 0; j < n_maps; ++j) per_map_h[j] = first[j + 1] - first[j];
     }
     if (m == 0) return hipSuccess;
-    double *pts = nullptr;
-    unsigned char *rgb = nullptr;
-    FCHK(hipMalloc(&pts, sizeof(double) * 3 * m));
-    hipError_t e = hipMalloc(&rgb, 3 * m);
-    if (e != hipSuccess) { (void)hipFree(pts); return e; }
-    hipLaunchKernelGGL(fuse_project_kernel, grid_for(m), dim3(256), 0, st, (const long long *)sel.p, m, depth, bgr, H,
-                       W, d_Kinv, d_poses, n_maps, pts, rgb);
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipFree(pts); (void)hipFree(rgb); return e; }
-    *pts_out = pts; *rgb_out = rgb;
-    return hipSuccess;
+    FCHK(pts_out.reserve(3 * (size_t)m, cache));
+    FCHK(rgb_out.reserve(3 * (size_t)m, cache));
+    hipLaunchKernelGGL(fuse_project_kernel, grid_for(m), dim3(256), 0, st, (const long long *)sel.get(), m, depth, bgr, H,
+                       W, d_Kinv, d_poses, n_maps, pts_out.get(), rgb_out.get());
+    return hipStreamSynchronize(st);
 }
 
 // points[chosen], colors[chosen] of a device cloud (dense_stereo.py:449-455: the random sub-sample of clouds above
 // 500 000 points; the caller draws `chosen` with numpy as the reference does): rows idx_h[0 .. m) in that order
 hipError_t cloud_take(const double *pts, const unsigned char *rgb, long long n, const long long *idx_h, long long m,
-                      double **pts_out, unsigned char **rgb_out, hipStream_t st)
+                      ScratchCache &cache, DeviceBuffer<double> &pts_out, DeviceBuffer<unsigned char> &rgb_out, hipStream_t st)
 {
-    *pts_out = nullptr; *rgb_out = nullptr;
     if (m <= 0) return hipSuccess;
     for (long long i = 0; i < m; ++i)
         if (idx_h[i] < 0 || idx_h[i] >= n) return hipErrorInvalidValue;
-    Scratch idx;
-    FCHK(idx.need(sizeof(long long) * m));
-    FCHK(hipMemcpyAsync(idx.p, idx_h, sizeof(long long) * m, hipMemcpyHostToDevice, st));
-    double *pts2 = nullptr;
-    unsigned char *rgb2 = nullptr;
-    FCHK(hipMalloc(&pts2, sizeof(double) * 3 * m));
-    hipError_t e = hipMalloc(&rgb2, 3 * m);
-    if (e != hipSuccess) { (void)hipFree(pts2); return e; }
-    hipLaunchKernelGGL(take_kernel, grid_for(m), dim3(256), 0, st, pts, rgb, (const long long *)idx.p, m, n, pts2, rgb2);
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipFree(pts2); (void)hipFree(rgb2); return e; }
-    *pts_out = pts2; *rgb_out = rgb2;
-    return hipSuccess;
+    Lease idx;
+    FCHK(cache.lease(idx, sizeof(long long) * m));
+    FCHK(hipMemcpyAsync(idx.get(), idx_h, sizeof(long long) * m, hipMemcpyHostToDevice, st));
+    FCHK(pts_out.reserve(3 * (size_t)m, cache));
+    FCHK(rgb_out.reserve(3 * (size_t)m, cache));
+    hipLaunchKernelGGL(take_kernel, grid_for(m), dim3(256), 0, st, pts, rgb, (const long long *)idx.get(), m, n, pts_out.get(),
+                       rgb_out.get());
+    return hipStreamSynchronize(st);
 }
 
 // DenseStereoReconstructor._voxel_down_sample (dense_stereo.py:475-492) of a device cloud, after an
@@ -427,24 +393,26 @@ hipError_t cloud_take(const double *pts, const unsigned char *rgb, long long n, 
 // key order.  The reference casts the voxel indices through int32 before forming the int64 key; for
 // clouds inside +-2^31 voxels that is the identity.
 hipError_t voxel_downsample(const double *pts, const unsigned char *rgb, long long m, const unsigned char *keep_h,
-                            double voxel, double **pts_out, unsigned char **rgb_out, long long *m_out, hipStream_t st)
+                            double voxel, ScratchCache &cache, DeviceBuffer<double> &pts_out,
+                            DeviceBuffer<unsigned char> &rgb_out, long long *m_out, hipStream_t st)
 {
-    *pts_out = nullptr; *rgb_out = nullptr; *m_out = 0;
+    *m_out = 0;
     if (m <= 0) return hipSuccess;
     if (m > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    Scratch tmp, flag, sel, cnt;
-    FCHK(flag.need(m));
-    FCHK(sel.need(sizeof(long long) * m));
-    FCHK(cnt.need(sizeof(long long)));
+    Lease tmp, flag, sel, cnt;
+    FCHK(cache.lease(flag, m));
+    FCHK(cache.lease(sel, sizeof(long long) * m));
+    FCHK(cache.lease(cnt, sizeof(long long)));
     long long m2 = m;
     if (keep_h) {
-        FCHK(hipMemcpyAsync(flag.p, keep_h, m, hipMemcpyHostToDevice, st));
-        FCHK(select_indices((unsigned char *)flag.p, m, (long long *)sel.p, (long long *)cnt.p, &m2, tmp, st));
+        FCHK(hipMemcpyAsync(flag.get(), keep_h, m, hipMemcpyHostToDevice, st));
+        FCHK(select_indices(flag.get<unsigned char>(), m, sel.get<long long>(), cnt.get<long long>(), &m2, cache, tmp, st));
     } else {
-        hipLaunchKernelGGL(iota_kernel, grid_for(m), dim3(256), 0, st, (long long *)sel.p, m);
+        hipLaunchKernelGGL(iota_kernel, grid_for(m), dim3(256), 0, st, sel.get<long long>(), m);
     }
     if (m2 == 0) return hipSuccess;
-    return voxel_first_of_key(pts, rgb, m, (const long long *)sel.p, m2, voxel, tmp, flag, cnt, pts_out, rgb_out, m_out, st);
+    return voxel_first_of_key(pts, rgb, m, (const long long *)sel.get(), m2, voxel, cache, tmp, flag, cnt, pts_out, rgb_out,
+                              m_out, st);
 }
 
 }  // namespace amvs

@@ -12,6 +12,9 @@
 
 namespace amvs {
 
+class ScratchCache;                   // amvs_buffer.h
+template <class T> class DeviceBuffer;
+
 // One source view of a job: everything its sampling needs in one 64-byte record (a single
 // s_load_dwordx16 and one wait per source instead of three load / wait rounds).
 struct alignas(64) SrcEntry {
@@ -131,7 +134,8 @@ hipError_t launch_box_stats_generic(int K, const float *images, long long img_st
 hipError_t launch_fast_stats_generic(int K, const uint16_t *pairs_view, int H, int W, float2 *out, hipStream_t st);
 int step_generic_waves_per_cu(int K, int S);
 bool knn_supported(int k);
-hipError_t knn_mean_distance(const double *points, long long n, int k, double *mean_out, hipStream_t st,
+// scratch from the context's `cache`; synchronises `st`
+hipError_t knn_mean_distance(const double *points, long long n, int k, double *mean_out, ScratchCache &cache, hipStream_t st,
                              bool points_on_device = false);
 int strip_out_width(int K);
 int step_waves_per_cu(int K, int S, bool u8, int wg_cap = 0);      // resident waves per CU under the cap (0 = default)
@@ -177,10 +181,12 @@ hipError_t launch_lean_math_check(unsigned long long *mismatch, hipStream_t st);
 hipError_t launch_rng_fill(unsigned long long seed, unsigned view, unsigned draw, long long n,
                            float *u_out, float *n_out, hipStream_t st);
 
-// amvs_fusion.hip: fusion (+ filter) of per-view maps into a cloud; results are hipMalloc'ed
+// amvs_fusion.hip: fusion (+ filter) of per-view maps into a cloud.  Every post-step of amvs_fusion.hip takes its
+// scratch from the context's `cache`, writes its cloud into EMPTY buffers pts_out / rgb_out (exactly the points found)
+// and synchronises `st`.
 hipError_t fuse_filter(const float *depth, const float *conf, const unsigned char *bgr, int n_maps, int H, int W,
-                       const double *Kinv_h, const double *poses_h, float min_views, bool do_filter,
-                       double **pts_out, unsigned char **rgb_out, long long counts[2], hipStream_t st);
+                       const double *Kinv_h, const double *poses_h, float min_views, bool do_filter, ScratchCache &cache,
+                       DeviceBuffer<double> &pts_out, DeviceBuffer<unsigned char> &rgb_out, long long counts[2], hipStream_t st);
 
 // amvs_extended.hip: the extended PatchMatch mode (slanted-plane cost, red-black schedule, view
 // propagation, geometric consistency); no reference counterpart
@@ -218,26 +224,29 @@ hipError_t launch_prep_bgr8(const unsigned char *src, int sh, int sw, int dh, in
 
 // amvs_fusion.hip: the stereo path's post-steps (dense_stereo.py:407-437, 475-492)
 hipError_t stereo_backproject(const float *depth, const float *conf, const unsigned char *bgr, int n_maps, int H, int W,
-                              const double *Kinv_h, const double *poses_h, float min_confidence, double **pts_out,
-                              unsigned char **rgb_out, long long *total, long long *per_map_h, hipStream_t st);
+                              const double *Kinv_h, const double *poses_h, float min_confidence, ScratchCache &cache,
+                              DeviceBuffer<double> &pts_out, DeviceBuffer<unsigned char> &rgb_out, long long *total,
+                              long long *per_map_h, hipStream_t st);
 hipError_t cloud_take(const double *pts, const unsigned char *rgb, long long n, const long long *idx_h, long long m,
-                      double **pts_out, unsigned char **rgb_out, hipStream_t st);
+                      ScratchCache &cache, DeviceBuffer<double> &pts_out, DeviceBuffer<unsigned char> &rgb_out, hipStream_t st);
 hipError_t voxel_downsample(const double *pts, const unsigned char *rgb, long long m, const unsigned char *keep_h,
-                            double voxel, double **pts_out, unsigned char **rgb_out, long long *m_out, hipStream_t st);
+                            double voxel, ScratchCache &cache, DeviceBuffer<double> &pts_out,
+                            DeviceBuffer<unsigned char> &rgb_out, long long *m_out, hipStream_t st);
 
 
 // amvs_mesh.hip: TSDF fusion of the per-view maps and marching-tetrahedra extraction (include/amvs.h
-// amvs_tsdf_*).  The state (volume, scans, mesh) is owned by a context and freed with it.
+// amvs_tsdf_*).  The state (volume, scans, mesh) is owned by a context and freed with it; its buffers are
+// allocated through the context's `cache`.
 struct TsdfState;
 TsdfState *tsdf_state_new();
 void tsdf_state_free(TsdfState *s);
 // depth / conf: [n_maps][H*W] (host or device); bgr: [bgr_images][H*W][3] BGR (host or device), map j takes
 // its colours from image slots_h[j]; poses_h: [n_maps][12] float32 R row-major, t.  Synchronises.
-hipError_t tsdf_integrate(TsdfState *s, const float *depth, const float *conf, bool maps_on_device, int n_maps, int H, int W,
-                          const unsigned char *bgr, bool bgr_on_device, long long bgr_images, const int *slots_h,
-                          const float K[9], const float *poses_h, float min_views, const float origin[3], float voxel,
-                          const int dims[3], float trunc, hipStream_t st);
-hipError_t tsdf_extract(TsdfState *s, long long *n_vertices, long long *n_faces, hipStream_t st);
+hipError_t tsdf_integrate(TsdfState *s, ScratchCache &cache, const float *depth, const float *conf, bool maps_on_device,
+                          int n_maps, int H, int W, const unsigned char *bgr, bool bgr_on_device, long long bgr_images,
+                          const int *slots_h, const float K[9], const float *poses_h, float min_views, const float origin[3],
+                          float voxel, const int dims[3], float trunc, hipStream_t st);
+hipError_t tsdf_extract(TsdfState *s, ScratchCache &cache, long long *n_vertices, long long *n_faces, hipStream_t st);
 bool tsdf_has_volume(const TsdfState *s);
 bool tsdf_has_mesh(const TsdfState *s);
 hipError_t tsdf_fetch_mesh(TsdfState *s, float *verts, int *faces, unsigned char *rgb, hipStream_t st);

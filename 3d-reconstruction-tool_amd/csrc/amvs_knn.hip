@@ -19,7 +19,7 @@
 #define AMVS_TU_ID 8
 #include "amvs_check.h"
 #include "amvs_kernels.h"
-#include "amvs_pool.h"
+#include "amvs_buffer.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -35,10 +35,11 @@ namespace amvs {
 
 namespace {
 
-#define KCHK(call)                                 \
-    do {                                           \
-        hipError_t e_ = (call);                    \
-        if (e_ != hipSuccess) return e_;           \
+// (a failure synchronises `st` first: the scratch leases go back to the cache with nothing in flight, amvs_buffer.h)
+#define KCHK(call)                                                  \
+    do {                                                            \
+        hipError_t e_ = (call);                                     \
+        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
     } while (0)
 
 constexpr int KNN_KMAX = 32;
@@ -365,7 +366,7 @@ hipError_t launch_query(const double *sorted, long long n, const Grid &gr, const
 bool knn_supported(int k) { return k == 8 || k == 10 || k == 16 || k == 20 || k == 32; }
 
 // points: [n][3] float64 on the host (or on the device: points_on_device); mean_out: host [n].  Needs n >= k.
-hipError_t knn_mean_distance(const double *points, long long n, int k, double *mean_out, hipStream_t st,
+hipError_t knn_mean_distance(const double *points, long long n, int k, double *mean_out, ScratchCache &cache, hipStream_t st,
                              bool points_on_device)
 {
     // The grid spans the 1st .. 99th percentile of every axis (estimated on a strided sample); points
@@ -387,14 +388,13 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
         if (points_on_device) {
             // gathered on the device, then ONE contiguous copy (a strided hipMemcpy2D of 65 536 rows of 24 bytes took
             // 2 ms; dereferencing device memory from the host works through the PCIe BAR but takes ~4 us per read)
-            double *d_sample = nullptr;
-            KCHK(pool_malloc(&d_sample, sizeof(double) * 3 * (size_t)cnt));
-            hipLaunchKernelGGL(knn_sample_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, points, stride, cnt, d_sample);
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(sample.data(), d_sample, sizeof(double) * 3 * (size_t)cnt, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            pool_free(d_sample);
-            if (e != hipSuccess) return e;
+            ScratchCache::Lease d_sample;
+            KCHK(cache.lease(d_sample, sizeof(double) * 3 * (size_t)cnt));
+            hipLaunchKernelGGL(knn_sample_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, points, stride, cnt,
+                               d_sample.get<double>());
+            KCHK(hipGetLastError());
+            KCHK(hipMemcpyAsync(sample.data(), d_sample.get(), sizeof(double) * 3 * (size_t)cnt, hipMemcpyDeviceToHost, st));
+            KCHK(hipStreamSynchronize(st));
         } else {
             for (long long j = 0; j < cnt; ++j)
                 for (int a = 0; a < 3; ++a) sample[(size_t)(3 * j + a)] = points[3 * j * stride + a];
@@ -423,33 +423,23 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
     h = std::max(h, h_min);
 
     const double t_sampled = debug ? now_ms() : 0.0;
-    double *d_pts = nullptr, *d_sorted = nullptr, *d_mean = nullptr;
-    int *d_cell = nullptr, *d_count = nullptr, *d_start = nullptr, *d_origin = nullptr;
-    unsigned char *d_pending = nullptr;
-    int *d_occ = nullptr;
-    void *d_tmp = nullptr;
-    size_t tmp_bytes = 0;
-    long long table_cap = 0;
-    auto cleanup = [&]() {
-        for (void *p : {(void *)d_pts, (void *)d_sorted, (void *)d_mean, (void *)d_cell, (void *)d_count,
-                        (void *)d_start, (void *)d_origin, (void *)d_pending, (void *)d_occ, d_tmp})
-            if (p) pool_free(p);
-    };
-#define KCHK_C(call)                                                   \
-    do {                                                               \
-        hipError_t e_ = (call);                                        \
-        if (e_ != hipSuccess) { cleanup(); return e_; }                \
-    } while (0)
-    KCHK_C(pool_malloc(&d_pts, sizeof(double) * 3 * n));
-    KCHK_C(pool_malloc(&d_sorted, sizeof(double) * 3 * n));
-    KCHK_C(pool_malloc(&d_mean, sizeof(double) * n));
-    KCHK_C(pool_malloc(&d_cell, sizeof(int) * n));
-    KCHK_C(pool_malloc(&d_origin, sizeof(int) * n));
-    KCHK_C(pool_malloc(&d_pending, (size_t)n));
-    KCHK_C(pool_malloc(&d_occ, sizeof(int)));
-    KCHK_C(hipMemcpyAsync(d_pts, points, sizeof(double) * 3 * n,
-                          points_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    KCHK_C(hipMemsetAsync(d_pending, 1, (size_t)n, st));
+    // device scratch: blocks of the context's cache, given back when this returns (after its last synchronisation);
+    // the cell tables and the scan / select temporary grow with the grid levels
+    ScratchCache::Lease l_pts, l_sorted, l_mean, l_cell, l_origin, l_pending, l_occ, l_iota, l_queries, l_nsel, l_count,
+        l_start, l_tmp;
+    KCHK(cache.lease(l_pts, sizeof(double) * 3 * n));
+    KCHK(cache.lease(l_sorted, sizeof(double) * 3 * n));
+    KCHK(cache.lease(l_mean, sizeof(double) * n));
+    KCHK(cache.lease(l_cell, sizeof(int) * n));
+    KCHK(cache.lease(l_origin, sizeof(int) * n));
+    KCHK(cache.lease(l_pending, (size_t)n));
+    KCHK(cache.lease(l_occ, sizeof(int)));
+    double *const d_pts = l_pts.get<double>(), *const d_sorted = l_sorted.get<double>(), *const d_mean = l_mean.get<double>();
+    int *const d_cell = l_cell.get<int>(), *const d_origin = l_origin.get<int>(), *const d_occ = l_occ.get<int>();
+    unsigned char *const d_pending = l_pending.get<unsigned char>();
+    KCHK(hipMemcpyAsync(d_pts, points, sizeof(double) * 3 * n,
+                        points_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    KCHK(hipMemsetAsync(d_pending, 1, (size_t)n, st));
 
     const int bx = (int)std::min<long long>((n + 255) / 256, 4096);
     Grid gr{};
@@ -460,26 +450,16 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
         gr.h = edge; gr.inv_h = 1.0 / edge;
         for (int a = 0; a < 3; ++a) gr.g[a] = std::max(1, std::min(KNN_GMAX, (int)std::floor(ext[a] / edge) + 1));
         cells = (long long)gr.g[0] * gr.g[1] * gr.g[2];
-        if (cells + 1 > table_cap) {
-            if (d_count) pool_free(d_count);
-            if (d_start) pool_free(d_start);
-            d_count = d_start = nullptr;
-            KCHK(pool_malloc(&d_count, sizeof(int) * (cells + 1)));
-            KCHK(pool_malloc(&d_start, sizeof(int) * (cells + 1)));
-            table_cap = cells + 1;
-        }
+        KCHK(cache.lease(l_count, sizeof(int) * (cells + 1)));
+        KCHK(cache.lease(l_start, sizeof(int) * (cells + 1)));
+        int *const d_count = l_count.get<int>(), *const d_start = l_start.get<int>();
         KCHK(hipMemsetAsync(d_count, 0, sizeof(int) * (cells + 1), st));
         hipLaunchKernelGGL(knn_count_kernel, dim3(bx), dim3(256), 0, st, d_pts, n, gr, d_cell, d_count);
         KCHK(hipGetLastError());
         size_t need = 0;
         KCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_count, d_start, (int)(cells + 1), st));
-        if (need > tmp_bytes) {
-            if (d_tmp) pool_free(d_tmp);
-            d_tmp = nullptr;
-            KCHK(pool_malloc(&d_tmp, need));
-            tmp_bytes = need;
-        }
-        KCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_count, d_start, (int)(cells + 1), st));
+        KCHK(cache.lease(l_tmp, need));
+        KCHK(hipcub::DeviceScan::ExclusiveSum(l_tmp.get(), need, d_count, d_start, (int)(cells + 1), st));
         if (per_cell >= 0.0) {
             KCHK(hipMemsetAsync(d_occ, 0, sizeof(int), st));
             const int cb = (int)std::min<long long>((cells + 255) / 256, 2048);
@@ -493,6 +473,7 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
         return hipSuccess;
     };
     auto query = [&](int max_shells) -> hipError_t {
+        int *const d_count = l_count.get<int>(), *const d_start = l_start.get<int>();
         KCHK(hipMemsetAsync(d_count, 0, sizeof(int) * (cells + 1), st));     // reused as the placement cursor
         hipLaunchKernelGGL(knn_place_kernel, dim3(bx), dim3(256), 0, st, d_pts, n, d_cell, d_start, d_count,
                            d_sorted, d_origin, cells);
@@ -512,7 +493,7 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
     int walk_again = 0;
     for (int attempt = 0; attempt < 6; ++attempt) {
         double per_cell = 0.0;
-        KCHK_C(bin(h, per_cell));
+        KCHK(bin(h, per_cell));
         fitted_per_cell = per_cell;
         const bool at_limit = gr.g[0] == KNN_GMAX || gr.g[1] == KNN_GMAX || gr.g[2] == KNN_GMAX;
         if (per_cell > 24.0 && !at_limit && h > h_min) { h = std::max(h * 0.5, h_min); continue; }
@@ -522,33 +503,19 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
     // coarser levels (edge x2 each) pick up the queries whose neighbourhood is sparser than two
     // shells of the level before; the last level may scan
     const double t_binned = debug ? ((void)hipStreamSynchronize(st), now_ms()) : 0.0;
-    int *d_iota = nullptr, *d_queries = nullptr, *d_nsel = nullptr;
-    auto cleanup2 = [&]() {
-        for (void *p : {(void *)d_iota, (void *)d_queries, (void *)d_nsel})
-            if (p) pool_free(p);
-        d_iota = d_queries = d_nsel = nullptr;
-    };
-#define KCHK_D(call)                                                   \
-    do {                                                               \
-        hipError_t e_ = (call);                                        \
-        if (e_ != hipSuccess) { cleanup2(); cleanup(); return e_; }    \
-    } while (0)
-    KCHK_D(pool_malloc(&d_iota, sizeof(int) * n));
-    KCHK_D(pool_malloc(&d_queries, sizeof(int) * n));
-    KCHK_D(pool_malloc(&d_nsel, sizeof(int)));
+    KCHK(cache.lease(l_iota, sizeof(int) * n));
+    KCHK(cache.lease(l_queries, sizeof(int) * n));
+    KCHK(cache.lease(l_nsel, sizeof(int)));
+    int *const d_iota = l_iota.get<int>(), *const d_queries = l_queries.get<int>(), *const d_nsel = l_nsel.get<int>();
+    const int *const d_start = l_start.get<int>();           // (the tables of the last level are final)
     hipLaunchKernelGGL(knn_iota_kernel, dim3(bx), dim3(256), 0, st, d_iota, n);
-    KCHK_D(hipGetLastError());
+    KCHK(hipGetLastError());
     // the still-pending queries, compacted (and counted) after every level
     auto pending_list = [&](int &count) -> hipError_t {
         size_t need = 0;
         KCHK(hipcub::DeviceSelect::Flagged(nullptr, need, d_iota, d_pending, d_queries, d_nsel, (int)n, st));
-        if (need > tmp_bytes) {
-            if (d_tmp) pool_free(d_tmp);
-            d_tmp = nullptr;
-            KCHK(pool_malloc(&d_tmp, need));
-            tmp_bytes = need;
-        }
-        KCHK(hipcub::DeviceSelect::Flagged(d_tmp, tmp_bytes, d_iota, d_pending, d_queries, d_nsel, (int)n, st));
+        KCHK(cache.lease(l_tmp, need));
+        KCHK(hipcub::DeviceSelect::Flagged(l_tmp.get(), need, d_iota, d_pending, d_queries, d_nsel, (int)n, st));
         KCHK(hipMemcpyAsync(&count, d_nsel, sizeof(int), hipMemcpyDeviceToHost, st));
         return hipStreamSynchronize(st);
     };
@@ -569,15 +536,15 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
         };
         // a thread per query walks shells 0..1; a wave per query left scans the box R = 2 (the cells of shells
         // 0..2); a block per query still left scans the boxes R = 4, 8, ... until its rule holds
-        KCHK_D(query(1));
-        KCHK_D(pending_list(left));
+        KCHK(query(1));
+        KCHK(pending_list(left));
         walk_again = left;
         if (left > 0) {
-            KCHK_D(box(KNN_SHELLS, KNN_SHELLS, left));
-            KCHK_D(pending_list(left));
+            KCHK(box(KNN_SHELLS, KNN_SHELLS, left));
+            KCHK(pending_list(left));
         }
         if (debug) (void)hipEventRecord(e1, st);
-        if (left > 0) KCHK_D(box(2 * KNN_SHELLS, 1 << 30, left));     // (R = 4 as a wave's pass of its own: no gain, measured)
+        if (left > 0) KCHK(box(2 * KNN_SHELLS, 1 << 30, left));     // (R = 4 as a wave's pass of its own: no gain, measured)
         if (debug) {
             (void)hipEventRecord(e2, st);
             (void)hipStreamSynchronize(st);
@@ -590,17 +557,12 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
         }
     }
     const double t_searched = debug ? ((void)hipStreamSynchronize(st), now_ms()) : 0.0;
-    cleanup2();
-#undef KCHK_D
-    KCHK_C(hipMemcpyAsync(mean_out, d_mean, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    KCHK_C(hipStreamSynchronize(st));
-    const double t_copied = debug ? now_ms() : 0.0;
-    cleanup();
+    KCHK(hipMemcpyAsync(mean_out, d_mean, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    KCHK(hipStreamSynchronize(st));
     if (debug)
-        std::fprintf(stderr, "knn: box sample %.2f ms, allocate + bin %.2f, search %.2f, result to the host %.2f, release %.2f\n",
-                     t_sampled - t_begin, t_binned - t_sampled, t_searched - t_binned, t_copied - t_searched, now_ms() - t_copied);
+        std::fprintf(stderr, "knn: box sample %.2f ms, allocate + bin %.2f, search %.2f, result to the host %.2f\n",
+                     t_sampled - t_begin, t_binned - t_sampled, t_searched - t_binned, now_ms() - t_searched);
     return hipSuccess;
-#undef KCHK_C
 }
 
 }  // namespace amvs

@@ -34,6 +34,7 @@
 #define AMVS_TU_ID 9
 #include "amvs_check.h"
 #include "amvs_kernels.h"
+#include "amvs_buffer.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -308,46 +309,34 @@ inline dim3 grid_of(long long n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
 
+// every buffer grows only: a volume, a scan or a mesh no larger than the largest before allocates nothing
 struct TsdfState {
     Grid g{};
-    long long n = 0, cap = 0;                     // grid points, allocated points
+    long long n = 0;                              // grid points
     bool have_volume = false, have_mesh = false;
-    float *tsdf = nullptr, *weight = nullptr, *color = nullptr;
-    unsigned char *mask = nullptr;
-    unsigned *vcount = nullptr, *vbase = nullptr, *tcount = nullptr, *tbase = nullptr;
-    void *scan_tmp = nullptr;
-    size_t cap_scan = 0;
-    float *cams = nullptr;                        // [n_maps][12] R, t
-    int *slots = nullptr;                         // colour image of every map
-    int cap_maps = 0;
-    float *stage_depth = nullptr, *stage_conf = nullptr;   // host maps
-    unsigned char *stage_bgr = nullptr;                    // host colour images
-    size_t cap_stage_depth = 0, cap_stage_conf = 0, cap_stage_bgr = 0;
-    float *verts = nullptr, *verts2 = nullptr;
-    int *faces = nullptr;
-    unsigned char *rgb = nullptr, *rgb2 = nullptr;
-    unsigned *vused = nullptr, *vnew = nullptr;   // (d): used flags and new ids of the vertices
-    long long n_vertices = 0, n_faces = 0, cap_vertices = 0, cap_faces = 0;
+    DeviceBuffer<float> tsdf, weight, color;      // [n], [n], [n][3]
+    DeviceBuffer<unsigned char> mask;
+    DeviceBuffer<unsigned> vcount, vbase, tcount, tbase;
+    DeviceBuffer<unsigned char> scan_tmp;
+    DeviceBuffer<float> cams;                     // [n_maps][12] R, t
+    DeviceBuffer<int> slots;                      // colour image of every map
+    DeviceBuffer<float> stage_depth, stage_conf;  // host maps
+    DeviceBuffer<unsigned char> stage_bgr;        // host colour images
+    DeviceBuffer<float> verts, verts2;
+    DeviceBuffer<int> faces;
+    DeviceBuffer<unsigned char> rgb, rgb2;
+    DeviceBuffer<unsigned> vused, vnew;           // (d): used flags and new ids of the vertices
+    long long n_vertices = 0, n_faces = 0;
 };
 
 namespace {
 
-template <class T> hipError_t grow(T **p, size_t need, size_t &cap)
-{
-    if (need <= cap && *p) return hipSuccess;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; cap = 0;
-    MCHK(hipMalloc((void **)p, need > 0 ? need : 1));
-    cap = need;
-    return hipSuccess;
-}
-
-hipError_t exclusive_scan(TsdfState *s, const unsigned *in, unsigned *out, long long n, hipStream_t st)
+hipError_t exclusive_scan(TsdfState *s, ScratchCache &cache, const unsigned *in, unsigned *out, long long n, hipStream_t st)
 {
     size_t bytes = 0;
     MCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, st));
-    MCHK(grow(&s->scan_tmp, bytes, s->cap_scan));
-    return hipcub::DeviceScan::ExclusiveSum(s->scan_tmp, bytes, in, out, (int)n, st);
+    MCHK(s->scan_tmp.reserve(bytes > 0 ? bytes : 1, cache));
+    return hipcub::DeviceScan::ExclusiveSum(s->scan_tmp.get(), bytes, in, out, (int)n, st);
 }
 
 // total of an exclusive scan: base[n-1] + count[n-1]
@@ -365,131 +354,96 @@ hipError_t scan_total(const unsigned *count, const unsigned *base, long long n, 
 
 TsdfState *tsdf_state_new() { return new TsdfState(); }
 
-void tsdf_state_free(TsdfState *s)
-{
-    if (!s) return;
-    void *bufs[] = {s->tsdf, s->weight, s->color, s->mask, s->vcount, s->vbase, s->tcount, s->tbase, s->scan_tmp, s->cams,
-                    s->slots, s->stage_depth, s->stage_conf, s->stage_bgr, s->verts, s->faces, s->rgb, s->verts2, s->rgb2,
-                    s->vused, s->vnew};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    delete s;
-}
+void tsdf_state_free(TsdfState *s) { delete s; }
 
-hipError_t tsdf_integrate(TsdfState *s, const float *depth, const float *conf, bool maps_on_device, int n_maps, int H, int W,
-                          const unsigned char *bgr, bool bgr_on_device, long long bgr_images, const int *slots_h,
-                          const float K[9], const float *poses_h, float min_views, const float origin[3], float voxel,
-                          const int dims[3], float trunc, hipStream_t st)
+hipError_t tsdf_integrate(TsdfState *s, ScratchCache &cache, const float *depth, const float *conf, bool maps_on_device,
+                          int n_maps, int H, int W, const unsigned char *bgr, bool bgr_on_device, long long bgr_images,
+                          const int *slots_h, const float K[9], const float *poses_h, float min_views, const float origin[3],
+                          float voxel, const int dims[3], float trunc, hipStream_t st)
 {
     s->have_volume = s->have_mesh = false;
     const long long n = (long long)dims[0] * dims[1] * dims[2];
     const size_t hw = (size_t)H * W, nmap = hw * (size_t)n_maps;
-    if (n > s->cap) {
-        for (float **b : {&s->tsdf, &s->weight, &s->color}) { if (*b) (void)hipFree(*b); *b = nullptr; }
-        for (unsigned **b : {&s->vcount, &s->vbase, &s->tcount, &s->tbase}) { if (*b) (void)hipFree(*b); *b = nullptr; }
-        if (s->mask) (void)hipFree(s->mask);
-        s->mask = nullptr; s->cap = 0;
-        MCHK(hipMalloc(&s->tsdf, 4 * n)); MCHK(hipMalloc(&s->weight, 4 * n)); MCHK(hipMalloc(&s->color, 12 * n));
-        MCHK(hipMalloc(&s->mask, n));
-        MCHK(hipMalloc(&s->vcount, 4 * n)); MCHK(hipMalloc(&s->vbase, 4 * n));
-        MCHK(hipMalloc(&s->tcount, 4 * n)); MCHK(hipMalloc(&s->tbase, 4 * n));
-        s->cap = n;
-    }
-    if (n_maps > s->cap_maps) {
-        if (s->cams) (void)hipFree(s->cams);
-        if (s->slots) (void)hipFree(s->slots);
-        s->cams = nullptr; s->slots = nullptr; s->cap_maps = 0;
-        MCHK(hipMalloc(&s->cams, sizeof(float) * 12 * n_maps));
-        MCHK(hipMalloc(&s->slots, sizeof(int) * n_maps));
-        s->cap_maps = n_maps;
-    }
-    MCHK(hipMemcpyAsync(s->cams, poses_h, sizeof(float) * 12 * n_maps, hipMemcpyHostToDevice, st));
-    MCHK(hipMemcpyAsync(s->slots, slots_h, sizeof(int) * n_maps, hipMemcpyHostToDevice, st));
+    MCHK(s->tsdf.reserve(n, cache)); MCHK(s->weight.reserve(n, cache)); MCHK(s->color.reserve(3 * n, cache));
+    MCHK(s->mask.reserve(n, cache));
+    MCHK(s->vcount.reserve(n, cache)); MCHK(s->vbase.reserve(n, cache));
+    MCHK(s->tcount.reserve(n, cache)); MCHK(s->tbase.reserve(n, cache));
+    MCHK(s->cams.reserve(12 * (size_t)n_maps, cache));
+    MCHK(s->slots.reserve(n_maps, cache));
+    MCHK(hipMemcpyAsync(s->cams.get(), poses_h, sizeof(float) * 12 * n_maps, hipMemcpyHostToDevice, st));
+    MCHK(hipMemcpyAsync(s->slots.get(), slots_h, sizeof(int) * n_maps, hipMemcpyHostToDevice, st));
     if (!maps_on_device) {
-        MCHK(grow(&s->stage_depth, 4 * nmap, s->cap_stage_depth));
-        MCHK(grow(&s->stage_conf, 4 * nmap, s->cap_stage_conf));
-        MCHK(hipMemcpyAsync(s->stage_depth, depth, 4 * nmap, hipMemcpyHostToDevice, st));
-        MCHK(hipMemcpyAsync(s->stage_conf, conf, 4 * nmap, hipMemcpyHostToDevice, st));
-        depth = s->stage_depth; conf = s->stage_conf;
+        MCHK(s->stage_depth.reserve(nmap, cache));
+        MCHK(s->stage_conf.reserve(nmap, cache));
+        MCHK(hipMemcpyAsync(s->stage_depth.get(), depth, 4 * nmap, hipMemcpyHostToDevice, st));
+        MCHK(hipMemcpyAsync(s->stage_conf.get(), conf, 4 * nmap, hipMemcpyHostToDevice, st));
+        depth = s->stage_depth.get(); conf = s->stage_conf.get();
     }
     if (!bgr_on_device) {
-        MCHK(grow(&s->stage_bgr, 3 * hw * (size_t)bgr_images, s->cap_stage_bgr));
-        MCHK(hipMemcpyAsync(s->stage_bgr, bgr, 3 * hw * (size_t)bgr_images, hipMemcpyHostToDevice, st));
-        bgr = s->stage_bgr;
+        MCHK(s->stage_bgr.reserve(3 * hw * (size_t)bgr_images, cache));
+        MCHK(hipMemcpyAsync(s->stage_bgr.get(), bgr, 3 * hw * (size_t)bgr_images, hipMemcpyHostToDevice, st));
+        bgr = s->stage_bgr.get();
     }
     s->g = Grid{origin[0], origin[1], origin[2], voxel, dims[0], dims[1], dims[2]};
     s->n = n;
     Kmat km;
     for (int q = 0; q < 9; ++q) km.k[q] = K[q];
     hipLaunchKernelGGL(tsdf_integrate_kernel, grid_of(n), dim3(256), 0, st, depth, conf, (long long)nmap, bgr,
-                       (long long)(hw * (size_t)bgr_images), (const int *)s->slots, (const float *)s->cams, km, n_maps, H, W,
-                       min_views, trunc, s->g, s->tsdf, s->weight, s->color);
+                       (long long)(hw * (size_t)bgr_images), (const int *)s->slots.get(), (const float *)s->cams.get(), km, n_maps,
+                       H, W, min_views, trunc, s->g, s->tsdf.get(), s->weight.get(), s->color.get());
     MCHK(hipGetLastError());
     MCHK(hipStreamSynchronize(st));
     s->have_volume = true;
     return hipSuccess;
 }
 
-hipError_t tsdf_extract(TsdfState *s, long long *n_vertices, long long *n_faces, hipStream_t st)
+hipError_t tsdf_extract(TsdfState *s, ScratchCache &cache, long long *n_vertices, long long *n_faces, hipStream_t st)
 {
     s->have_mesh = false;
     const long long n = s->n;
     // (a) vertices
-    hipLaunchKernelGGL(edge_mask_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf, (const float *)s->weight, s->g,
-                       s->mask, s->vcount);
+    hipLaunchKernelGGL(edge_mask_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf.get(), (const float *)s->weight.get(),
+                       s->g, s->mask.get(), s->vcount.get());
     MCHK(hipGetLastError());
-    MCHK(exclusive_scan(s, s->vcount, s->vbase, n, st));
+    MCHK(exclusive_scan(s, cache, s->vcount.get(), s->vbase.get(), n, st));
     long long nv = 0;
-    MCHK(scan_total(s->vcount, s->vbase, n, &nv, st));
-    size_t cap = (size_t)s->cap_vertices;
-    if ((size_t)nv > cap || !s->verts) {
-        for (void **b : {(void **)&s->verts, (void **)&s->rgb, (void **)&s->verts2, (void **)&s->rgb2, (void **)&s->vused,
-                         (void **)&s->vnew}) {
-            if (*b) (void)hipFree(*b);
-            *b = nullptr;
-        }
-        s->cap_vertices = 0;
-        const size_t m = (size_t)(nv > 0 ? nv : 1);
-        MCHK(hipMalloc(&s->verts, 12 * m)); MCHK(hipMalloc(&s->rgb, 3 * m));
-        MCHK(hipMalloc(&s->verts2, 12 * m)); MCHK(hipMalloc(&s->rgb2, 3 * m));
-        MCHK(hipMalloc(&s->vused, 4 * m)); MCHK(hipMalloc(&s->vnew, 4 * m));
-        s->cap_vertices = nv;
-    }
-    hipLaunchKernelGGL(vertex_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf, (const float *)s->weight,
-                       (const float *)s->color, s->g, (const unsigned char *)s->mask, (const unsigned *)s->vbase, nv, s->verts, s->rgb);
+    MCHK(scan_total(s->vcount.get(), s->vbase.get(), n, &nv, st));
+    const size_t m = (size_t)(nv > 0 ? nv : 1);
+    MCHK(s->verts.reserve(3 * m, cache)); MCHK(s->rgb.reserve(3 * m, cache));
+    MCHK(s->verts2.reserve(3 * m, cache)); MCHK(s->rgb2.reserve(3 * m, cache));
+    MCHK(s->vused.reserve(m, cache)); MCHK(s->vnew.reserve(m, cache));
+    hipLaunchKernelGGL(vertex_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf.get(), (const float *)s->weight.get(),
+                       (const float *)s->color.get(), s->g, (const unsigned char *)s->mask.get(), (const unsigned *)s->vbase.get(), nv,
+                       s->verts.get(), s->rgb.get());
     MCHK(hipGetLastError());
     // (b) triangle counts
-    hipLaunchKernelGGL(tri_count_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf, (const float *)s->weight, s->g,
-                       s->tcount);
+    hipLaunchKernelGGL(tri_count_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf.get(), (const float *)s->weight.get(),
+                       s->g, s->tcount.get());
     MCHK(hipGetLastError());
-    MCHK(exclusive_scan(s, s->tcount, s->tbase, n, st));
+    MCHK(exclusive_scan(s, cache, s->tcount.get(), s->tbase.get(), n, st));
     long long nf = 0;
-    MCHK(scan_total(s->tcount, s->tbase, n, &nf, st));
-    size_t capf = (size_t)s->cap_faces;
-    if ((size_t)nf > capf || !s->faces) {
-        if (s->faces) (void)hipFree(s->faces);
-        s->faces = nullptr; s->cap_faces = 0;
-        MCHK(hipMalloc(&s->faces, 12 * (size_t)(nf > 0 ? nf : 1)));
-        s->cap_faces = nf;
-    }
+    MCHK(scan_total(s->tcount.get(), s->tbase.get(), n, &nf, st));
+    MCHK(s->faces.reserve(3 * (size_t)(nf > 0 ? nf : 1), cache));
     // (c) faces
-    hipLaunchKernelGGL(face_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf, (const float *)s->weight, s->g,
-                       (const unsigned char *)s->mask, (const unsigned *)s->vbase, nv, (const unsigned *)s->tcount,
-                       (const unsigned *)s->tbase, nf, s->faces);
+    hipLaunchKernelGGL(face_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf.get(), (const float *)s->weight.get(), s->g,
+                       (const unsigned char *)s->mask.get(), (const unsigned *)s->vbase.get(), nv, (const unsigned *)s->tcount.get(),
+                       (const unsigned *)s->tbase.get(), nf, s->faces.get());
     MCHK(hipGetLastError());
     // (d) keep the vertices the faces use, in their order
     long long kept = 0;
     if (nv > 0 && nf > 0) {
-        MCHK(hipMemsetAsync(s->vused, 0, 4 * (size_t)nv, st));
-        hipLaunchKernelGGL(vertex_used_kernel, grid_of(3 * nf), dim3(256), 0, st, (const int *)s->faces, 3 * nf, nv, s->vused);
+        MCHK(hipMemsetAsync(s->vused.get(), 0, 4 * (size_t)nv, st));
+        hipLaunchKernelGGL(vertex_used_kernel, grid_of(3 * nf), dim3(256), 0, st, (const int *)s->faces.get(), 3 * nf, nv,
+                           s->vused.get());
         MCHK(hipGetLastError());
-        MCHK(exclusive_scan(s, s->vused, s->vnew, nv, st));
-        MCHK(scan_total(s->vused, s->vnew, nv, &kept, st));
-        hipLaunchKernelGGL(vertex_compact_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->verts,
-                           (const unsigned char *)s->rgb, (const unsigned *)s->vused, (const unsigned *)s->vnew, nv, kept,
-                           s->verts2, s->rgb2);
+        MCHK(exclusive_scan(s, cache, s->vused.get(), s->vnew.get(), nv, st));
+        MCHK(scan_total(s->vused.get(), s->vnew.get(), nv, &kept, st));
+        hipLaunchKernelGGL(vertex_compact_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->verts.get(),
+                           (const unsigned char *)s->rgb.get(), (const unsigned *)s->vused.get(), (const unsigned *)s->vnew.get(), nv,
+                           kept, s->verts2.get(), s->rgb2.get());
         MCHK(hipGetLastError());
-        hipLaunchKernelGGL(face_renumber_kernel, grid_of(3 * nf), dim3(256), 0, st, s->faces, 3 * nf, nv, (const unsigned *)s->vnew);
+        hipLaunchKernelGGL(face_renumber_kernel, grid_of(3 * nf), dim3(256), 0, st, s->faces.get(), 3 * nf, nv,
+                           (const unsigned *)s->vnew.get());
         MCHK(hipGetLastError());
         std::swap(s->verts, s->verts2);
         std::swap(s->rgb, s->rgb2);
@@ -507,18 +461,18 @@ bool tsdf_has_mesh(const TsdfState *s) { return s && s->have_mesh; }
 hipError_t tsdf_fetch_mesh(TsdfState *s, float *verts, int *faces, unsigned char *rgb, hipStream_t st)
 {
     if (s->n_vertices > 0) {
-        if (verts) MCHK(hipMemcpyAsync(verts, s->verts, 12 * (size_t)s->n_vertices, hipMemcpyDeviceToHost, st));
-        if (rgb) MCHK(hipMemcpyAsync(rgb, s->rgb, 3 * (size_t)s->n_vertices, hipMemcpyDeviceToHost, st));
+        if (verts) MCHK(hipMemcpyAsync(verts, s->verts.get(), 12 * (size_t)s->n_vertices, hipMemcpyDeviceToHost, st));
+        if (rgb) MCHK(hipMemcpyAsync(rgb, s->rgb.get(), 3 * (size_t)s->n_vertices, hipMemcpyDeviceToHost, st));
     }
-    if (s->n_faces > 0 && faces) MCHK(hipMemcpyAsync(faces, s->faces, 12 * (size_t)s->n_faces, hipMemcpyDeviceToHost, st));
+    if (s->n_faces > 0 && faces) MCHK(hipMemcpyAsync(faces, s->faces.get(), 12 * (size_t)s->n_faces, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
 hipError_t tsdf_fetch_volume(TsdfState *s, float *tsdf, float *weight, float *color_sum, hipStream_t st)
 {
-    if (tsdf) MCHK(hipMemcpyAsync(tsdf, s->tsdf, 4 * (size_t)s->n, hipMemcpyDeviceToHost, st));
-    if (weight) MCHK(hipMemcpyAsync(weight, s->weight, 4 * (size_t)s->n, hipMemcpyDeviceToHost, st));
-    if (color_sum) MCHK(hipMemcpyAsync(color_sum, s->color, 12 * (size_t)s->n, hipMemcpyDeviceToHost, st));
+    if (tsdf) MCHK(hipMemcpyAsync(tsdf, s->tsdf.get(), 4 * (size_t)s->n, hipMemcpyDeviceToHost, st));
+    if (weight) MCHK(hipMemcpyAsync(weight, s->weight.get(), 4 * (size_t)s->n, hipMemcpyDeviceToHost, st));
+    if (color_sum) MCHK(hipMemcpyAsync(color_sum, s->color.get(), 12 * (size_t)s->n, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 

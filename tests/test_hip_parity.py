@@ -586,6 +586,58 @@ def test_knn_mean_distance_matches_sklearn(eng_a):
     np.testing.assert_allclose(eng_a.knn_mean_distance(tiny, 20), np.mean(dists[:, 1:], axis=1), rtol=1e-12)
 
 
+def test_two_contexts_reuse_device_blocks_concurrently(amvs_mod):
+    """Two contexts on one device, each driven by its own thread (the ctypes calls release the GIL), run the
+    post-steps that reuse cached scratch blocks -- kNN and fusion + filter -- on clouds and maps of overlapping
+    sizes: every result equals the same call made single-threaded before.  (Each context owns its cache, so
+    neither can be handed a block the other's stream is still using.)"""
+    import threading
+    from amvs.synthetic import make_scene
+    rng = np.random.default_rng(5)
+    jobs = []
+    try:
+        for H, W, n_pts in ((96, 128, (20000, 26000)), (120, 160, (23000, 31000))):
+            sc = make_scene(4, H, W, seed=H)
+            conf = rng.integers(0, 5, (3, H, W)).astype(np.float32)
+            fuse_args = (np.stack(sc.depths[:3]), conf, np.stack(sc.colors[:3]), np.linalg.inv(sc.camera.K.astype(np.float64)),
+                         [(sc.poses[v].R, sc.poses[v].t) for v in range(3)], 2)
+            clouds = [rng.normal(size=(n, 3)) for n in n_pts]
+            jobs.append((amvs_mod.Engine(H, W, 4, sc.camera.K.astype(np.float32), device=0), fuse_args, clouds))
+
+        def run(eng, fuse_args, clouds):
+            out = []
+            for pts in clouds:
+                out.append(eng.knn_mean_distance(pts, 20))
+                out.extend(eng.fuse_filter(*fuse_args, do_filter=True)[:2])
+            return out
+
+        want = [run(*job) for job in jobs]
+        assert all(len(w[1]) > 100 for w in want)           # the filter kept a real cloud
+        results, errors = [[] for _ in jobs], []
+
+        def worker(i):
+            try:
+                for _ in range(4):
+                    results[i].append(run(*jobs[i]))
+            except Exception as e:                           # re-raised in the main thread below
+                errors.append(e)
+
+        threads = [threading.Thread(target=worker, args=(i,)) for i in range(len(jobs))]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        assert not errors, errors
+        for i, reps in enumerate(results):
+            assert len(reps) == 4
+            for rep in reps:
+                for j, (got, ref) in enumerate(zip(rep, want[i])):
+                    assert np.array_equal(got, ref), f"context {i}, result {j} differs from the single-threaded call"
+    finally:
+        for eng, _, _ in jobs:
+            eng.close()
+
+
 def test_stereo_outlier_filter_device_equals_host(eng_a, amvs_mod):
     """DenseStereoReconstructor._filter_outliers with the device neighbour search selects exactly
     the points the scikit-learn path selects."""
