@@ -4,7 +4,11 @@ sizes, view counts, source counts, patch sizes, schedules (2-3 iterations, so th
 offsets of odd iterations run), batch sizes and both arithmetic modes -- every swept view against the
 CPU oracle.  Prints one line per case; exits non-zero on the first mismatch.
 
-    python tools/fuzz_parity.py [--cases 60] [--seed 1]
+    python tools/fuzz_parity.py [--cases 60] [--seed 1] [--sweep] [--content CLASS]
+
+--content draws the images of every case from tests/degenerate_images.py (flat areas, saturation, black borders, a
+constant source view, a checkerboard against flat sources, non-8-bit flat areas; "any" draws a class per case), as
+tests/test_hip_degenerate.py does; float content runs in the exact mode only.
 """
 import argparse
 import os
@@ -14,6 +18,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
@@ -22,15 +27,18 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--sweep", action="store_true", help="plane sweep instead of PatchMatch (random planes incl. "
                                                          "depths behind / near the source cameras, thresholds, strip heights)")
+    ap.add_argument("--content", default="texture", help="content class of tests/degenerate_images.py, or 'any'")
     args = ap.parse_args()
+    import degenerate_images as di
+    if args.content not in di.CLASSES + ("any",):
+        ap.error(f"--content: one of {', '.join(di.CLASSES)}, any")
     import amvs
     from amvs.engine import make_pm_params
-    from amvs.synthetic import make_scene
     from oracle import oracle
     oracle.set_threads(16)
     rng = np.random.default_rng(args.seed)
     if args.sweep:
-        return fuzz_sweep(args, rng, amvs, make_scene, oracle)
+        return fuzz_sweep(args, rng, amvs, di, oracle)
     for case in range(args.cases):
         n = int(rng.integers(3, 8))
         H, W = int(rng.integers(9, 150)), int(rng.integers(9, 200))
@@ -40,8 +48,7 @@ def main():
         mode = str(rng.choice(["fast", "exact"]))
         vpl = int(rng.choice([0, 1, 2]))
         rows = int(rng.choice([0, 0, 3, 8, 17]))
-        sc = make_scene(n, H, W, seed=int(rng.integers(1, 1000)), arc_step_deg=float(rng.choice([4.0, 10.0, 25.0])))
-        grays = [(np.round(g * 255.0).clip(0, 255).astype(np.uint8)).astype(np.float32) / np.float32(255.0) for g in sc.grays]
+        sc, grays, mode, content = _images(di, args, rng, n, H, W, [4.0, 10.0, 25.0], mode)
         refs = list(range(n))
         srcs = [[int(j) for j in rng.permutation([j for j in refs if j != r])[:S]] for r in refs]
         K = sc.camera.K.astype(np.float32)
@@ -61,7 +68,7 @@ def main():
                 same = (a == b) | (np.isnan(a) & np.isnan(b))
                 bad += int((~same).sum())
             ctx.close()
-        print(f"case {case}: {n} views {W}x{H} k={k} S={S} {iters}x(2+{samples}) {mode} vpl={vpl} rows={rows} {p.schedule}: "
+        print(f"case {case}: {content} {n} views {W}x{H} k={k} S={S} {iters}x(2+{samples}) {mode} vpl={vpl} rows={rows} {p.schedule}: "
               f"{'ok' if bad == 0 else str(bad) + ' ELEMENTS DIFFER'}", flush=True)
         if bad:
             sys.exit(1)
@@ -80,7 +87,15 @@ def report_index_checks():
             sys.exit(2)
 
 
-def fuzz_sweep(args, rng, amvs, make_scene, oracle):
+def _images(di, args, rng, n, H, W, arcs, mode):
+    """(scene, grays, mode, content class) of one case: make_scene's 8-bit images, or a degenerate class's."""
+    seed, arc = int(rng.integers(1, 1000)), float(rng.choice(arcs))
+    content = str(rng.choice(di.DEGENERATE)) if args.content == "any" else args.content
+    case = di.make_case(content, n, H, W, seed, ref=0, arc_step_deg=arc)
+    return case.scene, case.grays, "exact" if content == "float" else mode, content
+
+
+def fuzz_sweep(args, rng, amvs, di, oracle):
     for case in range(args.cases):
         n = int(rng.integers(3, 8))
         H, W = int(rng.integers(9, 150)), int(rng.integers(9, 200))
@@ -89,8 +104,7 @@ def fuzz_sweep(args, rng, amvs, make_scene, oracle):
         D = int(rng.integers(1, 40))
         mode = str(rng.choice(["fast", "exact"]))
         thresh = float(rng.choice([0.8, 0.5, 0.0, -0.3, 0.3, 0.97, 0.0005]))
-        sc = make_scene(n, H, W, seed=int(rng.integers(1, 1000)), arc_step_deg=float(rng.choice([4.0, 10.0, 40.0])))
-        grays = [(np.round(g * 255.0).clip(0, 255).astype(np.uint8)).astype(np.float32) / np.float32(255.0) for g in sc.grays]
+        sc, grays, mode, content = _images(di, args, rng, n, H, W, [4.0, 10.0, 40.0], mode)
         # planes from well in front of the scene to beyond it (wide arcs put some of them behind a source)
         depths = (1.0 / np.linspace(1 / (sc.depth_max * 3), 1 / (sc.depth_min * 0.2), D)).astype(np.float32)
         refs = list(range(n))
@@ -108,7 +122,7 @@ def fuzz_sweep(args, rng, amvs, make_scene, oracle):
                 od, oc = ctx.plane_sweep(depths, thresh)
                 bad += int((dm != od).sum()) + int((cf != oc).sum())
                 ctx.close()
-        print(f"sweep case {case}: {n} views {W}x{H} k={k} S={S} D={D} t={thresh} {mode}: "
+        print(f"sweep case {case}: {content} {n} views {W}x{H} k={k} S={S} D={D} t={thresh} {mode}: "
               f"{'ok' if bad == 0 else str(bad) + ' ELEMENTS DIFFER'}", flush=True)
         if bad:
             sys.exit(1)
