@@ -1,0 +1,46 @@
+// amvs_dispatch.h -- what is compiled in, each list once, and the run-time -> template-argument dispatch over
+// such a list.  Plain C++17 (no HIP).  A new patch size, source count, tap count or kNN k is one entry here.
+#pragma once
+#include <type_traits>
+#include <utility>
+
+namespace amvs {
+
+template <int... Vs> using IntList = std::integer_sequence<int, Vs...>;
+
+using CompiledPatches = IntList<3, 5, 7, 9, 11, 13, 15, 17, 19, 21, 23, 25, 27, 29>;   // patch sizes K with kernels of their own
+using SourceCounts = IntList<2, 3, 4, 5, 6>;                                             // source views S per reference view
+using ExtendedTaps = IntList<3, 4, 5, 6, 7>;                                             // extended mode: cost taps per axis
+using KnnSizes = IntList<8, 10, 16, 20, 32>;                                             // neighbours k of the kNN statistic
+
+template <int... Vs>
+constexpr bool in_list(IntList<Vs...>, int v) { return ((v == Vs) || ...); }
+
+template <int V0, int... Vs>
+constexpr int list_max(IntList<V0, Vs...>)
+{
+    int m = V0;
+    ((m = Vs > m ? Vs : m), ...);
+    return m;
+}
+
+// f(std::integral_constant<int, V>) for the entry V of the list that equals v (inside f, `c()` is that entry as a
+// constant expression); `miss` when v is not in the list
+template <int... Vs, class R, class F>
+R dispatch(IntList<Vs...>, int v, R miss, F &&f)
+{
+    R r = miss;
+    (void)((v == Vs && ((r = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return r;
+}
+
+// f(K, S) over the compiled patch sizes and the source counts; `miss` when either is not in its list
+template <class R, class F>
+R dispatch_ks(int K, int S, R miss, F &&f)
+{
+    return dispatch(CompiledPatches{}, K, miss, [&](auto k) {
+        return dispatch(SourceCounts{}, S, miss, [&](auto s) { return f(k, s); });
+    });
+}
+
+}  // namespace amvs

@@ -529,22 +529,16 @@ hipError_t launch_xpm_view_candidates(const XArgs &a, hipStream_t st)
 hipError_t launch_xpm_sweep(const XArgs &a, hipStream_t st)
 {
     const dim3 grid = xgrid(((long long)a.H * a.W + 1) / 2, 128, a.n_jobs), blk(128);
-    // taps per axis; the specialised cost needs patch = (N - 1) stride + 1 with 3 <= N <= 7
+    // taps per axis; the specialised cost needs patch = (N - 1) stride + 1 with N in ExtendedTaps (amvs_dispatch.h)
     const int n = (a.patch - 1) / a.stride + 1;
     const bool fits = (n - 1) * a.stride + 1 == a.patch;
     const bool u8 = a.pairs != nullptr;
-#define AMVS_XSWEEP(NT_)                                                                                      \
-    if (u8) hipLaunchKernelGGL((xpm_sweep_kernel<NT_, true>), grid, blk, 0, st, a);                              \
-    else hipLaunchKernelGGL((xpm_sweep_kernel<NT_, false>), grid, blk, 0, st, a)
-    switch (fits ? n : 0) {
-    case 3: AMVS_XSWEEP(3); break;
-    case 4: AMVS_XSWEEP(4); break;
-    case 5: AMVS_XSWEEP(5); break;
-    case 6: AMVS_XSWEEP(6); break;
-    case 7: AMVS_XSWEEP(7); break;
-    default: hipLaunchKernelGGL((xpm_sweep_kernel<0, false>), grid, blk, 0, st, a); break;
-    }
-#undef AMVS_XSWEEP
+    const bool specialised = dispatch(ExtendedTaps{}, fits ? n : 0, false, [&](auto nt) {
+        if (u8) hipLaunchKernelGGL((xpm_sweep_kernel<nt(), true>), grid, blk, 0, st, a);
+        else hipLaunchKernelGGL((xpm_sweep_kernel<nt(), false>), grid, blk, 0, st, a);
+        return true;
+    });
+    if (!specialised) hipLaunchKernelGGL((xpm_sweep_kernel<0, false>), grid, blk, 0, st, a);
     return hipGetLastError();
 }
 
@@ -554,18 +548,12 @@ hipError_t launch_xpm_eval(const XArgs &a, float *cost_out, hipStream_t st)
     const int n = (a.patch - 1) / a.stride + 1;
     const bool fits = (n - 1) * a.stride + 1 == a.patch;
     const bool u8 = a.pairs != nullptr;
-#define AMVS_XEVAL(NT_)                                                                                       \
-    if (u8) hipLaunchKernelGGL((xpm_eval_kernel<NT_, true>), grid, blk, 0, st, a, cost_out);                     \
-    else hipLaunchKernelGGL((xpm_eval_kernel<NT_, false>), grid, blk, 0, st, a, cost_out)
-    switch (fits ? n : 0) {
-    case 3: AMVS_XEVAL(3); break;
-    case 4: AMVS_XEVAL(4); break;
-    case 5: AMVS_XEVAL(5); break;
-    case 6: AMVS_XEVAL(6); break;
-    case 7: AMVS_XEVAL(7); break;
-    default: hipLaunchKernelGGL((xpm_eval_kernel<0, false>), grid, blk, 0, st, a, cost_out); break;
-    }
-#undef AMVS_XEVAL
+    const bool specialised = dispatch(ExtendedTaps{}, fits ? n : 0, false, [&](auto nt) {
+        if (u8) hipLaunchKernelGGL((xpm_eval_kernel<nt(), true>), grid, blk, 0, st, a, cost_out);
+        else hipLaunchKernelGGL((xpm_eval_kernel<nt(), false>), grid, blk, 0, st, a, cost_out);
+        return true;
+    });
+    if (!specialised) hipLaunchKernelGGL((xpm_eval_kernel<0, false>), grid, blk, 0, st, a, cost_out);
     return hipGetLastError();
 }
 

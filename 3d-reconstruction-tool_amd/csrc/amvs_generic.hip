@@ -554,27 +554,13 @@ bool generic_patch_ok(int K) { return K >= 3 && K <= AMVS_MAX_PATCH && (K & 1) =
 hipError_t launch_step_generic(int K, int S, const StepArgs &a, hipStream_t st)
 {
     if (!generic_patch_ok(K) || a.paired || a.presampled) return hipErrorInvalidValue;
-    switch (S) {
-    case 2: return launch_step_generic_s<2>(K, a, st);
-    case 3: return launch_step_generic_s<3>(K, a, st);
-    case 4: return launch_step_generic_s<4>(K, a, st);
-    case 5: return launch_step_generic_s<5>(K, a, st);
-    case 6: return launch_step_generic_s<6>(K, a, st);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch(SourceCounts{}, S, hipErrorInvalidValue, [&](auto s) { return launch_step_generic_s<s()>(K, a, st); });
 }
 
 hipError_t launch_sweep_generic(int K, int S, const SweepArgs &a, hipStream_t st)
 {
     if (!generic_patch_ok(K)) return hipErrorInvalidValue;
-    switch (S) {
-    case 2: return launch_sweep_generic_s<2>(K, a, st);
-    case 3: return launch_sweep_generic_s<3>(K, a, st);
-    case 4: return launch_sweep_generic_s<4>(K, a, st);
-    case 5: return launch_sweep_generic_s<5>(K, a, st);
-    case 6: return launch_sweep_generic_s<6>(K, a, st);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch(SourceCounts{}, S, hipErrorInvalidValue, [&](auto s) { return launch_sweep_generic_s<s()>(K, a, st); });
 }
 
 // resident waves per CU of the generic step: LDS-limited (its rings), at most 16

@@ -3,6 +3,7 @@
 #pragma once
 #include "amvs_kernels.h"
 #include "amvs_device.h"
+#include "amvs_dispatch.h"
 
 #include <type_traits>
 
@@ -142,6 +143,18 @@ AMVS_DEV void propagate_normals(const uint32_t *nq, int head, int n, int lane, f
 #endif
 constexpr int PAIR_WAVES = 2 * AMVS_PAIR_COLS;
 constexpr bool step_pair_supported_ks(int K, int S) { return K >= 5 && K <= 11 && S <= 4; }
+
+static_assert(list_max(SourceCounts{}) == AMVS_KMAX_SRC, "SourceCounts ends at AMVS_KMAX_SRC (Job::src, Job::fsrc)");
+static_assert(list_max(CompiledPatches{}) <= AMVS_MAX_PATCH, "a compiled patch size beyond AMVS_MAX_PATCH");
+
+// The step kernels are specialised for these two modes; every other mode runs their <-1> instantiation, which
+// reads the mode from StepArgs.  The paired-band schedule exists for the listed modes only.
+using StepModes = IntList<MODE_REFINE, MODE_PROP>;
+template <class F>
+void dispatch_step_mode(int mode, F &&f)
+{
+    if (!dispatch(StepModes{}, mode, false, [&](auto m) { return f(m), true; })) f(std::integral_constant<int, -1>{});
+}
 
 #if defined(AMVS_HSUM_LDS) && AMVS_WG_WAVES > 1
 #error "the LDS horizontal-sum variant keeps one exchange buffer per workgroup: build it with -DAMVS_WG_WAVES=1"

@@ -122,8 +122,8 @@ struct SweepArgs : StepArgsBase {
 };
 
 bool patch_supported(int K);          // any odd patch size in 3 .. AMVS_MAX_PATCH
-bool patch_compiled(int K);           // ... with kernels specialised at compile time (3, 5, ..., 29); the others run
-                                      // the run-time-k kernels of amvs_generic.hip
+bool patch_compiled(int K);           // ... with kernels specialised at compile time (CompiledPatches, amvs_dispatch.h);
+                                      // the others run the run-time-k kernels of amvs_generic.hip
 // amvs_generic.hip: sweep step / plane sweep / statistics with the patch size as a launch argument (both
 // arithmetic modes, classic schedule); launch_step / launch_sweep / launch_box_stats / launch_fast_stats forward
 // to these for patch sizes that are not compiled in
@@ -147,8 +147,9 @@ hipError_t launch_step_fast(int K, int S, const StepArgs &a, hipStream_t st);
 hipError_t launch_sample_fast(int S, const StepArgs &a, hipStream_t st);      // split schedule, first half
 hipError_t launch_sweep_fast(int K, int S, const SweepArgs &a, hipStream_t st);
 int step_fast_waves_per_cu(int K, int S, int wg_cap = 0);
+// the paired-band schedule is compiled for this patch / source count: fast arithmetic, exact arithmetic (packed 8-bit maps)
 bool step_fast_pair_supported(int K, int S);
-bool step_pair_supported(int K, int S);            // ... of the exact arithmetic (packed 8-bit maps)       // the paired-band schedule is compiled for this patch / source count
+bool step_pair_supported(int K, int S);
 // test hook: per-source samples [S][H*W] and validity bits [H*W] of job 0 at the depth map a.d_in;
 // a.TH carries k/2, a.mode selects the bounds (MODE_EVAL patch bounds, MODE_CONF image bounds,
 // MODE_EVAL + 100 depth test only = plane sweep)

@@ -445,14 +445,7 @@ static hipError_t launch_sample_dump_s(const StepArgs &a, float *out, unsigned c
 hipError_t launch_sample_dump(int S, const StepArgs &a, float *out, unsigned char *valid_out, hipStream_t st)
 {
     if (a.fast) return launch_sample_dump_fast(S, a, out, valid_out, st);
-    switch (S) {
-    case 2: return launch_sample_dump_s<2>(a, out, valid_out, st);
-    case 3: return launch_sample_dump_s<3>(a, out, valid_out, st);
-    case 4: return launch_sample_dump_s<4>(a, out, valid_out, st);
-    case 5: return launch_sample_dump_s<5>(a, out, valid_out, st);
-    case 6: return launch_sample_dump_s<6>(a, out, valid_out, st);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch(SourceCounts{}, S, hipErrorInvalidValue, [&](auto s) { return launch_sample_dump_s<s()>(a, out, valid_out, st); });
 }
 
 // ------------------------------------------------------------------ ref stats ----
@@ -678,43 +671,25 @@ static hipError_t launch_step_ks(const StepArgs &a, int nblk, hipStream_t st)
 {
     const int nwg = (nblk + AMVS_WG_WAVES - 1) / AMVS_WG_WAVES;
     const dim3 grid(nwg), block(AMVS_WAVE * AMVS_WG_WAVES);
-#define AMVS_LAUNCH_STEP(U8, M) \
-    hipLaunchKernelGGL((pm_step_kernel<K, S, U8, M>), grid, block, (step_extra_lds<&pm_step_kernel<K, S, U8, M>>(a.wg_cap)), st, a)
     if constexpr (step_pair_supported_ks(K, S)) {
-        if (a.pairs && a.paired && (a.mode == MODE_REFINE || a.mode == MODE_PROP)) {
+        if (a.pairs && a.paired && in_list(StepModes{}, a.mode)) {
             const int pwg = a.n_jobs * ((a.tiles_x + AMVS_PAIR_COLS - 1) / AMVS_PAIR_COLS) * ((a.tiles_y + 1) / 2);
             const dim3 pgrid(pwg), pblock(AMVS_WAVE * PAIR_WAVES);
-            if (a.mode == MODE_REFINE)
-                hipLaunchKernelGGL((pm_step_kernel<K, S, true, MODE_REFINE, true>), pgrid, pblock,
-                                   (step_extra_lds<&pm_step_kernel<K, S, true, MODE_REFINE, true>>(a.wg_cap)), st, a);
-            else
-                hipLaunchKernelGGL((pm_step_kernel<K, S, true, MODE_PROP, true>), pgrid, pblock,
-                                   (step_extra_lds<&pm_step_kernel<K, S, true, MODE_PROP, true>>(a.wg_cap)), st, a);
-            return hipGetLastError();
+            return dispatch(StepModes{}, a.mode, hipErrorInvalidValue, [&](auto m) {
+                hipLaunchKernelGGL((pm_step_kernel<K, S, true, m(), true>), pgrid, pblock,
+                                   (step_extra_lds<&pm_step_kernel<K, S, true, m(), true>>(a.wg_cap)), st, a);
+                return hipGetLastError();
+            });
         }
     }
-    if (a.pairs) {
-        if (a.mode == MODE_REFINE) AMVS_LAUNCH_STEP(true, MODE_REFINE);
-        else if (a.mode == MODE_PROP) AMVS_LAUNCH_STEP(true, MODE_PROP);
-        else AMVS_LAUNCH_STEP(true, -1);
-    } else {
-        if (a.mode == MODE_REFINE) AMVS_LAUNCH_STEP(false, MODE_REFINE);
-        else if (a.mode == MODE_PROP) AMVS_LAUNCH_STEP(false, MODE_PROP);
-        else AMVS_LAUNCH_STEP(false, -1);
-    }
-#undef AMVS_LAUNCH_STEP
+    dispatch_step_mode(a.mode, [&](auto m) {
+        if (a.pairs)
+            hipLaunchKernelGGL((pm_step_kernel<K, S, true, m()>), grid, block, (step_extra_lds<&pm_step_kernel<K, S, true, m()>>(a.wg_cap)), st, a);
+        else
+            hipLaunchKernelGGL((pm_step_kernel<K, S, false, m()>), grid, block, (step_extra_lds<&pm_step_kernel<K, S, false, m()>>(a.wg_cap)), st, a);
+    });
     return hipGetLastError();
 }
-
-#define AMVS_FOR_S(K, FN, ...)                                      \
-    switch (S) {                                                    \
-    case 2: return FN<K, 2>(__VA_ARGS__);                           \
-    case 3: return FN<K, 3>(__VA_ARGS__);                           \
-    case 4: return FN<K, 4>(__VA_ARGS__);                           \
-    case 5: return FN<K, 5>(__VA_ARGS__);                           \
-    case 6: return FN<K, 6>(__VA_ARGS__);                           \
-    default: return decltype(FN<K, 2>(__VA_ARGS__))(1);             \
-    }
 
 template <int K, int S>
 static int step_occupancy_ks(bool u8, int wg_cap)
@@ -731,28 +706,13 @@ static int step_occupancy_ks(bool u8, int wg_cap)
 // resident waves per CU of the sweep kernel (register-limited)
 int step_waves_per_cu(int K, int S, bool u8, int wg_cap)
 {
-    switch (K) {
-    case 3: AMVS_FOR_S(3, step_occupancy_ks, u8, wg_cap)
-    case 5: AMVS_FOR_S(5, step_occupancy_ks, u8, wg_cap)
-    case 7: AMVS_FOR_S(7, step_occupancy_ks, u8, wg_cap)
-    case 9: AMVS_FOR_S(9, step_occupancy_ks, u8, wg_cap)
-    case 11: AMVS_FOR_S(11, step_occupancy_ks, u8, wg_cap)
-    case 13: AMVS_FOR_S(13, step_occupancy_ks, u8, wg_cap)
-    case 15: AMVS_FOR_S(15, step_occupancy_ks, u8, wg_cap)
-    case 17: AMVS_FOR_S(17, step_occupancy_ks, u8, wg_cap)
-    case 19: AMVS_FOR_S(19, step_occupancy_ks, u8, wg_cap)
-    case 21: AMVS_FOR_S(21, step_occupancy_ks, u8, wg_cap)
-    case 23: AMVS_FOR_S(23, step_occupancy_ks, u8, wg_cap)
-    case 25: AMVS_FOR_S(25, step_occupancy_ks, u8, wg_cap)
-    case 27: AMVS_FOR_S(27, step_occupancy_ks, u8, wg_cap)
-    case 29: AMVS_FOR_S(29, step_occupancy_ks, u8, wg_cap)
-    default: return step_generic_waves_per_cu(K, S);
-    }
+    if (!patch_compiled(K)) return step_generic_waves_per_cu(K, S);
+    return dispatch_ks(K, S, 1, [&](auto k, auto s) { return step_occupancy_ks<k(), s()>(u8, wg_cap); });    // (1: S not compiled)
 }
 
-bool patch_compiled(int K) { return K >= 3 && K <= 29 && (K & 1) == 1; }
+bool patch_compiled(int K) { return in_list(CompiledPatches{}, K); }
 bool patch_supported(int K) { return K >= 3 && K <= AMVS_MAX_PATCH && (K & 1) == 1; }
-bool step_pair_supported(int K, int S) { return patch_compiled(K) && S >= 2 && S <= AMVS_KMAX_SRC && step_pair_supported_ks(K, S); }
+bool step_pair_supported(int K, int S) { return patch_compiled(K) && in_list(SourceCounts{}, S) && step_pair_supported_ks(K, S); }
 int strip_out_width(int K) { return AMVS_WAVE - 2 * (K / 2); }
 
 hipError_t launch_step(int K, int S, const StepArgs &a, hipStream_t st)
@@ -760,23 +720,7 @@ hipError_t launch_step(int K, int S, const StepArgs &a, hipStream_t st)
     if (!patch_compiled(K)) return launch_step_generic(K, S, a, st);
     if (a.fast) return launch_step_fast(K, S, a, st);
     const int nblk = a.n_jobs * a.tiles_x * a.tiles_y;
-    switch (K) {
-    case 3: AMVS_FOR_S(3, launch_step_ks, a, nblk, st)
-    case 5: AMVS_FOR_S(5, launch_step_ks, a, nblk, st)
-    case 7: AMVS_FOR_S(7, launch_step_ks, a, nblk, st)
-    case 9: AMVS_FOR_S(9, launch_step_ks, a, nblk, st)
-    case 11: AMVS_FOR_S(11, launch_step_ks, a, nblk, st)
-    case 13: AMVS_FOR_S(13, launch_step_ks, a, nblk, st)
-    case 15: AMVS_FOR_S(15, launch_step_ks, a, nblk, st)
-    case 17: AMVS_FOR_S(17, launch_step_ks, a, nblk, st)
-    case 19: AMVS_FOR_S(19, launch_step_ks, a, nblk, st)
-    case 21: AMVS_FOR_S(21, launch_step_ks, a, nblk, st)
-    case 23: AMVS_FOR_S(23, launch_step_ks, a, nblk, st)
-    case 25: AMVS_FOR_S(25, launch_step_ks, a, nblk, st)
-    case 27: AMVS_FOR_S(27, launch_step_ks, a, nblk, st)
-    case 29: AMVS_FOR_S(29, launch_step_ks, a, nblk, st)
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_ks(K, S, hipErrorInvalidValue, [&](auto k, auto s) { return launch_step_ks<k(), s()>(a, nblk, st); });
 }
 
 hipError_t launch_box_stats(int K, const float *images, long long img_stride, int H, int W,
@@ -788,66 +732,11 @@ hipError_t launch_box_stats(int K, const float *images, long long img_stride, in
     const int tiles_x = (W + strip_out_width(K) - 1) / strip_out_width(K);
     const int tiles_y = (H + TH - 1) / TH;
     const dim3 grid(n_img * tiles_x * tiles_y), blk(AMVS_WAVE);
-    switch (K) {
-    case 3:
-        hipLaunchKernelGGL((box_stats_kernel<3>), grid, blk, 0, st, images, img_stride, H, W, TH,
+    return dispatch(CompiledPatches{}, K, hipErrorInvalidValue, [&](auto k) {
+        hipLaunchKernelGGL((box_stats_kernel<k()>), grid, blk, 0, st, images, img_stride, H, W, TH,
                            tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    case 9:
-        hipLaunchKernelGGL((box_stats_kernel<9>), grid, blk, 0, st, images, img_stride, H, W, TH,
-                           tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    case 5:
-        hipLaunchKernelGGL((box_stats_kernel<5>), grid, blk, 0, st, images, img_stride, H, W, TH,
-                           tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    case 7:
-        hipLaunchKernelGGL((box_stats_kernel<7>), grid, blk, 0, st, images, img_stride, H, W, TH,
-                           tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    case 11:
-        hipLaunchKernelGGL((box_stats_kernel<11>), grid, blk, 0, st, images, img_stride, H, W, TH,
-                           tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    case 13:
-        hipLaunchKernelGGL((box_stats_kernel<13>), grid, blk, 0, st, images, img_stride, H, W, TH,
-                           tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    case 15:
-        hipLaunchKernelGGL((box_stats_kernel<15>), grid, blk, 0, st, images, img_stride, H, W, TH,
-                           tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    case 17:
-        hipLaunchKernelGGL((box_stats_kernel<17>), grid, blk, 0, st, images, img_stride, H, W, TH,
-                           tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    case 19:
-        hipLaunchKernelGGL((box_stats_kernel<19>), grid, blk, 0, st, images, img_stride, H, W, TH,
-                           tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    case 21:
-        hipLaunchKernelGGL((box_stats_kernel<21>), grid, blk, 0, st, images, img_stride, H, W, TH,
-                           tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    case 23:
-        hipLaunchKernelGGL((box_stats_kernel<23>), grid, blk, 0, st, images, img_stride, H, W, TH,
-                           tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    case 25:
-        hipLaunchKernelGGL((box_stats_kernel<25>), grid, blk, 0, st, images, img_stride, H, W, TH,
-                           tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    case 27:
-        hipLaunchKernelGGL((box_stats_kernel<27>), grid, blk, 0, st, images, img_stride, H, W, TH,
-                           tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    case 29:
-        hipLaunchKernelGGL((box_stats_kernel<29>), grid, blk, 0, st, images, img_stride, H, W, TH,
-                           tiles_x, tiles_y, first_img, mean_out, var_out);
-        break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_init(const Job *jobs, int n_jobs, long long HW, unsigned long long seed,

@@ -462,14 +462,7 @@ static hipError_t launch_sample_dump_fast_s(const StepArgs &a, float *out, unsig
 
 hipError_t launch_sample_dump_fast(int S, const StepArgs &a, float *out, unsigned char *valid_out, hipStream_t st)
 {
-    switch (S) {
-    case 2: return launch_sample_dump_fast_s<2>(a, out, valid_out, st);
-    case 3: return launch_sample_dump_fast_s<3>(a, out, valid_out, st);
-    case 4: return launch_sample_dump_fast_s<4>(a, out, valid_out, st);
-    case 5: return launch_sample_dump_fast_s<5>(a, out, valid_out, st);
-    case 6: return launch_sample_dump_fast_s<6>(a, out, valid_out, st);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch(SourceCounts{}, S, hipErrorInvalidValue, [&](auto s) { return launch_sample_dump_fast_s<s()>(a, out, valid_out, st); });
 }
 
 // ------------------------------------------------------------------ ref stats ----
@@ -508,24 +501,10 @@ hipError_t launch_fast_stats(int K, const uint16_t *pairs_view, int H, int W, fl
     if (!patch_compiled(K)) return launch_fast_stats_generic(K, pairs_view, H, W, out, st);
     const long long n = (long long)H * W;
     const dim3 grid((unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192)), blk(256);
-    switch (K) {
-    case 3: hipLaunchKernelGGL((fast_stats_kernel<3>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    case 5: hipLaunchKernelGGL((fast_stats_kernel<5>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    case 7: hipLaunchKernelGGL((fast_stats_kernel<7>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    case 9: hipLaunchKernelGGL((fast_stats_kernel<9>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    case 11: hipLaunchKernelGGL((fast_stats_kernel<11>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    case 13: hipLaunchKernelGGL((fast_stats_kernel<13>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    case 15: hipLaunchKernelGGL((fast_stats_kernel<15>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    case 17: hipLaunchKernelGGL((fast_stats_kernel<17>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    case 19: hipLaunchKernelGGL((fast_stats_kernel<19>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    case 21: hipLaunchKernelGGL((fast_stats_kernel<21>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    case 23: hipLaunchKernelGGL((fast_stats_kernel<23>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    case 25: hipLaunchKernelGGL((fast_stats_kernel<25>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    case 27: hipLaunchKernelGGL((fast_stats_kernel<27>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    case 29: hipLaunchKernelGGL((fast_stats_kernel<29>), grid, blk, 0, st, pairs_view, H, W, out); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch(CompiledPatches{}, K, hipErrorInvalidValue, [&](auto k) {
+        hipLaunchKernelGGL((fast_stats_kernel<k()>), grid, blk, 0, st, pairs_view, H, W, out);
+        return hipGetLastError();
+    });
 }
 
 // ------------------------------------------------------------------ host side ----
@@ -568,27 +547,22 @@ static hipError_t launch_step_fast_ks(const StepArgs &a, int nblk, hipStream_t s
     const dim3 grid(nwg), block(AMVS_WAVE * AMVS_WG_WAVES);
     if (a.presampled) {
         if (!a.samples) return hipErrorInvalidValue;
-        if (a.mode == MODE_REFINE) hipLaunchKernelGGL((pm_step_fast_kernel<K, S, MODE_REFINE, true>), grid, block, 0, st, a);
-        else if (a.mode == MODE_PROP) hipLaunchKernelGGL((pm_step_fast_kernel<K, S, MODE_PROP, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((pm_step_fast_kernel<K, S, -1, true>), grid, block, 0, st, a);
+        dispatch_step_mode(a.mode, [&](auto m) { hipLaunchKernelGGL((pm_step_fast_kernel<K, S, m(), true>), grid, block, 0, st, a); });
         return hipGetLastError();
     }
     if constexpr (fast_pair_supported(K, S)) {
-        if (a.paired && (a.mode == MODE_REFINE || a.mode == MODE_PROP)) {
+        if (a.paired && in_list(StepModes{}, a.mode)) {
             const int pwg = a.n_jobs * ((a.tiles_x + AMVS_PAIR_COLS - 1) / AMVS_PAIR_COLS) * ((a.tiles_y + 1) / 2);
             const unsigned PXL = StepLds<K, S>::extra(a.wg_cap, true);
             const dim3 pblock(AMVS_WAVE * PAIR_WAVES);
-            if (a.mode == MODE_REFINE)
-                hipLaunchKernelGGL((pm_step_fast_kernel<K, S, MODE_REFINE, false, true>), dim3(pwg), pblock, PXL, st, a);
-            else
-                hipLaunchKernelGGL((pm_step_fast_kernel<K, S, MODE_PROP, false, true>), dim3(pwg), pblock, PXL, st, a);
-            return hipGetLastError();
+            return dispatch(StepModes{}, a.mode, hipErrorInvalidValue, [&](auto m) {
+                hipLaunchKernelGGL((pm_step_fast_kernel<K, S, m(), false, true>), dim3(pwg), pblock, PXL, st, a);
+                return hipGetLastError();
+            });
         }
     }
     const unsigned XL = StepLds<K, S>::extra(a.wg_cap);
-    if (a.mode == MODE_REFINE) hipLaunchKernelGGL((pm_step_fast_kernel<K, S, MODE_REFINE>), grid, block, XL, st, a);
-    else if (a.mode == MODE_PROP) hipLaunchKernelGGL((pm_step_fast_kernel<K, S, MODE_PROP>), grid, block, XL, st, a);
-    else hipLaunchKernelGGL((pm_step_fast_kernel<K, S, -1>), grid, block, XL, st, a);
+    dispatch_step_mode(a.mode, [&](auto m) { hipLaunchKernelGGL((pm_step_fast_kernel<K, S, m()>), grid, block, XL, st, a); });
     return hipGetLastError();
 }
 
@@ -602,60 +576,19 @@ static int step_fast_occupancy_ks(int wg_cap)
     return e == hipSuccess && n > 0 ? n * AMVS_WG_WAVES : 8;
 }
 
-#define AMVS_FOR_S(K, FN, ...)                                      \
-    switch (S) {                                                    \
-    case 2: return FN<K, 2>(__VA_ARGS__);                           \
-    case 3: return FN<K, 3>(__VA_ARGS__);                           \
-    case 4: return FN<K, 4>(__VA_ARGS__);                           \
-    case 5: return FN<K, 5>(__VA_ARGS__);                           \
-    case 6: return FN<K, 6>(__VA_ARGS__);                           \
-    default: return decltype(FN<K, 2>(__VA_ARGS__))(1);             \
-    }
-
 int step_fast_waves_per_cu(int K, int S, int wg_cap)
 {
-    switch (K) {
-    case 3: AMVS_FOR_S(3, step_fast_occupancy_ks, wg_cap)
-    case 5: AMVS_FOR_S(5, step_fast_occupancy_ks, wg_cap)
-    case 7: AMVS_FOR_S(7, step_fast_occupancy_ks, wg_cap)
-    case 9: AMVS_FOR_S(9, step_fast_occupancy_ks, wg_cap)
-    case 11: AMVS_FOR_S(11, step_fast_occupancy_ks, wg_cap)
-    case 13: AMVS_FOR_S(13, step_fast_occupancy_ks, wg_cap)
-    case 15: AMVS_FOR_S(15, step_fast_occupancy_ks, wg_cap)
-    case 17: AMVS_FOR_S(17, step_fast_occupancy_ks, wg_cap)
-    case 19: AMVS_FOR_S(19, step_fast_occupancy_ks, wg_cap)
-    case 21: AMVS_FOR_S(21, step_fast_occupancy_ks, wg_cap)
-    case 23: AMVS_FOR_S(23, step_fast_occupancy_ks, wg_cap)
-    case 25: AMVS_FOR_S(25, step_fast_occupancy_ks, wg_cap)
-    case 27: AMVS_FOR_S(27, step_fast_occupancy_ks, wg_cap)
-    case 29: AMVS_FOR_S(29, step_fast_occupancy_ks, wg_cap)
-    default: return step_generic_waves_per_cu(K, S);
-    }
+    if (!patch_compiled(K)) return step_generic_waves_per_cu(K, S);
+    return dispatch_ks(K, S, 1, [&](auto k, auto s) { return step_fast_occupancy_ks<k(), s()>(wg_cap); });    // (1: S not compiled)
 }
 
-bool step_fast_pair_supported(int K, int S) { return patch_compiled(K) && S >= 2 && S <= AMVS_KMAX_SRC && fast_pair_supported(K, S); }
+bool step_fast_pair_supported(int K, int S) { return patch_compiled(K) && in_list(SourceCounts{}, S) && fast_pair_supported(K, S); }
 
 hipError_t launch_step_fast(int K, int S, const StepArgs &a, hipStream_t st)
 {
     if (!a.pairs) return hipErrorInvalidValue;        // fast mode samples the packed 8-bit maps only
     const int nblk = a.n_jobs * a.tiles_x * a.tiles_y;
-    switch (K) {
-    case 3: AMVS_FOR_S(3, launch_step_fast_ks, a, nblk, st)
-    case 5: AMVS_FOR_S(5, launch_step_fast_ks, a, nblk, st)
-    case 7: AMVS_FOR_S(7, launch_step_fast_ks, a, nblk, st)
-    case 9: AMVS_FOR_S(9, launch_step_fast_ks, a, nblk, st)
-    case 11: AMVS_FOR_S(11, launch_step_fast_ks, a, nblk, st)
-    case 13: AMVS_FOR_S(13, launch_step_fast_ks, a, nblk, st)
-    case 15: AMVS_FOR_S(15, launch_step_fast_ks, a, nblk, st)
-    case 17: AMVS_FOR_S(17, launch_step_fast_ks, a, nblk, st)
-    case 19: AMVS_FOR_S(19, launch_step_fast_ks, a, nblk, st)
-    case 21: AMVS_FOR_S(21, launch_step_fast_ks, a, nblk, st)
-    case 23: AMVS_FOR_S(23, launch_step_fast_ks, a, nblk, st)
-    case 25: AMVS_FOR_S(25, launch_step_fast_ks, a, nblk, st)
-    case 27: AMVS_FOR_S(27, launch_step_fast_ks, a, nblk, st)
-    case 29: AMVS_FOR_S(29, launch_step_fast_ks, a, nblk, st)
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_ks(K, S, hipErrorInvalidValue, [&](auto k, auto s) { return launch_step_fast_ks<k(), s()>(a, nblk, st); });
 }
 
 // Resident workgroups of the sampling kernel per CU when it runs alone, through unused dynamic LDS;
@@ -670,23 +603,14 @@ static hipError_t launch_sample_fast_s(const StepArgs &a, hipStream_t st)
     const int nblk = a.n_jobs * a.s_tiles_x * a.s_tiles_y;
     const dim3 grid((nblk + AMVS_WG_WAVES - 1) / AMVS_WG_WAVES), block(AMVS_WAVE * AMVS_WG_WAVES);
     const unsigned XL = a.s_lds > 0 ? (unsigned)a.s_lds : (unsigned)AMVS_SAMPLE_LDS_BYTES;
-    if (a.mode == MODE_REFINE) hipLaunchKernelGGL((pm_sample_fast_kernel<S, MODE_REFINE>), grid, block, XL, st, a);
-    else if (a.mode == MODE_PROP) hipLaunchKernelGGL((pm_sample_fast_kernel<S, MODE_PROP>), grid, block, XL, st, a);
-    else hipLaunchKernelGGL((pm_sample_fast_kernel<S, -1>), grid, block, XL, st, a);
+    dispatch_step_mode(a.mode, [&](auto m) { hipLaunchKernelGGL((pm_sample_fast_kernel<S, m()>), grid, block, XL, st, a); });
     return hipGetLastError();
 }
 
 hipError_t launch_sample_fast(int S, const StepArgs &a, hipStream_t st)
 {
     if (!a.pairs || !a.samples || a.s_TH < 1) return hipErrorInvalidValue;
-    switch (S) {
-    case 2: return launch_sample_fast_s<2>(a, st);
-    case 3: return launch_sample_fast_s<3>(a, st);
-    case 4: return launch_sample_fast_s<4>(a, st);
-    case 5: return launch_sample_fast_s<5>(a, st);
-    case 6: return launch_sample_fast_s<6>(a, st);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch(SourceCounts{}, S, hipErrorInvalidValue, [&](auto s) { return launch_sample_fast_s<s()>(a, st); });
 }
 
 }  // namespace amvs

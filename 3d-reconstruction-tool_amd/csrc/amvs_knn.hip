@@ -20,6 +20,7 @@
 #include "amvs_check.h"
 #include "amvs_kernels.h"
 #include "amvs_buffer.h"
+#include "amvs_dispatch.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -363,7 +364,7 @@ hipError_t launch_query(const double *sorted, long long n, const Grid &gr, const
 
 }  // namespace
 
-bool knn_supported(int k) { return k == 8 || k == 10 || k == 16 || k == 20 || k == 32; }
+bool knn_supported(int k) { return in_list(KnnSizes{}, k); }
 
 // points: [n][3] float64 on the host (or on the device: points_on_device); mean_out: host [n].  Needs n >= k.
 hipError_t knn_mean_distance(const double *points, long long n, int k, double *mean_out, ScratchCache &cache, hipStream_t st,
@@ -478,14 +479,9 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
         hipLaunchKernelGGL(knn_place_kernel, dim3(bx), dim3(256), 0, st, d_pts, n, d_cell, d_start, d_count,
                            d_sorted, d_origin, cells);
         KCHK(hipGetLastError());
-        switch (k) {
-        case 8: return launch_query<8>(d_sorted, n, gr, d_start, d_origin, d_pending, max_shells, d_mean, st);
-        case 10: return launch_query<10>(d_sorted, n, gr, d_start, d_origin, d_pending, max_shells, d_mean, st);
-        case 16: return launch_query<16>(d_sorted, n, gr, d_start, d_origin, d_pending, max_shells, d_mean, st);
-        case 20: return launch_query<20>(d_sorted, n, gr, d_start, d_origin, d_pending, max_shells, d_mean, st);
-        case 32: return launch_query<32>(d_sorted, n, gr, d_start, d_origin, d_pending, max_shells, d_mean, st);
-        default: return hipErrorInvalidValue;
-        }
+        return dispatch(KnnSizes{}, k, hipErrorInvalidValue, [&](auto kc) {
+            return launch_query<kc()>(d_sorted, n, gr, d_start, d_origin, d_pending, max_shells, d_mean, st);
+        });
     };
 
     // level 0: edge fitted to the occupancy of the occupied cells (3 .. 24 points)
@@ -525,14 +521,9 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
         hipEvent_t e0, e1, e2;
         if (debug) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventCreate(&e2); (void)hipEventRecord(e0, st); }
         auto box = [&](int r_first, int r_last, int count) -> hipError_t {
-            switch (k) {
-            case 8: return launch_box<8>(d_pts, d_sorted, gr, d_start, r_first, r_last, d_queries, count, d_pending, d_mean, n, st);
-            case 10: return launch_box<10>(d_pts, d_sorted, gr, d_start, r_first, r_last, d_queries, count, d_pending, d_mean, n, st);
-            case 16: return launch_box<16>(d_pts, d_sorted, gr, d_start, r_first, r_last, d_queries, count, d_pending, d_mean, n, st);
-            case 20: return launch_box<20>(d_pts, d_sorted, gr, d_start, r_first, r_last, d_queries, count, d_pending, d_mean, n, st);
-            case 32: return launch_box<32>(d_pts, d_sorted, gr, d_start, r_first, r_last, d_queries, count, d_pending, d_mean, n, st);
-            default: return hipErrorInvalidValue;
-            }
+            return dispatch(KnnSizes{}, k, hipErrorInvalidValue, [&](auto kc) {
+                return launch_box<kc()>(d_pts, d_sorted, gr, d_start, r_first, r_last, d_queries, count, d_pending, d_mean, n, st);
+            });
         };
         // a thread per query walks shells 0..1; a wave per query left scans the box R = 2 (the cells of shells
         // 0..2); a block per query still left scans the boxes R = 4, 8, ... until its rule holds

@@ -298,38 +298,12 @@ static hipError_t launch_sweep_ks(const SweepArgs &a, int nblk, hipStream_t st)
     return hipGetLastError();
 }
 
-#define AMVS_FOR_S(K, FN, ...)                                      \
-    switch (S) {                                                    \
-    case 2: return FN<K, 2>(__VA_ARGS__);                           \
-    case 3: return FN<K, 3>(__VA_ARGS__);                           \
-    case 4: return FN<K, 4>(__VA_ARGS__);                           \
-    case 5: return FN<K, 5>(__VA_ARGS__);                           \
-    case 6: return FN<K, 6>(__VA_ARGS__);                           \
-    default: return decltype(FN<K, 2>(__VA_ARGS__))(1);             \
-    }
-
 hipError_t launch_sweep(int K, int S, const SweepArgs &a, hipStream_t st)
 {
     if (!patch_compiled(K)) return launch_sweep_generic(K, S, a, st);
     if (a.fast) return launch_sweep_fast(K, S, a, st);
     const int nblk = a.n_jobs * a.tiles_x * a.tiles_y * a.n_chunks;
-    switch (K) {
-    case 3: AMVS_FOR_S(3, launch_sweep_ks, a, nblk, st)
-    case 5: AMVS_FOR_S(5, launch_sweep_ks, a, nblk, st)
-    case 7: AMVS_FOR_S(7, launch_sweep_ks, a, nblk, st)
-    case 9: AMVS_FOR_S(9, launch_sweep_ks, a, nblk, st)
-    case 11: AMVS_FOR_S(11, launch_sweep_ks, a, nblk, st)
-    case 13: AMVS_FOR_S(13, launch_sweep_ks, a, nblk, st)
-    case 15: AMVS_FOR_S(15, launch_sweep_ks, a, nblk, st)
-    case 17: AMVS_FOR_S(17, launch_sweep_ks, a, nblk, st)
-    case 19: AMVS_FOR_S(19, launch_sweep_ks, a, nblk, st)
-    case 21: AMVS_FOR_S(21, launch_sweep_ks, a, nblk, st)
-    case 23: AMVS_FOR_S(23, launch_sweep_ks, a, nblk, st)
-    case 25: AMVS_FOR_S(25, launch_sweep_ks, a, nblk, st)
-    case 27: AMVS_FOR_S(27, launch_sweep_ks, a, nblk, st)
-    case 29: AMVS_FOR_S(29, launch_sweep_ks, a, nblk, st)
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_ks(K, S, hipErrorInvalidValue, [&](auto k, auto s) { return launch_sweep_ks<k(), s()>(a, nblk, st); });
 }
 
 hipError_t launch_sweep_finish(const SweepArgs &a, hipStream_t st)
