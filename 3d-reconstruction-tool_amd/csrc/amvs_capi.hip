@@ -1800,6 +1800,22 @@ int amvs_fetch_cloud(amvs_ctx *c, double *points, uint8_t *colors)
     return checked(c, AMVS_OK);
 }
 
+// the grid of a TSDF volume: finite origin, positive finite voxel, every dimension >= 2, the point budget
+static int check_tsdf_grid(amvs_ctx *c, const std::string &who, const float origin[3], float voxel, const int32_t dims[3])
+{
+    if (!(voxel > 0.0f) || !std::isfinite(voxel)) return fail(c, AMVS_EINVAL, who + ": voxel must be positive and finite");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(origin[a])) return fail(c, AMVS_EINVAL, who + ": origin must be finite");
+    if (dims[0] < 2 || dims[1] < 2 || dims[2] < 2) return fail(c, AMVS_EINVAL, who + ": every dimension must be >= 2");
+    const long long points = (long long)dims[0] * dims[1] * dims[2];
+    if (dims[0] > AMVS_TSDF_MAX_POINTS || dims[1] > AMVS_TSDF_MAX_POINTS || dims[2] > AMVS_TSDF_MAX_POINTS ||
+        points > AMVS_TSDF_MAX_POINTS)
+        return fail(c, AMVS_EINVAL, who + ": volume of " + std::to_string(dims[0]) + " x " + std::to_string(dims[1]) +
+                                        " x " + std::to_string(dims[2]) + " grid points is over the budget of " +
+                                        std::to_string((long long)AMVS_TSDF_MAX_POINTS) + " (AMVS_TSDF_MAX_POINTS)");
+    return AMVS_OK;
+}
+
 int amvs_tsdf_integrate(amvs_ctx *c, int n_maps, const void *depth, const void *conf, int maps_on_device,
                         const int *view_ids, const uint8_t *colors_bgr_host, const float K[9], const float *poses,
                         float min_views, const float origin[3], float voxel, const int32_t dims[3], float trunc)
@@ -1809,19 +1825,10 @@ int amvs_tsdf_integrate(amvs_ctx *c, int n_maps, const void *depth, const void *
         return fail(c, AMVS_EINVAL, "tsdf_integrate: bad argument");
     if ((view_ids != nullptr) == (colors_bgr_host != nullptr))
         return fail(c, AMVS_EINVAL, "tsdf_integrate: give exactly one colour source (view_ids or colors_bgr_host)");
-    if (!(voxel > 0.0f) || !std::isfinite(voxel) || !(trunc > 0.0f) || !std::isfinite(trunc))
-        return fail(c, AMVS_EINVAL, "tsdf_integrate: voxel and trunc must be positive and finite");
-    for (int a = 0; a < 3; ++a)
-        if (!std::isfinite(origin[a])) return fail(c, AMVS_EINVAL, "tsdf_integrate: origin must be finite");
-    if (dims[0] < 2 || dims[1] < 2 || dims[2] < 2) return fail(c, AMVS_EINVAL, "tsdf_integrate: every dimension must be >= 2");
-    const long long points = (long long)dims[0] * dims[1] * dims[2];
-    if (dims[0] > AMVS_TSDF_MAX_POINTS || dims[1] > AMVS_TSDF_MAX_POINTS || dims[2] > AMVS_TSDF_MAX_POINTS ||
-        points > AMVS_TSDF_MAX_POINTS)
-        return fail(c, AMVS_EINVAL, "tsdf_integrate: volume of " + std::to_string(dims[0]) + " x " + std::to_string(dims[1]) +
-                                        " x " + std::to_string(dims[2]) + " grid points is over the budget of " +
-                                        std::to_string((long long)AMVS_TSDF_MAX_POINTS) + " (AMVS_TSDF_MAX_POINTS)");
+    if (!(trunc > 0.0f) || !std::isfinite(trunc)) return fail(c, AMVS_EINVAL, "tsdf_integrate: trunc must be positive and finite");
+    int rc = check_tsdf_grid(c, "tsdf_integrate", origin, voxel, dims);
+    if (rc) return rc;
     std::vector<int> slots(n_maps);
-    int rc = AMVS_OK;
     if (view_ids && (rc = check_colour_views(c, n_maps, view_ids))) return rc;
     for (int j = 0; j < n_maps; ++j) slots[j] = view_ids ? view_ids[j] : j;
     if ((rc = bind_device(c))) return rc;
@@ -1831,6 +1838,20 @@ int amvs_tsdf_integrate(amvs_ctx *c, int n_maps, const void *depth, const void *
                                               view_ids ? c->n_views : n_maps, slots.data(), K, poses, min_views, origin, voxel,
                                               dims, trunc, c->stream);
     if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("tsdf_integrate: ") + hipGetErrorString(e));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_tsdf_set_volume(amvs_ctx *c, const float *tsdf, const float *weight, const float *color_sum, const float origin[3],
+                         float voxel, const int32_t dims[3])
+{
+    if (!c) return AMVS_EINVAL;
+    if (!tsdf || !weight || !color_sum || !origin || !dims) return fail(c, AMVS_EINVAL, "tsdf_set_volume: bad argument");
+    int rc = check_tsdf_grid(c, "tsdf_set_volume", origin, voxel, dims);
+    if (rc) return rc;
+    if ((rc = bind_device(c))) return rc;
+    if (!c->tsdf) c->tsdf.reset(amvs::tsdf_state_new());
+    const hipError_t e = amvs::tsdf_set_volume(c->tsdf.get(), c->cache, tsdf, weight, color_sum, origin, voxel, dims, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("tsdf_set_volume: ") + hipGetErrorString(e));
     return checked(c, AMVS_OK);
 }
 

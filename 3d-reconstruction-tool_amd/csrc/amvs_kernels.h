@@ -247,6 +247,9 @@ hipError_t tsdf_integrate(TsdfState *s, ScratchCache &cache, const float *depth,
                           int n_maps, int H, int W, const unsigned char *bgr, bool bgr_on_device, long long bgr_images,
                           const int *slots_h, const float K[9], const float *poses_h, float min_views, const float origin[3],
                           float voxel, const int dims[3], float trunc, hipStream_t st);
+// test hook: replaces the volume by host arrays in tsdf_fetch_volume's layout (copies only).  Synchronises.
+hipError_t tsdf_set_volume(TsdfState *s, ScratchCache &cache, const float *tsdf, const float *weight, const float *color_sum,
+                           const float origin[3], float voxel, const int dims[3], hipStream_t st);
 hipError_t tsdf_extract(TsdfState *s, ScratchCache &cache, long long *n_vertices, long long *n_faces, hipStream_t st);
 bool tsdf_has_volume(const TsdfState *s);
 bool tsdf_has_mesh(const TsdfState *s);

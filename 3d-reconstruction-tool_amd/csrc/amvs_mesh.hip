@@ -356,6 +356,20 @@ TsdfState *tsdf_state_new() { return new TsdfState(); }
 
 void tsdf_state_free(TsdfState *s) { delete s; }
 
+namespace {
+
+// the volume of n grid points and the per-point buffers of the extraction's passes (a) and (b)
+hipError_t reserve_volume(TsdfState *s, ScratchCache &cache, long long n)
+{
+    MCHK(s->tsdf.reserve(n, cache)); MCHK(s->weight.reserve(n, cache)); MCHK(s->color.reserve(3 * n, cache));
+    MCHK(s->mask.reserve(n, cache));
+    MCHK(s->vcount.reserve(n, cache)); MCHK(s->vbase.reserve(n, cache));
+    MCHK(s->tcount.reserve(n, cache)); MCHK(s->tbase.reserve(n, cache));
+    return hipSuccess;
+}
+
+}  // namespace
+
 hipError_t tsdf_integrate(TsdfState *s, ScratchCache &cache, const float *depth, const float *conf, bool maps_on_device,
                           int n_maps, int H, int W, const unsigned char *bgr, bool bgr_on_device, long long bgr_images,
                           const int *slots_h, const float K[9], const float *poses_h, float min_views, const float origin[3],
@@ -364,10 +378,7 @@ hipError_t tsdf_integrate(TsdfState *s, ScratchCache &cache, const float *depth,
     s->have_volume = s->have_mesh = false;
     const long long n = (long long)dims[0] * dims[1] * dims[2];
     const size_t hw = (size_t)H * W, nmap = hw * (size_t)n_maps;
-    MCHK(s->tsdf.reserve(n, cache)); MCHK(s->weight.reserve(n, cache)); MCHK(s->color.reserve(3 * n, cache));
-    MCHK(s->mask.reserve(n, cache));
-    MCHK(s->vcount.reserve(n, cache)); MCHK(s->vbase.reserve(n, cache));
-    MCHK(s->tcount.reserve(n, cache)); MCHK(s->tbase.reserve(n, cache));
+    MCHK(reserve_volume(s, cache, n));
     MCHK(s->cams.reserve(12 * (size_t)n_maps, cache));
     MCHK(s->slots.reserve(n_maps, cache));
     MCHK(hipMemcpyAsync(s->cams.get(), poses_h, sizeof(float) * 12 * n_maps, hipMemcpyHostToDevice, st));
@@ -393,6 +404,22 @@ hipError_t tsdf_integrate(TsdfState *s, ScratchCache &cache, const float *depth,
                        H, W, min_views, trunc, s->g, s->tsdf.get(), s->weight.get(), s->color.get());
     MCHK(hipGetLastError());
     MCHK(hipStreamSynchronize(st));
+    s->have_volume = true;
+    return hipSuccess;
+}
+
+hipError_t tsdf_set_volume(TsdfState *s, ScratchCache &cache, const float *tsdf, const float *weight, const float *color_sum,
+                           const float origin[3], float voxel, const int dims[3], hipStream_t st)
+{
+    s->have_volume = s->have_mesh = false;
+    const long long n = (long long)dims[0] * dims[1] * dims[2];
+    MCHK(reserve_volume(s, cache, n));
+    MCHK(hipMemcpyAsync(s->tsdf.get(), tsdf, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    MCHK(hipMemcpyAsync(s->weight.get(), weight, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    MCHK(hipMemcpyAsync(s->color.get(), color_sum, 12 * (size_t)n, hipMemcpyHostToDevice, st));
+    MCHK(hipStreamSynchronize(st));
+    s->g = Grid{origin[0], origin[1], origin[2], voxel, dims[0], dims[1], dims[2]};
+    s->n = n;
     s->have_volume = true;
     return hipSuccess;
 }

@@ -594,6 +594,23 @@ class Engine:
         self._chk(self._lib.amvs_tsdf_fetch_volume(self._h, _p(tsdf), _p(weight), _p(color)))
         return tsdf, weight, color
 
+    def tsdf_set_volume(self, tsdf, weight, color_sum, origin, voxel):
+        """Test hook (include/amvs.h amvs_tsdf_set_volume): make host arrays in tsdf_volume()'s layout the context's
+        volume -- tsdf, weight (nz,ny,nx) and colour sums (nz,ny,nx,3) RGB, float32 -- for tsdf_extract()."""
+        tsdf = _f32(tsdf)
+        if tsdf.ndim != 3:
+            raise ValueError("tsdf must be (nz, ny, nx)")
+        nz, ny, nx = tsdf.shape
+        weight = _f32(weight)
+        color = _f32(color_sum)
+        if weight.shape != tsdf.shape or color.shape != tsdf.shape + (3,):
+            raise ValueError(f"weight must be {tsdf.shape} and color_sum {tsdf.shape + (3,)}")
+        org = _f32(np.asarray(origin, np.float64).astype(np.float32).reshape(3))
+        dm, dmp = _ids([nx, ny, nz])
+        self._chk(self._lib.amvs_tsdf_set_volume(self._h, _p(tsdf), _p(weight), _p(color), _p(org),
+                                                 float(np.float32(voxel)), dmp))
+        self._tsdf_dims = (nx, ny, nz)
+
     def knn_mean_distance(self, points, k=20):
         """Mean distance of every point to its k-1 nearest other points, bit-identical to
         np.mean(NearestNeighbors(n_neighbors=k).fit(p).kneighbors(p)[0][:, 1:], axis=1)."""

@@ -297,6 +297,14 @@ int amvs_fetch_mesh(amvs_ctx *ctx, float *vertices, int32_t *faces, uint8_t *col
 /* Test hook: the last integrated volume, dims[2] x dims[1] x dims[0] float32 tsdf and weight (views counted) and
  * x 3 float32 RGB colour sums.  NULL skips an output.                                                      */
 int amvs_tsdf_fetch_volume(amvs_ctx *ctx, float *tsdf, float *weight, float *color_sum);
+/* Test hook: replace the context's volume by host arrays in the layout amvs_tsdf_fetch_volume returns (tsdf and
+ * weight dims[2] x dims[1] x dims[0] float32, color_sum x 3 float32 RGB) on the grid origin / voxel / dims, validated
+ * as in amvs_tsdf_integrate (finite origin, positive finite voxel, every dimension >= 2, AMVS_TSDF_MAX_POINTS).  Drops
+ * any mesh; amvs_tsdf_extract then behaves as after an integration.  Copies only, no kernel.  A point with weight
+ * <= 0 is unobserved and its tsdf and colour sums are never used; at observed points the values must be finite,
+ * which is NOT checked.  Synchronises.                                                                      */
+int amvs_tsdf_set_volume(amvs_ctx *ctx, const float *tsdf, const float *weight, const float *color_sum,
+                         const float origin[3], float voxel, const int32_t dims[3]);
 
 /* ---- extended mode: what the reference's docstring names but does not implement ----------------
  * (mvs_patchmatch.py:1-13 lists plane hypotheses with normals and VIEW propagation; its code ignores

@@ -8,6 +8,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mesh_restatement as mr  # noqa: E402
+import mesh_volumes as mv  # noqa: E402
 
 import amvs  # noqa: E402,F401
 
@@ -196,8 +197,165 @@ def test_mesh_grid_defaults():
 
 def test_abi_declares_the_mesh_entry_points():
     from amvs import _lib
-    for name in ("amvs_tsdf_integrate", "amvs_tsdf_extract", "amvs_fetch_mesh", "amvs_tsdf_fetch_volume"):
+    for name in ("amvs_tsdf_integrate", "amvs_tsdf_extract", "amvs_fetch_mesh", "amvs_tsdf_fetch_volume",
+                 "amvs_tsdf_set_volume"):
         assert name in _lib.SIGNATURES
     assert hasattr(amvs, "save_mesh_ply") or "save_mesh_ply" in amvs.__all__
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "amvs.h")).read()
     assert f"#define AMVS_TSDF_MAX_POINTS (1ll << {int(np.log2(_lib.TSDF_MAX_POINTS))})" in hdr
+
+
+# ---- the generated volumes and scenes of tests/mesh_volumes.py, on the restatement alone -------------------------
+
+def test_random_sign_family_reaches_every_tetrahedron_case():
+    """The coverage cap of the GPU comparison: over the random-sign family every one of the 84 (Kuhn tetrahedron,
+    sign case 1 .. 14) pairs occurs at least 10 times among the meshed tetrahedra (the volumes fused from the
+    height-field scenes reach 38 of the 84)."""
+    family = mv.random_sign_family()
+    total = np.zeros((6, 16), np.int64)
+    for vol in family:
+        total += mv.tet_case_coverage(vol.tsdf, vol.weight)
+    emitting = total[:, 1:15]
+    print("hits per (tetrahedron, case 1..14):\n", emitting)
+    assert emitting.shape == (6, 14) and emitting.min() >= 10, emitting
+    # the recipe: ragged sizes, thin axes, exact zeros of both signs, unobserved points with garbage behind them
+    assert sum(int(np.prod(v.dims)) % 256 != 0 for v in family) >= 3
+    assert {a for v in family for a in range(3) if v.dims[a] == 2} == {0, 1, 2}
+    for vol in family[:1]:
+        seen = vol.weight > 0
+        zero = vol.tsdf[seen] == 0
+        neg = np.signbit(vol.tsdf[seen])
+        assert 0.01 < (zero & ~neg).mean() < 0.06 and 0.01 < (zero & neg).mean() < 0.06
+        assert 0.15 < (~seen).mean() < 0.35
+        assert np.isnan(vol.tsdf[~seen]).any() and (vol.tsdf[~seen] < 0).any()
+        assert np.all(np.isfinite(vol.tsdf[seen])) and np.all(vol.color[seen] == np.floor(vol.color[seen]))
+        assert np.all(vol.color[seen] <= 255 * vol.weight[seen][:, None])
+    # the coverage function against the faces the restatement emits: 1 per odd case, 2 per two-two case
+    for vol in family:
+        c = mv.tet_case_coverage(vol.tsdf, vol.weight)
+        per_case = np.array([len(t) for t in mr.TRI_TABLE])
+        assert int((c * per_case[None, :]).sum()) == len(vol.extract()[1])
+
+
+@pytest.mark.parametrize("dims,seed", [((14, 11, 9), 5), ((19, 23, 21), 6)])
+def test_random_sign_surface_is_closed_and_consistently_oriented(dims, seed):
+    """A fully observed random-sign volume (exact 0.0 and -0.0 included) whose outermost layer is outside: every
+    directed edge of the restatement's mesh occurs exactly once and its opposite exactly once.  Zero-area triangles
+    from exact zeros count like any other; coincident vertices keep distinct ids."""
+    vol = mv.random_sign_volume(dims, seed, closed=True)
+    assert np.all(vol.weight > 0) and (vol.tsdf == 0).sum() > 10 and np.signbit(vol.tsdf[vol.tsdf == 0]).any()
+    verts, faces, _ = vol.extract()
+    assert len(faces) > 5000
+    assert np.array_equal(np.unique(faces), np.arange(len(verts)))
+    assert np.all(faces[:, 0] != faces[:, 1]) and np.all(faces[:, 1] != faces[:, 2]) and np.all(faces[:, 0] != faces[:, 2])
+    assert mv.directed_edge_defects(faces, len(verts)) == (0, 0)
+    assert len(np.unique(verts, axis=0)) < len(verts)              # coincident vertices exist and stay apart
+
+
+def test_corner_case_volumes():
+    for vol, expect in mv.corner_case_volumes():
+        verts, faces, cols = vol.extract()
+        if expect is not None:
+            assert (len(verts), len(faces)) == expect, vol.name
+            assert verts.shape == (0, 3) and faces.shape == (0, 3) and cols.shape == (0, 3)
+    # colour means that land exactly on x.5, on 0 and on 255
+    for vol, expect in mv.colour_tie_volumes():
+        verts, faces, cols = vol.extract()
+        assert len(verts) == 25 and np.all(cols == expect[None, :]), (vol.name, np.unique(cols, axis=0))
+    # the single cube: every pattern but all-outside and all-inside gives faces, complementary patterns the same
+    # number of them, and the vertices are the sign-changing ones among the cube's 19 tetrahedron edges
+    for pattern in range(256):
+        vol = mv.cube_volume(pattern)
+        verts, faces, _ = vol.extract()
+        assert (len(faces) == 0) == (pattern in (0, 255))
+        assert len(faces) == len(mv.cube_volume(255 - pattern).extract()[1])
+        crossing = sum(((pattern >> a) & 1) != ((pattern >> b) & 1) for a in range(8) for b in range(a + 1, 8) if a & b == a)
+        assert len(verts) == crossing and np.array_equal(np.unique(faces), np.arange(len(verts))), pattern
+
+
+def test_grid_plane_vertices_coincide_on_the_zero_layer():
+    for sign in (1.0, -1.0):
+        vol = mv.grid_plane_volume((9, 8, 11), 2, 5, sign=sign)
+        assert np.all(vol.tsdf[5] == 0) and np.all(np.signbit(vol.tsdf[5]) == (sign < 0))
+        verts, faces, _ = vol.extract()
+        assert len(faces) > 0 and np.all(verts[:, 2] == np.float32(1.0) + np.float32(5) * np.float32(0.125))
+        assert len(np.unique(verts, axis=0)) == 9 * 8 < len(verts)
+        nrm = _normals(verts, faces)
+        assert np.all(nrm[:, 2] * sign >= 0) and np.any(nrm[:, 2] != 0) and np.any(np.all(nrm == 0, axis=1))
+
+
+def test_inverted_sphere_is_closed_and_faces_inward():
+    plain = mv.sphere_volume(33, trunc=0.2)
+    inverted = mv.sphere_volume(33, trunc=0.2, inverted=True)
+    vol = {}
+    for name, v in (("plain", plain), ("inverted", inverted)):
+        verts, faces, _ = v.extract()
+        assert len(faces) > 10000 and mv.directed_edge_defects(faces, len(verts)) == (0, 0)
+        assert len(faces) == 2 * len(verts) - 4
+        vol[name] = mv.signed_volume(verts, faces)
+    ball = 4.0 / 3.0 * np.pi * 0.8 ** 3
+    assert vol["plain"] == pytest.approx(ball, rel=0.01) and vol["inverted"] == pytest.approx(-ball, rel=0.01)
+
+
+def test_integration_scenes_take_every_branch():
+    """The branch cap of the GPU comparison: over the hand-built scenes every guard of the integration is taken, and
+    every edge mesh_volumes.branch_counts names is met, at least 100 times: zc == 0, pixels u == -0.5 and u == W - 0.5,
+    depth -0.0 / NaN / inf, confidence NaN / just below / exactly min_views / inf, sdf == -trunc and one ulp beyond it,
+    sdf / trunc == 1, pixel ties."""
+    total = dict.fromkeys(mv.BRANCHES, 0)
+    scenes = mv.integration_scenes()
+    per_scene = []
+    for sc in scenes:
+        counts = mv.branch_counts(sc)
+        per_scene.append(counts)
+        print(sc.name, counts)
+        for k, n in counts.items():
+            total[k] += n
+        # the counter agrees with the restatement on what is kept
+        assert counts["kept"] == int(sc.integrate()[1].sum()), sc.name
+    assert set(total) == set(mv.BRANCHES)
+    for k, n in total.items():
+        assert n >= 100, (k, n)
+    # what each scene is there for, scene by scene
+    for counts in per_scene[:2]:                                     # exact arithmetic
+        for k in ("tie", "tie_first", "tie_last", "at_cut", "beyond_cut", "clamped", "at_one"):
+            assert counts[k] >= 100, (k, counts[k])
+    for k in ("behind", "zc_zero", "huge"):                          # cameras inside the box
+        assert per_scene[2][k] >= 100, (k, per_scene[2][k])
+    for k in ("depth_neg_zero", "depth_nan", "depth_inf", "conf_nan", "conf_below", "conf_at_min", "conf_inf"):
+        assert per_scene[3][k] >= 100, (k, per_scene[3][k])          # map content
+    # one ulp beyond the cut is outside the volume, sdf == -trunc inside it with the value -1
+    sc = scenes[0]
+    tsdf, weight, _ = mr.integrate(sc.depth[2:3], sc.conf[2:3], sc.colors[2:3], sc.K, sc.poses[2:3], sc.min_views,
+                                   sc.origin, sc.voxel, sc.dims, sc.trunc)
+    one = mv.branch_counts(mv.Scene("near map", sc.depth[2:3], sc.conf[2:3], sc.colors[2:3], sc.K, sc.poses[2:3],
+                                    sc.min_views, sc.origin, sc.voxel, sc.dims, sc.trunc))
+    assert one["beyond_cut"] > 0 and one["kept"] == one["at_cut"] > 0      # the layers behind Z = 0.5 are cut as well
+    assert int((weight[0] > 0).sum()) == one["at_cut"] and not np.any(weight[1:])
+    assert np.all(tsdf[0][weight[0] > 0] == -1.0)
+    # ties on whole columns of the exact scenes, at pixels -0.5 (inside) and W - 0.5 (outside) as well
+    for sc in scenes[:2]:
+        X, _, Z = mr.grid_coords(sc.origin, sc.voxel, sc.dims)
+        u = np.float32(8.0) * np.asarray(X)[np.asarray(Z) == 2.0] + sc.K[0, 2]
+        assert u.min() == -0.5 and (u == sc.W - 0.5).any() and mv.branch_counts(sc)["tie"] >= 1000
+    # many maps: at least 16, and every weight from 0 to the map count occurs
+    many = scenes[-1]
+    assert many.n >= 16
+    assert np.array_equal(np.unique(many.integrate()[1]), np.arange(many.n + 1))
+    # the content scene holds every kind of bad value
+    content = scenes[3]
+    assert np.isnan(content.depth).any() and np.isinf(content.depth).any() and (content.depth < 0).any()
+    assert (content.depth == 0).any() and np.isnan(content.conf).any() and np.isinf(content.conf).any()
+    assert (content.conf == content.min_views).any()
+
+
+def test_branch_counter_on_the_fronto_parallel_wall():
+    """branch_counts on a scene small enough to count by hand: one camera at the origin, a wall at depth 2, a
+    column of 21 grid points on the optical axis at Z = 1.5 .. 2.5 (trunc 0.25)."""
+    H, W = 8, 8
+    sc = mv.Scene("axis", np.full((1, H, W), 2.0), np.full((1, H, W), 3.0), np.zeros((1, H, W, 3), np.uint8),
+                  [[8.0, 0, 4.0], [0, 8.0, 4.0], [0, 0, 1]], mv._pose()[None], 2.0, (0.0, 0.0, 1.5), 0.0625, (2, 2, 17), 0.25)
+    c = mv.branch_counts(sc)
+    # Z = 1.5 + k / 16: sdf / trunc > 1 for k < 4, == 1 at k = 4, sdf == -trunc at k = 12, cut for k > 12; 4 points per layer
+    assert (c["clamped"], c["at_one"], c["at_cut"], c["cut"], c["kept"]) == (16, 4, 4, 16, 52)
+    assert c["behind"] == c["outside"] == c["no_depth"] == c["low_conf"] == 0
