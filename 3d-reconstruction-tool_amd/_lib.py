@@ -70,6 +70,10 @@ SIGNATURES = {
     "amvs_set_step_tuning": (C.c_int, [C.c_void_p, C.c_int, i32p, i32p]),
     "amvs_set_step_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "amvs_get_step_times": (C.c_int, [C.c_void_p, f32p, C.c_int, i32p]),
+    "amvs_set_launch_order": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "amvs_sweep_order": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, i32p, i32p]),
+    "amvs_fetch_step_trace": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64)]),
     "amvs_last_tile_rows": (C.c_int, [C.c_void_p]),
     "amvs_last_views_per_launch": (C.c_int, [C.c_void_p]),
     "amvs_plane_sweep": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, f32p, C.c_int, C.c_int,
@@ -181,6 +185,20 @@ def index_check(reset=True):
     r = (C.c_uint64 * 4)()
     load().amvs_index_check(r, int(bool(reset)))
     return int(r[0]), int(r[1]) >> 32, int(r[1]) & 0xFFFFFFFF, int(r[2]), int(r[3])
+
+
+def sweep_order(n_jobs, tiles_x, tiles_y, band_major=False, paired=False, edge_first=True):
+    """[n_blocks][4][5] int32 (job, strip row, strip column, up, partner) of every wave of a sweep step launch, -1 for a
+    wave without a strip (include/amvs.h amvs_sweep_order; no GPU involved)."""
+    import numpy as np
+    lib = load()
+    n = C.c_int32(0)
+    args = (int(n_jobs), int(tiles_x), int(tiles_y), int(bool(band_major)), int(bool(paired)), int(bool(edge_first)))
+    if lib.amvs_sweep_order(*args, 0, None, C.byref(n)) != 0:
+        raise AmvsError("amvs_sweep_order: bad launch shape")
+    out = np.full((n.value, 4, 5), -2, np.int32)
+    lib.amvs_sweep_order(*args, out.size, out.ctypes.data_as(i32p), C.byref(n))
+    return out
 
 
 def index_checks_enabled():

@@ -21,6 +21,17 @@
 #include <string>
 #include <vector>
 
+// Defaults of amvs_set_launch_order (A/B builds: ALL=1 tools/build_variant.sh NAME -DAMVS_DEFAULT_GROUP_OVERLAP=0 ...).
+// Measured on MI355X, bench.py main line, ms per step, five alternating runs each:
+// one stream top-to-bottom 59.65, one stream edge-first 59.86, two equal streams edge-first 58.77, top-to-bottom
+// 58.95, a high / low pair 60.81.  Hence edge-first exactly where the groups overlap (-1), two equal streams.
+#ifndef AMVS_DEFAULT_EDGE_FIRST
+#define AMVS_DEFAULT_EDGE_FIRST -1
+#endif
+#ifndef AMVS_DEFAULT_GROUP_OVERLAP
+#define AMVS_DEFAULT_GROUP_OVERLAP 1
+#endif
+
 static_assert(AMVS_MAX_SRC == AMVS_KMAX_SRC, "source-count limits out of sync");
 
 #ifdef AMVS_CHECK_INDICES
@@ -152,7 +163,17 @@ struct amvs_ctx {
     int n_step_events = 0;
     std::vector<hipEvent_t> ev_groups;   // per view group of the last PatchMatch call: init / steps / confidence
     int timing_groups = 0;
+    bool timing_overlapped = false;      // the groups of the last call ran on two streams (resolve_timing)
     bool timing_pending = false;
+    // Sweep-step dispatch order (amvs_set_launch_order): edge_first -- every XCD walks each view's bands from the image
+    // edge to its centre (amvs_strip_order.h; -1: where the groups overlap, else top to bottom); group_overlap -- the view groups of a batch dealt to two streams of the
+    // context (run_fused_schedule): 0 one stream, 1 two streams of equal priority, 2 a high / low pair
+    int edge_first = AMVS_DEFAULT_EDGE_FIRST, group_overlap = AMVS_DEFAULT_GROUP_OVERLAP;
+    hipStream_t group_streams[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [group_overlap - 1][stream]
+    hipEvent_t group_fork = nullptr, group_join = nullptr;
+    // -DAMVS_STEP_TRACE: [launch][trace_stride blocks][4] workgroup timeline of the last PatchMatch call
+    amvs::DeviceBuffer<unsigned long long> d_trace;
+    long long trace_stride = 0, trace_launches = 0;
     amvs_timing timing{};
     std::string err;
 };
@@ -467,7 +488,29 @@ void resolve_timing(amvs_ctx *c)
     if (!c->timing_pending) return;
     c->timing_pending = false;
     if (hipEventSynchronize(c->ev[3]) != hipSuccess) return;
-    if (c->timing_groups > 0) {
+    if (c->timing_groups > 0 && c->timing_overlapped) {
+        // Groups on two streams: the phases of different groups overlap, so each figure is the UNION of its groups'
+        // intervals (chip time, as on one stream), not their sum.  Group g ran on stream g % 2, after group g - 2.
+        std::vector<std::pair<float, float>> iv[3];
+        for (int g = 0; g < c->timing_groups; ++g) {
+            float t[4] = {0.f, 0.f, 0.f, 0.f};
+            if (g >= 2) (void)hipEventElapsedTime(&t[0], c->ev[0], c->ev_groups[3 * (g - 2) + 2]);
+            for (int k = 0; k < 3; ++k) (void)hipEventElapsedTime(&t[k + 1], c->ev[0], c->ev_groups[3 * g + k]);
+            for (int k = 0; k < 3; ++k) iv[k].emplace_back(t[k], t[k + 1]);
+        }
+        double u[3];
+        for (int k = 0; k < 3; ++k) {
+            std::sort(iv[k].begin(), iv[k].end());
+            double sum = 0.0, end = -1.0;
+            for (const auto &x : iv[k]) {
+                const double lo = std::max<double>(x.first, end), hi = x.second;
+                if (hi > lo) sum += hi - lo;
+                end = std::max<double>(end, hi);
+            }
+            u[k] = sum;
+        }
+        c->timing.init_ms = u[0]; c->timing.sweep_ms = u[1]; c->timing.confidence_ms = u[2];
+    } else if (c->timing_groups > 0) {
         // PatchMatch: per view group [start | init | steps | confidence]
         double t_init = 0, t_sweep = 0, t_conf = 0;
         hipEvent_t prev = c->ev[0];
@@ -544,8 +587,31 @@ void apply_step(amvs::StepArgs &a, const SchedStep &st)
     if (st.mode == amvs::MODE_REFINE) { a.depth_range = st.depth_range; a.normal_range = st.normal_range; a.draw = st.draw; }
 }
 
-// One stream: the batch in groups of `vpl` views, each group through the whole schedule with the
-// fused kernel (sampling + window sums + selection in one launch).
+// The two streams of amvs_ctx::group_overlap = 1 (equal priorities) or 2 (high / low: distinct priorities land on
+// distinct hardware queues, see run_split_schedule), created once per context.
+int group_streams(amvs_ctx *c, int overlap, hipStream_t out[2])
+{
+    hipStream_t *st = c->group_streams[overlap - 1];
+    if (!st[0]) {
+        int lo = 0, hi = 0;
+        HIPCHK(c, hipDeviceGetStreamPriorityRange(&lo, &hi));      // (numerically: hi <= lo)
+        for (int i = 0; i < 2; ++i)
+            HIPCHK(c, hipStreamCreateWithPriority(&st[i], hipStreamNonBlocking, overlap == 2 ? (i == 0 ? hi : lo) : lo));
+    }
+    if (!c->group_fork) {
+        HIPCHK(c, hipEventCreateWithFlags(&c->group_fork, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->group_join, hipEventDisableTiming));
+    }
+    out[0] = st[0]; out[1] = st[1];
+    return AMVS_OK;
+}
+
+// The batch in groups of `vpl` views, each group through the whole schedule with the fused kernel (sampling +
+// window sums + selection in one launch).  One stream, or (amvs_ctx::group_overlap) the groups dealt to two streams
+// that fork from the context's stream and join it again: the groups are independent (mvs_patchmatch.py:104-123) --
+// their StepArgs, state slots, job entries and confidence slots are disjoint, the images and the job table are
+// read-only, and the fused launches use no other scratch -- so the workgroups of one group fill the wave slots the
+// tail of the other leaves empty.  Every group still runs its whole schedule in order on its stream.
 int run_fused_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *p, uint64_t seed, int fast,
                        const std::vector<SchedStep> &sched, void *conf_dev, int cur0, bool do_init, bool do_conf)
 {
@@ -593,9 +659,33 @@ int run_fused_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
         c->ev_groups.push_back(ev);
     }
     c->timing_groups = n_groups;
+#ifdef AMVS_STEP_TRACE
+    // (cleared on the context's stream BEFORE the group streams fork from it)
+    {
+        long long blocks = 0;
+        for (const StepShape &sh : shapes) {
+            const long long b = (long long)vpl * base_args(c, p->patch_size, vpl, TH).tiles_x * ((c->H + sh.rows - 1) / sh.rows);
+            blocks = b > blocks ? b : blocks;                  // (one strip per block at most: the run-time-k kernels)
+        }
+        c->trace_stride = blocks;
+        c->trace_launches = (long long)n_groups * (long long)sched.size();
+        HIPCHK(c, c->d_trace.reserve((size_t)(4 * blocks * c->trace_launches) + 1, c->cache));
+        HIPCHK(c, hipMemsetAsync(c->d_trace.get(), 0, sizeof(unsigned long long) * (size_t)(4 * blocks * c->trace_launches), c->stream));
+    }
+#endif
+    const int overlap = n_groups > 1 ? c->group_overlap : 0;
+    c->timing_overlapped = overlap != 0;
+    hipStream_t lanes[2] = {c->stream, c->stream};
+    if (overlap) {
+        int rc = group_streams(c, overlap, lanes);
+        if (rc) return rc;
+        HIPCHK(c, hipEventRecord(c->group_fork, c->stream));
+        for (hipStream_t st : lanes) HIPCHK(c, hipStreamWaitEvent(st, c->group_fork, 0));
+    }
     int64_t launches = 0;
     for (int g = 0; g < n_groups; ++g) {
         const int j0 = g * vpl, nj = (n_ref - j0) < vpl ? (n_ref - j0) : vpl;
+        hipStream_t stream = lanes[g % 2];
         amvs::StepArgs a = base_args(c, p->patch_size, nj, TH);
         a.fast = fast;
         a.band_major = band_major;
@@ -603,13 +693,14 @@ int run_fused_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
         a.jobs = c->d_jobs.get() + j0;                   // slots stay global: job.slot = index in the batch
         a.depth_min = p->depth_min; a.depth_max = p->depth_max;
         a.seed = seed;
+        a.edge_first = c->edge_first < 0 ? (overlap != 0) : c->edge_first;
         int cur = cur0;
         // initialisation (mvs_patchmatch.py:268-284); a continuation call resumes the context's state
         if (do_init)
             HIPCHK(c, amvs::launch_init(a.jobs, nj, (long long)hw, seed, p->log_depth_scale, p->log_depth_min,
-                                        c->d_depth[cur].get(), c->d_normal[0].get(), c->d_cost.get(), c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_groups[3 * g], c->stream));
-        if (c->step_timing) HIPCHK(c, hipEventRecord(c->ev_steps[c->n_step_events++], c->stream));
+                                        c->d_depth[cur].get(), c->d_normal[0].get(), c->d_cost.get(), stream));
+        HIPCHK(c, hipEventRecord(c->ev_groups[3 * g], stream));
+        if (c->step_timing) HIPCHK(c, hipEventRecord(c->ev_steps[c->n_step_events++], stream));
         for (size_t i = 0; i < sched.size(); ++i) {
             const SchedStep &st = sched[i];
             apply_step(a, st);
@@ -617,23 +708,32 @@ int run_fused_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
             a.tiles_y = (c->H + a.TH - 1) / a.TH;
             a.wg_cap = shapes[i].wg_cap;
             set_io(a, c, cur);
-            HIPCHK(c, amvs::launch_step(p->patch_size, n_src, a, c->stream));
-            if (c->step_timing) HIPCHK(c, hipEventRecord(c->ev_steps[c->n_step_events++], c->stream));
+#ifdef AMVS_STEP_TRACE
+            a.trace = c->d_trace.get() + 4 * c->trace_stride * ((long long)g * (long long)sched.size() + (long long)i);
+#endif
+            HIPCHK(c, amvs::launch_step(p->patch_size, n_src, a, stream));
+            if (c->step_timing) HIPCHK(c, hipEventRecord(c->ev_steps[c->n_step_events++], stream));
             cur ^= st.flip_d; ++launches;
         }
         a.TH = TH;
         a.tiles_y = (c->H + TH - 1) / TH;
         a.wg_cap = 0;
-        HIPCHK(c, hipEventRecord(c->ev_groups[3 * g + 1], c->stream));
+        a.trace = nullptr;
+        HIPCHK(c, hipEventRecord(c->ev_groups[3 * g + 1], stream));
         // _compute_confidence (mvs_patchmatch.py:493-534), written straight into the output
         if (do_conf) {
             a.mode = amvs::MODE_CONF;
             set_io(a, c, cur);
             a.aux = conf_dev ? (float *)conf_dev : c->d_aux.get();
-            HIPCHK(c, amvs::launch_step(p->patch_size, n_src, a, c->stream));
+            HIPCHK(c, amvs::launch_step(p->patch_size, n_src, a, stream));
         }
-        HIPCHK(c, hipEventRecord(c->ev_groups[3 * g + 2], c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_groups[3 * g + 2], stream));
     }
+    if (overlap)
+        for (hipStream_t st : lanes) {
+            HIPCHK(c, hipEventRecord(c->group_join, st));
+            HIPCHK(c, hipStreamWaitEvent(c->stream, c->group_join, 0));
+        }
     c->timing.sweep_launches = launches;
     c->last_views_per_launch = vpl;
     return AMVS_OK;
@@ -842,7 +942,11 @@ extern "C" {
 #ifdef AMVS_CHECK_INDICES
 const char *amvs_version(void) { return "amvs 0.1 (gfx950) +index-checks"; }
 #else
+#ifdef AMVS_STEP_TRACE
+const char *amvs_version(void) { return "amvs 0.1 (gfx950) +step-trace"; }
+#else
 const char *amvs_version(void) { return "amvs 0.1 (gfx950)"; }
+#endif
 #endif
 
 int amvs_index_check(uint64_t report[4], int reset)
@@ -904,6 +1008,9 @@ int amvs_destroy(amvs_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)amvs_comm_destroy(c);
     for (auto &st : c->split_streams) (void)hipStreamDestroy(st);
+    for (auto &pair : c->group_streams)
+        for (auto &st : pair) if (st) (void)hipStreamDestroy(st);
+    for (hipEvent_t ev : {c->group_fork, c->group_join}) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->split_events) (void)hipEventDestroy(ev);
     for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->ev_groups) (void)hipEventDestroy(ev);
@@ -1206,6 +1313,50 @@ int amvs_set_step_tuning(amvs_ctx *c, int n_iterations, const int32_t *tile_rows
         }
         c->tune_rows.push_back(r); c->tune_cap.push_back(w);
     }
+    return AMVS_OK;
+}
+
+int amvs_set_launch_order(amvs_ctx *c, int edge_first, int group_overlap)
+{
+    if (!c) return AMVS_EINVAL;
+    if (edge_first < -1 || edge_first > 1 || group_overlap < -1 || group_overlap > 2)
+        return fail(c, AMVS_EINVAL, "launch order: edge_first in -1..1, group_overlap in -1..2");
+    c->edge_first = edge_first < 0 ? AMVS_DEFAULT_EDGE_FIRST : edge_first;
+    c->group_overlap = group_overlap < 0 ? AMVS_DEFAULT_GROUP_OVERLAP : group_overlap;
+    return AMVS_OK;
+}
+
+int amvs_sweep_order(int n_jobs, int tiles_x, int tiles_y, int band_major, int paired, int edge_first,
+                     int64_t capacity, int32_t *out, int32_t *n_blocks)
+{
+    if (n_jobs < 1 || tiles_x < 1 || tiles_y < 1 || !n_blocks || (capacity > 0 && !out)) return AMVS_EINVAL;
+    if ((long long)n_jobs * tiles_x * tiles_y > (1ll << 28)) return AMVS_EINVAL;
+    const int waves = amvs::step_wg_waves(paired != 0);
+    const int nblk = amvs::step_grid_blocks(n_jobs, tiles_x, tiles_y, paired != 0);
+    *n_blocks = nblk;
+    for (int bid = 0; bid < nblk; ++bid)
+        for (int wv = 0; wv < waves; ++wv) {
+            const int64_t o = 5 * ((int64_t)bid * waves + wv);
+            if (o + 5 > capacity) return AMVS_OK;
+            amvs::StripPos sp{};
+            const bool live = amvs::strip_decode_host(n_jobs, tiles_x, tiles_y, band_major, paired != 0, edge_first, bid, nblk, wv, sp);
+            out[o] = live ? sp.job : -1; out[o + 1] = live ? sp.ty : -1; out[o + 2] = live ? sp.tx : -1;
+            out[o + 3] = live ? sp.up : -1; out[o + 4] = live ? sp.paired : -1;
+        }
+    return AMVS_OK;
+}
+
+int amvs_fetch_step_trace(amvs_ctx *c, uint64_t *out, int64_t capacity, int64_t *n_launches, int64_t *blocks_per_launch)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!n_launches || !blocks_per_launch || (capacity > 0 && !out)) return fail(c, AMVS_EINVAL, "NULL argument");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    *n_launches = c->trace_launches; *blocks_per_launch = c->trace_stride;
+    const int64_t n = 4 * c->trace_launches * c->trace_stride;
+    if (n == 0 || capacity < n) return AMVS_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, c->d_trace.get(), sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
     return AMVS_OK;
 }
 

@@ -102,9 +102,9 @@ __global__ __launch_bounds__(AMVS_WAVE) void pm_step_generic_kernel(const StepAr
 
     const int lane = threadIdx.x;
     if (U8 && !FAST) fill_gray_lut(lut, lane);
-    const int t = xcd_remap(blockIdx.x, gridDim.x);
-    int job_id, ty, tx;
-    strip_of(a, t, job_id, ty, tx);
+    StripPos sp;
+    if (!sweep_strip(a, false, 1, 0, sp)) return;
+    const int job_id = sp.job, ty = sp.ty, tx = sp.tx;
 
     const JobCP job = (JobCP)(a.jobs + job_id);
     const int H = a.H, W = a.W, mode = a.mode;

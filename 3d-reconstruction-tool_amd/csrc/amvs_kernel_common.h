@@ -4,6 +4,7 @@
 #include "amvs_kernels.h"
 #include "amvs_device.h"
 #include "amvs_dispatch.h"
+#include "amvs_strip_order.h"
 
 #include <type_traits>
 
@@ -25,32 +26,6 @@ AMVS_DEV JobCP reload(JobCP p)
 
 // (Non-temporal hints on the streaming state were measured without effect on MI355X -- 31.8 vs 31.7
 // G px-hyp/s -- and are not used.)
-
-// contiguous strip ranges per XCD (blocks are dealt round-robin to XCDs); bijective
-AMVS_DEV int xcd_remap(int bid, int nblk)
-{
-    int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-    int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + (bid >> 3);
-}
-
-// strip index -> (job, strip row, strip column); see StepArgs::band_major
-AMVS_DEV void strip_of(const StepArgs &a, int t, int &job_id, int &ty, int &tx)
-{
-    if (a.band_major) {
-        const int per_band = a.n_jobs * a.tiles_x;
-        ty = t / per_band;
-        const int rem = t - ty * per_band;
-        job_id = rem / a.tiles_x;
-        tx = rem - job_id * a.tiles_x;
-    } else {
-        const int tiles_per_job = a.tiles_x * a.tiles_y;
-        job_id = t / tiles_per_job;
-        const int rem = t - job_id * tiles_per_job;
-        ty = rem / a.tiles_x;
-        tx = rem - ty * a.tiles_x;
-    }
-}
 
 // per-row validity bits of the last K/2+1 rows packed into one (or two) registers
 template <int K, int S> struct Hist {
@@ -142,7 +117,38 @@ AMVS_DEV void propagate_normals(const uint32_t *nq, int head, int n, int lane, f
 #define AMVS_PAIR_COLS 2
 #endif
 constexpr int PAIR_WAVES = 2 * AMVS_PAIR_COLS;
+
+// strip of wave `wv` of this block (amvs_strip_order.h; wave-uniform); false: the wave has none
+AMVS_DEV bool sweep_strip(const StepArgs &a, bool pair, int wg_waves, int wv, StripPos &p)
+{
+    return strip_decode(a.n_jobs, a.tiles_x, a.tiles_y, a.band_major, pair, AMVS_PAIR_COLS, wg_waves, a.edge_first,
+                        (int)blockIdx.x, (int)gridDim.x, wv, p);
+}
 constexpr bool step_pair_supported_ks(int K, int S) { return K >= 5 && K <= 11 && S <= 4; }
+
+// Workgroup timeline (-DAMVS_STEP_TRACE, tools/step_timeline.py; the shipped build compiles it away): wave 0 of
+// every sweep workgroup records, with ordinary stores, [0] the constant-rate wall clock (100 MHz) at entry, [1] before
+// exit, [2] the XCC it runs on, [3] job << 40 | strip row << 20 | strip column into StepArgs::trace[4 * block].
+#ifdef AMVS_STEP_TRACE
+AMVS_DEV void step_trace_entry(const StepArgs &a, int wv, int lane, int job_id, int ty, int tx)
+{
+    if (a.trace && wv == 0 && lane == 0) {
+        unsigned long long *r = a.trace + 4ull * blockIdx.x;
+        r[0] = wall_clock64();
+        r[2] = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xFu;              // hwreg(HW_REG_XCC_ID, 0, 4)
+        r[3] = ((unsigned long long)job_id << 40) | ((unsigned long long)ty << 20) | (unsigned long long)tx;
+    }
+}
+AMVS_DEV void step_trace_exit(const StepArgs &a, int wv, int lane)
+{
+    if (a.trace && wv == 0 && lane == 0) a.trace[4ull * blockIdx.x + 1] = wall_clock64();
+}
+#define AMVS_TRACE_ENTRY(...) step_trace_entry(__VA_ARGS__)
+#define AMVS_TRACE_EXIT(...) step_trace_exit(__VA_ARGS__)
+#else
+#define AMVS_TRACE_ENTRY(...) ((void)0)
+#define AMVS_TRACE_EXIT(...) ((void)0)
+#endif
 
 static_assert(list_max(SourceCounts{}) == AMVS_KMAX_SRC, "SourceCounts ends at AMVS_KMAX_SRC (Job::src, Job::fsrc)");
 static_assert(list_max(CompiledPatches{}) <= AMVS_MAX_PATCH, "a compiled patch size beyond AMVS_MAX_PATCH");

@@ -1,5 +1,6 @@
 // amvs_kernels.h -- host-visible launch interface of the gfx950 kernels.
 #pragma once
+#include "amvs_strip_order.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -102,6 +103,11 @@ struct StepArgs : StepArgsBase {
     // Paired-band schedule of the fast step (pm_step_fast_kernel<..., PAIR = true>): 2 x 2 strips per
     // workgroup, vertically adjacent bands exchange their boundary samples through LDS
     int paired;
+    // Dispatch order inside every XCD's range: 1 = each view's bands from the image edge towards its centre
+    // (amvs_strip_order.h), 0 = top to bottom.  Performance only.
+    int edge_first;
+    // -DAMVS_STEP_TRACE builds: [grid][4] workgroup timeline of this launch (amvs_kernel_common.h), or NULL
+    unsigned long long *trace;
 };
 
 #define AMVS_DEFAULT_WGS_PER_CU 4
@@ -140,6 +146,11 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
 int strip_out_width(int K);
 int step_waves_per_cu(int K, int S, bool u8, int wg_cap = 0);      // resident waves per CU under the cap (0 = default)
 hipError_t launch_step(int K, int S, const StepArgs &a, hipStream_t st);
+// launch geometry and strip decode of the step kernels on the host (amvs_strip_order.h; amvs_sweep_order)
+int step_wg_waves(bool paired);
+int step_grid_blocks(int n_jobs, int tiles_x, int tiles_y, bool paired);
+bool strip_decode_host(int n_jobs, int tiles_x, int tiles_y, int band_major, bool paired, int edge_first, int bid, int nblk,
+                       int wv, StripPos &p);
 hipError_t launch_sweep(int K, int S, const SweepArgs &a, hipStream_t st);
 // amvs_kernels_fast.hip: the same steps in the fast arithmetic (a.fast != 0; launch_step /
 // launch_sweep forward to these)

@@ -76,29 +76,17 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), mi
     int q_head = 0, q_tail = 0;                          // wave-uniform; at most 63 + 58 entries queued
     window_sums_init<K, S>(hbuf, lane);
     if (U8) fill_gray_lut(lut, lane);
-    const int tiles_per_job = a.tiles_x * a.tiles_y;
     int job_id, ty, tx;
     bool paired = false;                       // this wave has a partner band to exchange with
     int up = 0;                                // 1: the wave walks up the image (lower band of a pair)
-    if constexpr (PAIR) {
-        constexpr int PC = AMVS_PAIR_COLS;
-        const int col_pairs = (a.tiles_x + PC - 1) / PC, pair_rows = (a.tiles_y + 1) / 2;
-        const int wg = xcd_remap(blockIdx.x, gridDim.x);
-        job_id = wg / (col_pairs * pair_rows);
-        const int rem = wg - job_id * (col_pairs * pair_rows);
-        const int py = rem / col_pairs, px = rem - py * col_pairs;
-        tx = PC * px + (wv % PC);
-        up = wv / PC;
-        ty = 2 * py + up;
-        paired = 2 * py + 1 < a.tiles_y;
-        // (every wave fills the decode table first; a wave without a strip leaves before the first barrier of
-        //  the row loop, as do the partners of an odd last band that does not exist)
-        if (job_id >= a.n_jobs || tx >= a.tiles_x || ty >= a.tiles_y) return;
-    } else {
-        const int t = xcd_remap(blockIdx.x, gridDim.x) * AMVS_WG_WAVES + wv;
-        if (t >= a.n_jobs * tiles_per_job) return;                 // last workgroup only
-        strip_of(a, t, job_id, ty, tx);
+    {
+        // (a wave without a strip -- last workgroup, the partner of an odd last band -- leaves before the first
+        //  barrier of the row loop; its partner, if any, runs unpaired: `paired` is false)
+        StripPos sp;
+        if (!sweep_strip(a, PAIR, WGW, wv, sp)) return;
+        job_id = sp.job; ty = sp.ty; tx = sp.tx; up = sp.up; paired = sp.paired != 0;
     }
+    AMVS_TRACE_ENTRY(a, wv, lane, job_id, ty, tx);
 
     const JobCP job = (JobCP)(a.jobs + job_id);
     const int H = a.H, W = a.W, mode = MODE_T >= 0 ? MODE_T : a.mode;
@@ -392,6 +380,7 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), mi
             q_head += n;
         }
     }
+    AMVS_TRACE_EXIT(a, wv, lane);
 }
 
 // ------------------------------------------------------------------ split step (experiment) ---
@@ -714,6 +703,21 @@ bool patch_compiled(int K) { return in_list(CompiledPatches{}, K); }
 bool patch_supported(int K) { return K >= 3 && K <= AMVS_MAX_PATCH && (K & 1) == 1; }
 bool step_pair_supported(int K, int S) { return patch_compiled(K) && in_list(SourceCounts{}, S) && step_pair_supported_ks(K, S); }
 int strip_out_width(int K) { return AMVS_WAVE - 2 * (K / 2); }
+
+int step_wg_waves(bool paired) { return paired ? PAIR_WAVES : AMVS_WG_WAVES; }
+
+int step_grid_blocks(int n_jobs, int tiles_x, int tiles_y, bool paired)
+{
+    return paired ? n_jobs * ((tiles_x + AMVS_PAIR_COLS - 1) / AMVS_PAIR_COLS) * ((tiles_y + 1) / 2)
+                  : (n_jobs * tiles_x * tiles_y + AMVS_WG_WAVES - 1) / AMVS_WG_WAVES;
+}
+
+bool strip_decode_host(int n_jobs, int tiles_x, int tiles_y, int band_major, bool paired, int edge_first, int bid, int nblk,
+                       int wv, StripPos &p)
+{
+    return strip_decode(n_jobs, tiles_x, tiles_y, band_major, paired, AMVS_PAIR_COLS, step_wg_waves(paired), edge_first, bid,
+                        nblk, wv, p);
+}
 
 hipError_t launch_step(int K, int S, const StepArgs &a, hipStream_t st)
 {

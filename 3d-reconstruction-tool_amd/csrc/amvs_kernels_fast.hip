@@ -167,28 +167,17 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
     float *lring = lring_all + wv * ((NL > 0 ? NL : 1) * K * AMVS_WAVE);
     uint32_t *nq = nq_all + wv * NQ;
     int q_head = 0, q_tail = 0;
-    const int tiles_per_job = a.tiles_x * a.tiles_y;
     int job_id, ty, tx;
     bool paired = false;                       // this wave has a partner band to exchange with
     int up = 0;                                // 1: the wave walks up the image (lower band of a pair)
-    if constexpr (PAIR) {
-        constexpr int PC = AMVS_PAIR_COLS;                      // strip columns of a workgroup
-        const int col_pairs = (a.tiles_x + PC - 1) / PC, pair_rows = (a.tiles_y + 1) / 2;
-        const int wg = xcd_remap(blockIdx.x, gridDim.x);
-        job_id = wg / (col_pairs * pair_rows);
-        const int rem = wg - job_id * (col_pairs * pair_rows);
-        const int py = rem / col_pairs, px = rem - py * col_pairs;
-        tx = PC * px + (wv % PC);
-        up = wv / PC;
-        ty = 2 * py + up;
-        paired = 2 * py + 1 < a.tiles_y;
-        if (job_id >= a.n_jobs || tx >= a.tiles_x || ty >= a.tiles_y) return;   // (the partner of an exiting wave exits too,
-                                                                                //  or runs unpaired: `paired` is false)
-    } else {
-        const int t = xcd_remap(blockIdx.x, gridDim.x) * AMVS_WG_WAVES + wv;
-        if (t >= a.n_jobs * tiles_per_job) return;             // last workgroup only
-        strip_of(a, t, job_id, ty, tx);
+    {
+        // (a wave without a strip -- last workgroup, the partner of an odd last band -- leaves before the first
+        //  barrier of the row loop; its partner, if any, runs unpaired: `paired` is false)
+        StripPos sp;
+        if (!sweep_strip(a, PAIR, WGW, wv, sp)) return;
+        job_id = sp.job; ty = sp.ty; tx = sp.tx; up = sp.up; paired = sp.paired != 0;
     }
+    AMVS_TRACE_ENTRY(a, wv, lane, job_id, ty, tx);
 
     const JobCP job = (JobCP)(a.jobs + job_id);
     const int H = a.H, W = a.W, mode = MODE_T >= 0 ? MODE_T : a.mode;
@@ -423,6 +412,7 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
             q_head += n;
         }
     }
+    AMVS_TRACE_EXIT(a, wv, lane);
 }
 
 // ------------------------------------------------------------------ sample dump ---

@@ -107,6 +107,25 @@ class Engine:
         r, w = table(tile_rows), table(wgs_per_cu)
         self._chk(self._lib.amvs_set_step_tuning(self._h, n, r.ctypes.data_as(i32p), w.ctypes.data_as(i32p)))
 
+    def set_launch_order(self, edge_first=None, group_overlap=None):
+        """Dispatch order of the sweep steps (include/amvs.h amvs_set_launch_order): edge_first -- every XCD walks
+        each view's bands from the image edge to its centre; group_overlap -- 0 one stream, 1 / 2 the view groups on
+        two streams of equal / high-low priority.  None = the library's default.  Performance only."""
+        self._chk(self._lib.amvs_set_launch_order(self._h, -1 if edge_first is None else int(bool(edge_first)),
+                                                  -1 if group_overlap is None else int(group_overlap)))
+
+    def step_trace(self):
+        """(n_launches, blocks_per_launch, 4) uint64 workgroup timeline of the last PatchMatch call; needs a library
+        built with -DAMVS_STEP_TRACE (None from the shipped build)."""
+        nl, nb = C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.amvs_fetch_step_trace(self._h, None, 0, C.byref(nl), C.byref(nb)))
+        if nl.value == 0:
+            return None
+        out = np.zeros((nl.value, nb.value, 4), np.uint64)
+        self._chk(self._lib.amvs_fetch_step_trace(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64)), out.size,
+                                                  C.byref(nl), C.byref(nb)))
+        return out
+
     def set_step_timing(self, enable=True):
         self._chk(self._lib.amvs_set_step_timing(self._h, int(bool(enable))))
 

@@ -179,6 +179,32 @@ int amvs_set_step_tuning(amvs_ctx *ctx, int n_iterations, const int32_t *tile_ro
  * stream, recorded when enabled; view groups concatenated, schedule order within a group).      */
 int amvs_set_step_timing(amvs_ctx *ctx, int enable);
 int amvs_get_step_times(amvs_ctx *ctx, float *ms_out, int capacity, int *n_out);
+/* Dispatch order of the PatchMatch sweep steps (performance only; the maps do not depend on it --
+ * tests/test_hip_launch_order.py).  edge_first: 1 = inside the contiguous range of strips every XCD receives, each
+ * view's bands run from the image edge towards its centre -- the part in the upper half downwards, then the part
+ * in the lower half upwards -- so that the slow edge bands start first and do not form the tail of the launch;
+ * 0 = top to bottom.  group_overlap: the view groups of a batch (views_per_launch) run 0 = one after the other
+ * on the context's stream, 1 = dealt to two streams of equal priority, 2 = dealt to a high / low priority pair;
+ * the streams fork from the context's stream and join it before the call returns.  -1 = the library's default:
+ * two equal streams, and edge-first exactly in the calls whose groups overlap (measured: DESIGN.md section 5).
+ * With overlapping groups amvs_get_timing reports, for init_ms, sweep_ms and confidence_ms, the UNION of the
+ * groups' intervals (chip time, as on one stream; sweep_launches stays the launch count), and amvs_get_step_times
+ * keeps working per stream: a launch's time is then that of a launch sharing the chip with the other stream.   */
+int amvs_set_launch_order(amvs_ctx *ctx, int edge_first, int group_overlap);
+/* The strips of every wave of a sweep step launch as the kernels decode them (the host copy of the same function,
+ * csrc/amvs_strip_order.h; no GPU involved, ctx-free; test infrastructure): out is [n_blocks][4 waves][5] =
+ * (job, strip row, strip column, walks up, has a partner band), -1 for a wave without a strip; block b runs on
+ * XCD b % 8 and an XCD starts its blocks in ascending order.  Writes as many whole records as `capacity` int32
+ * values hold; *n_blocks is the grid of the launch.                                                           */
+int amvs_sweep_order(int n_jobs, int tiles_x, int tiles_y, int band_major, int paired, int edge_first,
+                     int64_t capacity, int32_t *out, int32_t *n_blocks);
+/* Workgroup timeline of the sweep launches of the LAST PatchMatch call, from a library built with
+ * -DAMVS_STEP_TRACE (amvs_version() then ends in "+step-trace"; tools/step_timeline.py): out is
+ * [n_launches][blocks_per_launch][4] = (100 MHz wall clock at entry, before exit, XCC id,
+ * job << 40 | strip row << 20 | strip column) of wave 0 of every workgroup, zeros beyond a launch's grid;
+ * launches in issue order (view groups concatenated).  The shipped build records nothing: *n_launches = 0.
+ * Nothing is copied when `capacity` (in values) is too small.                                                  */
+int amvs_fetch_step_trace(amvs_ctx *ctx, uint64_t *out, int64_t capacity, int64_t *n_launches, int64_t *blocks_per_launch);
 /* Split schedule (AMVS_SCHEDULE_SPLIT): number of view groups pipelined against each other (1..8),
  * rows per strip of the sampling kernel, and bytes of unused LDS per sampling workgroup (caps how
  * many of them a CU holds, which leaves room for the window kernel); 0 = automatic.              */

@@ -114,6 +114,17 @@ if "TCC_HIT_sum" in vals and "TCC_MISS_sum" in vals:
     out.append(f"L2 hit rate {vals['TCC_HIT_sum']/(vals['TCC_HIT_sum']+vals['TCC_MISS_sum']):.3f}; "
                f"misses are 128-byte lines: {vals['TCC_MISS_sum']*128/1e9:.2f} GB per launch from the fabric "
                "(FETCH_SIZE tallies them at 64 B, MI355X_MICROARCH.md)")
+if all(k in vals for k in ("SQ_WAVES", "SQ_WAVE_CYCLES", "SQ_BUSY_CYCLES")):
+    # Slot occupancy of a launch.  Units as read and then checked against the workgroup timeline
+    # (tools/step_timeline.py, profiles/r05_logs/step_timeline.log: its `used` share of the slot-time and its
+    # workgroup duration agree with these to a few points): SQ_WAVE_CYCLES counts quad-cycles, SQ_BUSY_CYCLES is
+    # summed over the 32 shader engines.  SLOTS: resident wave slots of the launch (256 CUs x 4 workgroups x 4 waves).
+    slots = int(os.environ.get("SLOTS", "4096"))
+    wave_cycles = vals["SQ_WAVE_CYCLES"] * 4.0
+    launch_cycles = vals["SQ_BUSY_CYCLES"] / 32.0
+    out.append(f"slot occupancy SQ_WAVE_CYCLES x 4 / ({slots} slots x SQ_BUSY_CYCLES / 32) = "
+               f"{wave_cycles / (slots * launch_cycles):.3f}; {wave_cycles / vals['SQ_WAVES']:.0f} cycles per wave, "
+               f"{launch_cycles:.0f} cycles per launch, {vals['SQ_WAVES'] / slots:.2f} waves per slot")
 print("\n".join(out))
 if workload_key and "FETCH_SIZE" in vals and "WRITE_SIZE" in vals:
     path = "profiles/traffic.json"
