@@ -131,7 +131,9 @@ class PatchMatchMVS:
 
     def reconstruct_mesh(self, images: List[dict], poses: Dict[int, CameraPose], sparse_points: np.ndarray = None, *,
                          voxel_size: Optional[float] = None, bounds=None, trunc_voxels: float = 4.0,
-                         max_dim: int = 256) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                         max_dim: int = 256, min_component_faces: int = 0, keep_largest: bool = False,
+                         smooth_iterations: int = 0, smooth_lambda: float = 0.5, smooth_mu: float = -0.53,
+                         fix_boundary: bool = True, with_normals: bool = False) -> Tuple[np.ndarray, ...]:
         """Surface mesh of the scene: reconstruct()'s preparation, sweep and fusion, then the per-view depth maps
         fused into a truncated signed distance volume and its zero level set extracted by marching tetrahedra on
         the GPU (csrc/amvs_mesh.hip; no reference counterpart).  Returns (vertices (V,3) float32, faces (F,3) int32,
@@ -139,15 +141,26 @@ class PatchMatchMVS:
 
         bounds: ((xmin, ymin, zmin), (xmax, ymax, zmax)) of the volume; default the fused cloud's box padded by the
         truncation distance.  voxel_size: default the longest side / (max_dim - 1).  The truncation distance is
-        trunc_voxels * voxel_size.  The volume holds at most AMVS_TSDF_MAX_POINTS grid points (include/amvs.h)."""
+        trunc_voxels * voxel_size.  The volume holds at most AMVS_TSDF_MAX_POINTS grid points (include/amvs.h).
+
+        Clean-up on the device (csrc/amvs_mesh_clean.hip), in this order and each only when asked for:
+        min_component_faces > 0 drops the connected components with fewer faces and keep_largest all but the one with
+        the most; smooth_iterations > 0 runs that many Taubin lambda | mu iterations (smooth_lambda, smooth_mu;
+        fix_boundary keeps the vertices on open edges where they are); with_normals=True appends area-weighted vertex
+        normals (V,3) float32 to the result, a 4-tuple then.  With the defaults none of it runs."""
         rank, world = _parallel.rank_world(self.process_group)
         if world > 1:
             raise NotImplementedError("reconstruct_mesh runs on one process: meshing with a process group of "
                                       f"{world} ranks is not implemented (call it without a process group)")
         if trunc_voxels <= 0:
             raise ValueError("trunc_voxels must be positive")
+        if smooth_iterations < 0:
+            raise ValueError("smooth_iterations must not be negative")
         points, _, maps = self._reconstruct_maps(images, poses, sparse_points)
+        do_filter = min_component_faces > 0 or keep_largest
         empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), np.zeros((0, 3), np.uint8))
+        if with_normals:
+            empty += (np.zeros((0, 3), np.float32),)
         if maps is None or (bounds is None and len(points) == 0):
             return empty
         origin, voxel, dims, trunc = self._mesh_grid(points, bounds, voxel_size, trunc_voxels, max_dim)
@@ -159,7 +172,28 @@ class PatchMatchMVS:
         verts, faces, colors = self._engine.tsdf_mesh(self.K_scaled, [(poses[i].R, poses[i].t) for i in ids], self.min_views,
                                                       origin, voxel, dims, trunc, **src)
         print(f"  Mesh: {len(verts):,} vertices, {len(faces):,} faces ({time.time() - t0:.2f}s)")
-        return verts, faces, colors
+        if not (do_filter or smooth_iterations > 0 or with_normals):
+            return verts, faces, colors
+        t0 = time.time()
+        eng = self._engine
+        n_comp = 0
+        if do_filter:
+            n_comp, _, _ = eng.mesh_filter_components(min_component_faces, keep_largest)
+        if smooth_iterations > 0:
+            eng.mesh_smooth(smooth_iterations, smooth_lambda, smooth_mu, fix_boundary)
+        if with_normals:
+            eng.mesh_normals()
+        out = eng.mesh_fetch(normals=with_normals, labels=do_filter)
+        line = []
+        if do_filter:
+            line.append(f"{n_comp:,} components -> {len(np.unique(out[-1])):,}, {len(out[1]):,} faces")
+            out = out[:-1]
+        if smooth_iterations > 0:
+            line.append(f"{smooth_iterations} Taubin iterations")
+        if with_normals:
+            line.append("normals")
+        print(f"  Clean-up: {', '.join(line)} ({time.time() - t0:.2f}s)")
+        return out
 
     def _mesh_inputs(self, maps):
         """(view indices, Engine.tsdf_integrate keyword arguments) of the maps _reconstruct_maps returned: the device

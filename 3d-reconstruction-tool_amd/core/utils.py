@@ -28,10 +28,11 @@ def save_ply(points: np.ndarray, colors: np.ndarray, output_path: str):
     print(f"Saved {n:,} points to {output_path}")
 
 
-def save_mesh_ply(vertices: np.ndarray, faces: np.ndarray, colors: np.ndarray, output_path: str):
+def save_mesh_ply(vertices: np.ndarray, faces: np.ndarray, colors: np.ndarray, output_path: str, normals: np.ndarray = None):
     """Save a triangle mesh as binary little-endian PLY (read by MeshLab, Open3D and most tools): `element vertex`
     with float x, y, z and uchar red, green, blue; `element face` with `property list uchar int vertex_indices`.
-    vertices (V,3), faces (F,3) vertex ids, colors (V,3) RGB in 0..255."""
+    vertices (V,3), faces (F,3) vertex ids, colors (V,3) RGB in 0..255.  With normals (V,3) the vertex element is
+    x y z nx ny nz red green blue (the order MeshLab and Open3D write); without, the file is as it always was."""
     output_path = Path(output_path)
     output_path.parent.mkdir(parents=True, exist_ok=True)
     verts = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
@@ -42,8 +43,14 @@ def save_mesh_ply(vertices: np.ndarray, faces: np.ndarray, colors: np.ndarray, o
         raise ValueError("face vertex ids out of range")
     if cols.size and (cols.min() < 0 or cols.max() > 255):
         raise ValueError("colours must lie in 0..255")
-    vrec = np.empty(n_v, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("r", "u1"), ("g", "u1"), ("b", "u1")])
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        nrm = np.asarray(normals, dtype=np.float32).reshape(n_v, 3)
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    vrec = np.empty(n_v, dtype=fields + [("r", "u1"), ("g", "u1"), ("b", "u1")])
     vrec["x"], vrec["y"], vrec["z"] = verts[:, 0], verts[:, 1], verts[:, 2]
+    if normals is not None:
+        vrec["nx"], vrec["ny"], vrec["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     vrec["r"], vrec["g"], vrec["b"] = cols[:, 0], cols[:, 1], cols[:, 2]
     frec = np.empty(len(tris), dtype=[("n", "u1"), ("v", "<i4", (3,))])
     frec["n"] = 3
@@ -51,6 +58,7 @@ def save_mesh_ply(vertices: np.ndarray, faces: np.ndarray, colors: np.ndarray, o
     header = ("ply\nformat binary_little_endian 1.0\n"
               f"element vertex {n_v}\n"
               "property float x\nproperty float y\nproperty float z\n"
+              + ("property float nx\nproperty float ny\nproperty float nz\n" if normals is not None else "") +
               "property uchar red\nproperty uchar green\nproperty uchar blue\n"
               f"element face {len(tris)}\n"
               "property list uchar int vertex_indices\n"

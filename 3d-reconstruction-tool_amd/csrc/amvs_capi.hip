@@ -46,6 +46,7 @@ void check_fetch_extended(unsigned long long out[4], bool reset);
 void check_fetch_fusion(unsigned long long out[4], bool reset);
 void check_fetch_knn(unsigned long long out[4], bool reset);
 void check_fetch_mesh(unsigned long long out[4], bool reset);
+void check_fetch_mesh_clean(unsigned long long out[4], bool reset);
 }  // namespace amvs
 #endif
 
@@ -55,7 +56,7 @@ std::string g_create_error;
 
 // Sum of the violations all kernels have counted since the last reset and the record of the first one found
 // (out[1] = translation unit << 32 | source line: 1 amvs_kernels, 2 amvs_kernels_fast, 3 amvs_sweep_fast,
-// 4 amvs_sweep_exact, 5 amvs_generic, 6 amvs_extended, 7 amvs_fusion, 8 amvs_knn, 9 amvs_mesh; out[2] = the index, out[3] = the
+// 4 amvs_sweep_exact, 5 amvs_generic, 6 amvs_extended, 7 amvs_fusion, 8 amvs_knn, 9 amvs_mesh, 10 amvs_mesh_clean; out[2] = the index, out[3] = the
 // extent it was compared with).  Zeros in the shipped build.
 void index_report(uint64_t out[4], bool reset)
 {
@@ -65,7 +66,7 @@ void index_report(uint64_t out[4], bool reset)
     void (*const fetch[])(unsigned long long[4], bool) = {
         amvs::check_fetch_kernels, amvs::check_fetch_kernels_fast, amvs::check_fetch_sweep_fast, amvs::check_fetch_sweep_exact,
         amvs::check_fetch_generic, amvs::check_fetch_extended, amvs::check_fetch_fusion, amvs::check_fetch_knn,
-        amvs::check_fetch_mesh};
+        amvs::check_fetch_mesh, amvs::check_fetch_mesh_clean};
     for (auto f : fetch) {
         unsigned long long r[4] = {0, 0, 0, 0};
         f(r, reset);
@@ -2037,6 +2038,88 @@ int amvs_tsdf_fetch_volume(amvs_ctx *c, float *tsdf, float *weight, float *color
     int rc = bind_device(c);
     if (rc) return rc;
     HIPCHK(c, amvs::tsdf_fetch_volume(c->tsdf.get(), tsdf, weight, color_sum, c->stream));
+    return checked(c, AMVS_OK);
+}
+
+// ---- mesh clean-up (amvs_mesh_clean.hip): in place on the context's current mesh ----
+int amvs_mesh_set(amvs_ctx *c, const float *vertices, int64_t n_vertices, const int32_t *faces, int64_t n_faces,
+                  const uint8_t *colors_rgb)
+{
+    if (!c) return AMVS_EINVAL;
+    if (n_vertices < 0 || n_faces < 0 || (n_vertices > 0 && !vertices) || (n_faces > 0 && !faces))
+        return fail(c, AMVS_EINVAL, "mesh_set: bad argument");
+    if (n_vertices > INT32_MAX || 3 * n_faces > INT32_MAX)
+        return fail(c, AMVS_EINVAL, "mesh_set: mesh too large (int32 vertex ids, 3 * n_faces <= INT32_MAX)");
+    for (int64_t i = 0; i < 3 * n_vertices; ++i)
+        if (!std::isfinite(vertices[i])) return fail(c, AMVS_EINVAL, "mesh_set: vertex " + std::to_string(i / 3) + " is not finite");
+    for (int64_t f = 0; f < n_faces; ++f) {
+        const int32_t a = faces[3 * f], b = faces[3 * f + 1], d = faces[3 * f + 2];
+        if (a < 0 || b < 0 || d < 0 || a >= n_vertices || b >= n_vertices || d >= n_vertices)
+            return fail(c, AMVS_EINVAL, "mesh_set: face " + std::to_string(f) + " has a vertex id out of range");
+        if (a == b || a == d || b == d)
+            return fail(c, AMVS_EINVAL, "mesh_set: face " + std::to_string(f) + " has a repeated vertex id");
+    }
+    int rc = bind_device(c);
+    if (rc) return rc;
+    if (!c->tsdf) c->tsdf.reset(amvs::tsdf_state_new());
+    const hipError_t e = amvs::mesh_set(c->tsdf.get(), c->cache, vertices, n_vertices, faces, n_faces, colors_rgb, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_set: ") + hipGetErrorString(e));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_mesh_filter_components(amvs_ctx *c, int64_t min_faces, int keep_largest, int64_t *n_components, int64_t *n_vertices,
+                                int64_t *n_faces)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!n_components || !n_vertices || !n_faces) return fail(c, AMVS_EINVAL, "mesh_filter_components: NULL output");
+    if (!amvs::tsdf_has_mesh(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "mesh_filter_components: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    long long nc = 0, nv = 0, nf = 0;
+    const hipError_t e = amvs::mesh_filter_components(c->tsdf.get(), c->cache, min_faces, keep_largest != 0, &nc, &nv, &nf, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_filter_components: ") + hipGetErrorString(e));
+    *n_components = nc; *n_vertices = nv; *n_faces = nf;
+    return checked(c, AMVS_OK);
+}
+
+int amvs_mesh_smooth(amvs_ctx *c, int iterations, float lambda, float mu, int fix_boundary)
+{
+    if (!c) return AMVS_EINVAL;
+    if (iterations < 0 || iterations > 1000) return fail(c, AMVS_EINVAL, "mesh_smooth: iterations must lie in 0 .. 1000");
+    if (!(lambda > 0.0f && lambda <= 1.0f)) return fail(c, AMVS_EINVAL, "mesh_smooth: lambda must lie in (0, 1]");
+    if (!std::isfinite(mu)) return fail(c, AMVS_EINVAL, "mesh_smooth: mu must be finite");
+    if (!amvs::tsdf_has_mesh(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_smooth: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    const hipError_t e = amvs::mesh_smooth(c->tsdf.get(), c->cache, iterations, lambda, mu, fix_boundary != 0, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_smooth: ") + hipGetErrorString(e));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_mesh_normals(amvs_ctx *c)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::tsdf_has_mesh(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_normals: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    const hipError_t e = amvs::mesh_normals(c->tsdf.get(), c->cache, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_normals: ") + hipGetErrorString(e));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_fetch_mesh_attributes(amvs_ctx *c, float *normals, int32_t *labels)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::tsdf_has_mesh(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "fetch_mesh_attributes: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    if (normals && !amvs::mesh_has_normals(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "fetch_mesh_attributes: no current normals (amvs_mesh_normals)");
+    if (labels && !amvs::mesh_has_labels(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "fetch_mesh_attributes: no current labels (amvs_mesh_filter_components)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    HIPCHK(c, amvs::mesh_fetch_attributes(c->tsdf.get(), normals, labels, c->stream));
     return checked(c, AMVS_OK);
 }
 

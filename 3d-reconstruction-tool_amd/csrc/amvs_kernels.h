@@ -267,4 +267,17 @@ bool tsdf_has_mesh(const TsdfState *s);
 hipError_t tsdf_fetch_mesh(TsdfState *s, float *verts, int *faces, unsigned char *rgb, hipStream_t st);
 hipError_t tsdf_fetch_volume(TsdfState *s, float *tsdf, float *weight, float *color_sum, hipStream_t st);
 
+// amvs_mesh_clean.hip: clean-up of the state's current mesh in place (include/amvs.h amvs_mesh_*).  All synchronise.
+// replaces the mesh by host arrays the caller has validated (copies only); rgb NULL: zeros
+hipError_t mesh_set(TsdfState *s, ScratchCache &cache, const float *verts, long long nv, const int *faces, long long nf,
+                    const unsigned char *rgb, hipStream_t st);
+// n_components: before the filter; n_vertices, n_faces: after it
+hipError_t mesh_filter_components(TsdfState *s, ScratchCache &cache, long long min_faces, bool keep_largest, long long *n_components,
+                                  long long *n_vertices, long long *n_faces, hipStream_t st);
+hipError_t mesh_smooth(TsdfState *s, ScratchCache &cache, int iterations, float lambda, float mu, bool fix_boundary, hipStream_t st);
+hipError_t mesh_normals(TsdfState *s, ScratchCache &cache, hipStream_t st);
+bool mesh_has_normals(const TsdfState *s);
+bool mesh_has_labels(const TsdfState *s);
+hipError_t mesh_fetch_attributes(TsdfState *s, float *normals, int *labels, hipStream_t st);
+
 }  // namespace amvs

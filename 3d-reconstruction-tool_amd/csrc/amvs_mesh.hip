@@ -34,22 +34,11 @@
 #define AMVS_TU_ID 9
 #include "amvs_check.h"
 #include "amvs_kernels.h"
-#include "amvs_buffer.h"
-
-#include <hipcub/hipcub.hpp>
-
-#include <cstdint>
-#include <utility>
+#include "amvs_mesh_state.h"
 
 namespace amvs {
 
 namespace {
-
-#define MCHK(call)                                 \
-    do {                                           \
-        hipError_t e_ = (call);                    \
-        if (e_ != hipSuccess) return e_;           \
-    } while (0)
 
 // tetrahedron edges (local vertex pairs) 0:(0,1) 1:(0,2) 2:(0,3) 3:(1,2) 4:(1,3) 5:(2,3)
 __constant__ unsigned char k_edge_a[6] = {0, 0, 0, 1, 1, 2};
@@ -70,11 +59,6 @@ __constant__ unsigned char k_tet_c1[6] = {1, 1, 2, 2, 4, 4};
 __constant__ unsigned char k_tet_c2[6] = {3, 5, 3, 6, 5, 6};
 
 __device__ __forceinline__ int tri_count(unsigned c) { const int b = __popc(c); return b == 2 ? 2 : (b & 1); }
-
-struct Grid {
-    float ox, oy, oz, voxel;
-    int nx, ny, nz;
-};
 
 struct Kmat { float k[9]; };
 
@@ -277,81 +261,9 @@ __global__ __launch_bounds__(256) void face_kernel(const float *__restrict__ tsd
     }
 }
 
-// (d) drop the vertices no face uses (their edges are shared only by tetrahedra with an unobserved corner):
-// flag the used ones (every writer stores the same 1), scan, move the kept vertices down, renumber the faces
-__global__ __launch_bounds__(256) void vertex_used_kernel(const int *__restrict__ faces, long long n_ids, long long n_vertices,
-                                                          unsigned *__restrict__ used)
-{
-    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f < n_ids) used[AMVS_IDX((long long)faces[f], n_vertices)] = 1u;
-}
-
-__global__ __launch_bounds__(256) void vertex_compact_kernel(const float *__restrict__ verts, const unsigned char *__restrict__ rgb,
-                                                             const unsigned *__restrict__ used, const unsigned *__restrict__ new_id,
-                                                             long long n_vertices, long long n_kept, float *__restrict__ verts_out,
-                                                             unsigned char *__restrict__ rgb_out)
-{
-    const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= n_vertices || !used[v]) return;
-    const long long o = AMVS_IDX((long long)new_id[v], n_kept);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { verts_out[3 * o + c] = verts[3 * v + c]; rgb_out[3 * o + c] = rgb[3 * v + c]; }
-}
-
-__global__ __launch_bounds__(256) void face_renumber_kernel(int *__restrict__ faces, long long n_ids, long long n_vertices,
-                                                            const unsigned *__restrict__ new_id)
-{
-    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f < n_ids) faces[f] = (int)new_id[AMVS_IDX((long long)faces[f], n_vertices)];
-}
-
-inline dim3 grid_of(long long n) { return dim3((unsigned)((n + 255) / 256)); }
-
 }  // namespace
 
-// every buffer grows only: a volume, a scan or a mesh no larger than the largest before allocates nothing
-struct TsdfState {
-    Grid g{};
-    long long n = 0;                              // grid points
-    bool have_volume = false, have_mesh = false;
-    DeviceBuffer<float> tsdf, weight, color;      // [n], [n], [n][3]
-    DeviceBuffer<unsigned char> mask;
-    DeviceBuffer<unsigned> vcount, vbase, tcount, tbase;
-    DeviceBuffer<unsigned char> scan_tmp;
-    DeviceBuffer<float> cams;                     // [n_maps][12] R, t
-    DeviceBuffer<int> slots;                      // colour image of every map
-    DeviceBuffer<float> stage_depth, stage_conf;  // host maps
-    DeviceBuffer<unsigned char> stage_bgr;        // host colour images
-    DeviceBuffer<float> verts, verts2;
-    DeviceBuffer<int> faces;
-    DeviceBuffer<unsigned char> rgb, rgb2;
-    DeviceBuffer<unsigned> vused, vnew;           // (d): used flags and new ids of the vertices
-    long long n_vertices = 0, n_faces = 0;
-};
-
-namespace {
-
-hipError_t exclusive_scan(TsdfState *s, ScratchCache &cache, const unsigned *in, unsigned *out, long long n, hipStream_t st)
-{
-    size_t bytes = 0;
-    MCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, st));
-    MCHK(s->scan_tmp.reserve(bytes > 0 ? bytes : 1, cache));
-    return hipcub::DeviceScan::ExclusiveSum(s->scan_tmp.get(), bytes, in, out, (int)n, st);
-}
-
-// total of an exclusive scan: base[n-1] + count[n-1]
-hipError_t scan_total(const unsigned *count, const unsigned *base, long long n, long long *total, hipStream_t st)
-{
-    unsigned h[2] = {0, 0};
-    MCHK(hipMemcpyAsync(&h[0], count + n - 1, 4, hipMemcpyDeviceToHost, st));
-    MCHK(hipMemcpyAsync(&h[1], base + n - 1, 4, hipMemcpyDeviceToHost, st));
-    MCHK(hipStreamSynchronize(st));
-    *total = (long long)h[0] + (long long)h[1];
-    return hipSuccess;
-}
-
-}  // namespace
-
+// TsdfState, the scans and pass (d): amvs_mesh_state.h
 TsdfState *tsdf_state_new() { return new TsdfState(); }
 
 void tsdf_state_free(TsdfState *s) { delete s; }
@@ -375,7 +287,8 @@ hipError_t tsdf_integrate(TsdfState *s, ScratchCache &cache, const float *depth,
                           const int *slots_h, const float K[9], const float *poses_h, float min_views, const float origin[3],
                           float voxel, const int dims[3], float trunc, hipStream_t st)
 {
-    s->have_volume = s->have_mesh = false;
+    s->have_volume = false;
+    s->drop_mesh();
     const long long n = (long long)dims[0] * dims[1] * dims[2];
     const size_t hw = (size_t)H * W, nmap = hw * (size_t)n_maps;
     MCHK(reserve_volume(s, cache, n));
@@ -411,7 +324,8 @@ hipError_t tsdf_integrate(TsdfState *s, ScratchCache &cache, const float *depth,
 hipError_t tsdf_set_volume(TsdfState *s, ScratchCache &cache, const float *tsdf, const float *weight, const float *color_sum,
                            const float origin[3], float voxel, const int dims[3], hipStream_t st)
 {
-    s->have_volume = s->have_mesh = false;
+    s->have_volume = false;
+    s->drop_mesh();
     const long long n = (long long)dims[0] * dims[1] * dims[2];
     MCHK(reserve_volume(s, cache, n));
     MCHK(hipMemcpyAsync(s->tsdf.get(), tsdf, 4 * (size_t)n, hipMemcpyHostToDevice, st));
@@ -426,7 +340,7 @@ hipError_t tsdf_set_volume(TsdfState *s, ScratchCache &cache, const float *tsdf,
 
 hipError_t tsdf_extract(TsdfState *s, ScratchCache &cache, long long *n_vertices, long long *n_faces, hipStream_t st)
 {
-    s->have_mesh = false;
+    s->drop_mesh();
     const long long n = s->n;
     // (a) vertices
     hipLaunchKernelGGL(edge_mask_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf.get(), (const float *)s->weight.get(),
@@ -459,21 +373,7 @@ hipError_t tsdf_extract(TsdfState *s, ScratchCache &cache, long long *n_vertices
     // (d) keep the vertices the faces use, in their order
     long long kept = 0;
     if (nv > 0 && nf > 0) {
-        MCHK(hipMemsetAsync(s->vused.get(), 0, 4 * (size_t)nv, st));
-        hipLaunchKernelGGL(vertex_used_kernel, grid_of(3 * nf), dim3(256), 0, st, (const int *)s->faces.get(), 3 * nf, nv,
-                           s->vused.get());
-        MCHK(hipGetLastError());
-        MCHK(exclusive_scan(s, cache, s->vused.get(), s->vnew.get(), nv, st));
-        MCHK(scan_total(s->vused.get(), s->vnew.get(), nv, &kept, st));
-        hipLaunchKernelGGL(vertex_compact_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->verts.get(),
-                           (const unsigned char *)s->rgb.get(), (const unsigned *)s->vused.get(), (const unsigned *)s->vnew.get(), nv,
-                           kept, s->verts2.get(), s->rgb2.get());
-        MCHK(hipGetLastError());
-        hipLaunchKernelGGL(face_renumber_kernel, grid_of(3 * nf), dim3(256), 0, st, s->faces.get(), 3 * nf, nv,
-                           (const unsigned *)s->vnew.get());
-        MCHK(hipGetLastError());
-        std::swap(s->verts, s->verts2);
-        std::swap(s->rgb, s->rgb2);
+        MCHK(drop_unused_vertices(s, cache, nv, nf, &kept, st));
     }
     nv = kept;
     MCHK(hipStreamSynchronize(st));

@@ -589,6 +589,7 @@ class Engine:
         colors (V,3) uint8 RGB)."""
         nv, nf = C.c_int64(0), C.c_int64(0)
         self._chk(self._lib.amvs_tsdf_extract(self._h, C.byref(nv), C.byref(nf)))
+        self._mesh_counts = (nv.value, nf.value)
         verts = np.empty((nv.value, 3), np.float32)
         faces = np.empty((nf.value, 3), np.int32)
         rgb = np.empty((nv.value, 3), np.uint8)
@@ -629,6 +630,60 @@ class Engine:
         self._chk(self._lib.amvs_tsdf_set_volume(self._h, _p(tsdf), _p(weight), _p(color), _p(org),
                                                  float(np.float32(voxel)), dmp))
         self._tsdf_dims = (nx, ny, nz)
+
+    # -- mesh clean-up (components, Taubin smoothing, normals), in place on the context's current mesh ----
+    def mesh_set(self, vertices, faces, colors=None):
+        """Make host arrays the context's mesh (include/amvs.h amvs_mesh_set): vertices (V,3) float32, faces (F,3)
+        int32, colors (V,3) uint8 RGB or None for zeros.  Finite positions, ids in [0, V) and no face with a repeated
+        id, else AmvsError."""
+        verts = _f32(np.asarray(vertices).reshape(-1, 3))
+        tris = np.ascontiguousarray(np.asarray(faces).reshape(-1, 3), dtype=np.int32)
+        cols = None
+        if colors is not None:
+            cols = np.ascontiguousarray(np.asarray(colors).reshape(-1, 3), dtype=np.uint8)
+            if len(cols) != len(verts):
+                raise ValueError(f"colors must be ({len(verts)}, 3)")
+        self._chk(self._lib.amvs_mesh_set(self._h, _p(verts), len(verts), tris.ctypes.data_as(i32p), len(tris),
+                                          None if cols is None else cols.ctypes.data_as(C.POINTER(C.c_uint8))))
+        self._mesh_counts = (len(verts), len(tris))
+
+    def mesh_filter_components(self, min_faces=0, keep_largest=False):
+        """Label the connected components and keep those with at least min_faces faces (keep_largest: only the one
+        with the most faces).  Returns (components before the filter, vertices, faces after it)."""
+        nc, nv, nf = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.amvs_mesh_filter_components(self._h, int(min_faces), int(bool(keep_largest)), C.byref(nc),
+                                                        C.byref(nv), C.byref(nf)))
+        self._mesh_counts = (nv.value, nf.value)
+        return nc.value, nv.value, nf.value
+
+    def mesh_smooth(self, iterations, lam=0.5, mu=-0.53, fix_boundary=True):
+        """Taubin smoothing of the current mesh's positions (include/amvs.h amvs_mesh_smooth)."""
+        self._chk(self._lib.amvs_mesh_smooth(self._h, int(iterations), float(lam), float(mu), int(bool(fix_boundary))))
+
+    def mesh_normals(self):
+        """Area-weighted vertex normals of the current mesh, fetched with mesh_fetch(normals=True)."""
+        self._chk(self._lib.amvs_mesh_normals(self._h))
+
+    def mesh_fetch(self, normals=False, labels=False):
+        """The current mesh: (vertices (V,3) float32, faces (F,3) int32, colors (V,3) uint8[, normals (V,3) float32]
+        [, labels (V,) int32])."""
+        counts = getattr(self, "_mesh_counts", None)
+        if counts is None:
+            raise AmvsError("no mesh: call tsdf_extract or mesh_set first")
+        nv, nf = counts
+        verts = np.empty((nv, 3), np.float32)
+        faces = np.empty((nf, 3), np.int32)
+        rgb = np.empty((nv, 3), np.uint8)
+        self._chk(self._lib.amvs_fetch_mesh(self._h, _p(verts), faces.ctypes.data_as(i32p),
+                                            rgb.ctypes.data_as(C.POINTER(C.c_uint8))))
+        out = [verts, faces, rgb]
+        nrm = np.empty((nv, 3), np.float32) if normals else None
+        lab = np.empty(nv, np.int32) if labels else None
+        if normals or labels:
+            self._chk(self._lib.amvs_fetch_mesh_attributes(self._h, None if nrm is None else _p(nrm),
+                                                           None if lab is None else lab.ctypes.data_as(i32p)))
+        out += [a for a in (nrm, lab) if a is not None]
+        return tuple(out)
 
     def knn_mean_distance(self, points, k=20):
         """Mean distance of every point to its k-1 nearest other points, bit-identical to

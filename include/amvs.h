@@ -332,6 +332,43 @@ int amvs_tsdf_fetch_volume(amvs_ctx *ctx, float *tsdf, float *weight, float *col
 int amvs_tsdf_set_volume(amvs_ctx *ctx, const float *tsdf, const float *weight, const float *color_sum,
                          const float origin[3], float voxel, const int32_t dims[3]);
 
+/* ---- mesh clean-up: components, Taubin smoothing, vertex normals (csrc/amvs_mesh_clean.hip) ------
+ * No reference counterpart (the reference has no mesh): judged against a NumPy restatement of the definitions below,
+ * bit for bit (tests/mesh_clean_restatement.py, DESIGN.md section 8 "Clean-up").  Every call works in place on the
+ * context's current mesh -- the one amvs_tsdf_extract made or amvs_mesh_set uploaded -- and synchronises;
+ * amvs_fetch_mesh returns the current mesh, cleaned or not.  No float atomics: every float sum runs in a fixed order
+ * over the corners c = 3 * face + k that hold the vertex, in ascending c.  Limits: int32 vertex ids and
+ * 3 * n_faces <= INT32_MAX.  Labels and normals are attributes of the current mesh: amvs_tsdf_integrate,
+ * amvs_tsdf_set_volume, amvs_tsdf_extract and amvs_mesh_set drop both, amvs_mesh_filter_components drops the normals
+ * and leaves fresh labels, amvs_mesh_smooth drops the normals and keeps the labels.                               */
+/* Replace the context's mesh by host arrays: n_vertices x 3 float32 positions, n_faces x 3 int32 vertex ids,
+ * n_vertices x 3 uint8 RGB colours (NULL: zeros).  A test hook, and the way to clean a mesh made elsewhere.
+ * Validated on the host before anything is copied -- finite positions, ids in [0, n_vertices), no face with a
+ * repeated id, the size limits -- else AMVS_EINVAL.  Copies only, no kernel.                                      */
+int amvs_mesh_set(amvs_ctx *ctx, const float *vertices, int64_t n_vertices, const int32_t *faces, int64_t n_faces,
+                  const uint8_t *colors_rgb);
+/* Connected components (vertices joined through faces; the label of a vertex is the smallest vertex id of its
+ * component; a vertex no face uses is a component of 0 faces) and their filter: keep the components with at least
+ * min_faces faces and, with keep_largest, only the one with the most faces (a tie goes to the smallest label).
+ * Faces, then vertices and colours, are compacted in their order and the labels renamed to the new ids.
+ * min_faces <= 0 without keep_largest removes nothing and only labels.  n_components counts the components BEFORE
+ * the filter; n_vertices and n_faces are the mesh after it.                                                       */
+int amvs_mesh_filter_components(amvs_ctx *ctx, int64_t min_faces, int keep_largest, int64_t *n_components,
+                                int64_t *n_vertices, int64_t *n_faces);
+/* Taubin smoothing: `iterations` (0 .. 1000) times an umbrella step with factor lambda (0 < lambda <= 1), then one with
+ * factor mu (finite; skipped if 0) on ping-pong buffers.  A step moves vertex p with deg incident corners to
+ * p + factor * (s / (2.0f * (float)deg) - p), s the float32 sum, in corner order, of the face's next vertex and the one
+ * after it; every operation is rounded to float32.  deg == 0 copies through, and so does, with fix_boundary, a vertex
+ * with an edge that exactly one face has.  Faces and colours are untouched.                                       */
+int amvs_mesh_smooth(amvs_ctx *ctx, int iterations, float lambda, float mu, int fix_boundary);
+/* Area-weighted vertex normals: the float32 sum, in corner order, of cross(p1 - p0, p2 - p0) of the incident faces,
+ * divided by its length sqrtf((x * x + y * y) + z * z); (0, 0, 0) unless the length is > 0.  They point the way the
+ * faces do (amvs_tsdf_extract: toward increasing TSDF, the cameras' side).                                        */
+int amvs_mesh_normals(amvs_ctx *ctx);
+/* n_vertices x 3 float32 normals (amvs_mesh_normals) and n_vertices int32 labels (amvs_mesh_filter_components) of
+ * the current mesh.  NULL skips an output; asking for one that is not current is AMVS_EINVAL.                     */
+int amvs_fetch_mesh_attributes(amvs_ctx *ctx, float *normals, int32_t *labels);
+
 /* ---- extended mode: what the reference's docstring names but does not implement ----------------
  * (mvs_patchmatch.py:1-13 lists plane hypotheses with normals and VIEW propagation; its code ignores
  * the normal in the cost, :323-390, and has no view propagation.)  Slanted-plane homography cost,
@@ -451,7 +488,7 @@ int amvs_write_ply(const char *path, const double *points, const int64_t *colors
  * with its buffer's extent before the access; a violation is counted, the first is recorded and the access
  * redirected to a safe index.  report[0] = violations since the last reset, report[1] = translation unit << 32 |
  * source line of the first, report[2] = its index, report[3] = the extent; amvs_sync, amvs_patchmatch,
- * amvs_plane_sweep, amvs_fetch_cloud and the amvs_tsdf_* / amvs_fetch_mesh calls return AMVS_EINDEX while a
+ * amvs_plane_sweep, amvs_fetch_cloud and the amvs_tsdf_* / amvs_mesh_* / amvs_fetch_mesh calls return AMVS_EINDEX while a
  * violation is on record.  The shipped build
  * compiles the checks away: it reports zeros.  (The reference has no counterpart; test infrastructure of the
  * device code.)                                                                                             */

@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
-"""Device time of the surface-mesh kernels (csrc/amvs_mesh.hip) at the CLI operating point (run on the GPU box):
+"""Device time of the surface-mesh kernels (csrc/amvs_mesh.hip, csrc/amvs_mesh_clean.hip) at the CLI operating point (run on the GPU box):
 16 views at 1008 x 756, patch 11, the maps of the extended mode (the reference's algorithm leaves too few correct
 depths for a surface) resident on the device, a 256^3 TSDF volume around the fused cloud.  Integration and extraction are timed separately with HIP events on the engine's stream (the extraction
 includes its two count read-backs); the first-order bounds of DESIGN.md section 8 are printed next to them.
+Then the clean-up stage on that mesh and on the mesh of a 256^3 sphere: the vertex -> corner index, labelling + filter,
+10 Taubin iterations and the normals, each the median of 5 after a warm-up, with a first-order byte estimate; and
+the labelling of a shuffled strip of 100 000 faces next to a sphere of about as many.
 
     python tools/mesh_time.py [n_views W H dim]
 """
@@ -57,7 +60,6 @@ for rep in range(REPS + 1):
     ms2, wall2, mesh = timed(eng.tsdf_extract)
     if rep:                                   # the first round loads the code objects and grows the buffers
         t_int.append(ms); t_ext.append(ms2); w_int.append(wall); w_ext.append(wall2)
-eng.set_stream(None)
 verts, faces, _ = mesh
 tsdf, weight, _ = eng.tsdf_volume()
 n_pts = dim ** 3
@@ -75,3 +77,74 @@ ext_bytes = n_pts * (8 + 1 + 4 + 4 + 4) * 2 + n_pts * 8 * 2
 print(f"  bounds (estimates): integrate VALU {valu_ms:.3f} ms / bytes {gather_ms:.3f} ms "
       f"({voxel_views:,} voxel-views x 30 VALU ops, x 11 B gathered + 20 B written per point); "
       f"extract streaming {ext_bytes / 8e12 * 1e3:.3f} ms ({ext_bytes / n_pts:.0f} B per point)")
+
+
+# ---- clean-up (csrc/amvs_mesh_clean.hip) ----
+sys.path.insert(0, "tests")
+import mesh_clean_inputs as ci  # noqa: E402
+import mesh_volumes as mv  # noqa: E402
+
+
+def clean_times(name, restore, min_faces=8):
+    """restore() makes the mesh current again (and drops its index).  The index is built by the first call that needs
+    it, so its time is that of normals on a fresh topology minus normals with the index in place."""
+    t = {k: [] for k in ("index", "label+filter", "pinned+1 it", "10 Taubin", "normals")}
+    for rep in range(REPS + 1):
+        nv, nf = restore()
+        first, _, _ = timed(eng.mesh_normals)
+        again, _, _ = timed(eng.mesh_normals)
+        one, _, _ = timed(lambda: eng.mesh_smooth(1))
+        ten, _, _ = timed(lambda: eng.mesh_smooth(10))
+        restore()
+        lab, _, counts = timed(lambda: eng.mesh_filter_components(min_faces))
+        if rep:
+            for k, x in zip(t, (first - again, lab, one, ten, again)):
+                t[k].append(x)
+    V, F = nv, nf
+    est = {"index": 3 * F * 4 * (2 + 4 * 4) + V * 8,                   # counts + keys + ids, 4 radix passes in and out
+           "label+filter": F * 12 * 3 + V * 4 * 4 + F * 8,              # hooks, flatten, face counts, keep flags + scan
+           "pinned+1 it": 3 * F * (12 + 6 * 12) + 2 * (V * 6 * 2 * 12 + V * 24),
+           "10 Taubin": 20 * (V * 6 * 2 * 12 + V * 6 * (4 + 12) + V * 24),  # per half-step: gathered positions, row, in + out
+           "normals": F * (12 + 36 + 12) + V * (6 * 16 + 12)}
+    print(f"clean-up of {name}: {V:,} vertices, {F:,} faces; filter at {min_faces} faces: {counts[0]:,} components, "
+          f"{counts[2]:,} faces kept")
+    for k in t:
+        print(f"  {k:13s} median {np.median(t[k]):8.3f} ms device (min {min(t[k]):.3f}); first-order bytes (estimate) "
+              f"{est[k] / 1e6:7.1f} MB = {est[k] / 8e12 * 1e3:.4f} ms at 8 TB/s")
+    return t
+
+
+def restore_volume():
+    v, f, _ = eng.tsdf_extract()
+    return len(v), len(f)
+
+
+clean_times(f"the CLI operating point ({dim}^3)", restore_volume)
+sphere = mv.sphere_volume(256, radius=0.8)
+eng.tsdf_set_volume(*sphere.arrays())
+clean_times("the 256^3 sphere", restore_volume)
+
+
+def label_time(name, restore):
+    ts = []
+    for rep in range(REPS + 1):
+        nv, nf = restore()
+        ms, _, counts = timed(eng.mesh_filter_components)
+        if rep:
+            ts.append(ms)
+    print(f"labelling of {name}: {nf:,} faces, {counts[0]} component(s): median {np.median(ts):.3f} ms (min {min(ts):.3f})")
+
+
+strip = ci.strip()
+
+
+def restore_strip():
+    eng.mesh_set(*strip.arrays())
+    return len(strip.verts), len(strip.faces)
+
+
+label_time("the shuffled strip", restore_strip)
+small_sphere = mv.sphere_volume(76, radius=0.8, trunc=0.1)
+eng.tsdf_set_volume(*small_sphere.arrays())
+label_time("a 76^3 sphere", restore_volume)
+eng.set_stream(None)
