@@ -1,0 +1,184 @@
+// amvs_capi_mesh.hip -- the TSDF and mesh entry points of the C ABI (include/amvs.h; amvs_mesh.hip,
+// amvs_mesh_clean.hip).
+#include "amvs_ctx.h"
+
+#include <cmath>
+
+using namespace amvs::host;
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+// the grid of a TSDF volume: finite origin, positive finite voxel, every dimension >= 2, the point budget
+static int check_tsdf_grid(amvs_ctx *c, const std::string &who, const float origin[3], float voxel, const int32_t dims[3])
+{
+    if (!(voxel > 0.0f) || !std::isfinite(voxel)) return fail(c, AMVS_EINVAL, who + ": voxel must be positive and finite");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(origin[a])) return fail(c, AMVS_EINVAL, who + ": origin must be finite");
+    if (dims[0] < 2 || dims[1] < 2 || dims[2] < 2) return fail(c, AMVS_EINVAL, who + ": every dimension must be >= 2");
+    const long long points = (long long)dims[0] * dims[1] * dims[2];
+    if (dims[0] > AMVS_TSDF_MAX_POINTS || dims[1] > AMVS_TSDF_MAX_POINTS || dims[2] > AMVS_TSDF_MAX_POINTS ||
+        points > AMVS_TSDF_MAX_POINTS)
+        return fail(c, AMVS_EINVAL, who + ": volume of " + std::to_string(dims[0]) + " x " + std::to_string(dims[1]) +
+                                        " x " + std::to_string(dims[2]) + " grid points is over the budget of " +
+                                        std::to_string((long long)AMVS_TSDF_MAX_POINTS) + " (AMVS_TSDF_MAX_POINTS)");
+    return AMVS_OK;
+}
+
+int amvs_tsdf_integrate(amvs_ctx *c, int n_maps, const void *depth, const void *conf, int maps_on_device,
+                        const int *view_ids, const uint8_t *colors_bgr_host, const float K[9], const float *poses,
+                        float min_views, const float origin[3], float voxel, const int32_t dims[3], float trunc)
+{
+    if (!c) return AMVS_EINVAL;
+    if (n_maps < 1 || !depth || !conf || !K || !poses || !origin || !dims)
+        return fail(c, AMVS_EINVAL, "tsdf_integrate: bad argument");
+    if ((view_ids != nullptr) == (colors_bgr_host != nullptr))
+        return fail(c, AMVS_EINVAL, "tsdf_integrate: give exactly one colour source (view_ids or colors_bgr_host)");
+    if (!(trunc > 0.0f) || !std::isfinite(trunc)) return fail(c, AMVS_EINVAL, "tsdf_integrate: trunc must be positive and finite");
+    int rc = check_tsdf_grid(c, "tsdf_integrate", origin, voxel, dims);
+    if (rc) return rc;
+    std::vector<int> slots(n_maps);
+    if (view_ids && (rc = check_colour_views(c, n_maps, view_ids))) return rc;
+    for (int j = 0; j < n_maps; ++j) slots[j] = view_ids ? view_ids[j] : j;
+    if ((rc = bind_device(c))) return rc;
+    if (!c->tsdf) c->tsdf.reset(amvs::tsdf_state_new());
+    const hipError_t e = amvs::tsdf_integrate(c->tsdf.get(), c->cache, (const float *)depth, (const float *)conf, maps_on_device != 0,
+                                              n_maps, c->H, c->W, view_ids ? c->d_bgr.get() : colors_bgr_host, view_ids != nullptr,
+                                              view_ids ? c->n_views : n_maps, slots.data(), K, poses, min_views, origin, voxel,
+                                              dims, trunc, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("tsdf_integrate: ") + hipGetErrorString(e));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_tsdf_set_volume(amvs_ctx *c, const float *tsdf, const float *weight, const float *color_sum, const float origin[3],
+                         float voxel, const int32_t dims[3])
+{
+    if (!c) return AMVS_EINVAL;
+    if (!tsdf || !weight || !color_sum || !origin || !dims) return fail(c, AMVS_EINVAL, "tsdf_set_volume: bad argument");
+    int rc = check_tsdf_grid(c, "tsdf_set_volume", origin, voxel, dims);
+    if (rc) return rc;
+    if ((rc = bind_device(c))) return rc;
+    if (!c->tsdf) c->tsdf.reset(amvs::tsdf_state_new());
+    const hipError_t e = amvs::tsdf_set_volume(c->tsdf.get(), c->cache, tsdf, weight, color_sum, origin, voxel, dims, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("tsdf_set_volume: ") + hipGetErrorString(e));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_tsdf_extract(amvs_ctx *c, int64_t *n_vertices, int64_t *n_faces)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!n_vertices || !n_faces) return fail(c, AMVS_EINVAL, "tsdf_extract: NULL output");
+    if (!amvs::tsdf_has_volume(c->tsdf.get())) return fail(c, AMVS_EINVAL, "tsdf_extract: no volume (amvs_tsdf_integrate)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    long long nv = 0, nf = 0;
+    const hipError_t e = amvs::tsdf_extract(c->tsdf.get(), c->cache, &nv, &nf, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("tsdf_extract: ") + hipGetErrorString(e));
+    *n_vertices = nv; *n_faces = nf;
+    return checked(c, AMVS_OK);
+}
+
+int amvs_fetch_mesh(amvs_ctx *c, float *vertices, int32_t *faces, uint8_t *colors_rgb)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::tsdf_has_mesh(c->tsdf.get())) return fail(c, AMVS_EINVAL, "fetch_mesh: no mesh (amvs_tsdf_extract)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    HIPCHK(c, amvs::tsdf_fetch_mesh(c->tsdf.get(), vertices, faces, colors_rgb, c->stream));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_tsdf_fetch_volume(amvs_ctx *c, float *tsdf, float *weight, float *color_sum)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::tsdf_has_volume(c->tsdf.get())) return fail(c, AMVS_EINVAL, "tsdf_fetch_volume: no volume (amvs_tsdf_integrate)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    HIPCHK(c, amvs::tsdf_fetch_volume(c->tsdf.get(), tsdf, weight, color_sum, c->stream));
+    return checked(c, AMVS_OK);
+}
+
+// ---- mesh clean-up (amvs_mesh_clean.hip): in place on the context's current mesh ----
+int amvs_mesh_set(amvs_ctx *c, const float *vertices, int64_t n_vertices, const int32_t *faces, int64_t n_faces,
+                  const uint8_t *colors_rgb)
+{
+    if (!c) return AMVS_EINVAL;
+    if (n_vertices < 0 || n_faces < 0 || (n_vertices > 0 && !vertices) || (n_faces > 0 && !faces))
+        return fail(c, AMVS_EINVAL, "mesh_set: bad argument");
+    if (n_vertices > INT32_MAX || 3 * n_faces > INT32_MAX)
+        return fail(c, AMVS_EINVAL, "mesh_set: mesh too large (int32 vertex ids, 3 * n_faces <= INT32_MAX)");
+    for (int64_t i = 0; i < 3 * n_vertices; ++i)
+        if (!std::isfinite(vertices[i])) return fail(c, AMVS_EINVAL, "mesh_set: vertex " + std::to_string(i / 3) + " is not finite");
+    for (int64_t f = 0; f < n_faces; ++f) {
+        const int32_t a = faces[3 * f], b = faces[3 * f + 1], d = faces[3 * f + 2];
+        if (a < 0 || b < 0 || d < 0 || a >= n_vertices || b >= n_vertices || d >= n_vertices)
+            return fail(c, AMVS_EINVAL, "mesh_set: face " + std::to_string(f) + " has a vertex id out of range");
+        if (a == b || a == d || b == d)
+            return fail(c, AMVS_EINVAL, "mesh_set: face " + std::to_string(f) + " has a repeated vertex id");
+    }
+    int rc = bind_device(c);
+    if (rc) return rc;
+    if (!c->tsdf) c->tsdf.reset(amvs::tsdf_state_new());
+    const hipError_t e = amvs::mesh_set(c->tsdf.get(), c->cache, vertices, n_vertices, faces, n_faces, colors_rgb, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_set: ") + hipGetErrorString(e));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_mesh_filter_components(amvs_ctx *c, int64_t min_faces, int keep_largest, int64_t *n_components, int64_t *n_vertices,
+                                int64_t *n_faces)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!n_components || !n_vertices || !n_faces) return fail(c, AMVS_EINVAL, "mesh_filter_components: NULL output");
+    if (!amvs::tsdf_has_mesh(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "mesh_filter_components: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    long long nc = 0, nv = 0, nf = 0;
+    const hipError_t e = amvs::mesh_filter_components(c->tsdf.get(), c->cache, min_faces, keep_largest != 0, &nc, &nv, &nf, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_filter_components: ") + hipGetErrorString(e));
+    *n_components = nc; *n_vertices = nv; *n_faces = nf;
+    return checked(c, AMVS_OK);
+}
+
+int amvs_mesh_smooth(amvs_ctx *c, int iterations, float lambda, float mu, int fix_boundary)
+{
+    if (!c) return AMVS_EINVAL;
+    if (iterations < 0 || iterations > 1000) return fail(c, AMVS_EINVAL, "mesh_smooth: iterations must lie in 0 .. 1000");
+    if (!(lambda > 0.0f && lambda <= 1.0f)) return fail(c, AMVS_EINVAL, "mesh_smooth: lambda must lie in (0, 1]");
+    if (!std::isfinite(mu)) return fail(c, AMVS_EINVAL, "mesh_smooth: mu must be finite");
+    if (!amvs::tsdf_has_mesh(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_smooth: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    const hipError_t e = amvs::mesh_smooth(c->tsdf.get(), c->cache, iterations, lambda, mu, fix_boundary != 0, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_smooth: ") + hipGetErrorString(e));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_mesh_normals(amvs_ctx *c)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::tsdf_has_mesh(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_normals: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    const hipError_t e = amvs::mesh_normals(c->tsdf.get(), c->cache, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_normals: ") + hipGetErrorString(e));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_fetch_mesh_attributes(amvs_ctx *c, float *normals, int32_t *labels)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::tsdf_has_mesh(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "fetch_mesh_attributes: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    if (normals && !amvs::mesh_has_normals(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "fetch_mesh_attributes: no current normals (amvs_mesh_normals)");
+    if (labels && !amvs::mesh_has_labels(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "fetch_mesh_attributes: no current labels (amvs_mesh_filter_components)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    HIPCHK(c, amvs::mesh_fetch_attributes(c->tsdf.get(), normals, labels, c->stream));
+    return checked(c, AMVS_OK);
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

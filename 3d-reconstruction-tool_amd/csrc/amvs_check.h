@@ -9,7 +9,7 @@
 // rounds).  The C ABI reports it: every synchronising entry point returns AMVS_EINDEX, amvs_index_check() returns
 // the record.  In the shipped build the macros are the identity and cost nothing.
 //
-// A translation unit defines AMVS_TU_ID (a small integer, see amvs_capi.hip: index_report) before including this
+// A translation unit defines AMVS_TU_ID (a small integer, see amvs_context.hip: index_report) before including this
 // header and places AMVS_CHECK_TU(name) once at file scope (outside any namespace).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -20,6 +20,7 @@
 #include "amvs_check.h"
 #include "amvs_kernels.h"
 #include "amvs_buffer.h"
+#include "amvs_handles.h"
 #include "amvs_dispatch.h"
 
 #include <hipcub/hipcub.hpp>
@@ -518,8 +519,8 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
     // the cell walk on the fine grid, then one cooperative box scan per query it left pending
     int left = (int)n;
     {
-        hipEvent_t e0, e1, e2;
-        if (debug) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventCreate(&e2); (void)hipEventRecord(e0, st); }
+        Event e0, e1, e2;
+        if (debug) { (void)e0.create(true); (void)e1.create(true); (void)e2.create(true); (void)hipEventRecord(e0.get(), st); }
         auto box = [&](int r_first, int r_last, int count) -> hipError_t {
             return dispatch(KnnSizes{}, k, hipErrorInvalidValue, [&](auto kc) {
                 return launch_box<kc()>(d_pts, d_sorted, gr, d_start, r_first, r_last, d_queries, count, d_pending, d_mean, n, st);
@@ -534,14 +535,14 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
             KCHK(box(KNN_SHELLS, KNN_SHELLS, left));
             KCHK(pending_list(left));
         }
-        if (debug) (void)hipEventRecord(e1, st);
+        if (debug) (void)hipEventRecord(e1.get(), st);
         if (left > 0) KCHK(box(2 * KNN_SHELLS, 1 << 30, left));     // (R = 4 as a wave's pass of its own: no gain, measured)
         if (debug) {
-            (void)hipEventRecord(e2, st);
+            (void)hipEventRecord(e2.get(), st);
             (void)hipStreamSynchronize(st);
             float ms0 = 0.f, ms1 = 0.f;
-            (void)hipEventElapsedTime(&ms0, e0, e1);
-            (void)hipEventElapsedTime(&ms1, e1, e2);
+            (void)hipEventElapsedTime(&ms0, e0.get(), e1.get());
+            (void)hipEventElapsedTime(&ms1, e1.get(), e2.get());
             std::fprintf(stderr, "knn: h %.4g grid %dx%dx%d (%.1f points per occupied cell)  cell walk + box 2: %.2f ms (%d queries to the box), "
                          "%d of %lld pending -> boxes 4, 8, ...: %.2f ms\n", gr.h, gr.g[0], gr.g[1], gr.g[2], fitted_per_cell, ms0, walk_again,
                          left, n, ms1);

@@ -128,3 +128,31 @@ def test_second_context_sweeping_at_the_same_time(mode):
         for rep in range(4):
             for a, b, what in zip(results[i][rep], alone[i], ("depth", "normal", "confidence")):
                 _eq(a, b, f"{mode} context {i} run {rep} {what}: concurrent vs alone")
+
+
+def test_handles_survive_three_context_lifetimes():
+    """Every stream and event a context owns is created, reused and destroyed: one PatchMatch call each with the
+    groups on one stream, on two equal streams and on a high / low pair, with the split schedule and with step
+    timing on, then the engine is destroyed -- three times over in one process.  Every configuration gives the same
+    maps bit for bit in every round, and within a round the three group_overlap settings agree bit for bit."""
+    sc = _u8_scene(N_VIEWS, H, W, 77)
+    refs, srcs = _batch(sc)
+    rounds = []
+    for _ in range(3):
+        maps = {}
+        with _engine(sc, "fast") as eng:
+            for overlap in (0, 1, 2):
+                eng.set_launch_order(1, overlap)
+                maps[f"overlap {overlap}"] = eng.patchmatch(refs, srcs, _params(sc, "fast", "auto"), 11)
+            maps["split"] = eng.patchmatch(refs, srcs, _params(sc, "fast", "split"), 11)
+            eng.set_step_timing(True)
+            maps["step timing"] = eng.patchmatch(refs, srcs, _params(sc, "fast", "auto"), 11)
+            assert len(eng.step_times()) == eng.timing()["sweep_launches"]
+        rounds.append(maps)
+    for n, maps in enumerate(rounds):
+        for config in maps:
+            for a, b, what in zip(maps[config], rounds[0][config], ("depth", "normal", "confidence")):
+                _eq(a, b, f"{config} {what}: round {n} vs round 0")
+        for overlap in (1, 2):
+            for a, b, what in zip(maps[f"overlap {overlap}"], maps["overlap 0"], ("depth", "normal", "confidence")):
+                _eq(a, b, f"round {n} {what}: overlap {overlap} vs one stream")
