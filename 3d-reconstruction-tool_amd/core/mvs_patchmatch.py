@@ -133,7 +133,8 @@ class PatchMatchMVS:
                          voxel_size: Optional[float] = None, bounds=None, trunc_voxels: float = 4.0,
                          max_dim: int = 256, min_component_faces: int = 0, keep_largest: bool = False,
                          smooth_iterations: int = 0, smooth_lambda: float = 0.5, smooth_mu: float = -0.53,
-                         fix_boundary: bool = True, with_normals: bool = False) -> Tuple[np.ndarray, ...]:
+                         fix_boundary: bool = True, with_normals: bool = False,
+                         decimate_voxels: float = 0.0) -> Tuple[np.ndarray, ...]:
         """Surface mesh of the scene: reconstruct()'s preparation, sweep and fusion, then the per-view depth maps
         fused into a truncated signed distance volume and its zero level set extracted by marching tetrahedra on
         the GPU (csrc/amvs_mesh.hip; no reference counterpart).  Returns (vertices (V,3) float32, faces (F,3) int32,
@@ -146,8 +147,11 @@ class PatchMatchMVS:
         Clean-up on the device (csrc/amvs_mesh_clean.hip), in this order and each only when asked for:
         min_component_faces > 0 drops the connected components with fewer faces and keep_largest all but the one with
         the most; smooth_iterations > 0 runs that many Taubin lambda | mu iterations (smooth_lambda, smooth_mu;
-        fix_boundary keeps the vertices on open edges where they are); with_normals=True appends area-weighted vertex
-        normals (V,3) float32 to the result, a 4-tuple then.  With the defaults none of it runs."""
+        fix_boundary keeps the vertices on open edges where they are); decimate_voxels > 0 decimates by vertex
+        clustering (csrc/amvs_mesh_decimate.hip) on cells of float32(decimate_voxels) * float32(voxel_size) that sit on
+        the volume's origin: one vertex per cell, and the faces that collapse or cancel go (a twelfth stay at 2);
+        with_normals=True appends area-weighted vertex normals (V,3) float32 to the result, a 4-tuple then.  With the
+        defaults none of it runs.  The grid of the last call is kept in last_mesh_grid (origin, voxel, dims, trunc)."""
         rank, world = _parallel.rank_world(self.process_group)
         if world > 1:
             raise NotImplementedError("reconstruct_mesh runs on one process: meshing with a process group of "
@@ -156,6 +160,8 @@ class PatchMatchMVS:
             raise ValueError("trunc_voxels must be positive")
         if smooth_iterations < 0:
             raise ValueError("smooth_iterations must not be negative")
+        if not (np.isfinite(decimate_voxels) and decimate_voxels >= 0):
+            raise ValueError("decimate_voxels must be finite and not negative")
         points, _, maps = self._reconstruct_maps(images, poses, sparse_points)
         do_filter = min_component_faces > 0 or keep_largest
         empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), np.zeros((0, 3), np.uint8))
@@ -164,6 +170,7 @@ class PatchMatchMVS:
         if maps is None or (bounds is None and len(points) == 0):
             return empty
         origin, voxel, dims, trunc = self._mesh_grid(points, bounds, voxel_size, trunc_voxels, max_dim)
+        self.last_mesh_grid = (origin, voxel, dims, trunc)
         print(f"\nMeshing: {dims[0]} x {dims[1]} x {dims[2]} TSDF grid, voxel {voxel:.4g}, truncation {trunc:.4g}")
         t0 = time.time()
         ids, src = self._mesh_inputs(maps)
@@ -172,24 +179,35 @@ class PatchMatchMVS:
         verts, faces, colors = self._engine.tsdf_mesh(self.K_scaled, [(poses[i].R, poses[i].t) for i in ids], self.min_views,
                                                       origin, voxel, dims, trunc, **src)
         print(f"  Mesh: {len(verts):,} vertices, {len(faces):,} faces ({time.time() - t0:.2f}s)")
-        if not (do_filter or smooth_iterations > 0 or with_normals):
+        decimate = decimate_voxels > 0
+        if not (do_filter or smooth_iterations > 0 or with_normals or decimate):
             return verts, faces, colors
         t0 = time.time()
         eng = self._engine
-        n_comp = 0
+        n_comp, n_faces = 0, len(faces)
         if do_filter:
-            n_comp, _, _ = eng.mesh_filter_components(min_component_faces, keep_largest)
+            n_comp, _, n_faces = eng.mesh_filter_components(min_component_faces, keep_largest)
         if smooth_iterations > 0:
             eng.mesh_smooth(smooth_iterations, smooth_lambda, smooth_mu, fix_boundary)
+        filtered = None
+        if decimate:
+            # the labels do not survive the decimation: what the line says of the filter is taken before it
+            filtered = (len(np.unique(eng.mesh_fetch(labels=True)[-1])) if do_filter else 0, n_faces)
+            cell = np.float32(decimate_voxels) * np.float32(voxel)
+            eng.mesh_decimate(np.asarray(origin, np.float64).astype(np.float32), cell)
         if with_normals:
             eng.mesh_normals()
-        out = eng.mesh_fetch(normals=with_normals, labels=do_filter)
+        out = eng.mesh_fetch(normals=with_normals, labels=do_filter and not decimate)
         line = []
-        if do_filter:
+        if do_filter and decimate:
+            line.append(f"{n_comp:,} components -> {filtered[0]:,}, {filtered[1]:,} faces")
+        elif do_filter:
             line.append(f"{n_comp:,} components -> {len(np.unique(out[-1])):,}, {len(out[1]):,} faces")
             out = out[:-1]
         if smooth_iterations > 0:
             line.append(f"{smooth_iterations} Taubin iterations")
+        if decimate:
+            line.append(f"decimation at {decimate_voxels:g} voxels: {filtered[1]:,} faces -> {len(out[1]):,}")
         if with_normals:
             line.append("normals")
         print(f"  Clean-up: {', '.join(line)} ({time.time() - t0:.2f}s)")

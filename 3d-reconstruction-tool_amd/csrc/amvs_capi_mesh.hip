@@ -1,5 +1,5 @@
 // amvs_capi_mesh.hip -- the TSDF and mesh entry points of the C ABI (include/amvs.h; amvs_mesh.hip,
-// amvs_mesh_clean.hip).
+// amvs_mesh_clean.hip, amvs_mesh_decimate.hip).
 #include "amvs_ctx.h"
 
 #include <cmath>
@@ -162,6 +162,25 @@ int amvs_mesh_normals(amvs_ctx *c)
     if (rc) return rc;
     const hipError_t e = amvs::mesh_normals(c->tsdf.get(), c->cache, c->stream);
     if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_normals: ") + hipGetErrorString(e));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_mesh_decimate(amvs_ctx *c, const float origin[3], float cell, int64_t *n_vertices, int64_t *n_faces)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!n_vertices || !n_faces) return fail(c, AMVS_EINVAL, "mesh_decimate: NULL output");
+    if (!origin) return fail(c, AMVS_EINVAL, "mesh_decimate: NULL origin");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(origin[a])) return fail(c, AMVS_EINVAL, "mesh_decimate: origin must be finite");
+    if (!(cell > 0.0f) || !std::isfinite(cell)) return fail(c, AMVS_EINVAL, "mesh_decimate: cell must be positive and finite");
+    if (!amvs::tsdf_has_mesh(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_decimate: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    long long bad = -1, nv = 0, nf = 0;
+    const hipError_t e = amvs::mesh_decimate(c->tsdf.get(), c->cache, origin, cell, &bad, &nv, &nf, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_decimate: ") + hipGetErrorString(e));
+    if (bad >= 0) return fail(c, AMVS_EINVAL, "mesh_decimate: vertex " + std::to_string(bad) + " outside the cluster grid");
+    *n_vertices = nv; *n_faces = nf;
     return checked(c, AMVS_OK);
 }
 

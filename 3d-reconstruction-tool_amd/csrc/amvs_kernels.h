@@ -280,4 +280,10 @@ bool mesh_has_normals(const TsdfState *s);
 bool mesh_has_labels(const TsdfState *s);
 hipError_t mesh_fetch_attributes(TsdfState *s, float *normals, int *labels, hipStream_t st);
 
+// amvs_mesh_decimate.hip: vertex clustering of the state's current mesh in place on the grid of cells of side `cell`
+// at `origin` (include/amvs.h amvs_mesh_decimate).  bad_vertex: -1, or the smallest id of a vertex outside the cluster
+// grid -- then nothing was changed.  Otherwise drops labels, normals and the index.  Synchronises.
+hipError_t mesh_decimate(TsdfState *s, ScratchCache &cache, const float origin[3], float cell, long long *bad_vertex,
+                         long long *n_vertices, long long *n_faces, hipStream_t st);
+
 }  // namespace amvs

@@ -1,0 +1,307 @@
+// amvs_mesh_decimate.hip -- decimation of the context's current mesh in place by vertex clustering on a grid of cubic
+// cells.  No reference counterpart.  Judged against tests/mesh_decimate_restatement.py, a NumPy statement of the same
+// definition with the same float32 operations in the same order (bit-identical positions, faces and colours).
+//
+// No float atomics: a cluster's position is a sequential sum over its members in ascending vertex id.  The one
+// integer atomic (the minimum of the out-of-range vertex ids) gives a result that does not depend on arrival order.
+//
+// (1) Cell.  Per vertex and axis q = (p - origin) / cell (two float32 operations, the division IEEE), i = floorf(q);
+//     -2^20 <= i < 2^20 or the call is refused before anything of the mesh is overwritten.
+//     key = (iz + 2^20) << 42 | (iy + 2^20) << 21 | (ix + 2^20).
+// (2) Clusters.  A stable radix sort of (key, vertex id) over the 63 key bits; the heads of the runs of equal keys,
+//     scanned, number the clusters in ascending key order (x fastest, the extraction's own point order) and every
+//     run lists its members in ascending vertex id.
+// (3) Representative.  One thread per cluster: s = 0; s += p[v] along the run; s / (float)count.  Colour: per channel
+//     the integer sum, (2 sum + count) / (2 count) in integer division (round half up).
+// (4) Faces.  The three ids go through the clustering; a face with a repeated id is dropped.  Of the others the triple
+//     rotated to start at its smallest id is (a, b, c): the face's group is (a, min(b, c), max(b, c)) and its winding
+//     b < c or not.  Three stable sorts of a permutation (by the largest id, then the middle, then the smallest one)
+//     lay the groups end to end, every group in ascending face index.  One thread per group head walks its group:
+//     net = faces of the one winding minus faces of the other; net == 0 drops the group (a flattened pocket, two
+//     sheets back to back), otherwise the first face of the majority winding stays.  The kept faces are compacted in
+//     their order, each in its own corner order.
+// (5) The clusters no kept face uses leave the mesh as in extraction pass (d).
+#define AMVS_TU_ID 11
+#include "amvs_check.h"
+#include "amvs_kernels.h"
+#include "amvs_mesh_state.h"
+
+namespace amvs {
+
+namespace {
+
+constexpr int DEC_HALF = 1 << 20;
+constexpr unsigned DEC_NONE = 0xFFFFFFFFu;
+
+struct Cells { float ox, oy, oz, cell; };
+
+// (1) keys and vertex ids for the sort; the smallest vertex id with a cell index outside the grid, if any
+__global__ __launch_bounds__(256) void cell_key_kernel(const float *__restrict__ verts, long long n_vertices, Cells g,
+                                                       unsigned long long *__restrict__ key, unsigned *__restrict__ id,
+                                                       unsigned *__restrict__ first_bad)
+{
+    const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_vertices) return;
+    const float ix = floorf((verts[3 * v] - g.ox) / g.cell);
+    const float iy = floorf((verts[3 * v + 1] - g.oy) / g.cell);
+    const float iz = floorf((verts[3 * v + 2] - g.oz) / g.cell);
+    const float lo = -(float)DEC_HALF, hi = (float)DEC_HALF;
+    const bool ok = ix >= lo && ix < hi && iy >= lo && iy < hi && iz >= lo && iz < hi;       // false for inf and NaN
+    unsigned long long k = 0;
+    if (ok)
+        k = ((unsigned long long)((int)iz + DEC_HALF) << 42) | ((unsigned long long)((int)iy + DEC_HALF) << 21) |
+            (unsigned long long)((int)ix + DEC_HALF);
+    else
+        atomicMin(first_bad, (unsigned)v);
+    key[v] = k;
+    id[v] = (unsigned)v;
+}
+
+// (2) j heads a run of equal keys
+__global__ __launch_bounds__(256) void key_head_kernel(const unsigned long long *__restrict__ key, long long n, unsigned *__restrict__ head)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) head[j] = (j == 0 || key[j] != key[j - 1]) ? 1u : 0u;
+}
+
+// (2) cluster of every vertex and the start of every run; start[n_clusters] = n
+__global__ __launch_bounds__(256) void cluster_map_kernel(const unsigned *__restrict__ id, const unsigned *__restrict__ head,
+                                                          const unsigned *__restrict__ before, long long n, long long n_clusters,
+                                                          unsigned *__restrict__ cluster_of, unsigned *__restrict__ start)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const long long c = AMVS_IDX((long long)before[j] + head[j] - 1, n_clusters);
+    cluster_of[AMVS_IDX((long long)id[j], n)] = (unsigned)c;
+    if (head[j]) start[c] = (unsigned)j;
+    if (j == 0) start[n_clusters] = (unsigned)n;
+}
+
+// (3) one thread per cluster: the ordered sum over its run
+__global__ __launch_bounds__(256) void representative_kernel(const float *__restrict__ verts, const unsigned char *__restrict__ rgb,
+                                                             const unsigned *__restrict__ id, const unsigned *__restrict__ start,
+                                                             long long n_vertices, long long n_clusters, float *__restrict__ verts_out,
+                                                             unsigned char *__restrict__ rgb_out)
+{
+    const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_clusters) return;
+    const unsigned r0 = start[c], r1 = start[c + 1];
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    unsigned long long cr = 0, cg = 0, cb = 0;
+    for (unsigned r = r0; r < r1; ++r) {
+        const long long v = AMVS_IDX((long long)id[AMVS_IDX((long long)r, n_vertices)], n_vertices);
+        sx += verts[3 * v]; sy += verts[3 * v + 1]; sz += verts[3 * v + 2];
+        cr += rgb[3 * v]; cg += rgb[3 * v + 1]; cb += rgb[3 * v + 2];
+    }
+    const unsigned long long count = r1 - r0;
+    const float den = (float)(r1 - r0);
+    verts_out[3 * c] = sx / den; verts_out[3 * c + 1] = sy / den; verts_out[3 * c + 2] = sz / den;
+    rgb_out[3 * c] = (unsigned char)((2 * cr + count) / (2 * count));
+    rgb_out[3 * c + 1] = (unsigned char)((2 * cg + count) / (2 * count));
+    rgb_out[3 * c + 2] = (unsigned char)((2 * cb + count) / (2 * count));
+}
+
+// (4) the face in cluster ids, rotated to start at its smallest: group (a, lo, hi) and winding; live = no repeated id
+__global__ __launch_bounds__(256) void face_triple_kernel(const int *__restrict__ faces, const unsigned *__restrict__ cluster_of,
+                                                          long long n_faces, long long n_vertices, unsigned *__restrict__ ta,
+                                                          unsigned *__restrict__ tlo, unsigned *__restrict__ thi,
+                                                          unsigned char *__restrict__ even, unsigned *__restrict__ live)
+{
+    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n_faces) return;
+    const unsigned g0 = cluster_of[AMVS_IDX((long long)faces[3 * f], n_vertices)];
+    const unsigned g1 = cluster_of[AMVS_IDX((long long)faces[3 * f + 1], n_vertices)];
+    const unsigned g2 = cluster_of[AMVS_IDX((long long)faces[3 * f + 2], n_vertices)];
+    unsigned a = g0, b = g1, c = g2;
+    if (g1 < g0 && g1 <= g2) { a = g1; b = g2; c = g0; }
+    else if (g2 < g0 && g2 < g1) { a = g2; b = g0; c = g1; }
+    ta[f] = a;
+    tlo[f] = b < c ? b : c;
+    thi[f] = b < c ? c : b;
+    even[f] = b < c ? 1 : 0;
+    live[f] = (g0 != g1 && g0 != g2 && g1 != g2) ? 1u : 0u;
+}
+
+// (4) the live faces in ascending index, with the first sort's keys
+__global__ __launch_bounds__(256) void live_list_kernel(const unsigned *__restrict__ live, const unsigned *__restrict__ slot,
+                                                        const unsigned *__restrict__ field, long long n_faces, long long n_live,
+                                                        unsigned *__restrict__ perm, unsigned *__restrict__ key)
+{
+    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n_faces || !live[f]) return;
+    const long long o = AMVS_IDX((long long)slot[f], n_live);
+    perm[o] = (unsigned)f;
+    key[o] = field[f];
+}
+
+// (4) the next sort's keys: a field of the faces in the permutation's order
+__global__ __launch_bounds__(256) void gather_key_kernel(const unsigned *__restrict__ perm, const unsigned *__restrict__ field,
+                                                         long long n_live, long long n_faces, unsigned *__restrict__ key)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n_live) key[j] = field[AMVS_IDX((long long)perm[j], n_faces)];
+}
+
+__device__ __forceinline__ bool same_group(const unsigned *__restrict__ ta, const unsigned *__restrict__ tlo,
+                                           const unsigned *__restrict__ thi, long long f, long long g)
+{
+    return ta[f] == ta[g] && tlo[f] == tlo[g] && thi[f] == thi[g];
+}
+
+// (4) one thread per position of the sorted permutation; the heads of the groups walk their group and keep at most
+// one face.  keep[] is zero before.
+__global__ __launch_bounds__(256) void group_decide_kernel(const unsigned *__restrict__ perm, const unsigned *__restrict__ ta,
+                                                           const unsigned *__restrict__ tlo, const unsigned *__restrict__ thi,
+                                                           const unsigned char *__restrict__ even, long long n_live, long long n_faces,
+                                                           unsigned *__restrict__ keep)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_live) return;
+    const long long f0 = AMVS_IDX((long long)perm[j], n_faces);
+    if (j > 0 && same_group(ta, tlo, thi, f0, AMVS_IDX((long long)perm[j - 1], n_faces))) return;
+    long long net = 0, first_even = -1, first_odd = -1;
+    for (long long k = j; k < n_live; ++k) {
+        const long long f = AMVS_IDX((long long)perm[k], n_faces);
+        if (k > j && !same_group(ta, tlo, thi, f0, f)) break;
+        if (even[f]) { ++net; if (first_even < 0) first_even = f; }
+        else { --net; if (first_odd < 0) first_odd = f; }
+    }
+    if (net > 0) keep[first_even] = 1u;
+    else if (net < 0) keep[first_odd] = 1u;
+}
+
+// (4) the kept faces in their order, in cluster ids and their own corner order
+__global__ __launch_bounds__(256) void face_keep_mapped_kernel(const int *__restrict__ faces, const unsigned *__restrict__ cluster_of,
+                                                               const unsigned *__restrict__ keep, const unsigned *__restrict__ new_id,
+                                                               long long n_faces, long long n_vertices, long long n_kept,
+                                                               int *__restrict__ out)
+{
+    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n_faces || !keep[f]) return;
+    const long long o = AMVS_IDX((long long)new_id[f], n_kept);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[3 * o + k] = (int)cluster_of[AMVS_IDX((long long)faces[3 * f + k], n_vertices)];
+}
+
+inline int bits_for(long long n)
+{
+    int bits = 1;
+    while (bits < 32 && (1ll << bits) < n) ++bits;
+    return bits;
+}
+
+// stable sort of (key, value) pairs on the low `bits` bits of the key
+template <class K>
+hipError_t sort_pairs(TsdfState *s, ScratchCache &cache, const K *key_in, K *key_out, const unsigned *val_in, unsigned *val_out,
+                      long long n, int bits, hipStream_t st)
+{
+    size_t bytes = 0;
+    MCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key_in, key_out, val_in, val_out, (int)n, 0, bits, st));
+    MCHK(s->scan_tmp.reserve(bytes > 0 ? bytes : 1, cache));
+    return hipcub::DeviceRadixSort::SortPairs(s->scan_tmp.get(), bytes, key_in, key_out, val_in, val_out, (int)n, 0, bits, st);
+}
+
+}  // namespace
+
+hipError_t mesh_decimate(TsdfState *s, ScratchCache &cache, const float origin[3], float cell, long long *bad_vertex,
+                         long long *n_vertices, long long *n_faces, hipStream_t st)
+{
+    const long long nv = s->n_vertices, nf = s->n_faces;
+    *bad_vertex = -1;
+    *n_vertices = nv; *n_faces = nf;
+    long long nc = 0;
+    if (nv > 0) {
+        // (1), (2): nothing of the mesh or of its attributes is written before the range flag is back
+        MCHK(s->dec_key.reserve((size_t)nv, cache)); MCHK(s->dec_key2.reserve((size_t)nv, cache));
+        MCHK(s->dec_id.reserve((size_t)nv, cache)); MCHK(s->dec_id2.reserve((size_t)nv, cache));
+        MCHK(s->dec_head.reserve((size_t)nv, cache)); MCHK(s->dec_before.reserve((size_t)nv, cache));
+        MCHK(s->dec_cluster.reserve((size_t)nv, cache)); MCHK(s->dec_start.reserve((size_t)nv + 1, cache));
+        MCHK(s->dec_flag.reserve(1, cache));
+        MCHK(hipMemsetAsync(s->dec_flag.get(), 0xFF, 4, st));
+        hipLaunchKernelGGL(cell_key_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->verts.get(), nv,
+                           Cells{origin[0], origin[1], origin[2], cell}, s->dec_key.get(), s->dec_id.get(), s->dec_flag.get());
+        MCHK(hipGetLastError());
+        unsigned bad = DEC_NONE;
+        MCHK(hipMemcpyAsync(&bad, s->dec_flag.get(), 4, hipMemcpyDeviceToHost, st));
+        MCHK(hipStreamSynchronize(st));
+        if (bad != DEC_NONE) { *bad_vertex = (long long)bad; return hipSuccess; }
+        MCHK(sort_pairs(s, cache, (const unsigned long long *)s->dec_key.get(), s->dec_key2.get(), (const unsigned *)s->dec_id.get(),
+                        s->dec_id2.get(), nv, 63, st));
+        hipLaunchKernelGGL(key_head_kernel, grid_of(nv), dim3(256), 0, st, (const unsigned long long *)s->dec_key2.get(), nv,
+                           s->dec_head.get());
+        MCHK(hipGetLastError());
+        MCHK(exclusive_scan(s, cache, s->dec_head.get(), s->dec_before.get(), nv, st));
+        MCHK(scan_total(s->dec_head.get(), s->dec_before.get(), nv, &nc, st));
+        hipLaunchKernelGGL(cluster_map_kernel, grid_of(nv), dim3(256), 0, st, (const unsigned *)s->dec_id2.get(),
+                           (const unsigned *)s->dec_head.get(), (const unsigned *)s->dec_before.get(), nv, nc, s->dec_cluster.get(),
+                           s->dec_start.get());
+        MCHK(hipGetLastError());
+    }
+    s->have_csr = s->have_pinned = s->have_labels = s->have_normals = false;
+    long long kept_f = 0, kept_v = 0;
+    if (nf > 0 && nv > 0) {
+        // (4) before (3): the faces still hold the old ids
+        MCHK(s->dec_ta.reserve((size_t)nf, cache)); MCHK(s->dec_tlo.reserve((size_t)nf, cache)); MCHK(s->dec_thi.reserve((size_t)nf, cache));
+        MCHK(s->dec_even.reserve((size_t)nf, cache));
+        MCHK(s->dec_fkey.reserve((size_t)nf, cache)); MCHK(s->dec_fkey2.reserve((size_t)nf, cache));
+        MCHK(s->dec_perm.reserve((size_t)nf, cache)); MCHK(s->dec_perm2.reserve((size_t)nf, cache));
+        MCHK(s->fkeep.reserve((size_t)nf, cache)); MCHK(s->fnew.reserve((size_t)nf, cache)); MCHK(s->faces2.reserve(3 * (size_t)nf, cache));
+        hipLaunchKernelGGL(face_triple_kernel, grid_of(nf), dim3(256), 0, st, (const int *)s->faces.get(),
+                           (const unsigned *)s->dec_cluster.get(), nf, nv, s->dec_ta.get(), s->dec_tlo.get(), s->dec_thi.get(),
+                           s->dec_even.get(), s->fkeep.get());
+        MCHK(hipGetLastError());
+        long long n_live = 0;
+        MCHK(exclusive_scan(s, cache, s->fkeep.get(), s->fnew.get(), nf, st));
+        MCHK(scan_total(s->fkeep.get(), s->fnew.get(), nf, &n_live, st));
+        if (n_live > 0) {
+            const int bits = bits_for(nc);
+            hipLaunchKernelGGL(live_list_kernel, grid_of(nf), dim3(256), 0, st, (const unsigned *)s->fkeep.get(),
+                               (const unsigned *)s->fnew.get(), (const unsigned *)s->dec_thi.get(), nf, n_live, s->dec_perm.get(),
+                               s->dec_fkey.get());
+            MCHK(hipGetLastError());
+            MCHK(sort_pairs(s, cache, (const unsigned *)s->dec_fkey.get(), s->dec_fkey2.get(), (const unsigned *)s->dec_perm.get(),
+                            s->dec_perm2.get(), n_live, bits, st));
+            const unsigned *const fields[2] = {s->dec_tlo.get(), s->dec_ta.get()};
+            for (const unsigned *field : fields) {
+                std::swap(s->dec_perm, s->dec_perm2);
+                hipLaunchKernelGGL(gather_key_kernel, grid_of(n_live), dim3(256), 0, st, (const unsigned *)s->dec_perm.get(), field, n_live,
+                                   nf, s->dec_fkey.get());
+                MCHK(hipGetLastError());
+                MCHK(sort_pairs(s, cache, (const unsigned *)s->dec_fkey.get(), s->dec_fkey2.get(), (const unsigned *)s->dec_perm.get(),
+                                s->dec_perm2.get(), n_live, bits, st));
+            }
+            MCHK(hipMemsetAsync(s->fkeep.get(), 0, 4 * (size_t)nf, st));
+            hipLaunchKernelGGL(group_decide_kernel, grid_of(n_live), dim3(256), 0, st, (const unsigned *)s->dec_perm2.get(),
+                               (const unsigned *)s->dec_ta.get(), (const unsigned *)s->dec_tlo.get(), (const unsigned *)s->dec_thi.get(),
+                               (const unsigned char *)s->dec_even.get(), n_live, nf, s->fkeep.get());
+            MCHK(hipGetLastError());
+            MCHK(exclusive_scan(s, cache, s->fkeep.get(), s->fnew.get(), nf, st));
+            MCHK(scan_total(s->fkeep.get(), s->fnew.get(), nf, &kept_f, st));
+        }
+        if (kept_f > 0) {
+            hipLaunchKernelGGL(face_keep_mapped_kernel, grid_of(nf), dim3(256), 0, st, (const int *)s->faces.get(),
+                               (const unsigned *)s->dec_cluster.get(), (const unsigned *)s->fkeep.get(), (const unsigned *)s->fnew.get(),
+                               nf, nv, kept_f, s->faces2.get());
+            MCHK(hipGetLastError());
+            std::swap(s->faces, s->faces2);
+        }
+    }
+    if (kept_f > 0) {
+        // (3) into the second buffers, (5) back into the first
+        hipLaunchKernelGGL(representative_kernel, grid_of(nc), dim3(256), 0, st, (const float *)s->verts.get(),
+                           (const unsigned char *)s->rgb.get(), (const unsigned *)s->dec_id2.get(), (const unsigned *)s->dec_start.get(),
+                           nv, nc, s->verts2.get(), s->rgb2.get());
+        MCHK(hipGetLastError());
+        std::swap(s->verts, s->verts2);
+        std::swap(s->rgb, s->rgb2);
+        MCHK(drop_unused_vertices(s, cache, nc, kept_f, &kept_v, st));
+    }
+    MCHK(hipStreamSynchronize(st));
+    s->n_vertices = kept_v; s->n_faces = kept_f;
+    *n_vertices = kept_v; *n_faces = kept_f;
+    return hipSuccess;
+}
+
+}  // namespace amvs
+
+AMVS_CHECK_TU(mesh_decimate)

@@ -1,6 +1,7 @@
 // amvs_mesh_state.h -- what the two surface-mesh translation units share: the context's volume-and-mesh state
-// (amvs_mesh.hip builds the mesh, amvs_mesh_clean.hip works on it in place), the hipCUB scan with its read-back, and
-// the kernels of extraction pass (d) that drop unused vertices, which the component filter runs again.
+// (amvs_mesh.hip builds the mesh, amvs_mesh_clean.hip and amvs_mesh_decimate.hip work on it in place), the hipCUB scan
+// with its read-back, and the kernels of extraction pass (d) that drop unused vertices, which the component filter and
+// the decimation run again.
 // Include after defining AMVS_TU_ID (amvs_check.h): the kernels here are compiled into each including unit.
 #pragma once
 #include "amvs_check.h"
@@ -54,6 +55,16 @@ struct TsdfState {
     DeviceBuffer<unsigned> fkeep, fnew;           // [F]: kept flags and new ids of the faces
     DeviceBuffer<int> faces2;                     // [3 F]
     DeviceBuffer<float> face_normal, normals;     // [F][3], [V][3]
+
+    // ---- decimation (amvs_mesh_decimate.hip): scratch of one call, nothing here outlives it ----
+    DeviceBuffer<unsigned long long> dec_key, dec_key2;   // [V]: cell keys, as computed and sorted
+    DeviceBuffer<unsigned> dec_id, dec_id2;       // [V]: vertex ids, ascending and in sorted-key order (the clusters' runs)
+    DeviceBuffer<unsigned> dec_head, dec_before;  // [V]: run heads of the sorted keys and their exclusive scan
+    DeviceBuffer<unsigned> dec_cluster, dec_start;        // [V]: cluster of every vertex; [C + 1]: start of every run
+    DeviceBuffer<unsigned> dec_flag;              // [1]: smallest vertex id outside the cluster grid, or all ones
+    DeviceBuffer<unsigned> dec_ta, dec_tlo, dec_thi;      // [F]: smallest, middle and largest cluster id of the face
+    DeviceBuffer<unsigned char> dec_even;         // [F]: winding of the face, rotated to start at its smallest id
+    DeviceBuffer<unsigned> dec_fkey, dec_fkey2, dec_perm, dec_perm2;      // [F]: the group sorts' keys and permutation
 
     // the mesh is about to be replaced: nothing derived from it stays
     void drop_mesh()

@@ -631,7 +631,7 @@ class Engine:
                                                  float(np.float32(voxel)), dmp))
         self._tsdf_dims = (nx, ny, nz)
 
-    # -- mesh clean-up (components, Taubin smoothing, normals), in place on the context's current mesh ----
+    # -- mesh clean-up (components, Taubin smoothing, decimation, normals), in place on the context's current mesh ----
     def mesh_set(self, vertices, faces, colors=None):
         """Make host arrays the context's mesh (include/amvs.h amvs_mesh_set): vertices (V,3) float32, faces (F,3)
         int32, colors (V,3) uint8 RGB or None for zeros.  Finite positions, ids in [0, V) and no face with a repeated
@@ -663,6 +663,15 @@ class Engine:
     def mesh_normals(self):
         """Area-weighted vertex normals of the current mesh, fetched with mesh_fetch(normals=True)."""
         self._chk(self._lib.amvs_mesh_normals(self._h))
+
+    def mesh_decimate(self, origin, cell):
+        """Vertex clustering of the current mesh on the grid of cubic cells of side `cell` with a corner at `origin`
+        (include/amvs.h amvs_mesh_decimate).  Returns (vertices, faces) after it; drops labels and normals."""
+        org = _f32(np.asarray(origin, np.float64).astype(np.float32).reshape(3))
+        nv, nf = C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.amvs_mesh_decimate(self._h, _p(org), float(np.float32(cell)), C.byref(nv), C.byref(nf)))
+        self._mesh_counts = (nv.value, nf.value)
+        return nv.value, nf.value
 
     def mesh_fetch(self, normals=False, labels=False):
         """The current mesh: (vertices (V,3) float32, faces (F,3) int32, colors (V,3) uint8[, normals (V,3) float32]

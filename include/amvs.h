@@ -332,15 +332,16 @@ int amvs_tsdf_fetch_volume(amvs_ctx *ctx, float *tsdf, float *weight, float *col
 int amvs_tsdf_set_volume(amvs_ctx *ctx, const float *tsdf, const float *weight, const float *color_sum,
                          const float origin[3], float voxel, const int32_t dims[3]);
 
-/* ---- mesh clean-up: components, Taubin smoothing, vertex normals (csrc/amvs_mesh_clean.hip) ------
+/* ---- mesh clean-up: components, Taubin smoothing, vertex normals, decimation (csrc/amvs_mesh_clean.hip) ------
  * No reference counterpart (the reference has no mesh): judged against a NumPy restatement of the definitions below,
  * bit for bit (tests/mesh_clean_restatement.py, DESIGN.md section 8 "Clean-up").  Every call works in place on the
  * context's current mesh -- the one amvs_tsdf_extract made or amvs_mesh_set uploaded -- and synchronises;
  * amvs_fetch_mesh returns the current mesh, cleaned or not.  No float atomics: every float sum runs in a fixed order
  * over the corners c = 3 * face + k that hold the vertex, in ascending c.  Limits: int32 vertex ids and
  * 3 * n_faces <= INT32_MAX.  Labels and normals are attributes of the current mesh: amvs_tsdf_integrate,
- * amvs_tsdf_set_volume, amvs_tsdf_extract and amvs_mesh_set drop both, amvs_mesh_filter_components drops the normals
- * and leaves fresh labels, amvs_mesh_smooth drops the normals and keeps the labels.                               */
+ * amvs_tsdf_set_volume, amvs_tsdf_extract, amvs_mesh_set and amvs_mesh_decimate drop both,
+ * amvs_mesh_filter_components drops the normals and leaves fresh labels, amvs_mesh_smooth drops the normals and keeps
+ * the labels.                                                                                                      */
 /* Replace the context's mesh by host arrays: n_vertices x 3 float32 positions, n_faces x 3 int32 vertex ids,
  * n_vertices x 3 uint8 RGB colours (NULL: zeros).  A test hook, and the way to clean a mesh made elsewhere.
  * Validated on the host before anything is copied -- finite positions, ids in [0, n_vertices), no face with a
@@ -365,6 +366,24 @@ int amvs_mesh_smooth(amvs_ctx *ctx, int iterations, float lambda, float mu, int 
  * divided by its length sqrtf((x * x + y * y) + z * z); (0, 0, 0) unless the length is > 0.  They point the way the
  * faces do (amvs_tsdf_extract: toward increasing TSDF, the cameras' side).                                        */
 int amvs_mesh_normals(amvs_ctx *ctx);
+/* Decimation by vertex clustering (csrc/amvs_mesh_decimate.hip; tests/mesh_decimate_restatement.py, DESIGN.md
+ * section 8 "Decimation") on a grid of cubic cells of side `cell` (finite, > 0) with a cell corner at `origin` (finite).
+ * All float32, every operation rounded on its own, the divisions IEEE.
+ * 1. Cell of a vertex: per axis q = (p - origin) / cell, i = floorf(q).  -2^20 <= i < 2^20 must hold on every axis,
+ *    otherwise the call fails with AMVS_EINVAL ("mesh_decimate: vertex ... outside the cluster grid") and the mesh,
+ *    with its attributes, is exactly as before.  key = (iz + 2^20) << 42 | (iy + 2^20) << 21 | (ix + 2^20).
+ * 2. Clusters: the distinct keys in ascending order (x fastest) are the provisional new vertex ids.
+ * 3. Representative: position s / (float)count, s the sum of the members' positions in ascending old vertex id
+ *    starting from 0; colour per channel (2 * sum + count) / (2 * count) of the integer sum (round half up).
+ * 4. Faces: the three ids go through the clustering; a face with a repeated id is dropped.  The others are grouped by
+ *    their unordered id triple; a face's winding is its triple rotated so that the smallest id comes first.  net = the
+ *    faces of one winding minus those of the other.  net == 0: the whole group goes (two sheets back to back).
+ *    Otherwise exactly one face stays, the one with the smallest face index among those of the majority winding, in
+ *    its own corner order.  The faces that stay keep their relative order.
+ * 5. The clusters no face uses leave the mesh as in amvs_tsdf_extract's last pass.
+ * n_vertices and n_faces are the mesh after it; the empty mesh and a mesh of vertices only give 0 / 0.  Drops labels
+ * and normals.                                                                                                    */
+int amvs_mesh_decimate(amvs_ctx *ctx, const float origin[3], float cell, int64_t *n_vertices, int64_t *n_faces);
 /* n_vertices x 3 float32 normals (amvs_mesh_normals) and n_vertices int32 labels (amvs_mesh_filter_components) of
  * the current mesh.  NULL skips an output; asking for one that is not current is AMVS_EINVAL.                     */
 int amvs_fetch_mesh_attributes(amvs_ctx *ctx, float *normals, int32_t *labels);

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Device time of the surface-mesh kernels (csrc/amvs_mesh.hip, csrc/amvs_mesh_clean.hip) at the CLI operating point (run on the GPU box):
+"""Device time of the surface-mesh kernels (csrc/amvs_mesh.hip, csrc/amvs_mesh_clean.hip, csrc/amvs_mesh_decimate.hip) at the CLI operating point (run on the GPU box):
 16 views at 1008 x 756, patch 11, the maps of the extended mode (the reference's algorithm leaves too few correct
 depths for a surface) resident on the device, a 256^3 TSDF volume around the fused cloud.  Integration and extraction are timed separately with HIP events on the engine's stream (the extraction
 includes its two count read-backs); the first-order bounds of DESIGN.md section 8 are printed next to them.
 Then the clean-up stage on that mesh and on the mesh of a 256^3 sphere: the vertex -> corner index, labelling + filter,
-10 Taubin iterations and the normals, each the median of 5 after a warm-up, with a first-order byte estimate; and
+10 Taubin iterations and the normals, each the median of 5 after a warm-up, with a first-order byte estimate; the
+decimation of either mesh at a cell of 2 voxels, likewise; and
 the labelling of a shuffled strip of 100 000 faces next to a sphere of about as many.
 
     python tools/mesh_time.py [n_views W H dim]
@@ -119,10 +120,37 @@ def restore_volume():
     return len(v), len(f)
 
 
+def decimate_time(name, restore, grid_origin, cell):
+    """Decimation (csrc/amvs_mesh_decimate.hip) of the restored mesh at a cell of 2 voxels on the volume's origin."""
+    ts = []
+    for rep in range(REPS + 1):
+        V, F = restore()
+        ms, _, counts = timed(lambda: eng.mesh_decimate(grid_origin, cell))
+        if rep:
+            ts.append(ms)
+    C, K = counts                                                 # clusters that stay, faces that stay
+    live = max(F // 8, K)                                         # faces without a repeated id: first order, an eighth
+    bits = max(int(np.ceil(np.log2(max(C, 2)))), 1)
+    passes = (bits + 7) // 8
+    est = (V * (12 + 12)                                          # positions in, key + id out
+           + V * 12 * 2 * 8 + V * 8                               # 63-bit sort: 8 passes of (key, id) in and out, histogram
+           + V * (8 + 4) + V * 8 + V * (4 + 4 + 4 + 4)            # heads, scan, cluster map
+           + V * (4 + 15) + C * 15                                # representatives
+           + F * (12 + 12 + 17) + F * 8 + live * 8                # triples, live flags + scan, live list
+           + 3 * live * (8 * 2 * passes + 4 + 8)                  # three sorts of (key, face) and the keys' gathers
+           + live * (4 + 13) + F * 4 + F * 8 + K * (12 + 12 + 12)  # decision, keep flags + scan, compaction
+           + C * (4 + 4 + 15) + K * 24 + C * 15)                  # unused clusters: flags, scan, move, renumber
+    print(f"decimation of {name} at 2 voxels: {V:,} vertices, {F:,} faces -> {C:,} / {K:,}: median {np.median(ts):.3f} ms device "
+          f"(min {min(ts):.3f}); first-order bytes of the sorts and passes (estimate) {est / 1e6:.1f} MB = "
+          f"{est / 8e12 * 1e3:.4f} ms at 8 TB/s")
+
+
 clean_times(f"the CLI operating point ({dim}^3)", restore_volume)
+decimate_time(f"the CLI operating point ({dim}^3)", restore_volume, origin, 2.0 * voxel)
 sphere = mv.sphere_volume(256, radius=0.8)
 eng.tsdf_set_volume(*sphere.arrays())
 clean_times("the 256^3 sphere", restore_volume)
+decimate_time("the 256^3 sphere", restore_volume, sphere.origin, 2.0 * float(sphere.voxel))
 
 
 def label_time(name, restore):
