@@ -145,17 +145,16 @@ __global__ __launch_bounds__(AMVS_WAVE) void pm_step_generic_kernel(const StepAr
         const bool inb = live & ((unsigned)(yr + oy) < (unsigned)H) & ((unsigned)(xr + ox) < (unsigned)W);
         const int pix = yr * W + xr;
         const float d_raw = d_in[AMVS_IDX(inb ? pix + noff : 0, HW)];
-        // (clamped index, no branch in the load path: dead lanes read element 0)
         float rv;
         if constexpr (U8) {
-            const uint32_t code = ref_pairs[AMVS_IDX_LOHI(live ? pix + PADW * yr : 0, -((long long)AMVS_PAIR_BORDER * (W + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER), (long long)(H + 2 * AMVS_PAIR_BORDER) * (W + 2 * AMVS_PAIR_BORDER) - ((long long)AMVS_PAIR_BORDER * (W + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER))] & 0xFFu;
+            const uint32_t code = ref_pairs[AMVS_REF_PAIR_IDX(live ? pix + PADW * yr : 0, H, W)] & 0xFFu;
             rv = FAST ? (float)code : lut[code];
         } else {
             rv = ref[AMVS_IDX(live ? pix : 0, HW)];
         }
         rv = live ? rv : 0.0f;
 
-        // ---- candidate depth of this (possibly halo) pixel (mvs_patchmatch.py:430-436, :468-473) ----
+        // ---- candidate depth of this (possibly halo) pixel: candidate_depth (amvs_kernel_common.h), written out ----
         float dc = inb ? depth_untag(d_raw, a.depth_mask) : a.depth_min;
         const uint32_t h0 = pixel_hash((uint32_t)pix, key);
         {
@@ -244,11 +243,7 @@ __global__ __launch_bounds__(AMVS_WAVE) void pm_step_generic_kernel(const StepAr
             continue;
         }
         // average over valid sources, +inf when fewer than two (mvs_patchmatch.py:387-388)
-        const float cden = cnt + 1e-8f;
-        bool cden_ok = true;
-        const float rc = rcp_t<true>(cden, cden_ok);
-        const float avg = FAST ? total * rc : qdiv(total, cden, rc);
-        const float newc = cnt >= 2.0f ? avg : __builtin_inff();
+        const float newc = average_cost<!FAST>(total, cnt);
         if (mode == MODE_EVAL) {
             if (act) aux[pc] = newc;
             continue;
@@ -352,10 +347,9 @@ __global__ __launch_bounds__(AMVS_WAVE) void plane_sweep_generic_kernel(const Sw
             const int yr = y0 - HALF + r;
             const bool live = col_in & ((unsigned)yr < (unsigned)H);
             const int pix = yr * W + xr;
-            // (clamped index, no branch in the load path: dead lanes read element 0)
             float rv;
             if constexpr (U8) {
-                const uint32_t code = ref_pairs[AMVS_IDX_LOHI(live ? pix + PADW * yr : 0, -((long long)AMVS_PAIR_BORDER * (W + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER), (long long)(H + 2 * AMVS_PAIR_BORDER) * (W + 2 * AMVS_PAIR_BORDER) - ((long long)AMVS_PAIR_BORDER * (W + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER))] & 0xFFu;
+                const uint32_t code = ref_pairs[AMVS_REF_PAIR_IDX(live ? pix + PADW * yr : 0, H, W)] & 0xFFu;
                 rv = FAST ? (float)code : lut[code];
             } else {
                 rv = ref[AMVS_IDX(live ? pix : 0, HW)];
@@ -426,11 +420,7 @@ __global__ __launch_bounds__(AMVS_WAVE) void plane_sweep_generic_kernel(const Sw
                     if (ncc > a.thresh && ((okc >> s) & 1u)) votes += 1u;   // :303-304
                 }
             }
-            if (outl) {
-                const uint32_t keyv = (votes << 12) | (uint32_t)(AMVS_SWEEP_MAX_CHUNK - 1 - (d - d_begin));
-                const uint32_t cur = best[(yc - y0) * AMVS_WAVE + lane];
-                if (keyv > cur) best[(yc - y0) * AMVS_WAVE + lane] = (uint16_t)keyv;
-            }
+            if (outl) sweep_best_update(best, yc, y0, lane, votes, d, d_begin);
         }
     }
 

@@ -1,5 +1,7 @@
-// amvs_kernel_common.h -- device helpers shared by the exact (amvs_kernels.hip) and the fast
-// (amvs_kernels_fast.hip) sweep kernels.
+// amvs_kernel_common.h -- device helpers shared by the five sweep translation units: the sweep step in its exact
+// (amvs_kernels.hip), fast (amvs_kernels_fast.hip) and run-time-patch (amvs_generic.hip) form and the plane sweeps
+// (amvs_sweep_exact.hip, amvs_sweep_fast.hip, amvs_generic.hip).  What is stated here is stated once; DESIGN.md
+// section 4 lists the row stages that are still written out per kernel, and why.
 #pragma once
 #include "amvs_kernels.h"
 #include "amvs_device.h"
@@ -39,6 +41,45 @@ template <int K, int S> struct Hist {
 AMVS_DEV float depth_untag(float d, unsigned mask) { return __uint_as_float(__float_as_uint(d) & mask); }
 AMVS_DEV unsigned depth_buffer(float d) { return __float_as_uint(d) >> 31; }
 AMVS_DEV float depth_tag(float d, unsigned buffer) { return __uint_as_float(__float_as_uint(d) | (buffer << 31)); }
+
+// Reference gray of the packed path: the low byte of the view's padded row-pair map, which is addressed from its
+// pixel (0,0) (row pitch W + 2 AMVS_PAIR_BORDER): valid texel indices are [-origin, elems - origin).  The row loads
+// use clamped indices -- `live ? pix + PADW * yr : 0`: dead lanes read element 0 -- so there is no branch in the load
+// path.  (Macros, so that the index-checked build records the line of the kernel that expands them.)
+#define AMVS_REF_PAIR_IDX(i, H, W) AMVS_IDX_LOHI((i), -((long long)AMVS_PAIR_BORDER * ((W) + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER), (long long)((H) + 2 * AMVS_PAIR_BORDER) * ((W) + 2 * AMVS_PAIR_BORDER) - ((long long)AMVS_PAIR_BORDER * ((W) + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER))
+// texel i of such a map (AMVS_CODE_BYTES, amvs_device.h: one byte per texel instead of a row pair)
+#if AMVS_CODE_BYTES
+#define AMVS_REF_CODE(ref_pairs, i) (((const __attribute__((address_space(1))) uint8_t *)(ref_pairs))[i])
+#else
+#define AMVS_REF_CODE(ref_pairs, i) ((ref_pairs)[i])
+#endif
+
+// Depth hypothesis a pixel is sampled at in this step: the (offset) pixel's current depth for
+// propagation / evaluation / confidence -- depth_min outside the image (the F.pad value) --, a clamped random
+// perturbation of it, depth + (rand*2-1)*range, for refinement (mvs_patchmatch.py:430-436, :468-473).
+// `d_raw` is d_in at the pixel (+ offset) when `inb`.
+AMVS_DEV float candidate_depth(const StepArgs &a, int mode, bool inb, float d_raw, uint32_t h0)
+{
+    const float dc = inb ? depth_untag(d_raw, a.depth_mask) : a.depth_min;
+    const float delta = (rng_uniform(h0) * 2.0f - 1.0f) * a.depth_range;
+    float d = dc + delta;
+    d = d < a.depth_min ? a.depth_min : d;
+    d = d > a.depth_max ? a.depth_max : d;
+    return mode == MODE_REFINE ? d : dc;
+}
+
+// Cost of a pixel from the sum over its valid sources: their average, +inf when fewer than two
+// (mvs_patchmatch.py:387-388).  QDIV: the exact arithmetic's correctly rounded quotient; otherwise
+// total * RN(1 / cden) (fast arithmetic).
+template <bool QDIV>
+AMVS_DEV float average_cost(float total, float cnt)
+{
+    const float cden = cnt + 1e-8f;              // 1e-8 ... S: always inside the lean reciprocal's range
+    bool cden_ok = true;
+    const float rc = rcp_t<true>(cden, cden_ok);
+    const float avg = QDIV ? qdiv(total, cden, rc) : total * rc;
+    return cnt >= 2.0f ? avg : __builtin_inff();
+}
 
 // Queued winners: one 32-bit entry each (the queue of a wave is 2 x 64 entries = 512 bytes of LDS; round 4 --
 // 8-byte entries before -- so that the paired-band exchange of the 11 x 11 patch fits beside the rings at four
@@ -149,6 +190,21 @@ AMVS_DEV void step_trace_exit(const StepArgs &a, int wv, int lane)
 #define AMVS_TRACE_ENTRY(...) ((void)0)
 #define AMVS_TRACE_EXIT(...) ((void)0)
 #endif
+
+// Plane sweep: the running best of a strip's output pixels lives in LDS ([row][lane]) as 16-bit keys
+// (votes << 12 | 4095 - plane of the chunk), or -- SweepArgs::key8, chunks of at most 32 planes -- as 8-bit keys
+// (votes << 5 | 31 - plane) in the same array, for strips twice as high; KeyT selects the width.  Plane d of the chunk
+// that starts at d_begin enters row yc of the strip that starts at y0.  The chunk's first plane always enters
+// (torch.max over a volume that starts at 0 votes): its key (0 << 12) | 4095 -- (0 << 5) | 31 -- beats the initial 0.
+template <class KeyT>
+AMVS_DEV void sweep_best_update(KeyT *best, int yc, int y0, int lane, uint32_t votes, int d, int d_begin)
+{
+    constexpr int PLANE_BITS = sizeof(KeyT) == 1 ? 5 : 12;
+    static_assert((1 << PLANE_BITS) == (sizeof(KeyT) == 1 ? AMVS_SWEEP_MAX_CHUNK8 : AMVS_SWEEP_MAX_CHUNK), "planes of a chunk");
+    const uint32_t keyv = (votes << PLANE_BITS) | (uint32_t)((1 << PLANE_BITS) - 1 - (d - d_begin));
+    const uint32_t cur = best[(yc - y0) * AMVS_WAVE + lane];
+    if (keyv > cur) best[(yc - y0) * AMVS_WAVE + lane] = (KeyT)keyv;
+}
 
 static_assert(list_max(SourceCounts{}) == AMVS_KMAX_SRC, "SourceCounts ends at AMVS_KMAX_SRC (Job::src, Job::fsrc)");
 static_assert(list_max(CompiledPatches{}) <= AMVS_MAX_PATCH, "a compiled patch size beyond AMVS_MAX_PATCH");

@@ -96,11 +96,6 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), mi
     // ref gray of the packed path: low byte of the padded row-pair map (pitch W+4, origin at pixel (0,0))
     const GlobalU16 ref_pairs = U8 ? (GlobalU16)job->ref_pairs : (GlobalU16)a.pairs;   // global, not FLAT, loads
     constexpr int PADW = U8 ? 2 * AMVS_PAIR_BORDER : 0;
-#if AMVS_CODE_BYTES
-#define AMVS_REF_CODE(i) (((const __attribute__((address_space(1))) uint8_t *)ref_pairs)[i])
-#else
-#define AMVS_REF_CODE(i) (ref_pairs[i])
-#endif
     const float *__restrict__ d_in = a.d_in + job->slot * HW;
     float *__restrict__ d_out = a.d_out + job->slot * HW;
     float *cost_io = a.cost + job->slot * HW;          // read and (where the candidate wins) written
@@ -177,10 +172,10 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), mi
         const float d_raw = d_in[AMVS_IDX(inb ? pix + noff : 0, HW)];       // re-read by neighbours: cached
         // ref gray: in the packed path the low byte of the row-pair map decoded through the table
         // (the same float as the float32 map holds, at half the bytes)
-        const float r_raw = U8 ? lut[AMVS_REF_CODE(AMVS_IDX_LOHI(live ? pix + PADW * yr : 0, -((long long)AMVS_PAIR_BORDER * (W + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER), (long long)(H + 2 * AMVS_PAIR_BORDER) * (W + 2 * AMVS_PAIR_BORDER) - ((long long)AMVS_PAIR_BORDER * (W + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER))) & 0xFFu]
+        const float r_raw = U8 ? lut[AMVS_REF_CODE(ref_pairs, AMVS_REF_PAIR_IDX(live ? pix + PADW * yr : 0, H, W)) & 0xFFu]
                                : ref[AMVS_IDX(live ? pix : 0, HW)];
 
-        // ---- candidate depth of this (possibly halo) pixel ----
+        // ---- candidate depth of this (possibly halo) pixel: candidate_depth (amvs_kernel_common.h), written out ----
         // outside the image the pulled candidate is depth_min (F.pad value)
         float dc = inb ? depth_untag(d_raw, a.depth_mask) : a.depth_min;
         // depth + (rand*2-1)*range, clamped (mvs_patchmatch.py:471-472)
@@ -315,10 +310,7 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), mi
         }
 
         // average over valid sources, +inf when fewer than two (mvs_patchmatch.py:387-388)
-        const float cden = cnt + 1e-8f;              // 1e-8 ... S: always inside the lean reciprocal's range
-        bool cden_ok = true;
-        const float avg = qdiv(total, cden, rcp_t<true>(cden, cden_ok));
-        const float newc = cnt >= 2.0f ? avg : __builtin_inff();
+        const float newc = average_cost<true>(total, cnt);
         if (mode == MODE_EVAL) {
             if (act) aux[pc] = newc;
             continue;
@@ -332,9 +324,8 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), mi
         if (better) cost_io[pc] = newc;
         if (mode == MODE_PROP) {
             // candidate = the neighbour's pre-step state; out-of-image neighbour: depth_min and a
-            // zero normal (F.pad, :431-442).  Only the winners' normals move (StepArgs::nbuf).
-            // out-of-image neighbour: depth_min and a zero normal (F.pad, :431-442).  Only the winners'
-            // normals move (StepArgs::nbuf), queued and moved 64 at a time like the refinement winners'.
+            // zero normal (F.pad, :431-442).  Only the winners' normals move (StepArgs::nbuf), queued and
+            // moved 64 at a time like the refinement winners'.
             const float nb_d = depth_untag(nb_tagged, a.depth_mask);
             if (act) d_out[pc] = better ? depth_tag(inb_c ? nb_d : a.depth_min, buf_c ^ 1u) : oldd_tagged;
             const unsigned long long won = __ballot(better);
@@ -382,12 +373,6 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), mi
     }
     AMVS_TRACE_EXIT(a, wv, lane);
 }
-
-// ------------------------------------------------------------------ split step (experiment) ---
-// Sampling stage of a sweep step as a kernel of its own: one thread per PX pixels of the reference
-// view (every pixel exactly once, no strip halo, no rings): candidate depth, back-projection, the S
-// projections / gathers / bilinear samples.  Writes the samples ([pixel][S] float32), the candidate
-// depth and the validity bits for a window / NCC / select kernel to stream.
 
 // ------------------------------------------------------------------ sample dump ---
 // Test hook (amvs_sample_sources): the bilinear sample of every pixel in every source at the

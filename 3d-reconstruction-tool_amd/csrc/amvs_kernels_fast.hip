@@ -23,9 +23,6 @@
 
 namespace amvs {
 
-// the reference view's packed map is addressed from its pixel (0,0): valid texel indices [-origin, elems - origin)
-#define AMVS_REF_PAIR_IDX(i) AMVS_IDX_LOHI((i), -((long long)AMVS_PAIR_BORDER * (W + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER), (long long)(H + 2 * AMVS_PAIR_BORDER) * (W + 2 * AMVS_PAIR_BORDER) - ((long long)AMVS_PAIR_BORDER * (W + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER))
-
 template <int K, int S> struct StepLds {
     static constexpr unsigned PER_WAVE = (FRing<K, S>::NL > 0 ? FRing<K, S>::NL : 1) * K * AMVS_WAVE * 4u + 2u * AMVS_WAVE * 4u;
     static constexpr unsigned STATIC = AMVS_WG_WAVES * PER_WAVE;
@@ -55,19 +52,6 @@ constexpr bool fast_pair_supported(int K, int S)
 constexpr int fast_min_waves(int K, int S)
 {
     return ((S + 1) * K <= 40 ? 4 : ((S + 1) * K <= 60 ? 3 : 2)) + AMVS_FAST_MIN_WAVES_BIAS;
-}
-
-// Depth hypothesis a pixel is sampled at in this step: the (offset) pixel's current depth for
-// propagation / evaluation / confidence, a clamped random perturbation of it for refinement
-// (mvs_patchmatch.py:430-436, :468-473).  `d_raw` is d_in at the pixel (+ offset) when `inb`.
-AMVS_DEV float candidate_depth(const StepArgs &a, int mode, bool inb, float d_raw, uint32_t h0)
-{
-    const float dc = inb ? depth_untag(d_raw, a.depth_mask) : a.depth_min;
-    const float delta = (rng_uniform(h0) * 2.0f - 1.0f) * a.depth_range;
-    float d = dc + delta;
-    d = d < a.depth_min ? a.depth_min : d;
-    d = d > a.depth_max ? a.depth_max : d;
-    return mode == MODE_REFINE ? d : dc;
 }
 
 // Sample maps of the split schedule (StepArgs::samples): [slot][source][H*W] floats, the sampled
@@ -258,7 +242,7 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
         const bool live = col_in & ((unsigned)yr < (unsigned)H);
         const bool inb = live & ((unsigned)(yr + oy) < (unsigned)H) & ((unsigned)(xr + ox) < (unsigned)W);
         const int pix = yr * W + xr;
-        const uint32_t rc_raw = ref_pairs[AMVS_REF_PAIR_IDX(live ? pix + PADW * yr : 0)];
+        const uint32_t rc_raw = ref_pairs[AMVS_REF_PAIR_IDX(live ? pix + PADW * yr : 0, H, W)];
         const uint32_t h0 = pixel_hash((uint32_t)pix, key);
         float v[S];
         unsigned okbits = 0u;
@@ -281,7 +265,7 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
                 okbits |= (w[s] >> 31) ? 0u : (1u << s);
             }
         } else {
-            // ---- candidate depth of this (possibly halo) pixel: as in the exact kernel ----
+            // ---- candidate depth of this (possibly halo) pixel ----
             const float d_raw = d_in[AMVS_IDX(inb ? pix + noff : 0, HW)];
             const float dc = candidate_depth(a, mode, inb, d_raw, h0);
             okbits = fast_sample_sources_checked<S, true, true>(job, fc, cols, (float)yr, dc, live, v);
@@ -357,10 +341,7 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
         }
 
         // average over valid sources, +inf when fewer than two (mvs_patchmatch.py:387-388)
-        const float cden = cnt + 1e-8f;
-        bool cden_ok = true;
-        const float avg = total * rcp_t<true>(cden, cden_ok);
-        const float newc = cnt >= 2.0f ? avg : __builtin_inff();
+        const float newc = average_cost<false>(total, cnt);
         if (mode == MODE_EVAL) {
             if (act) aux[pc] = newc;
             continue;

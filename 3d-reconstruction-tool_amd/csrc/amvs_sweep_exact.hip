@@ -155,8 +155,7 @@ __global__ __launch_bounds__(AMVS_WAVE) void plane_sweep_kernel(const SweepArgs 
         rc.c0 = px * job->Kinv[0]; rc.c1 = px * job->Kinv[3]; rc.c2 = px * job->Kinv[6];
     }
 
-    // running best per output pixel of the strip: 16-bit keys (votes << 12 | 4095 - plane of the chunk), or -- a.key8,
-    // chunks of at most 32 planes -- 8-bit keys (votes << 5 | 31 - plane) in the same array, for strips twice as high
+    // running best per output pixel of the strip (sweep_best_update): 16-bit or -- a.key8 -- 8-bit keys
     uint8_t *best8 = (uint8_t *)&best[0][0];
     if (a.key8) { for (int i = 0; i < trows; ++i) best8[i * AMVS_WAVE + lane] = (uint8_t)0; }
     else { for (int i = 0; i < trows; ++i) best[i][lane] = (uint16_t)0; }
@@ -180,7 +179,7 @@ __global__ __launch_bounds__(AMVS_WAVE) void plane_sweep_kernel(const SweepArgs 
             const int pix = yr * W + xr;
             // ref gray: in the packed path the low byte of the row-pair map decoded through the table (the
             // same float as the float32 map holds, at half the bytes)
-            const float rvl = U8 ? lut[ref_pairs[AMVS_IDX_LOHI(live ? pix + PADW * yr : 0, -((long long)AMVS_PAIR_BORDER * (W + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER), (long long)(H + 2 * AMVS_PAIR_BORDER) * (W + 2 * AMVS_PAIR_BORDER) - ((long long)AMVS_PAIR_BORDER * (W + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER))] & 0xFFu]
+            const float rvl = U8 ? lut[ref_pairs[AMVS_REF_PAIR_IDX(live ? pix + PADW * yr : 0, H, W)] & 0xFFu]
                                  : ref[AMVS_IDX(live ? pix : 0, HW)];
             const float rv = live ? rvl : 0.0f;
             JobCP jr = reload(job);
@@ -245,17 +244,8 @@ __global__ __launch_bounds__(AMVS_WAVE) void plane_sweep_kernel(const SweepArgs 
                 if (__builtin_expect(!__all(vok), 0)) vote_stage(std::false_type{}, vok);
             }
             if (outl) {
-                // the chunk's first plane always enters (torch.max over a volume that starts at 0
-                // votes): its key (0 << 12) | 4095 -- (0 << 5) | 31 -- beats the initial 0
-                if (a.key8) {
-                    const uint32_t keyv = (votes << 5) | (uint32_t)(AMVS_SWEEP_MAX_CHUNK8 - 1 - (d - d_begin));
-                    const uint32_t cur = best8[(yc - y0) * AMVS_WAVE + lane];
-                    if (keyv > cur) best8[(yc - y0) * AMVS_WAVE + lane] = (uint8_t)keyv;
-                } else {
-                    const uint32_t keyv = (votes << 12) | (uint32_t)(AMVS_SWEEP_MAX_CHUNK - 1 - (d - d_begin));
-                    const uint32_t cur = best[yc - y0][lane];
-                    if (keyv > cur) best[yc - y0][lane] = (uint16_t)keyv;
-                }
+                if (a.key8) sweep_best_update(best8, yc, y0, lane, votes, d, d_begin);
+                else sweep_best_update(&best[0][0], yc, y0, lane, votes, d, d_begin);
             }
         }
     }

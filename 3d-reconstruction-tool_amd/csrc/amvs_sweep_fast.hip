@@ -54,8 +54,7 @@ __global__ __launch_bounds__(AMVS_WAVE) void plane_sweep_fast_kernel(const Sweep
     const int trows = min(a.TH, H - y0);
     const int rows = trows + 2 * HALF;
 
-    // running best per output pixel of the strip: 16-bit keys (votes << 12 | 4095 - plane of the chunk), or -- a.key8,
-    // chunks of at most 32 planes -- 8-bit keys (votes << 5 | 31 - plane) in the same array, for strips twice as high
+    // running best per output pixel of the strip (sweep_best_update): 16-bit or -- a.key8 -- 8-bit keys
     uint8_t *best8 = (uint8_t *)&best[0][0];
     if (a.key8) { for (int i = 0; i < trows; ++i) best8[i * AMVS_WAVE + lane] = (uint8_t)0; }
     else { for (int i = 0; i < trows; ++i) best[i][lane] = (uint16_t)0; }
@@ -98,7 +97,7 @@ __global__ __launch_bounds__(AMVS_WAVE) void plane_sweep_fast_kernel(const Sweep
             const int yr = y0 - HALF + r;
             const bool live = col_in & ((unsigned)yr < (unsigned)H);
             const int pix = yr * W + xr;
-            const uint32_t rc_raw = ref_pairs[AMVS_IDX_LOHI(live ? pix + PADW * yr : 0, -((long long)AMVS_PAIR_BORDER * (W + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER), (long long)(H + 2 * AMVS_PAIR_BORDER) * (W + 2 * AMVS_PAIR_BORDER) - ((long long)AMVS_PAIR_BORDER * (W + 2 * AMVS_PAIR_BORDER) + AMVS_PAIR_BORDER))];
+            const uint32_t rc_raw = ref_pairs[AMVS_REF_PAIR_IDX(live ? pix + PADW * yr : 0, H, W)];
             const uint32_t rcode = live ? (rc_raw & 0xFFu) : 0u;
             float v[S];
             bool unused_ok = true;
@@ -156,15 +155,8 @@ __global__ __launch_bounds__(AMVS_WAVE) void plane_sweep_fast_kernel(const Sweep
                 if (__builtin_expect(!__all(ok), 0)) vote_stage(std::false_type{}, ok);
             }
             if (outl) {
-                if (a.key8) {
-                    const uint32_t keyv = (votes << 5) | (uint32_t)(AMVS_SWEEP_MAX_CHUNK8 - 1 - (d - d_begin));
-                    const uint32_t cur = best8[(yc - y0) * AMVS_WAVE + lane];
-                    if (keyv > cur) best8[(yc - y0) * AMVS_WAVE + lane] = (uint8_t)keyv;
-                } else {
-                    const uint32_t keyv = (votes << 12) | (uint32_t)(AMVS_SWEEP_MAX_CHUNK - 1 - (d - d_begin));
-                    const uint32_t cur = best[yc - y0][lane];
-                    if (keyv > cur) best[yc - y0][lane] = (uint16_t)keyv;
-                }
+                if (a.key8) sweep_best_update(best8, yc, y0, lane, votes, d, d_begin);
+                else sweep_best_update(&best[0][0], yc, y0, lane, votes, d, d_begin);
             }
         }
     }
