@@ -131,6 +131,8 @@ SIGNATURES = {
     "amvs_mesh_smooth": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int]),
     "amvs_mesh_normals": (C.c_int, [C.c_void_p]),
     "amvs_mesh_decimate": (C.c_int, [C.c_void_p, f32p, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "amvs_mesh_decimate_quadric": (C.c_int, [C.c_void_p, f32p, C.c_float, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int64)]),
     "amvs_fetch_mesh_attributes": (C.c_int, [C.c_void_p, f32p, i32p]),
     "amvs_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "amvs_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),

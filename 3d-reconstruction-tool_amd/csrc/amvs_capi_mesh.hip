@@ -184,6 +184,29 @@ int amvs_mesh_decimate(amvs_ctx *c, const float origin[3], float cell, int64_t *
     return checked(c, AMVS_OK);
 }
 
+int amvs_mesh_decimate_quadric(amvs_ctx *c, const float origin[3], float cell, float regularisation, int64_t *n_vertices,
+                               int64_t *n_faces, int64_t *n_fallback)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!n_vertices || !n_faces || !n_fallback) return fail(c, AMVS_EINVAL, "mesh_decimate_quadric: NULL output");
+    if (!origin) return fail(c, AMVS_EINVAL, "mesh_decimate_quadric: NULL origin");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(origin[a])) return fail(c, AMVS_EINVAL, "mesh_decimate_quadric: origin must be finite");
+    if (!(cell > 0.0f) || !std::isfinite(cell)) return fail(c, AMVS_EINVAL, "mesh_decimate_quadric: cell must be positive and finite");
+    if (!(regularisation > 0.0f && regularisation <= 1.0f))
+        return fail(c, AMVS_EINVAL, "mesh_decimate_quadric: regularisation must be in (0, 1]");
+    if (!amvs::tsdf_has_mesh(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "mesh_decimate_quadric: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    long long bad = -1, nv = 0, nf = 0, nk = 0;
+    const hipError_t e = amvs::mesh_decimate_quadric(c->tsdf.get(), c->cache, origin, cell, regularisation, &bad, &nv, &nf, &nk, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_decimate_quadric: ") + hipGetErrorString(e));
+    if (bad >= 0) return fail(c, AMVS_EINVAL, "mesh_decimate_quadric: vertex " + std::to_string(bad) + " outside the cluster grid");
+    *n_vertices = nv; *n_faces = nf; *n_fallback = nk;
+    return checked(c, AMVS_OK);
+}
+
 int amvs_fetch_mesh_attributes(amvs_ctx *c, float *normals, int32_t *labels)
 {
     if (!c) return AMVS_EINVAL;

@@ -279,11 +279,20 @@ hipError_t mesh_normals(TsdfState *s, ScratchCache &cache, hipStream_t st);
 bool mesh_has_normals(const TsdfState *s);
 bool mesh_has_labels(const TsdfState *s);
 hipError_t mesh_fetch_attributes(TsdfState *s, float *normals, int *labels, hipStream_t st);
+// for amvs_mesh_decimate.hip: the vertex -> corner index of the current faces (built once per topology) and the face
+// normals cross(p1 - p0, p2 - p0) of the current faces and positions into the state's face_normal.  Neither synchronises.
+hipError_t ensure_index(TsdfState *s, ScratchCache &cache, hipStream_t st);
+hipError_t mesh_face_normals(TsdfState *s, ScratchCache &cache, hipStream_t st);
 
 // amvs_mesh_decimate.hip: vertex clustering of the state's current mesh in place on the grid of cells of side `cell`
 // at `origin` (include/amvs.h amvs_mesh_decimate).  bad_vertex: -1, or the smallest id of a vertex outside the cluster
 // grid -- then nothing was changed.  Otherwise drops labels, normals and the index.  Synchronises.
 hipError_t mesh_decimate(TsdfState *s, ScratchCache &cache, const float origin[3], float cell, long long *bad_vertex,
                          long long *n_vertices, long long *n_faces, hipStream_t st);
+// the same with quadric placement of the clusters' vertices (include/amvs.h amvs_mesh_decimate_quadric).  n_fallback:
+// the clusters that kept the mean.  Builds the index of the mesh before the decimation, after the range check.
+hipError_t mesh_decimate_quadric(TsdfState *s, ScratchCache &cache, const float origin[3], float cell, float regularisation,
+                                 long long *bad_vertex, long long *n_vertices, long long *n_faces, long long *n_fallback,
+                                 hipStream_t st);
 
 }  // namespace amvs

@@ -263,6 +263,8 @@ __global__ __launch_bounds__(256) void vertex_normal_kernel(const float *__restr
 
 inline size_t at_least_one(long long n) { return (size_t)(n > 0 ? n : 1); }
 
+}  // namespace
+
 // (a): row_start[0 .. V] and corners[0 .. 3 F) of the current faces
 hipError_t ensure_index(TsdfState *s, ScratchCache &cache, hipStream_t st)
 {
@@ -291,6 +293,21 @@ hipError_t ensure_index(TsdfState *s, ScratchCache &cache, hipStream_t st)
     s->have_csr = true;
     return hipSuccess;
 }
+
+// (d): face_normal[0 .. F) of the current faces and positions
+hipError_t mesh_face_normals(TsdfState *s, ScratchCache &cache, hipStream_t st)
+{
+    const long long nv = s->n_vertices, nf = s->n_faces;
+    MCHK(s->face_normal.reserve(3 * at_least_one(nf), cache));
+    if (nf > 0) {
+        hipLaunchKernelGGL(face_normal_kernel, grid_of(nf), dim3(256), 0, st, (const float *)s->verts.get(), (const int *)s->faces.get(), nf,
+                           nv, s->face_normal.get());
+        MCHK(hipGetLastError());
+    }
+    return hipSuccess;
+}
+
+namespace {
 
 hipError_t ensure_pinned(TsdfState *s, ScratchCache &cache, hipStream_t st)
 {
@@ -451,12 +468,7 @@ hipError_t mesh_normals(TsdfState *s, ScratchCache &cache, hipStream_t st)
     const long long nv = s->n_vertices, nf = s->n_faces;
     MCHK(ensure_index(s, cache, st));
     MCHK(s->normals.reserve(3 * at_least_one(nv), cache));
-    MCHK(s->face_normal.reserve(3 * at_least_one(nf), cache));
-    if (nf > 0) {
-        hipLaunchKernelGGL(face_normal_kernel, grid_of(nf), dim3(256), 0, st, (const float *)s->verts.get(), (const int *)s->faces.get(), nf,
-                           nv, s->face_normal.get());
-        MCHK(hipGetLastError());
-    }
+    MCHK(mesh_face_normals(s, cache, st));
     if (nv > 0) {
         hipLaunchKernelGGL(vertex_normal_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->face_normal.get(),
                            (const unsigned *)s->row_start.get(), (const unsigned *)s->corners.get(), 3 * nf, nv, s->normals.get());

@@ -2,8 +2,9 @@
 // cells.  No reference counterpart.  Judged against tests/mesh_decimate_restatement.py, a NumPy statement of the same
 // definition with the same float32 operations in the same order (bit-identical positions, faces and colours).
 //
-// No float atomics: a cluster's position is a sequential sum over its members in ascending vertex id.  The one
-// integer atomic (the minimum of the out-of-range vertex ids) gives a result that does not depend on arrival order.
+// No float atomics: a cluster's position is a sequential sum over its members in ascending vertex id.  The integer
+// atomics (the minimum of the out-of-range vertex ids; the count of the clusters that kept the mean, quadric placement)
+// give results that do not depend on arrival order.
 //
 // (1) Cell.  Per vertex and axis q = (p - origin) / cell (two float32 operations, the division IEEE), i = floorf(q);
 //     -2^20 <= i < 2^20 or the call is refused before anything of the mesh is overwritten.
@@ -21,6 +22,17 @@
 //     sheets back to back), otherwise the first face of the majority winding stays.  The kept faces are compacted in
 //     their order, each in its own corner order.
 // (5) The clusters no kept face uses leave the mesh as in extraction pass (d).
+//
+// Quadric placement (mesh_decimate_quadric; tests/mesh_quadric_restatement.py): steps (1), (2), (4), (5) and the colour
+// of (3) as above; the position of a cluster is the minimiser of its members' area-weighted plane quadrics, tied to
+// the mean m of (3) by a regulariser, or m itself where the solve is not trusted.  On the OLD faces and positions:
+//     face normal   n = cross(p1 - p0, p2 - p0) as in amvs_mesh_clean.hip (d), not normalised
+//     vertex v      Qv = 0; for the corners of v in ascending corner index, f the corner's face: e = p[faces[3 f]] - m,
+//                   d = (nx ex + ny ey) + nz ez, Qv += (nx nx, nx ny, nx nz, ny ny, ny nz, nz nz, d nx, d ny, d nz)
+//     cluster       S = 0; S += Qv along the run = (a00 a01 a02 a11 a12 a22 b0 b1 b2); the regularised LDL^T solve of
+//                   cluster_solve_kernel in its stated order gives y; cand = m + y is taken iff t > 0, d1 > 0, d2 > 0,
+//                   cand is finite and |y| <= 0.5f * cell on every axis (NaN compares false)
+// The clusters that kept m are counted with one integer add per wave.
 #define AMVS_TU_ID 11
 #include "amvs_check.h"
 #include "amvs_kernels.h"
@@ -183,6 +195,72 @@ __global__ __launch_bounds__(256) void face_keep_mapped_kernel(const int *__rest
     for (int k = 0; k < 3; ++k) out[3 * o + k] = (int)cluster_of[AMVS_IDX((long long)faces[3 * f + k], n_vertices)];
 }
 
+// quadric placement: one thread per old vertex walks its row of the vertex -> corner index; mean = the representatives
+__global__ __launch_bounds__(256) void vertex_quadric_kernel(const float *__restrict__ verts, const int *__restrict__ faces,
+                                                             const float *__restrict__ fn, const unsigned *__restrict__ row_start,
+                                                             const unsigned *__restrict__ corners, const unsigned *__restrict__ cluster_of,
+                                                             const float *__restrict__ mean, long long n_ids, long long n_vertices,
+                                                             long long n_clusters, float *__restrict__ quadric)
+{
+    const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_vertices) return;
+    const long long c = AMVS_IDX((long long)cluster_of[v], n_clusters);
+    const float mx = mean[3 * c], my = mean[3 * c + 1], mz = mean[3 * c + 2];
+    float q[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (unsigned r = row_start[v]; r < row_start[v + 1]; ++r) {
+        const long long f = AMVS_IDX((long long)corners[AMVS_IDX((long long)r, n_ids)], n_ids) / 3;
+        const long long v0 = AMVS_IDX((long long)faces[3 * f], n_vertices);
+        const float ex = verts[3 * v0] - mx, ey = verts[3 * v0 + 1] - my, ez = verts[3 * v0 + 2] - mz;
+        const float nx = fn[3 * f], ny = fn[3 * f + 1], nz = fn[3 * f + 2];
+        const float d = (nx * ex + ny * ey) + nz * ez;
+        q[0] += nx * nx; q[1] += nx * ny; q[2] += nx * nz; q[3] += ny * ny; q[4] += ny * nz; q[5] += nz * nz;
+        q[6] += d * nx; q[7] += d * ny; q[8] += d * nz;
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) quadric[9 * v + i] = q[i];
+}
+
+// quadric placement: one thread per cluster sums its members' quadrics along the run, solves and, where the candidate
+// is accepted, overwrites the mean in pos; the others are counted, one add per wave
+__global__ __launch_bounds__(256) void cluster_solve_kernel(const float *__restrict__ quadric, const unsigned *__restrict__ id,
+                                                            const unsigned *__restrict__ start, long long n_vertices, long long n_clusters,
+                                                            float regularisation, float cell, float *__restrict__ pos,
+                                                            unsigned *__restrict__ n_fallback)
+{
+    const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool fallback = false;
+    if (c < n_clusters) {
+        float s[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        for (unsigned r = start[c]; r < start[c + 1]; ++r) {
+            const long long v = AMVS_IDX((long long)id[AMVS_IDX((long long)r, n_vertices)], n_vertices);
+#pragma unroll
+            for (int i = 0; i < 9; ++i) s[i] += quadric[9 * v + i];
+        }
+        const float a00 = s[0], a01 = s[1], a02 = s[2], a11 = s[3], a12 = s[4], a22 = s[5], b0 = s[6], b1 = s[7], b2 = s[8];
+        const float t = (a00 + a11) + a22;
+        const float lam = regularisation * t;
+        const float m00 = a00 + lam, m11 = a11 + lam, m22 = a22 + lam;
+        const float l10 = a01 / m00, l20 = a02 / m00;
+        const float d1 = m11 - l10 * a01;
+        const float u12 = a12 - l20 * a01;
+        const float l21 = u12 / d1;
+        const float d2 = (m22 - l20 * a02) - l21 * u12;
+        const float z1 = b1 - l10 * b0;
+        const float z2 = (b2 - l20 * b0) - l21 * z1;
+        const float y2 = z2 / d2;
+        const float y1 = z1 / d1 - l21 * y2;
+        const float y0 = (b0 / m00 - l10 * y1) - l20 * y2;
+        const float cx = pos[3 * c] + y0, cy = pos[3 * c + 1] + y1, cz = pos[3 * c + 2] + y2;
+        const float half = 0.5f * cell;
+        const bool accept = t > 0.0f && d1 > 0.0f && d2 > 0.0f && isfinite(cx) && isfinite(cy) && isfinite(cz) &&
+                            fabsf(y0) <= half && fabsf(y1) <= half && fabsf(y2) <= half;          // NaN is false
+        if (accept) { pos[3 * c] = cx; pos[3 * c + 1] = cy; pos[3 * c + 2] = cz; }
+        fallback = !accept;
+    }
+    const unsigned long long kept = __ballot(fallback);
+    if (kept && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)kept) - 1)) atomicAdd(n_fallback, (unsigned)__popcll(kept));
+}
+
 inline int bits_for(long long n)
 {
     int bits = 1;
@@ -201,14 +279,14 @@ hipError_t sort_pairs(TsdfState *s, ScratchCache &cache, const K *key_in, K *key
     return hipcub::DeviceRadixSort::SortPairs(s->scan_tmp.get(), bytes, key_in, key_out, val_in, val_out, (int)n, 0, bits, st);
 }
 
-}  // namespace
-
-hipError_t mesh_decimate(TsdfState *s, ScratchCache &cache, const float origin[3], float cell, long long *bad_vertex,
-                         long long *n_vertices, long long *n_faces, hipStream_t st)
+// both placements: quadric == false is mesh_decimate, launch for launch
+hipError_t decimate(TsdfState *s, ScratchCache &cache, const float origin[3], float cell, bool quadric, float regularisation,
+                    long long *bad_vertex, long long *n_vertices, long long *n_faces, long long *n_fallback, hipStream_t st)
 {
     const long long nv = s->n_vertices, nf = s->n_faces;
+    const bool place = quadric && nv > 0 && nf > 0;      // without faces every cluster has t = 0 and keeps the mean
     *bad_vertex = -1;
-    *n_vertices = nv; *n_faces = nf;
+    *n_vertices = nv; *n_faces = nf; *n_fallback = 0;
     long long nc = 0;
     if (nv > 0) {
         // (1), (2): nothing of the mesh or of its attributes is written before the range flag is back
@@ -216,7 +294,7 @@ hipError_t mesh_decimate(TsdfState *s, ScratchCache &cache, const float origin[3
         MCHK(s->dec_id.reserve((size_t)nv, cache)); MCHK(s->dec_id2.reserve((size_t)nv, cache));
         MCHK(s->dec_head.reserve((size_t)nv, cache)); MCHK(s->dec_before.reserve((size_t)nv, cache));
         MCHK(s->dec_cluster.reserve((size_t)nv, cache)); MCHK(s->dec_start.reserve((size_t)nv + 1, cache));
-        MCHK(s->dec_flag.reserve(1, cache));
+        MCHK(s->dec_flag.reserve(2, cache));
         MCHK(hipMemsetAsync(s->dec_flag.get(), 0xFF, 4, st));
         hipLaunchKernelGGL(cell_key_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->verts.get(), nv,
                            Cells{origin[0], origin[1], origin[2], cell}, s->dec_key.get(), s->dec_id.get(), s->dec_flag.get());
@@ -236,7 +314,14 @@ hipError_t mesh_decimate(TsdfState *s, ScratchCache &cache, const float origin[3
                            (const unsigned *)s->dec_head.get(), (const unsigned *)s->dec_before.get(), nv, nc, s->dec_cluster.get(),
                            s->dec_start.get());
         MCHK(hipGetLastError());
+        if (place) {
+            // the index and the face normals of the mesh as it still is
+            MCHK(ensure_index(s, cache, st));
+            MCHK(mesh_face_normals(s, cache, st));
+            MCHK(s->dec_quadric.reserve(9 * (size_t)nv, cache));
+        }
     }
+    const int *const old_faces = s->faces.get();
     s->have_csr = s->have_pinned = s->have_labels = s->have_normals = false;
     long long kept_f = 0, kept_v = 0;
     if (nf > 0 && nv > 0) {
@@ -286,12 +371,30 @@ hipError_t mesh_decimate(TsdfState *s, ScratchCache &cache, const float origin[3
             std::swap(s->faces, s->faces2);
         }
     }
-    if (kept_f > 0) {
-        // (3) into the second buffers, (5) back into the first
+    unsigned fallback = 0;
+    if (kept_f > 0 || place) {
+        // (3) into the second buffers
         hipLaunchKernelGGL(representative_kernel, grid_of(nc), dim3(256), 0, st, (const float *)s->verts.get(),
                            (const unsigned char *)s->rgb.get(), (const unsigned *)s->dec_id2.get(), (const unsigned *)s->dec_start.get(),
                            nv, nc, s->verts2.get(), s->rgb2.get());
         MCHK(hipGetLastError());
+    }
+    if (place) {
+        // the quadrics read the old faces (step (4) may have swapped them away) and the old positions; the count comes
+        // back with the next read-back
+        MCHK(hipMemsetAsync(s->dec_flag.get() + 1, 0, 4, st));
+        hipLaunchKernelGGL(vertex_quadric_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->verts.get(), old_faces,
+                           (const float *)s->face_normal.get(), (const unsigned *)s->row_start.get(), (const unsigned *)s->corners.get(),
+                           (const unsigned *)s->dec_cluster.get(), (const float *)s->verts2.get(), 3 * nf, nv, nc, s->dec_quadric.get());
+        MCHK(hipGetLastError());
+        hipLaunchKernelGGL(cluster_solve_kernel, grid_of(nc), dim3(256), 0, st, (const float *)s->dec_quadric.get(),
+                           (const unsigned *)s->dec_id2.get(), (const unsigned *)s->dec_start.get(), nv, nc, regularisation, cell,
+                           s->verts2.get(), s->dec_flag.get() + 1);
+        MCHK(hipGetLastError());
+        MCHK(hipMemcpyAsync(&fallback, s->dec_flag.get() + 1, 4, hipMemcpyDeviceToHost, st));
+    }
+    if (kept_f > 0) {
+        // (5) back into the first buffers
         std::swap(s->verts, s->verts2);
         std::swap(s->rgb, s->rgb2);
         MCHK(drop_unused_vertices(s, cache, nc, kept_f, &kept_v, st));
@@ -299,7 +402,24 @@ hipError_t mesh_decimate(TsdfState *s, ScratchCache &cache, const float origin[3
     MCHK(hipStreamSynchronize(st));
     s->n_vertices = kept_v; s->n_faces = kept_f;
     *n_vertices = kept_v; *n_faces = kept_f;
+    *n_fallback = place ? (long long)fallback : nc;
     return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t mesh_decimate(TsdfState *s, ScratchCache &cache, const float origin[3], float cell, long long *bad_vertex,
+                         long long *n_vertices, long long *n_faces, hipStream_t st)
+{
+    long long n_fallback = 0;
+    return decimate(s, cache, origin, cell, false, 0.0f, bad_vertex, n_vertices, n_faces, &n_fallback, st);
+}
+
+hipError_t mesh_decimate_quadric(TsdfState *s, ScratchCache &cache, const float origin[3], float cell, float regularisation,
+                                 long long *bad_vertex, long long *n_vertices, long long *n_faces, long long *n_fallback,
+                                 hipStream_t st)
+{
+    return decimate(s, cache, origin, cell, true, regularisation, bad_vertex, n_vertices, n_faces, n_fallback, st);
 }
 
 }  // namespace amvs

@@ -61,10 +61,11 @@ struct TsdfState {
     DeviceBuffer<unsigned> dec_id, dec_id2;       // [V]: vertex ids, ascending and in sorted-key order (the clusters' runs)
     DeviceBuffer<unsigned> dec_head, dec_before;  // [V]: run heads of the sorted keys and their exclusive scan
     DeviceBuffer<unsigned> dec_cluster, dec_start;        // [V]: cluster of every vertex; [C + 1]: start of every run
-    DeviceBuffer<unsigned> dec_flag;              // [1]: smallest vertex id outside the cluster grid, or all ones
+    DeviceBuffer<unsigned> dec_flag;              // [2]: smallest vertex id outside the cluster grid, or all ones; quadric fallbacks
     DeviceBuffer<unsigned> dec_ta, dec_tlo, dec_thi;      // [F]: smallest, middle and largest cluster id of the face
     DeviceBuffer<unsigned char> dec_even;         // [F]: winding of the face, rotated to start at its smallest id
     DeviceBuffer<unsigned> dec_fkey, dec_fkey2, dec_perm, dec_perm2;      // [F]: the group sorts' keys and permutation
+    DeviceBuffer<float> dec_quadric;              // [V][9]: quadric placement, a00 a01 a02 a11 a12 a22 b0 b1 b2 of every vertex
 
     // the mesh is about to be replaced: nothing derived from it stays
     void drop_mesh()

@@ -673,6 +673,17 @@ class Engine:
         self._mesh_counts = (nv.value, nf.value)
         return nv.value, nf.value
 
+    def mesh_decimate_quadric(self, origin, cell, regularisation=1e-3):
+        """mesh_decimate with every cluster's vertex placed by its members' plane quadrics instead of at their mean
+        (include/amvs.h amvs_mesh_decimate_quadric); faces, colours and counts are mesh_decimate's.  Returns (vertices,
+        faces, clusters that kept the mean); drops labels and normals."""
+        org = _f32(np.asarray(origin, np.float64).astype(np.float32).reshape(3))
+        nv, nf, nk = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.amvs_mesh_decimate_quadric(self._h, _p(org), float(np.float32(cell)), float(np.float32(regularisation)),
+                                                       C.byref(nv), C.byref(nf), C.byref(nk)))
+        self._mesh_counts = (nv.value, nf.value)
+        return nv.value, nf.value, nk.value
+
     def mesh_fetch(self, normals=False, labels=False):
         """The current mesh: (vertices (V,3) float32, faces (F,3) int32, colors (V,3) uint8[, normals (V,3) float32]
         [, labels (V,) int32])."""

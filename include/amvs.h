@@ -339,7 +339,7 @@ int amvs_tsdf_set_volume(amvs_ctx *ctx, const float *tsdf, const float *weight, 
  * amvs_fetch_mesh returns the current mesh, cleaned or not.  No float atomics: every float sum runs in a fixed order
  * over the corners c = 3 * face + k that hold the vertex, in ascending c.  Limits: int32 vertex ids and
  * 3 * n_faces <= INT32_MAX.  Labels and normals are attributes of the current mesh: amvs_tsdf_integrate,
- * amvs_tsdf_set_volume, amvs_tsdf_extract, amvs_mesh_set and amvs_mesh_decimate drop both,
+ * amvs_tsdf_set_volume, amvs_tsdf_extract, amvs_mesh_set, amvs_mesh_decimate and amvs_mesh_decimate_quadric drop both,
  * amvs_mesh_filter_components drops the normals and leaves fresh labels, amvs_mesh_smooth drops the normals and keeps
  * the labels.                                                                                                      */
 /* Replace the context's mesh by host arrays: n_vertices x 3 float32 positions, n_faces x 3 int32 vertex ids,
@@ -384,6 +384,37 @@ int amvs_mesh_normals(amvs_ctx *ctx);
  * n_vertices and n_faces are the mesh after it; the empty mesh and a mesh of vertices only give 0 / 0.  Drops labels
  * and normals.                                                                                                    */
 int amvs_mesh_decimate(amvs_ctx *ctx, const float origin[3], float cell, int64_t *n_vertices, int64_t *n_faces);
+/* amvs_mesh_decimate with quadric placement of the clusters' vertices (Lindstrom's out-of-core simplification, stated
+ * so that it runs data-parallel and compares bit for bit: tests/mesh_quadric_restatement.py, DESIGN.md section 8
+ * "Quadric placement").  Steps 1, 2, 4 and 5 and the colour of step 3 are amvs_mesh_decimate's: faces, colours and
+ * counts are identical, only positions differ.  `regularisation` must be finite and in (0, 1], else AMVS_EINVAL; origin
+ * and cell as above; the messages are amvs_mesh_decimate's with this call's name.  All float32, every operation rounded
+ * on its own (no fused multiply-add), the divisions IEEE.  The position of a cluster, on the OLD faces and positions:
+ * a. m = the representative of step 3.
+ * b. Face normal n = cross(p1 - p0, p2 - p0) as amvs_mesh_normals forms it (u * v - w * x per component, not normalised).
+ * c. Vertex quadric of old vertex v in cluster c: Qv = nine zeros; for every corner of v in ascending corner index
+ *    3 * face + k, f the corner's face: e = p[faces[3 f]] - m_c per axis, d = (n.x * e.x + n.y * e.y) + n.z * e.z, and the
+ *    nine products nx nx, nx ny, nx nz, ny ny, ny nz, nz nz, d nx, d ny, d nz are added to Qv component by component.
+ * d. Cluster quadric S = 0; S += Qv along the cluster's members in ascending old vertex id:
+ *    (a00 a01 a02 a11 a12 a22 b0 b1 b2).  It minimises sum (n . y - d)^2 over y = x - m, weighted by area squared.
+ * e. Solve, in exactly this order:
+ *        t   = (a00 + a11) + a22            lam = regularisation * t
+ *        m00 = a00 + lam;  m11 = a11 + lam;  m22 = a22 + lam
+ *        l10 = a01 / m00;  l20 = a02 / m00
+ *        d1  = m11 - l10 * a01              u12 = a12 - l20 * a01           l21 = u12 / d1
+ *        d2  = (m22 - l20 * a02) - l21 * u12
+ *        z1  = b1 - l10 * b0                z2  = (b2 - l20 * b0) - l21 * z1
+ *        y2  = z2 / d2                      y1  = z1 / d1 - l21 * y2        y0 = (b0 / m00 - l10 * y1) - l20 * y2
+ *        cand = m + y
+ * f. cand is the position iff t > 0, d1 > 0 and d2 > 0, every component of cand is finite and |y_a| <= 0.5f * cell on
+ *    every axis (comparisons false for NaN); otherwise the position is m.
+ * The regulariser ties the null space of a flat cluster to the mean (in a plane only the normal component moves), a
+ * cluster whose vertices have no faces has t = 0 and keeps the mean, and the half-cell bound keeps a near-singular
+ * solve from throwing a vertex away.  n_fallback counts the clusters of step 2 that kept m, those that step 5 removes
+ * included.  A vertex outside the cluster grid refuses the call as above, before anything of the mesh or its attributes
+ * changes.  Drops labels and normals.                                                                              */
+int amvs_mesh_decimate_quadric(amvs_ctx *ctx, const float origin[3], float cell, float regularisation, int64_t *n_vertices,
+                               int64_t *n_faces, int64_t *n_fallback);
 /* n_vertices x 3 float32 normals (amvs_mesh_normals) and n_vertices int32 labels (amvs_mesh_filter_components) of
  * the current mesh.  NULL skips an output; asking for one that is not current is AMVS_EINVAL.                     */
 int amvs_fetch_mesh_attributes(amvs_ctx *ctx, float *normals, int32_t *labels);

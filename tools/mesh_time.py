@@ -5,7 +5,8 @@ depths for a surface) resident on the device, a 256^3 TSDF volume around the fus
 includes its two count read-backs); the first-order bounds of DESIGN.md section 8 are printed next to them.
 Then the clean-up stage on that mesh and on the mesh of a 256^3 sphere: the vertex -> corner index, labelling + filter,
 10 Taubin iterations and the normals, each the median of 5 after a warm-up, with a first-order byte estimate; the
-decimation of either mesh at a cell of 2 voxels, likewise; and
+decimation of either mesh at a cell of 2 voxels with either placement of the clusters' vertices (the mean, the quadrics),
+likewise; and
 the labelling of a shuffled strip of 100 000 faces next to a sphere of about as many.
 
     python tools/mesh_time.py [n_views W H dim]
@@ -122,12 +123,14 @@ def restore_volume():
 
 def decimate_time(name, restore, grid_origin, cell):
     """Decimation (csrc/amvs_mesh_decimate.hip) of the restored mesh at a cell of 2 voxels on the volume's origin."""
-    ts = []
+    ts, tq = [], []
     for rep in range(REPS + 1):
         V, F = restore()
         ms, _, counts = timed(lambda: eng.mesh_decimate(grid_origin, cell))
+        restore()                                                 # a fresh topology: the quadric call builds its index
+        mq, _, qcounts = timed(lambda: eng.mesh_decimate_quadric(grid_origin, cell))
         if rep:
-            ts.append(ms)
+            ts.append(ms); tq.append(mq)
     C, K = counts                                                 # clusters that stay, faces that stay
     live = max(F // 8, K)                                         # faces without a repeated id: first order, an eighth
     bits = max(int(np.ceil(np.log2(max(C, 2)))), 1)
@@ -143,6 +146,13 @@ def decimate_time(name, restore, grid_origin, cell):
     print(f"decimation of {name} at 2 voxels: {V:,} vertices, {F:,} faces -> {C:,} / {K:,}: median {np.median(ts):.3f} ms device "
           f"(min {min(ts):.3f}); first-order bytes of the sorts and passes (estimate) {est / 1e6:.1f} MB = "
           f"{est / 8e12 * 1e3:.4f} ms at 8 TB/s")
+    # what the quadric placement adds: the vertex -> corner index (clean_times' estimate), the face normals, the rows
+    # walked once with the first vertex, the normal and the mean behind every corner, 36 B per vertex out and in
+    extra = 3 * F * 4 * (2 + 4 * 4) + V * 8 + F * (12 + 36 + 12) + 3 * F * (4 + 4 + 12 + 12) + V * (4 + 12 + 36) + V * (4 + 36) + C * 24
+    print(f"  with quadric placement ({qcounts[2]:,} of the clusters kept the mean): median {np.median(tq):.3f} ms device "
+          f"(min {min(tq):.3f}), {np.median(tq) / np.median(ts):.2f} x the mean placement; first-order bytes it adds (estimate) "
+          f"{extra / 1e6:.1f} MB = {extra / 8e12 * 1e3:.4f} ms at 8 TB/s")
+    assert qcounts[:2] == counts
 
 
 clean_times(f"the CLI operating point ({dim}^3)", restore_volume)
