@@ -23,30 +23,21 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from .camera import Camera, CameraPose
-from .imageprep import prepare_views
-from .. import engine as _engine
+from .view_cache import ResidentViews
 from .. import parallel as _parallel
-
-
-def _torch_cuda():
-    """torch with a usable HIP device, or None (then maps travel through host arrays)."""
-    try:
-        import torch
-    except Exception:  # noqa: BLE001
-        return None
-    return torch if torch.cuda.is_available() else None
 
 
 _DRAW_BUF = threading.local()     # .pair = (arange, scratch) of DenseStereoReconstructor._draw_without_replacement
 
 
-class DenseStereoReconstructor:
+class DenseStereoReconstructor(ResidentViews):
     NUM_NEIGHBORS = 6        # reference :109
 
     def __init__(self, camera: Camera, scale: float = 0.25, num_depths: int = 64,
                  patch_size: int = 5, min_views: int = 3, consistency_thresh: float = 0.8, *,
                  device: Optional[int] = None, device_filter: bool = True, mode: str = "exact",
                  process_group=None, device_prep: Optional[bool] = None):
+        super().__init__(device_prep)            # the resident-view cache and the device_prep default
         self.camera = camera
         self.scale = scale
         self.num_depths = num_depths
@@ -56,10 +47,6 @@ class DenseStereoReconstructor:
         self.device_id = _parallel.local_device() if device is None else int(device)
         self.device_filter = device_filter       # outlier filter's neighbour search on the GPU
         self.process_group = process_group       # torch.distributed group the reference views are sharded over
-        # resize / gray conversion on the GPU (amvs_set_view_bgr8): the default only where cv2 is not
-        # importable (see PatchMatchMVS.__init__)
-        from . import imageprep as _ip
-        self.device_prep = (_ip._cv is None) if device_prep is None else bool(device_prep)
         if mode not in ("exact", "fast"):
             raise ValueError("mode must be 'exact' or 'fast'")
         self.mode = mode                         # arithmetic of the sweep (include/amvs.h AMVS_MODE_*)
@@ -68,11 +55,10 @@ class DenseStereoReconstructor:
         self.K_scaled = camera.K.copy()
         for r, c in ((0, 0), (1, 1), (0, 2), (1, 2)):
             self.K_scaled[r, c] *= scale
-        self._engine = None
-        self._engine_key = None
-        self._engine_images = None
-        self._resident_colors = False    # the engine holds the prepared colour images (device image prep)
-        self._slot = {}
+        self._subsample_on_host = False  # test switch: sub-sample clouds above 500 000 points as the host path does
+
+    def _engine_mode(self) -> str:
+        return self.mode                 # the engine is created in this object's mode (no mode per call here)
 
     def reconstruct(self, images: List[dict], poses: Dict[int, CameraPose],
                     max_pairs: int = 30) -> Tuple[np.ndarray, np.ndarray]:
@@ -142,12 +128,11 @@ class DenseStereoReconstructor:
         single = world == 1 and len(groups) == 1
         if single:
             js = next(iter(groups.values()))
-            eng.plane_sweep_batch([self._slot[jobs[j][0]] for j in js],
-                                  [[self._slot[i] for i in jobs[j][1]] for j in js],
-                                  depths, self.patch_size, self.consistency_thresh)
+            refs, nbrs = self._job_slots(jobs, js)
+            eng.plane_sweep_batch(refs, nbrs, depths, self.patch_size, self.consistency_thresh)
             view_poses = [(poses[jobs[j][0]].R, poses[jobs[j][0]].t) for j in js]
             if self._resident_colors and processed is self._engine_images:
-                counts, total = eng.stereo_backproject_views([self._slot[jobs[j][0]] for j in js], K_inv, view_poses, min_conf)
+                counts, total = eng.stereo_backproject_views(refs, K_inv, view_poses, min_conf)
             else:
                 cols = np.stack([processed[jobs[j][0]]["color"] for j in js])
                 counts, total = eng.stereo_backproject(cols, K_inv, view_poses, min_conf)
@@ -155,15 +140,8 @@ class DenseStereoReconstructor:
         # several batches and / or several ranks: the maps of every view are collected first -- in
         # device tensors when torch-ROCm is there (job j in row j; the sweeps write their rows, RCCL
         # gathers the rank blocks in place, the back-projection reads them: nothing crosses PCIe)
-        torch = _torch_cuda()
-        runs, cur = [], []
-        for j in mine:                                     # launches = runs of consecutive jobs, one neighbour count
-            if cur and (len(jobs[j][1]) != len(jobs[cur[-1]][1]) or j != cur[-1] + 1):
-                runs.append(cur)
-                cur = []
-            cur.append(j)
-        if cur:
-            runs.append(cur)
+        torch = _parallel._torch_cuda()
+        runs = _parallel.runs_of_one_count(jobs, mine)     # launches = runs of consecutive jobs, one neighbour count
         order = list(range(len(jobs))) if world > 1 else mine
         view_poses = [(poses[jobs[j][0]].R, poses[jobs[j][0]].t) for j in order]
         cols = np.stack([processed[jobs[j][0]]["color"] for j in order])
@@ -176,9 +154,7 @@ class DenseStereoReconstructor:
             cmaps = torch.zeros((world * per, hw), dtype=torch.float32, device=dev)
             torch.cuda.synchronize(dev)
             for js in runs:
-                eng.plane_sweep_device([self._slot[jobs[j][0]] for j in js],
-                                       [[self._slot[i] for i in jobs[j][1]] for j in js],
-                                       depths, self.patch_size, self.consistency_thresh,
+                eng.plane_sweep_device(*self._job_slots(jobs, js), depths, self.patch_size, self.consistency_thresh,
                                        dmaps[js[0]].data_ptr(), cmaps[js[0]].data_ptr())
             eng.sync()
             if world > 1:
@@ -200,9 +176,7 @@ class DenseStereoReconstructor:
         cmaps = np.zeros((len(mine), H, W), np.float32)
         row = {j: n for n, j in enumerate(mine)}
         for js in runs:
-            eng.plane_sweep_batch([self._slot[jobs[j][0]] for j in js],
-                                  [[self._slot[i] for i in jobs[j][1]] for j in js],
-                                  depths, self.patch_size, self.consistency_thresh)
+            eng.plane_sweep_batch(*self._job_slots(jobs, js), depths, self.patch_size, self.consistency_thresh)
             d, c = eng.fetch_sweep_maps(0, len(js))
             for n, j in enumerate(js):
                 dmaps[row[j]], cmaps[row[j]] = d[n], c[n]
@@ -219,7 +193,7 @@ class DenseStereoReconstructor:
         host_path = not self.device_filter or not eng.knn_supported(k) or k >= min(total, 500000) // 2
         if total < k + 1:
             keep = None
-        elif total > 500000 and not host_path and not getattr(self, "_subsample_on_host", False):
+        elif total > 500000 and not host_path and not self._subsample_on_host:
             # the reference sub-samples clouds above 500 000 points at random (unseeded np.random.choice, :449-451)
             # and filters the sample: the same draw, the sample taken on the device (amvs_cloud_take), so that the
             # cloud never travels to the host -- the same points as the host path returns for the same draw
@@ -261,38 +235,6 @@ class DenseStereoReconstructor:
         return idx[:size]
 
     # ------------------------------------------------------------------ host ------
-    def _prepare_images(self, images: List[dict], indices: List[int]) -> Dict:
-        return dict(zip(indices, prepare_views([images[idx]["image"] for idx in indices], self.scale)))
-
-    def _prepare_images_device(self, images: List[dict], indices: List[int], poses: Dict[int, CameraPose]) -> Dict:
-        """_prepare_images on the GPU (amvs_set_view_bgr8): upload the 8-bit BGR images, resize and
-        convert there; the engine is cached for the returned dict ('gray' is None)."""
-        h, w = images[indices[0]]["image"].shape[:2]
-        H, W = int(h * self.scale), int(w * self.scale)
-        eng = self._engine
-        if eng is None or not eng.reusable_for(H, W, len(indices), self.K_scaled, self.device_id, self.mode):
-            if eng is not None:
-                eng.close()
-                self._engine = None
-            eng = _engine.Engine(H, W, len(indices), self.K_scaled.astype(np.float32), device=self.device_id, mode=self.mode)
-        self._slot = {idx: s for s, idx in enumerate(indices)}
-        prepared = {}
-        for idx in indices:
-            img = images[idx]["image"]
-            same = (H, W) == tuple(img.shape[:2])
-            color = eng.set_view_bgr8(self._slot[idx], img, poses[idx].R, poses[idx].t, want_color=not same)
-            prepared[idx] = {"color": img if same else color, "gray": None, "shape": (H, W)}
-        self._engine, self._engine_images, self._resident_colors = eng, prepared, True
-        self._engine_key = self._make_engine_key(prepared, poses)
-        return prepared
-
-    def _make_engine_key(self, processed: Dict, poses: Dict[int, CameraPose]):
-        indices = sorted(processed.keys())
-        H, W = processed[indices[0]]["shape"]
-        pose_print = b"".join(np.asarray(poses[i].R, np.float64).tobytes() + np.asarray(poses[i].t, np.float64).tobytes()
-                              for i in indices)
-        return (tuple(indices), (int(H), int(W)), pose_print, self.K_scaled.tobytes(), self.device_id)
-
     def _find_neighbors(self, ref_idx: int, all_indices: List[int],
                         poses: Dict[int, CameraPose], k: int = 6) -> List[int]:
         """k nearest camera centres, stable order (reference :178-191)."""
@@ -300,25 +242,6 @@ class DenseStereoReconstructor:
         ranked = sorted(((idx, np.linalg.norm(poses[idx].center - c_ref))
                          for idx in all_indices if idx != ref_idx), key=lambda item: item[1])
         return [idx for idx, _ in ranked[:k]]
-
-    def _ensure_engine(self, processed: Dict, poses: Dict[int, CameraPose]):
-        indices = sorted(processed.keys())
-        H, W = processed[indices[0]]["shape"]
-        # strong reference to the dict + pose fingerprint (see PatchMatchMVS._ensure_engine)
-        key = self._make_engine_key(processed, poses)
-        if self._engine is not None and self._engine_images is processed and self._engine_key == key:
-            return self._engine
-        if self._engine is not None:
-            self._engine.close()
-            self._engine = None
-        eng = _engine.Engine(H, W, len(indices), self.K_scaled.astype(np.float32), device=self.device_id,
-                             mode=self.mode)
-        self._slot = {idx: s for s, idx in enumerate(indices)}
-        for idx in indices:
-            eng.set_view(self._slot[idx], processed[idx]["gray"], poses[idx].R, poses[idx].t)
-        self._engine, self._engine_key, self._engine_images = eng, key, processed
-        self._resident_colors = False
-        return eng
 
     def _compute_depth_map_gpu(self, ref_idx: int, neighbor_indices: List[int], processed: Dict,
                                poses: Dict[int, CameraPose], depth_min: float, depth_max: float):

@@ -31,7 +31,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from .camera import Camera, CameraPose
-from .imageprep import prepare_view, prepare_views
+from .view_cache import ResidentViews
 from .. import engine as _engine
 from .. import parallel as _parallel
 
@@ -60,21 +60,11 @@ class _ResidentMaps:
                                   confidence=c[i].reshape(H, W)) for i, r in enumerate(self.ref_ids)}
 
 
-def _imageprep_has_cv2():
-    from . import imageprep
-    return imageprep._cv is not None
+def _print_view_progress(cam_indices, ref_idx, valid, per_view):
+    print(f"  [{cam_indices.index(ref_idx)+1}/{len(cam_indices)}] Cam {ref_idx}: {int(valid):,} valid pixels ({per_view:.1f}s)")
 
 
-def _torch_cuda():
-    """torch with a usable HIP device, or None (then maps travel through host arrays)."""
-    try:
-        import torch
-    except Exception:  # noqa: BLE001
-        return None
-    return torch if torch.cuda.is_available() else None
-
-
-class PatchMatchMVS:
+class PatchMatchMVS(ResidentViews):
     NUM_SOURCES = 4          # reference :108
 
     def __init__(self, camera: Camera, scale: float = 0.25, patch_size: int = 11,
@@ -83,6 +73,7 @@ class PatchMatchMVS:
                  seed: int = 0, device: Optional[int] = None, views_per_batch: int = 16,
                  process_group=None, device_fusion: bool = True, mode: str = "exact",
                  device_prep: Optional[bool] = None, extended: bool = False, gather_normals: bool = True):
+        super().__init__(device_prep)            # the resident-view cache and the device_prep default
         self.camera = camera
         self.scale = scale
         self.patch_size = patch_size
@@ -95,11 +86,6 @@ class PatchMatchMVS:
         self.views_per_batch = max(1, int(views_per_batch))
         self.process_group = process_group
         self.device_fusion = device_fusion
-        # resize / gray conversion on the GPU (amvs_set_view_bgr8).  The device arithmetic restates
-        # OpenCV's 8-bit algorithm and cannot be pinned against cv2 in the build container (DESIGN.md
-        # section 2), so the default is the device path only where cv2 is NOT importable; where it is,
-        # the host path calls cv2 itself and is the reference's by construction.
-        self.device_prep = (not _imageprep_has_cv2()) if device_prep is None else bool(device_prep)
         # several ranks: also all-gather the normal maps (12 of the 20 B/pixel; north_star's exchange).
         # reconstruct() itself fuses depth and confidence only (reference :536-570).
         self.gather_normals = gather_normals
@@ -116,12 +102,12 @@ class PatchMatchMVS:
         # scaled intrinsics: first two rows times `scale` (reference :69-70)
         self.K_scaled = camera.K.copy()
         self.K_scaled[:2] *= scale
-        self._engine = None
-        self._engine_key = None
-        self._engine_images = None       # strong reference to the prepared dict the engine holds
-        self._resident_colors = False    # the engine holds the prepared colour images (device image prep)
-        self._slot = {}
         self.last_timing = None
+        self.last_mesh_grid = None       # (origin, voxel, dims, trunc) of the last reconstruct_mesh
+        # run the multi-rank code path -- row groups, second stream, collectives -- on a one-rank process group
+        # as well; how the RCCL calls are rehearsed on a one-GPU box
+        self.exercise_exchange = False
+        self._streams = None             # (device, sweep stream, exchange stream) of _exchange_streams
 
     # ------------------------------------------------------------------ public ----
     def reconstruct(self, images: List[dict], poses: Dict[int, CameraPose],
@@ -238,7 +224,7 @@ class PatchMatchMVS:
             if not ids:
                 return ids, {}
             src = dict(depth=np.stack([data[i].depth for i in ids]), conf=np.stack([data[i].confidence for i in ids]))
-        if getattr(self, "_resident_colors", False) and proc_images is self._engine_images:
+        if self._resident_colors and proc_images is self._engine_images:
             src["view_ids"] = [self._slot[i] for i in ids]
         else:
             src["colors_bgr"] = np.stack([proc_images[i]["color"] for i in ids])
@@ -302,45 +288,34 @@ class PatchMatchMVS:
             jobs.append((ref_idx, src))
 
         if self.extended and jobs:
-            torch = _torch_cuda()
+            torch = _parallel._torch_cuda()
             if torch is None:
                 raise RuntimeError("the extended mode keeps its state in device tensors: PyTorch-ROCm with a GPU is required")
-            resident = self._sweep_extended(torch, jobs, proc_images, poses, cam_indices)
-            print("\nFusing depth maps...")
-            points, colors, raw = self._fuse_filter_resident(resident, proc_images, poses)
-            print(f"  Raw points: {raw:,}")
-            if raw > 0:
-                print(f"  After filtering: {len(points):,}")
-            print(f"\nPatchMatch MVS completed in {time.time() - t0:.1f}s")
-            return points, colors, ("resident", resident, proc_images)
-
-        torch = _torch_cuda() if self.device_fusion else None
-        if torch is not None and jobs:
-            resident = self._sweep_resident(torch, jobs, proc_images, poses, cam_indices)
-            print("\nFusing depth maps...")
-            points, colors, raw = self._fuse_filter_resident(resident, proc_images, poses)
-            print(f"  Raw points: {raw:,}")
-            if raw > 0:
-                print(f"  After filtering: {len(points):,}")
-            print(f"\nPatchMatch MVS completed in {time.time() - t0:.1f}s")
-            return points, colors, ("resident", resident, proc_images)
-
-        depth_maps = self._sweep(jobs, proc_images, poses, cam_indices)
-
-        print("\nFusing depth maps...")
-        if self.device_fusion and self._engine is not None and depth_maps:
-            points, colors, raw = self._fuse_filter_device(depth_maps, proc_images, poses)
-            print(f"  Raw points: {raw:,}")
-            if raw > 0:
-                print(f"  After filtering: {len(points):,}")
+            sweep = self._sweep_extended
         else:
-            points, colors = self._fuse_depth_maps(depth_maps, proc_images, poses)
-            print(f"  Raw points: {len(points):,}")
-            if len(points) > 0:
-                points, colors = self._filter_points(points, colors)
-                print(f"  After filtering: {len(points):,}")
+            torch = _parallel._torch_cuda() if self.device_fusion and jobs else None
+            sweep = self._sweep_resident
+        if torch is not None:
+            resident = sweep(torch, jobs, proc_images, poses, cam_indices)
+            print("\nFusing depth maps...")
+            points, colors, raw = self._fuse_filter_resident(resident, proc_images, poses)
+            maps = ("resident", resident, proc_images)
+        else:
+            depth_maps = self._sweep(jobs, proc_images, poses, cam_indices)
+            print("\nFusing depth maps...")
+            if self.device_fusion and self._engine is not None and depth_maps:
+                points, colors, raw = self._fuse_filter_device(depth_maps, proc_images, poses)
+            else:
+                points, colors = self._fuse_depth_maps(depth_maps, proc_images, poses)
+                raw = len(points)
+                if raw > 0:
+                    points, colors = self._filter_points(points, colors)
+            maps = ("host", depth_maps, proc_images)
+        print(f"  Raw points: {raw:,}")
+        if raw > 0:
+            print(f"  After filtering: {len(points):,}")
         print(f"\nPatchMatch MVS completed in {time.time() - t0:.1f}s")
-        return points, colors, ("host", depth_maps, proc_images)
+        return points, colors, maps
 
     # ------------------------------------------------------------- host geometry --
     def _estimate_depth_range(self, poses: Dict[int, CameraPose], sparse_points: np.ndarray = None):
@@ -362,45 +337,6 @@ class PatchMatchMVS:
         scene_scale = np.percentile(spread, 90)
         self.depth_min = max(0.1, scene_scale * 0.05)
         self.depth_max = scene_scale * 10.0
-
-    def _prepare_images(self, images: List[dict], indices: List[int]) -> Dict:
-        """Scaled colour + float32 gray in [0,1] per view (reference :167-191; the Sobel
-        gradients computed there are never read and are not produced here)."""
-        prepared = prepare_views([images[idx]["image"] for idx in indices], self.scale)
-        return dict(zip(indices, prepared))
-
-    def _prepare_images_device(self, images: List[dict], indices: List[int], poses: Dict[int, CameraPose]) -> Dict:
-        """_prepare_images on the GPU: every view's 8-bit BGR image is uploaded as it is (3 B/pixel) and
-        resized / converted there (amvs_set_view_bgr8), which also leaves it resident for the sweep.
-        Returns the prepared dict without host gray maps ('gray': None); the engine is cached for it."""
-        h, w = images[indices[0]]["image"].shape[:2]
-        H, W = int(h * self.scale), int(w * self.scale)
-        eng = self._engine
-        if eng is None or not eng.reusable_for(H, W, len(indices), self.K_scaled, self.device_id):
-            if eng is not None:
-                eng.close()
-                self._engine = None
-            eng = _engine.Engine(H, W, len(indices), self.K_scaled.astype(np.float32), device=self.device_id)
-        self._slot = {idx: s for s, idx in enumerate(indices)}
-        prepared = {}
-        for idx in indices:
-            img = images[idx]["image"]
-            if img.shape[:2] != (h, w):
-                raise ValueError("all views must share one size")
-            # the prepared colour image stays on the device for the fusion; the host copy the reference's
-            # dict holds is the input itself at scale 1 and a (small) download otherwise
-            same = (H, W) == (h, w)
-            color = eng.set_view_bgr8(self._slot[idx], img, poses[idx].R, poses[idx].t, want_color=not same)
-            prepared[idx] = {"color": img if same else color, "gray": None, "shape": (H, W)}
-        self._engine, self._engine_images, self._resident_colors = eng, prepared, True
-        self._engine_key = self._make_engine_key(prepared, poses, indices)
-        return prepared
-
-    def _make_engine_key(self, images: Dict, poses: Dict[int, CameraPose], indices: List[int]):
-        H, W = images[indices[0]]["shape"]
-        pose_print = b"".join(np.asarray(poses[i].R, np.float64).tobytes() + np.asarray(poses[i].t, np.float64).tobytes()
-                              for i in indices)
-        return (tuple(indices), (int(H), int(W)), pose_print, self.K_scaled.tobytes(), self.device_id)
 
     def _select_source_views(self, ref_idx: int, all_indices: List[int],
                              poses: Dict[int, CameraPose], k: int = 4) -> List[int]:
@@ -425,33 +361,9 @@ class PatchMatchMVS:
         return _engine.make_pm_params(self.patch_size, self.num_iterations, self.num_samples,
                                       self.depth_min, self.depth_max, mode=self.mode)
 
-    def _ensure_engine(self, images: Dict, poses: Dict[int, CameraPose], indices: List[int]):
-        """Upload every view once; cached while the same prepared-image dict, the same poses and
-        the same intrinsics are in use.  The key holds a strong reference to the dict (an id() of a
-        freed dict can be reused by CPython) and a fingerprint of every R|t, so a second call with
-        refined poses re-uploads instead of sweeping with stale ones."""
-        H, W = images[indices[0]]["shape"]
-        key = self._make_engine_key(images, poses, indices)
-        if self._engine is not None and self._engine_images is images and self._engine_key == key:
-            return self._engine
-        if self._engine is not None:
-            self._engine.close()
-            self._engine = None
-        for idx in indices:
-            if tuple(images[idx]["shape"]) != (H, W):
-                raise ValueError("all views must share one processed size")
-        eng = _engine.Engine(H, W, len(indices), self.K_scaled.astype(np.float32), device=self.device_id)
-        self._slot = {idx: s for s, idx in enumerate(indices)}
-        for idx in indices:
-            eng.set_view(self._slot[idx], images[idx]["gray"], poses[idx].R, poses[idx].t)
-        self._engine, self._engine_key, self._engine_images = eng, key, images
-        self._resident_colors = False            # gray uploads: the colour images stay on the host
-        return eng
-
     def _run_batch(self, eng, batch):
         """batch: list of (ref_idx, src_indices) with equal source counts -> maps per ref."""
-        refs = [self._slot[r] for r, _ in batch]
-        srcs = [[self._slot[s] for s in src] for _, src in batch]
+        refs, srcs = self._job_slots(batch, range(len(batch)))
         depth, normal, conf = eng.patchmatch(refs, srcs, self._pm_params(), self.seed_for_stream())
         self.last_timing = eng.timing()
         return depth, normal, conf
@@ -469,7 +381,6 @@ class PatchMatchMVS:
     def _sweep(self, jobs, proc_images, poses, cam_indices) -> Dict[int, DepthNormalMap]:
         """All reference views: sharded over ranks when torch.distributed is initialised,
         batched per GPU, one progress line per view (reference :104-123)."""
-        n_cams = len(cam_indices)
         rank, world = _parallel.rank_world(self.process_group)
         mine = _parallel.shard(len(jobs), rank, world)
         eng = self._ensure_engine(proc_images, poses, cam_indices)
@@ -485,27 +396,11 @@ class PatchMatchMVS:
                 per_view = (time.time() - t1) / len(chunk)
                 for n, j in enumerate(chunk):
                     local[j] = DepthNormalMap(depth=depth[n], normal=normal[n], confidence=conf[n])
-                    ref_idx = jobs[j][0]
-                    valid = int(np.sum(conf[n] >= self.min_views))
-                    print(f"  [{cam_indices.index(ref_idx)+1}/{n_cams}] Cam {ref_idx}: "
-                          f"{valid:,} valid pixels ({per_view:.1f}s)")
+                    _print_view_progress(cam_indices, jobs[j][0], np.sum(conf[n] >= self.min_views), per_view)
         if world > 1:
             local = _parallel.allgather_maps(local, len(jobs), proc_images[cam_indices[0]]["shape"],
                                              self.process_group, DepthNormalMap, device_id=self.device_id)
         return {jobs[j][0]: local[j] for j in sorted(local)}
-
-    def _batches_in_row_order(self, jobs, mine, cap):
-        """This rank's jobs as launches: runs of consecutive jobs with one source count, at most `cap`
-        long, in row order (a launch writes its views to consecutive rows of the output tensors)."""
-        runs, cur = [], []
-        for j in mine:
-            if cur and (len(jobs[j][1]) != len(jobs[cur[-1]][1]) or j != cur[-1] + 1 or len(cur) == cap):
-                runs.append(cur)
-                cur = []
-            cur.append(j)
-        if cur:
-            runs.append(cur)
-        return runs
 
     def _plan_group_launches(self, jobs, mine, per, base, views_per_batch):
         """The launch / exchange plan of one rank in the several-rank _sweep_resident: its block of `per`
@@ -518,7 +413,7 @@ class PatchMatchMVS:
         group_rows = (per + n_groups - 1) // n_groups
         groups = [(g * group_rows, min((g + 1) * group_rows, per)) for g in range(n_groups)]
         plan, next_group = [], 0
-        for chunk in self._batches_in_row_order(jobs, mine, min(views_per_batch, group_rows)):
+        for chunk in _parallel.runs_of_one_count(jobs, mine, min(views_per_batch, group_rows)):
             lo = 0
             while lo < len(chunk):
                 row = chunk[lo] - base
@@ -549,7 +444,6 @@ class PatchMatchMVS:
         call only waits for the sweep stream while it stages its job table); the progress lines are
         printed afterwards.  The reference loops serially and has no
         exchange (:104-123)."""
-        n_cams = len(cam_indices)
         rank, world = _parallel.rank_world(self.process_group)
         mine = _parallel.shard(len(jobs), rank, world)
         eng = self._ensure_engine(proc_images, poses, cam_indices)
@@ -557,18 +451,15 @@ class PatchMatchMVS:
         hw = H * W
         dev = torch.device("cuda", self.device_id)
         n = len(jobs)
-        # (exercise_exchange: run the multi-rank code path -- row groups, second stream, collectives --
-        # on a one-rank process group as well; how the RCCL calls are rehearsed on a one-GPU box)
-        if world == 1 and not (getattr(self, "exercise_exchange", False) and torch.distributed.is_initialized()):
+        if world == 1 and not (self.exercise_exchange and torch.distributed.is_initialized()):
             depth = torch.empty((n, hw), dtype=torch.float32, device=dev)
             normal = torch.empty((n, 3 * hw), dtype=torch.float32, device=dev)
             conf = torch.empty((n, hw), dtype=torch.float32, device=dev)
             torch.cuda.synchronize(dev)
-            for chunk in self._batches_in_row_order(jobs, mine, self.views_per_batch):
+            for chunk in _parallel.runs_of_one_count(jobs, mine, self.views_per_batch):
                 t1 = time.time()
                 r0 = chunk[0]
-                refs = [self._slot[jobs[j][0]] for j in chunk]
-                srcs = [[self._slot[s] for s in jobs[j][1]] for j in chunk]
+                refs, srcs = self._job_slots(jobs, chunk)
                 eng.patchmatch_device(refs, srcs, self._pm_params(), self.seed_for_stream(),
                                       depth[r0].data_ptr(), normal[r0].data_ptr(), conf[r0].data_ptr())
                 eng.sync()
@@ -576,9 +467,7 @@ class PatchMatchMVS:
                 per_view = (time.time() - t1) / len(chunk)
                 valid = (conf[r0:r0 + len(chunk)] >= self.min_views).sum(dim=1).tolist()
                 for k, j in enumerate(chunk):
-                    ref_idx = jobs[j][0]
-                    print(f"  [{cam_indices.index(ref_idx)+1}/{n_cams}] Cam {ref_idx}: "
-                          f"{int(valid[k]):,} valid pixels ({per_view:.1f}s)")
+                    _print_view_progress(cam_indices, jobs[j][0], valid[k], per_view)
             return _ResidentMaps(ref_ids=[jobs[j][0] for j in range(n)], depth=depth, normal=normal,
                                  confidence=conf, shape=(H, W))
 
@@ -626,8 +515,7 @@ class PatchMatchMVS:
             for piece, ready in plan:
                 if piece is not None:
                     r0 = store_row(piece[0])              # (a launch never straddles a group: consecutive storage rows)
-                    refs = [self._slot[jobs[j][0]] for j in piece]
-                    srcs = [[self._slot[s] for s in jobs[j][1]] for j in piece]
+                    refs, srcs = self._job_slots(jobs, piece)
                     eng.patchmatch_device(refs, srcs, self._pm_params(), self.seed_for_stream(),
                                           depth[r0].data_ptr(), normal[r0].data_ptr(), conf[r0].data_ptr())
                 for g in ready:                           # (a rank without views still takes part in every collective)
@@ -650,9 +538,7 @@ class PatchMatchMVS:
         normal = normal[:n] if identity else normal.index_select(0, order)
         valid = (conf >= self.min_views).sum(dim=1).tolist()
         for j in mine:
-            ref_idx = jobs[j][0]
-            print(f"  [{cam_indices.index(ref_idx)+1}/{n_cams}] Cam {ref_idx}: "
-                  f"{int(valid[j]):,} valid pixels ({per_view:.1f}s)")
+            _print_view_progress(cam_indices, jobs[j][0], valid[j], per_view)
         return _ResidentMaps(ref_ids=[jobs[j][0] for j in range(n)], depth=depth, normal=normal,
                              confidence=conf, shape=(H, W))
 
@@ -668,7 +554,7 @@ class PatchMatchMVS:
     def _exchange_streams(self, torch, dev):
         """The sweep / exchange streams of the several-rank path, created once per device and reused by every
         later reconstruct of this object."""
-        cached = getattr(self, "_streams", None)
+        cached = self._streams
         if cached is None or cached[0] != dev:
             cached = (dev, torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
             self._streams = cached
@@ -680,7 +566,6 @@ class PatchMatchMVS:
         all-gather the depth / normal / cost maps -- the exchange `north_star` places between the
         propagation sweeps, feeding the next iteration's view propagation and the final geometric
         consistency.  Confidence = number of geometrically consistent source views."""
-        n_cams = len(cam_indices)
         rank, world = _parallel.rank_world(self.process_group)
         mine = _parallel.shard(len(jobs), rank, world)
         eng = self._ensure_engine(proc_images, poses, cam_indices)
@@ -696,8 +581,7 @@ class PatchMatchMVS:
         groups = {}
         for j in mine:                                     # one call has one source count
             groups.setdefault(len(jobs[j][1]), []).append(j)
-        calls = [([self._slot[jobs[j][0]] for j in js], [[self._slot[s] for s in jobs[j][1]] for j in js], js)
-                 for _, js in sorted(groups.items())]
+        calls = [(*self._job_slots(jobs, js), js) for _, js in sorted(groups.items())]
         slots_all = torch.tensor([self._slot[jobs[j][0]] for j in range(len(jobs))], dtype=torch.long, device=dev)
         slots_mine = torch.tensor([self._slot[jobs[j][0]] for j in mine], dtype=torch.long, device=dev)
         direct = world > 1 and torch.distributed.get_backend(self.process_group) == "nccl"
@@ -750,8 +634,7 @@ class PatchMatchMVS:
         per_view = (time.time() - t1) / max(len(mine), 1)
         valid = (conf >= self.min_views).sum(dim=1).tolist()
         for j in range(len(jobs)):
-            ref_idx = jobs[j][0]
-            print(f"  [{cam_indices.index(ref_idx)+1}/{n_cams}] Cam {ref_idx}: {int(valid[j]):,} valid pixels ({per_view:.1f}s)")
+            _print_view_progress(cam_indices, jobs[j][0], valid[j], per_view)
         return _ResidentMaps(ref_ids=[jobs[j][0] for j in range(len(jobs))], depth=depth[slots_all].contiguous(),
                              normal=normal[slots_all].contiguous(), confidence=conf.contiguous(), shape=(H, W))
 
@@ -764,7 +647,7 @@ class PatchMatchMVS:
             return np.array([]).reshape(0, 3), np.array([]).reshape(0, 3), 0
         K_inv = np.linalg.inv(self.K_scaled)
         torch.cuda.synchronize(maps.depth.device)
-        if getattr(self, "_resident_colors", False) and images is self._engine_images:
+        if self._resident_colors and images is self._engine_images:
             return self._engine.fuse_filter_views([self._slot[i] for i in maps.ref_ids], maps.depth.data_ptr(),
                                                   maps.confidence.data_ptr(), K_inv,
                                                   [(poses[i].R, poses[i].t) for i in maps.ref_ids], self.min_views,

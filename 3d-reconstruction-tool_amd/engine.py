@@ -23,6 +23,44 @@ def _ids(a):
     return a, a.ctypes.data_as(i32p)
 
 
+# Pointers into arrays: the array stays referenced by the caller (a local, or the tuple `keep` a helper returns)
+# until the C call has returned.
+def _u8(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def _f64(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _r32(a, *shape):
+    """float64 values rounded to a contiguous float32 array of `shape`."""
+    return _f32(np.asarray(a, np.float64).astype(np.float32).reshape(shape))
+
+
+def _pose32(R, t):
+    return _r32(R, 3, 3), _r32(t, 3)
+
+
+def _poses64(poses):
+    """(n, 12) float64: R (row-major) | t of every (R, t)."""
+    return np.ascontiguousarray(np.stack([np.concatenate([np.asarray(R, np.float64).reshape(9),
+                                                          np.asarray(t, np.float64).reshape(3)]) for R, t in poses]))
+
+
+def _kinv64(K_inv64):
+    return np.ascontiguousarray(K_inv64, dtype=np.float64).reshape(9)
+
+
+def _job_ids(ref_ids, src_ids):
+    """(n jobs, reference id pointer, source id pointer, sources per job, keep) of n reference views and their
+    (n, S) source views; keep holds the two int32 arrays the pointers point into."""
+    ref, refp = _ids(ref_ids)
+    src, srcp = _ids(src_ids)
+    n = ref.shape[0]
+    return n, refp, srcp, src.reshape(n, -1).shape[1], (ref, src)
+
+
 def make_pm_params(patch_size, num_iterations, num_samples, depth_min, depth_max, tile_rows=0,
                    views_per_launch=0, mode="default", schedule="auto", first_iteration=0, confidence=True):
     """amvs_pm_params with the log-range formed in double as mvs_patchmatch.py:268-271 does.
@@ -190,8 +228,7 @@ class Engine:
     # -- scene -------------------------------------------------------------
     def set_view(self, view, gray, R, t):
         gray = _f32(gray, (self.H, self.W))
-        R = _f32(np.asarray(R, np.float64).astype(np.float32).reshape(3, 3))
-        t = _f32(np.asarray(t, np.float64).astype(np.float32).reshape(3))
+        R, t = _pose32(R, t)
         self._chk(self._lib.amvs_set_view(self._h, int(view), _p(gray), _p(R), _p(t)))
 
     def set_view_bgr8(self, view, image_bgr_u8, R, t, want_color=True):
@@ -201,12 +238,10 @@ class Engine:
         img = np.ascontiguousarray(image_bgr_u8, dtype=np.uint8)
         if img.ndim != 3 or img.shape[2] != 3:
             raise ValueError("expected an (h, w, 3) uint8 BGR image")
-        R = _f32(np.asarray(R, np.float64).astype(np.float32).reshape(3, 3))
-        t = _f32(np.asarray(t, np.float64).astype(np.float32).reshape(3))
+        R, t = _pose32(R, t)
         out = np.empty((self.H, self.W, 3), np.uint8) if want_color else None
         self._chk(self._lib.amvs_set_view_bgr8(
-            self._h, int(view), img.ctypes.data_as(C.POINTER(C.c_uint8)), img.shape[0], img.shape[1], _p(R), _p(t),
-            out.ctypes.data_as(C.POINTER(C.c_uint8)) if want_color else None))
+            self._h, int(view), _u8(img), img.shape[0], img.shape[1], _p(R), _p(t), _u8(out) if want_color else None))
         return out
 
     def set_view_colors(self, view, image_bgr_u8):
@@ -215,33 +250,26 @@ class Engine:
         img = np.ascontiguousarray(image_bgr_u8, dtype=np.uint8)
         if img.shape != (self.H, self.W, 3):
             raise ValueError(f"expected a ({self.H}, {self.W}, 3) uint8 BGR image")
-        self._chk(self._lib.amvs_set_view_colors(self._h, int(view), img.ctypes.data_as(C.POINTER(C.c_uint8))))
+        self._chk(self._lib.amvs_set_view_colors(self._h, int(view), _u8(img)))
 
     def set_view_device(self, view, gray_ptr, R, t):
-        R = _f32(np.asarray(R, np.float64).astype(np.float32).reshape(3, 3))
-        t = _f32(np.asarray(t, np.float64).astype(np.float32).reshape(3))
+        R, t = _pose32(R, t)
         self._chk(self._lib.amvs_set_view_device(self._h, int(view), C.c_void_p(gray_ptr), _p(R), _p(t)))
 
     # -- PatchMatch --------------------------------------------------------
     def patchmatch(self, ref_ids, src_ids, params, seed):
         """Returns depth (n,H,W), normal (n,H,W,3), confidence (n,H,W) as numpy arrays."""
-        ref, refp = _ids(ref_ids)
-        src, srcp = _ids(src_ids)
-        n = ref.shape[0]
-        src = src.reshape(n, -1)
+        n, refp, srcp, n_src, keep = _job_ids(ref_ids, src_ids)
         depth = np.empty((n, self.H, self.W), np.float32)
         normal = np.empty((n, self.H, self.W, 3), np.float32)
         conf = np.empty((n, self.H, self.W), np.float32)
-        self._chk(self._lib.amvs_patchmatch(self._h, n, refp, srcp, src.shape[1], C.byref(params),
+        self._chk(self._lib.amvs_patchmatch(self._h, n, refp, srcp, n_src, C.byref(params),
                                             int(seed), _p(depth), _p(normal), _p(conf)))
         return depth, normal, conf
 
     def patchmatch_device(self, ref_ids, src_ids, params, seed, depth_ptr, normal_ptr, conf_ptr):
-        ref, refp = _ids(ref_ids)
-        src, srcp = _ids(src_ids)
-        n = ref.shape[0]
-        src = src.reshape(n, -1)
-        self._chk(self._lib.amvs_patchmatch_device(self._h, n, refp, srcp, src.shape[1], C.byref(params),
+        n, refp, srcp, n_src, keep = _job_ids(ref_ids, src_ids)
+        self._chk(self._lib.amvs_patchmatch_device(self._h, n, refp, srcp, n_src, C.byref(params),
                                                    int(seed), C.c_void_p(depth_ptr),
                                                    C.c_void_p(normal_ptr), C.c_void_p(conf_ptr)))
 
@@ -264,7 +292,7 @@ class Engine:
     # -- plane sweep -------------------------------------------------------
     def plane_sweep(self, ref, nbr_ids, depths, patch_size, thresh):
         nbr, nbrp = _ids(nbr_ids)
-        depths = _f32(np.asarray(depths, np.float64).astype(np.float32))
+        depths = _r32(depths, -1)
         d = np.empty((self.H, self.W), np.float32)
         conf = np.empty((self.H, self.W), np.float32)
         self._chk(self._lib.amvs_plane_sweep(self._h, int(ref), nbrp, nbr.size, _p(depths), depths.size,
@@ -272,24 +300,18 @@ class Engine:
         return d, conf
 
     def plane_sweep_device(self, ref_ids, nbr_ids, depths, patch_size, thresh, depth_ptr, conf_ptr):
-        ref, refp = _ids(ref_ids)
-        nbr, nbrp = _ids(nbr_ids)
-        n = ref.shape[0]
-        nbr = nbr.reshape(n, -1)
-        depths = _f32(np.asarray(depths, np.float64).astype(np.float32))
-        self._chk(self._lib.amvs_plane_sweep_device(self._h, n, refp, nbrp, nbr.shape[1], _p(depths),
+        n, refp, nbrp, n_nbr, keep = _job_ids(ref_ids, nbr_ids)
+        depths = _r32(depths, -1)
+        self._chk(self._lib.amvs_plane_sweep_device(self._h, n, refp, nbrp, n_nbr, _p(depths),
                                                     depths.size, int(patch_size), float(thresh),
                                                     C.c_void_p(depth_ptr), C.c_void_p(conf_ptr)))
 
     def plane_sweep_batch(self, ref_ids, nbr_ids, depths, patch_size, thresh):
         """All reference views in one launch; the maps stay in the context (fetch_sweep_maps,
         stereo_backproject(resident=True))."""
-        ref, refp = _ids(ref_ids)
-        nbr, nbrp = _ids(nbr_ids)
-        n = ref.shape[0]
-        nbr = nbr.reshape(n, -1)
-        depths = _f32(np.asarray(depths, np.float64).astype(np.float32))
-        self._chk(self._lib.amvs_plane_sweep_batch(self._h, n, refp, nbrp, nbr.shape[1], _p(depths), depths.size,
+        n, refp, nbrp, n_nbr, keep = _job_ids(ref_ids, nbr_ids)
+        depths = _r32(depths, -1)
+        self._chk(self._lib.amvs_plane_sweep_batch(self._h, n, refp, nbrp, n_nbr, _p(depths), depths.size,
                                                    int(patch_size), float(thresh)))
         return n
 
@@ -301,11 +323,8 @@ class Engine:
 
     # -- extended mode ----------------------------------------------------------
     def _xpm_call(self, fn, ref_ids, src_ids, params, extra, ptrs):
-        ref, refp = _ids(ref_ids)
-        src, srcp = _ids(src_ids)
-        n = ref.shape[0]
-        src = src.reshape(n, -1)
-        self._chk(fn(self._h, n, refp, srcp, src.shape[1], C.byref(params), *extra, *[C.c_void_p(p) for p in ptrs]))
+        n, refp, srcp, n_src, keep = _job_ids(ref_ids, src_ids)
+        self._chk(fn(self._h, n, refp, srcp, n_src, C.byref(params), *extra, *[C.c_void_p(p) for p in ptrs]))
 
     def xpm_init(self, ref_ids, src_ids, params, seed, depth_ptr, normal_ptr, cost_ptr):
         self._xpm_call(self._lib.amvs_xpm_init, ref_ids, src_ids, params, (int(seed),), (depth_ptr, normal_ptr, cost_ptr))
@@ -324,14 +343,9 @@ class Engine:
                  snapshot_depth_ptr=0, snapshot_normal_ptr=0, cost_out_ptr=0):
         """One phase of an iteration ("candidates", "red", "black") or the test hook "eval" (cost of the
         current planes into cost_out_ptr)."""
-        ref, refp = _ids(ref_ids)
-        src, srcp = _ids(src_ids)
-        n = ref.shape[0]
-        src = src.reshape(n, -1)
-        self._chk(self._lib.amvs_xpm_step(self._h, n, refp, srcp, src.shape[1], C.byref(params), int(iteration), int(seed),
-                                          self.XPM_PHASES[phase], C.c_void_p(depth_ptr), C.c_void_p(normal_ptr),
-                                          C.c_void_p(cost_ptr), C.c_void_p(snapshot_depth_ptr or None),
-                                          C.c_void_p(snapshot_normal_ptr or None), C.c_void_p(cost_out_ptr or None)))
+        self._xpm_call(self._lib.amvs_xpm_step, ref_ids, src_ids, params, (int(iteration), int(seed), self.XPM_PHASES[phase]),
+                       (depth_ptr, normal_ptr, cost_ptr, snapshot_depth_ptr or None, snapshot_normal_ptr or None,
+                        cost_out_ptr or None))
 
     def xpm_fetch_candidates(self, n_ref):
         d = np.empty((n_ref, self.H, self.W), np.float32)
@@ -353,10 +367,8 @@ class Engine:
         cols = np.ascontiguousarray(colors_bgr, dtype=np.uint8)
         n = cols.shape[0]
         cols = cols.reshape(n, self.H, self.W, 3)
-        kinv = np.ascontiguousarray(K_inv64, dtype=np.float64).reshape(9)
-        pp = np.ascontiguousarray(np.stack([np.concatenate([np.asarray(R, np.float64).reshape(9),
-                                                            np.asarray(t, np.float64).reshape(3)])
-                                            for R, t in poses]))
+        kinv = _kinv64(K_inv64)
+        pp = _poses64(poses)
         if device_ptrs is not None:
             dptr, cptr, where = C.c_void_p(device_ptrs[0]), C.c_void_p(device_ptrs[1]), 1
         elif depth is None:
@@ -367,9 +379,7 @@ class Engine:
         per = (C.c_int64 * n)()
         total = C.c_int64(0)
         self._chk(self._lib.amvs_stereo_backproject(
-            self._h, n, dptr, cptr, where, cols.ctypes.data_as(C.POINTER(C.c_uint8)),
-            kinv.ctypes.data_as(C.POINTER(C.c_double)), pp.ctypes.data_as(C.POINTER(C.c_double)),
-            float(min_confidence), per, C.byref(total)))
+            self._h, n, dptr, cptr, where, _u8(cols), _f64(kinv), _f64(pp), float(min_confidence), per, C.byref(total)))
         counts = [int(x) for x in per]
         if not fetch:
             return counts, int(total.value)
@@ -379,25 +389,21 @@ class Engine:
         pts = np.empty((m, 3), np.float64)
         rgb = np.empty((m, 3), np.uint8)
         if m:
-            self._chk(self._lib.amvs_fetch_cloud(self._h, pts.ctypes.data_as(C.POINTER(C.c_double)),
-                                                 rgb.ctypes.data_as(C.POINTER(C.c_uint8))))
+            self._chk(self._lib.amvs_fetch_cloud(self._h, _f64(pts), _u8(rgb)))
         return pts, rgb
 
     def cloud_knn_mean_distance(self, n_points, k=20):
         out = np.empty(int(n_points), np.float64)
-        self._chk(self._lib.amvs_cloud_knn_mean_distance(self._h, int(k), out.ctypes.data_as(C.POINTER(C.c_double))))
+        self._chk(self._lib.amvs_cloud_knn_mean_distance(self._h, int(k), _f64(out)))
         return out
 
     def cloud_voxel_downsample(self, voxel_size, keep_mask=None):
         """dense_stereo.py:475-492 on the resident cloud (after the optional boolean keep mask);
         returns the new point count."""
         cnt = C.c_int64(0)
-        if keep_mask is None:
-            mp = None
-        else:
-            km = np.ascontiguousarray(keep_mask, dtype=np.uint8)
-            mp = km.ctypes.data_as(C.POINTER(C.c_uint8))
-        self._chk(self._lib.amvs_cloud_voxel_downsample(self._h, mp, float(voxel_size), C.byref(cnt)))
+        km = None if keep_mask is None else np.ascontiguousarray(keep_mask, dtype=np.uint8)
+        self._chk(self._lib.amvs_cloud_voxel_downsample(self._h, None if km is None else _u8(km), float(voxel_size),
+                                                        C.byref(cnt)))
         return int(cnt.value)
 
     def cloud_take(self, indices):
@@ -425,7 +431,7 @@ class Engine:
         out = np.empty((src.size, self.H, self.W), np.float32)
         bits = np.empty((self.H, self.W), np.uint8)
         self._chk(self._lib.amvs_sample_sources(self._h, int(ref), srcp, src.size, int(patch_size), int(bounds),
-                                                _p(depth), _p(out), bits.ctypes.data_as(C.POINTER(C.c_uint8))))
+                                                _p(depth), _p(out), _u8(bits)))
         valid = np.stack([(bits >> s) & 1 for s in range(src.size)]).astype(bool)
         return out, valid
 
@@ -489,22 +495,12 @@ class Engine:
             dptr, cptr, n = C.c_void_p(device_ptrs[0]), C.c_void_p(device_ptrs[1]), int(device_ptrs[2])
             on_dev = 1
         cols = np.ascontiguousarray(colors_bgr, dtype=np.uint8).reshape(n, self.H, self.W, 3)
-        kinv = np.ascontiguousarray(K_inv64, dtype=np.float64).reshape(9)
-        pp = np.ascontiguousarray(np.stack([np.concatenate([np.asarray(R, np.float64).reshape(9),
-                                                            np.asarray(t, np.float64).reshape(3)])
-                                            for R, t in poses]))
+        kinv = _kinv64(K_inv64)
+        pp = _poses64(poses)
         counts = (C.c_int64 * 2)()
-        self._chk(self._lib.amvs_fuse_filter(
-            self._h, n, dptr, cptr, on_dev,
-            cols.ctypes.data_as(C.POINTER(C.c_uint8)), kinv.ctypes.data_as(C.POINTER(C.c_double)),
-            pp.ctypes.data_as(C.POINTER(C.c_double)), float(min_views), int(bool(do_filter)), counts))
-        m = int(counts[1])
-        pts = np.empty((m, 3), np.float64)
-        rgb = np.empty((m, 3), np.uint8)
-        if m:
-            self._chk(self._lib.amvs_fetch_cloud(self._h, pts.ctypes.data_as(C.POINTER(C.c_double)),
-                                                 rgb.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return pts, rgb, int(counts[0])
+        self._chk(self._lib.amvs_fuse_filter(self._h, n, dptr, cptr, on_dev, _u8(cols), _f64(kinv), _f64(pp),
+                                             float(min_views), int(bool(do_filter)), counts))
+        return self.fetch_cloud(int(counts[1])) + (int(counts[0]),)
 
     def stereo_backproject_views(self, view_ids, K_inv64, poses, min_confidence):
         """stereo_backproject for the resident maps of the last plane_sweep_batch with the colour images
@@ -512,15 +508,12 @@ class Engine:
         counts, total); the cloud stays on the device."""
         ids, idp = _ids(view_ids)
         n = ids.shape[0]
-        kinv = np.ascontiguousarray(K_inv64, dtype=np.float64).reshape(9)
-        pp = np.ascontiguousarray(np.stack([np.concatenate([np.asarray(R, np.float64).reshape(9),
-                                                            np.asarray(t, np.float64).reshape(3)])
-                                            for R, t in poses]))
+        kinv = _kinv64(K_inv64)
+        pp = _poses64(poses)
         per = (C.c_int64 * n)()
         total = C.c_int64(0)
         self._chk(self._lib.amvs_stereo_backproject_views(
-            self._h, n, idp, kinv.ctypes.data_as(C.POINTER(C.c_double)), pp.ctypes.data_as(C.POINTER(C.c_double)),
-            float(min_confidence), per, C.byref(total)))
+            self._h, n, idp, _f64(kinv), _f64(pp), float(min_confidence), per, C.byref(total)))
         return [int(x) for x in per], int(total.value)
 
     def fuse_filter_views(self, view_ids, depth_ptr, conf_ptr, K_inv64, poses, min_views, do_filter=True):
@@ -528,21 +521,13 @@ class Engine:
         (set_view_bgr8): map j belongs to view view_ids[j].  Returns (points, colors RGB, raw_count)."""
         ids, idp = _ids(view_ids)
         n = ids.shape[0]
-        kinv = np.ascontiguousarray(K_inv64, dtype=np.float64).reshape(9)
-        pp = np.ascontiguousarray(np.stack([np.concatenate([np.asarray(R, np.float64).reshape(9),
-                                                            np.asarray(t, np.float64).reshape(3)])
-                                            for R, t in poses]))
+        kinv = _kinv64(K_inv64)
+        pp = _poses64(poses)
         counts = (C.c_int64 * 2)()
         self._chk(self._lib.amvs_fuse_filter_views(
-            self._h, n, idp, C.c_void_p(depth_ptr), C.c_void_p(conf_ptr), kinv.ctypes.data_as(C.POINTER(C.c_double)),
-            pp.ctypes.data_as(C.POINTER(C.c_double)), float(min_views), int(bool(do_filter)), counts))
-        m = int(counts[1])
-        pts = np.empty((m, 3), np.float64)
-        rgb = np.empty((m, 3), np.uint8)
-        if m:
-            self._chk(self._lib.amvs_fetch_cloud(self._h, pts.ctypes.data_as(C.POINTER(C.c_double)),
-                                                 rgb.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return pts, rgb, int(counts[0])
+            self._h, n, idp, C.c_void_p(depth_ptr), C.c_void_p(conf_ptr), _f64(kinv), _f64(pp), float(min_views),
+            int(bool(do_filter)), counts))
+        return self.fetch_cloud(int(counts[1])) + (int(counts[0]),)
 
     # -- surface mesh (TSDF fusion + marching tetrahedra) -------------------
     def tsdf_integrate(self, K, poses, min_views, origin, voxel, dims, trunc, depth=None, conf=None, device_ptrs=None,
@@ -570,11 +555,10 @@ class Engine:
                 raise ValueError(f"{ids.shape[0]} view ids for {n} maps")
         if colors_bgr is not None:
             cols = np.ascontiguousarray(colors_bgr, dtype=np.uint8).reshape(n, self.H, self.W, 3)
-            colp = cols.ctypes.data_as(C.POINTER(C.c_uint8))
-        Kf = _f32(np.asarray(K, np.float64).astype(np.float32).reshape(9))
-        pp = _f32(np.stack([np.concatenate([np.asarray(R, np.float64).reshape(9), np.asarray(t, np.float64).reshape(3)])
-                            for R, t in poses]).astype(np.float32))
-        org = _f32(np.asarray(origin, np.float64).astype(np.float32).reshape(3))
+            colp = _u8(cols)
+        Kf = _r32(K, 9)
+        pp = _r32(_poses64(poses), n, 12)
+        org = _r32(origin, 3)
         dims = [int(d) for d in np.asarray(dims).reshape(3)]
         if any(d < 2 or d > 2 ** 31 - 1 for d in dims):
             raise ValueError(f"TSDF dims {dims}: every dimension must be in [2, 2^31)")
@@ -590,12 +574,7 @@ class Engine:
         nv, nf = C.c_int64(0), C.c_int64(0)
         self._chk(self._lib.amvs_tsdf_extract(self._h, C.byref(nv), C.byref(nf)))
         self._mesh_counts = (nv.value, nf.value)
-        verts = np.empty((nv.value, 3), np.float32)
-        faces = np.empty((nf.value, 3), np.int32)
-        rgb = np.empty((nv.value, 3), np.uint8)
-        self._chk(self._lib.amvs_fetch_mesh(self._h, _p(verts), faces.ctypes.data_as(i32p),
-                                            rgb.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return verts, faces, rgb
+        return self.mesh_fetch()
 
     def tsdf_mesh(self, K, poses, min_views, origin, voxel, dims, trunc, **maps_and_colors):
         """tsdf_integrate(...) then tsdf_extract(): (vertices, faces, colors)."""
@@ -625,7 +604,7 @@ class Engine:
         color = _f32(color_sum)
         if weight.shape != tsdf.shape or color.shape != tsdf.shape + (3,):
             raise ValueError(f"weight must be {tsdf.shape} and color_sum {tsdf.shape + (3,)}")
-        org = _f32(np.asarray(origin, np.float64).astype(np.float32).reshape(3))
+        org = _r32(origin, 3)
         dm, dmp = _ids([nx, ny, nz])
         self._chk(self._lib.amvs_tsdf_set_volume(self._h, _p(tsdf), _p(weight), _p(color), _p(org),
                                                  float(np.float32(voxel)), dmp))
@@ -644,7 +623,7 @@ class Engine:
             if len(cols) != len(verts):
                 raise ValueError(f"colors must be ({len(verts)}, 3)")
         self._chk(self._lib.amvs_mesh_set(self._h, _p(verts), len(verts), tris.ctypes.data_as(i32p), len(tris),
-                                          None if cols is None else cols.ctypes.data_as(C.POINTER(C.c_uint8))))
+                                          None if cols is None else _u8(cols)))
         self._mesh_counts = (len(verts), len(tris))
 
     def mesh_filter_components(self, min_faces=0, keep_largest=False):
@@ -667,7 +646,7 @@ class Engine:
     def mesh_decimate(self, origin, cell):
         """Vertex clustering of the current mesh on the grid of cubic cells of side `cell` with a corner at `origin`
         (include/amvs.h amvs_mesh_decimate).  Returns (vertices, faces) after it; drops labels and normals."""
-        org = _f32(np.asarray(origin, np.float64).astype(np.float32).reshape(3))
+        org = _r32(origin, 3)
         nv, nf = C.c_int64(0), C.c_int64(0)
         self._chk(self._lib.amvs_mesh_decimate(self._h, _p(org), float(np.float32(cell)), C.byref(nv), C.byref(nf)))
         self._mesh_counts = (nv.value, nf.value)
@@ -677,7 +656,7 @@ class Engine:
         """mesh_decimate with every cluster's vertex placed by its members' plane quadrics instead of at their mean
         (include/amvs.h amvs_mesh_decimate_quadric); faces, colours and counts are mesh_decimate's.  Returns (vertices,
         faces, clusters that kept the mean); drops labels and normals."""
-        org = _f32(np.asarray(origin, np.float64).astype(np.float32).reshape(3))
+        org = _r32(origin, 3)
         nv, nf, nk = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         self._chk(self._lib.amvs_mesh_decimate_quadric(self._h, _p(org), float(np.float32(cell)), float(np.float32(regularisation)),
                                                        C.byref(nv), C.byref(nf), C.byref(nk)))
@@ -694,8 +673,7 @@ class Engine:
         verts = np.empty((nv, 3), np.float32)
         faces = np.empty((nf, 3), np.int32)
         rgb = np.empty((nv, 3), np.uint8)
-        self._chk(self._lib.amvs_fetch_mesh(self._h, _p(verts), faces.ctypes.data_as(i32p),
-                                            rgb.ctypes.data_as(C.POINTER(C.c_uint8))))
+        self._chk(self._lib.amvs_fetch_mesh(self._h, _p(verts), faces.ctypes.data_as(i32p), _u8(rgb)))
         out = [verts, faces, rgb]
         nrm = np.empty((nv, 3), np.float32) if normals else None
         lab = np.empty(nv, np.int32) if labels else None
@@ -710,8 +688,7 @@ class Engine:
         np.mean(NearestNeighbors(n_neighbors=k).fit(p).kneighbors(p)[0][:, 1:], axis=1)."""
         pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
         out = np.empty(pts.shape[0], np.float64)
-        self._chk(self._lib.amvs_knn_mean_distance(self._h, pts.ctypes.data_as(C.POINTER(C.c_double)),
-                                                   pts.shape[0], int(k), out.ctypes.data_as(C.POINTER(C.c_double))))
+        self._chk(self._lib.amvs_knn_mean_distance(self._h, _f64(pts), pts.shape[0], int(k), _f64(out)))
         return out
 
     def selftest_lean_math(self):

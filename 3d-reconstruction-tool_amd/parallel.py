@@ -24,6 +24,15 @@ def _dist():
     return dist if dist.is_available() and dist.is_initialized() else None
 
 
+def _torch_cuda():
+    """torch with a usable HIP device, or None (then maps travel through host arrays)."""
+    try:
+        import torch
+    except Exception:  # noqa: BLE001
+        return None
+    return torch if torch.cuda.is_available() else None
+
+
 def rank_world(group=None):
     dist = _dist()
     if dist is None:
@@ -39,6 +48,21 @@ def shard(n_items: int, rank: int, world: int):
 
 def shard_sizes(n_items: int, world: int):
     return [len(shard(n_items, r, world)) for r in range(world)]
+
+
+def runs_of_one_count(jobs, mine, cap=None):
+    """The jobs `mine` (ascending indices into jobs = [(ref, sources)]) as launches: runs of consecutive jobs
+    with one source count, at most `cap` long (None: any length), in row order (a launch writes its views to
+    consecutive rows of the output tensors)."""
+    runs, cur = [], []
+    for j in mine:
+        if cur and (len(jobs[j][1]) != len(jobs[cur[-1]][1]) or j != cur[-1] + 1 or len(cur) == cap):
+            runs.append(cur)
+            cur = []
+        cur.append(j)
+    if cur:
+        runs.append(cur)
+    return runs
 
 
 def allgather_packed(local, n_items: int, width: int, group=None, device=None):

@@ -301,6 +301,89 @@ def test_engine_cache_follows_the_poses(monkeypatch, scene_a):
     assert len(uploads) == 3 * scene_a.n
 
 
+class _UploadFake:
+    """Engine stand-in for the upload paths of the resident-view cache: records every upload in `log` (shared by all
+    instances made by one _upload_fake class) and raises in set_view_bgr8 when `fail_at` names the running count."""
+
+    def __init__(self, H, W, n, K, device=0, mode="exact"):
+        self.H, self.W, self.n, self.K, self.device, self._mode, self.open = H, W, n, np.asarray(K, np.float32), device, mode, True
+
+    def reusable_for(self, H, W, n_views, K, device, mode="exact"):
+        return (self.open and (self.H, self.W, self.n, self.device) == (H, W, n_views, device)
+                and np.array_equal(self.K, np.asarray(K, np.float32)) and self._mode == mode)
+
+    def mode(self):
+        return self._mode
+
+    def set_view_bgr8(self, slot, img, R, t, want_color=True):
+        if len(self.log) == self.fail_at[0]:
+            raise RuntimeError("upload failed")
+        self.log.append(("bgr8", self, slot, tuple(img.shape[:2])))
+        return np.zeros((self.H, self.W, 3), np.uint8) if want_color else None
+
+    def set_view(self, slot, gray, R, t):
+        self.log.append(("gray", self, slot, None))
+
+    def close(self):
+        self.open = False
+
+
+def _upload_fake():
+    return type("UploadFake", (_UploadFake,), {"log": [], "fail_at": [None]})
+
+
+def _cache_owners(scene):
+    import amvs
+    cam = amvs.Camera(K=scene.K.copy(), dist=np.zeros(5))
+    return (("patchmatch", lambda: amvs.PatchMatchMVS(cam, scale=1.0, patch_size=7, device=0)),
+            ("stereo", lambda: amvs.DenseStereoReconstructor(cam, scale=1.0, device=0)))
+
+
+def test_a_failed_re_upload_leaves_nothing_stale(monkeypatch, scene_a, capsys):
+    """ADVICE (low, mvs_patchmatch.py:231 / dense_stereo.py:272): _prepare_images_device re-uploads into the live
+    engine view by view.  When an upload raises part-way, the cache must not go on describing the previous scene: the
+    key and the prepared dict are cleared before the first upload, so _ensure_engine with the first scene's dict
+    uploads all its views again instead of returning the context that holds a mix of the two scenes."""
+    from amvs import engine as engine_mod
+    poses = {i: scene_a.poses()[i] for i in range(4)}
+    first = [{"image": np.full((8, 8, 3), 10 + i, np.uint8)} for i in range(4)]
+    second = [{"image": np.full((8, 8, 3), 90 + i, np.uint8)} for i in range(4)]
+    for name, make in _cache_owners(scene_a):
+        fake = _upload_fake()
+        monkeypatch.setattr(engine_mod, "Engine", fake)
+        obj = make()
+        prepared = obj._prepare_images_device(first, [0, 1, 2, 3], poses)
+        assert [u[2] for u in fake.log] == [0, 1, 2, 3] and obj._engine_images is prepared and obj._engine_key is not None
+        half_written = obj._engine
+        fake.fail_at[0] = len(fake.log) + 2                    # the second scene's third view
+        with pytest.raises(RuntimeError, match="upload failed"):
+            obj._prepare_images_device(second, [0, 1, 2, 3], poses)
+        assert len(fake.log) == 6 and fake.log[-1][1] is half_written, name      # two views of it were overwritten
+        assert obj._engine_key is None and obj._engine_images is None, name
+        fake.fail_at[0] = None
+        eng = obj._ensure_engine(prepared, poses, [0, 1, 2, 3]) if name == "patchmatch" else obj._ensure_engine(prepared, poses)
+        assert [(u[0], u[2]) for u in fake.log[6:]] == [("gray", s) for s in range(4)], name
+        assert eng is not half_written and all(u[1] is eng for u in fake.log[6:]), name
+        assert obj._engine is eng and obj._engine_images is prepared and obj._slot == {i: i for i in range(4)}
+    capsys.readouterr()
+
+
+def test_stereo_rejects_a_view_of_another_size(monkeypatch, scene_a, capsys):
+    """DenseStereoReconstructor._prepare_images_device checks what PatchMatchMVS's always did: a view of another size
+    raises before it is uploaded (amvs_set_view_bgr8 would rescale it to H x W under the wrong intrinsics)."""
+    from amvs import engine as engine_mod
+    images = [{"image": np.zeros((8, 8, 3), np.uint8)}, {"image": np.zeros((8, 10, 3), np.uint8)}]
+    for name, make in _cache_owners(scene_a):
+        fake = _upload_fake()
+        monkeypatch.setattr(engine_mod, "Engine", fake)
+        obj = make()
+        with pytest.raises(ValueError, match="share one size"):
+            obj._prepare_images_device(images, [0, 1], scene_a.poses())
+        assert [u[3] for u in fake.log] == [(8, 8)], name      # the odd view never reached the engine
+        assert obj._engine_key is None and obj._engine_images is None, name
+    capsys.readouterr()
+
+
 def test_group_launch_plan_is_consistent_across_ranks():
     """PatchMatchMVS._plan_group_launches (the several-rank _sweep_resident): for many scene sizes, world
     sizes, batch caps and source-count patterns every rank issues the same sequence of group gathers, each
@@ -309,7 +392,24 @@ def test_group_launch_plan_is_consistent_across_ranks():
     the cap.  (The RCCL collectives of the ranks must match one for one -- this is the part of the
     multi-GPU path that no one-GPU box can execute with real peers.)"""
     import amvs
-    from amvs.parallel import shard
+    from amvs.parallel import runs_of_one_count, shard
+    # the run-splitting both classes share: consecutive jobs of one source count, optionally capped
+    jobs = [(j, list(range(c))) for j, c in enumerate([4, 4, 3, 3, 4])]
+    assert runs_of_one_count(jobs, range(5)) == [[0, 1], [2, 3], [4]]
+    assert runs_of_one_count(jobs, range(5), 1) == [[0], [1], [2], [3], [4]]
+    assert runs_of_one_count(jobs, range(5), 2) == [[0, 1], [2, 3], [4]]
+    assert runs_of_one_count(jobs, [0, 1, 4]) == [[0, 1], [4]]               # a gap in `mine`, same source count
+    assert runs_of_one_count(jobs, [0, 2, 3]) == [[0], [2, 3]] and runs_of_one_count(jobs, []) == []
+    many = [(j, list(range(c))) for j, c in enumerate([4] * 5 + [3] * 3 + [4, 2, 2])]
+    for mine in (list(range(11)), [0, 1, 2, 4, 5, 6, 7, 9, 10], [3, 4, 5, 6], [10]):
+        for cap in (1, 2, None):
+            runs = runs_of_one_count(many, mine, cap)
+            assert sum(runs, []) == mine, "every job of `mine` exactly once, in order"
+            for run in runs:
+                assert run == list(range(run[0], run[0] + len(run))) and len({len(many[j][1]) for j in run}) == 1
+                assert cap is None or len(run) <= cap
+            for a, b in zip(runs, runs[1:]):                   # no run ends where it could have gone on
+                assert (len(a) == cap or b[0] != a[-1] + 1 or len(many[b[0]][1]) != len(many[a[-1]][1])), (mine, cap, runs)
     pm = amvs.PatchMatchMVS.__new__(amvs.PatchMatchMVS)
     rng = np.random.default_rng(0)
     for n in (1, 2, 3, 4, 5, 7, 8, 16, 17, 32, 33, 64):
