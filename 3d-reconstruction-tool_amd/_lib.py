@@ -134,6 +134,12 @@ SIGNATURES = {
     "amvs_mesh_decimate_quadric": (C.c_int, [C.c_void_p, f32p, C.c_float, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                              C.POINTER(C.c_int64)]),
     "amvs_fetch_mesh_attributes": (C.c_int, [C.c_void_p, f32p, i32p]),
+    "amvs_mesh_render": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p, C.c_float, C.POINTER(C.c_int64)]),
+    "amvs_fetch_render": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, i32p]),
+    "amvs_mesh_visibility": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_int64)]),
+    "amvs_fetch_mesh_visibility": (C.c_int, [C.c_void_p, i32p]),
+    "amvs_mesh_filter_visible": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "amvs_set_render_tuning": (C.c_int, [C.c_void_p, C.c_int]),
     "amvs_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "amvs_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "amvs_allgather_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),

@@ -104,6 +104,7 @@ class PatchMatchMVS(ResidentViews):
         self.K_scaled[:2] *= scale
         self.last_timing = None
         self.last_mesh_grid = None       # (origin, voxel, dims, trunc) of the last reconstruct_mesh
+        self.last_mesh_views = None      # ... and the views it fused, in map order
         # run the multi-rank code path -- row groups, second stream, collectives -- on a one-rank process group
         # as well; how the RCCL calls are rehearsed on a one-GPU box
         self.exercise_exchange = False
@@ -121,7 +122,8 @@ class PatchMatchMVS(ResidentViews):
                          smooth_iterations: int = 0, smooth_lambda: float = 0.5, smooth_mu: float = -0.53,
                          fix_boundary: bool = True, with_normals: bool = False,
                          decimate_voxels: float = 0.0, decimate_placement: str = "mean",
-                         decimate_regularisation: float = 1e-3) -> Tuple[np.ndarray, ...]:
+                         decimate_regularisation: float = 1e-3, min_visible_views: int = 0,
+                         visibility_tolerance_voxels: float = 1.0) -> Tuple[np.ndarray, ...]:
         """Surface mesh of the scene: reconstruct()'s preparation, sweep and fusion, then the per-view depth maps
         fused into a truncated signed distance volume and its zero level set extracted by marching tetrahedra on
         the GPU (csrc/amvs_mesh.hip; no reference counterpart).  Returns (vertices (V,3) float32, faces (F,3) int32,
@@ -132,6 +134,11 @@ class PatchMatchMVS(ResidentViews):
         trunc_voxels * voxel_size.  The volume holds at most AMVS_TSDF_MAX_POINTS grid points (include/amvs.h).
 
         Clean-up on the device (csrc/amvs_mesh_clean.hip), in this order and each only when asked for:
+        min_visible_views > 0 renders the mesh into the views that were fused (csrc/amvs_mesh_render.hip; near plane one
+        voxel), counts for every vertex the views that see it -- in the image and not behind the rendered surface by
+        more than float32(visibility_tolerance_voxels) * float32(voxel_size) -- and keeps the faces whose three vertices
+        each reach min_visible_views: the inner sheets and back sides behind the observed surface go, and what that
+        detaches is left to the component filter that follows;
         min_component_faces > 0 drops the connected components with fewer faces and keep_largest all but the one with
         the most; smooth_iterations > 0 runs that many Taubin lambda | mu iterations (smooth_lambda, smooth_mu;
         fix_boundary keeps the vertices on open edges where they are); decimate_voxels > 0 decimates by vertex
@@ -141,7 +148,8 @@ class PatchMatchMVS(ResidentViews):
         their faces meet best (Engine.mesh_decimate_quadric with decimate_regularisation; same faces and colours, a
         smaller error on curved surfaces and at edges);
         with_normals=True appends area-weighted vertex normals (V,3) float32 to the result, a 4-tuple then.  With the
-        defaults none of it runs.  The grid of the last call is kept in last_mesh_grid (origin, voxel, dims, trunc)."""
+        defaults none of it runs.  The grid of the last call is kept in last_mesh_grid (origin, voxel, dims, trunc), the views
+        it fused in last_mesh_views."""
         rank, world = _parallel.rank_world(self.process_group)
         if world > 1:
             raise NotImplementedError("reconstruct_mesh runs on one process: meshing with a process group of "
@@ -154,6 +162,14 @@ class PatchMatchMVS(ResidentViews):
             raise ValueError("decimate_voxels must be finite and not negative")
         if decimate_placement not in ("mean", "quadric"):
             raise ValueError(f"decimate_placement must be 'mean' or 'quadric', not {decimate_placement!r}")
+        try:
+            whole = not isinstance(min_visible_views, bool) and int(min_visible_views) == min_visible_views
+        except (TypeError, ValueError, OverflowError):
+            whole = False
+        if not whole or min_visible_views < 0:
+            raise ValueError("min_visible_views must be an integer and not negative")
+        if not (np.isfinite(visibility_tolerance_voxels) and visibility_tolerance_voxels >= 0):
+            raise ValueError("visibility_tolerance_voxels must be finite and not negative")
         points, _, maps = self._reconstruct_maps(images, poses, sparse_points)
         do_filter = min_component_faces > 0 or keep_largest
         empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), np.zeros((0, 3), np.uint8))
@@ -168,15 +184,23 @@ class PatchMatchMVS(ResidentViews):
         ids, src = self._mesh_inputs(maps)
         if not ids:
             return empty
-        verts, faces, colors = self._engine.tsdf_mesh(self.K_scaled, [(poses[i].R, poses[i].t) for i in ids], self.min_views,
-                                                      origin, voxel, dims, trunc, **src)
+        fused = [(poses[i].R, poses[i].t) for i in ids]
+        self.last_mesh_views = None
+        verts, faces, colors = self._engine.tsdf_mesh(self.K_scaled, fused, self.min_views, origin, voxel, dims, trunc, **src)
+        self.last_mesh_views = list(ids)
         print(f"  Mesh: {len(verts):,} vertices, {len(faces):,} faces ({time.time() - t0:.2f}s)")
         decimate = decimate_voxels > 0
-        if not (do_filter or smooth_iterations > 0 or with_normals or decimate):
+        cull = min_visible_views > 0
+        if not (cull or do_filter or smooth_iterations > 0 or with_normals or decimate):
             return verts, faces, colors
         t0 = time.time()
         eng = self._engine
         n_comp, n_faces = 0, len(faces)
+        if cull:
+            eng.mesh_render(self.K_scaled, fused, near=np.float32(voxel))
+            eng.mesh_visibility(np.float32(visibility_tolerance_voxels) * np.float32(voxel))
+            n_faces = eng.mesh_filter_visible(int(min_visible_views))[1]
+            culled = f"visibility >= {int(min_visible_views)} views: {len(faces):,} faces -> {n_faces:,}"
         if do_filter:
             n_comp, _, n_faces = eng.mesh_filter_components(min_component_faces, keep_largest)
         if smooth_iterations > 0:
@@ -194,7 +218,7 @@ class PatchMatchMVS(ResidentViews):
         if with_normals:
             eng.mesh_normals()
         out = eng.mesh_fetch(normals=with_normals, labels=do_filter and not decimate)
-        line = []
+        line = [culled] if cull else []
         if do_filter and decimate:
             line.append(f"{n_comp:,} components -> {filtered[0]:,}, {filtered[1]:,} faces")
         elif do_filter:

@@ -1,8 +1,9 @@
 // amvs_capi_mesh.hip -- the TSDF and mesh entry points of the C ABI (include/amvs.h; amvs_mesh.hip,
-// amvs_mesh_clean.hip, amvs_mesh_decimate.hip).
+// amvs_mesh_clean.hip, amvs_mesh_decimate.hip, amvs_mesh_render.hip).
 #include "amvs_ctx.h"
 
 #include <cmath>
+#include <vector>
 
 using namespace amvs::host;
 
@@ -219,6 +220,97 @@ int amvs_fetch_mesh_attributes(amvs_ctx *c, float *normals, int32_t *labels)
     int rc = bind_device(c);
     if (rc) return rc;
     HIPCHK(c, amvs::mesh_fetch_attributes(c->tsdf.get(), normals, labels, c->stream));
+    return checked(c, AMVS_OK);
+}
+
+// ---- rendering and visibility (amvs_mesh_render.hip): the current mesh seen from given cameras ----
+int amvs_set_render_tuning(amvs_ctx *c, int large_face_pixels)
+{
+    if (!c) return AMVS_EINVAL;
+    if (large_face_pixels < 0) return fail(c, AMVS_EINVAL, "set_render_tuning: large_face_pixels must be >= 0 (0 = automatic)");
+    if (!c->tsdf) c->tsdf.reset(amvs::tsdf_state_new());
+    amvs::mesh_set_render_tuning(c->tsdf.get(), large_face_pixels);
+    return AMVS_OK;
+}
+
+int amvs_mesh_render(amvs_ctx *c, int n_views, const float K[9], const float *poses, float near, int64_t *n_skipped)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::tsdf_has_mesh(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_render: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    if (n_views < 1) return fail(c, AMVS_EINVAL, "mesh_render: n_views must be >= 1");
+    if (!K || !poses) return fail(c, AMVS_EINVAL, "mesh_render: NULL K or poses");
+    if (!(near > 0.0f) || !std::isfinite(near)) return fail(c, AMVS_EINVAL, "mesh_render: near must be positive and finite");
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(K[i])) return fail(c, AMVS_EINVAL, "mesh_render: K must be finite");
+    if ((long long)n_views * c->H * c->W > INT32_MAX)
+        return fail(c, AMVS_EINVAL, "mesh_render: " + std::to_string(n_views) + " views of " + std::to_string(c->H) + " x " +
+                                        std::to_string(c->W) + " pixels are over the limit (n_views * H * W <= INT32_MAX)");
+    for (long long i = 0; i < 12ll * n_views; ++i)
+        if (!std::isfinite(poses[i])) return fail(c, AMVS_EINVAL, "mesh_render: pose " + std::to_string(i / 12) + " is not finite");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    std::vector<long long> skipped(n_skipped ? (size_t)n_views : 0);
+    const hipError_t e = amvs::mesh_render(c->tsdf.get(), c->cache, n_views, c->H, c->W, K, poses, near,
+                                           n_skipped ? skipped.data() : nullptr, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_render: ") + hipGetErrorString(e));
+    for (size_t m = 0; m < skipped.size(); ++m) n_skipped[m] = skipped[m];
+    return checked(c, AMVS_OK);
+}
+
+int amvs_fetch_render(amvs_ctx *c, int first, int count, float *depth_out, int32_t *face_out)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::mesh_has_render(c->tsdf.get())) return fail(c, AMVS_EINVAL, "fetch_render: no current render (amvs_mesh_render)");
+    const int n = amvs::mesh_render_views(c->tsdf.get());
+    if (first < 0 || count < 1 || first > n - count)
+        return fail(c, AMVS_EINVAL, "fetch_render: views " + std::to_string(first) + " .. " + std::to_string((long long)first + count - 1) +
+                                        " are not among the " + std::to_string(n) + " rendered");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    HIPCHK(c, amvs::mesh_fetch_render(c->tsdf.get(), first, count, depth_out, face_out, c->stream));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_mesh_visibility(amvs_ctx *c, float depth_tolerance, int64_t *n_seen)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::mesh_has_render(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_visibility: no current render (amvs_mesh_render)");
+    if (!(depth_tolerance >= 0.0f) || !std::isfinite(depth_tolerance))
+        return fail(c, AMVS_EINVAL, "mesh_visibility: depth_tolerance must be finite and not negative");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    long long seen = 0;
+    const hipError_t e = amvs::mesh_visibility(c->tsdf.get(), c->cache, depth_tolerance, &seen, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_visibility: ") + hipGetErrorString(e));
+    if (n_seen) *n_seen = seen;
+    return checked(c, AMVS_OK);
+}
+
+int amvs_fetch_mesh_visibility(amvs_ctx *c, int32_t *counts)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::mesh_has_visibility(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "fetch_mesh_visibility: no current counts (amvs_mesh_visibility)");
+    if (!counts) return fail(c, AMVS_EINVAL, "fetch_mesh_visibility: NULL output");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    HIPCHK(c, amvs::mesh_fetch_visibility(c->tsdf.get(), counts, c->stream));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_mesh_filter_visible(amvs_ctx *c, int min_views, int64_t *n_vertices, int64_t *n_faces)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!n_vertices || !n_faces) return fail(c, AMVS_EINVAL, "mesh_filter_visible: NULL output");
+    if (!amvs::mesh_has_visibility(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "mesh_filter_visible: no current counts (amvs_mesh_visibility)");
+    if (min_views < 1) return fail(c, AMVS_EINVAL, "mesh_filter_visible: min_views must be >= 1");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    long long nv = 0, nf = 0;
+    const hipError_t e = amvs::mesh_filter_visible(c->tsdf.get(), c->cache, min_views, &nv, &nf, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_filter_visible: ") + hipGetErrorString(e));
+    *n_vertices = nv; *n_faces = nf;
     return checked(c, AMVS_OK);
 }
 

@@ -295,4 +295,20 @@ hipError_t mesh_decimate_quadric(TsdfState *s, ScratchCache &cache, const float 
                                  long long *bad_vertex, long long *n_vertices, long long *n_faces, long long *n_fallback,
                                  hipStream_t st);
 
+// amvs_mesh_render.hip: the state's current mesh drawn into views, the visibility counts and their filter
+// (include/amvs.h amvs_mesh_render ...).  The maps and the counts are attributes of the current mesh.  All synchronise.
+// poses_h: [n_views][12] float32 R row-major, t; n_skipped_h: NULL or [n_views].  The caller has validated the arguments.
+void mesh_set_render_tuning(TsdfState *s, int large_face_pixels);
+hipError_t mesh_render(TsdfState *s, ScratchCache &cache, int n_views, int H, int W, const float K[9], const float *poses_h,
+                       float near, long long *n_skipped_h, hipStream_t st);
+bool mesh_has_render(const TsdfState *s);
+bool mesh_has_visibility(const TsdfState *s);
+int mesh_render_views(const TsdfState *s);       // views of the current render, 0 without one
+hipError_t mesh_fetch_render(TsdfState *s, int first, int count, float *depth, int *face, hipStream_t st);
+hipError_t mesh_visibility(TsdfState *s, ScratchCache &cache, float tolerance, long long *n_seen, hipStream_t st);
+hipError_t mesh_fetch_visibility(TsdfState *s, int *counts, hipStream_t st);
+// drops the maps, the counts, labels, normals and the index
+hipError_t mesh_filter_visible(TsdfState *s, ScratchCache &cache, int min_views, long long *n_vertices, long long *n_faces,
+                               hipStream_t st);
+
 }  // namespace amvs

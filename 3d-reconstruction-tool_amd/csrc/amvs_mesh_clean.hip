@@ -382,6 +382,7 @@ hipError_t mesh_filter_components(TsdfState *s, ScratchCache &cache, long long m
                                   long long *n_vertices, long long *n_faces, hipStream_t st)
 {
     s->have_labels = s->have_normals = false;
+    s->drop_views();
     const long long nv = s->n_vertices, nf = s->n_faces;
     MCHK(label_components(s, cache, n_components, st));
     *n_vertices = nv; *n_faces = nf;
@@ -443,6 +444,7 @@ hipError_t mesh_filter_components(TsdfState *s, ScratchCache &cache, long long m
 hipError_t mesh_smooth(TsdfState *s, ScratchCache &cache, int iterations, float lambda, float mu, bool fix_boundary, hipStream_t st)
 {
     s->have_normals = false;
+    s->drop_views();
     const long long nv = s->n_vertices, nc = 3 * s->n_faces;
     if (iterations > 0 && nv > 0) {
         MCHK(ensure_index(s, cache, st));

@@ -323,6 +323,7 @@ hipError_t decimate(TsdfState *s, ScratchCache &cache, const float origin[3], fl
     }
     const int *const old_faces = s->faces.get();
     s->have_csr = s->have_pinned = s->have_labels = s->have_normals = false;
+    s->drop_views();
     long long kept_f = 0, kept_v = 0;
     if (nf > 0 && nv > 0) {
         // (4) before (3): the faces still hold the old ids

@@ -1,5 +1,6 @@
-// amvs_mesh_state.h -- what the two surface-mesh translation units share: the context's volume-and-mesh state
-// (amvs_mesh.hip builds the mesh, amvs_mesh_clean.hip and amvs_mesh_decimate.hip work on it in place), the hipCUB scan
+// amvs_mesh_state.h -- what the surface-mesh translation units share: the context's volume-and-mesh state
+// (amvs_mesh.hip builds the mesh, amvs_mesh_clean.hip and amvs_mesh_decimate.hip work on it in place,
+// amvs_mesh_render.hip draws it into views and filters it by what they see), the hipCUB scan
 // with its read-back, and the kernels of extraction pass (d) that drop unused vertices, which the component filter and
 // the decimation run again.
 // Include after defining AMVS_TU_ID (amvs_check.h): the kernels here are compiled into each including unit.
@@ -67,10 +68,28 @@ struct TsdfState {
     DeviceBuffer<unsigned> dec_fkey, dec_fkey2, dec_perm, dec_perm2;      // [F]: the group sorts' keys and permutation
     DeviceBuffer<float> dec_quadric;              // [V][9]: quadric placement, a00 a01 a02 a11 a12 a22 b0 b1 b2 of every vertex
 
+    // ---- rendering (amvs_mesh_render.hip): the maps and the counts are attributes of the current mesh ----
+    bool have_render = false, have_visibility = false;
+    int render_large = 0;                         // amvs_set_render_tuning: box pixels of a large face, 0 = automatic
+    int render_views = 0, render_H = 0, render_W = 0;     // what the maps were rendered with; the counts use the same
+    float render_near = 0.0f, render_K[9] = {};
+    DeviceBuffer<float> render_cams;              // [n_views][12] R, t
+    DeviceBuffer<unsigned long long> render_keys; // [n_views][H][W]: bits(depth) << 32 | face, all ones = nothing drawn
+    DeviceBuffer<float> render_depth;             // [n_views][H][W]
+    DeviceBuffer<int> render_face;                // [n_views][H][W]
+    DeviceBuffer<unsigned> render_list, render_count;     // [n_views][F]: the large faces of every view; [n_views]: how many
+    DeviceBuffer<unsigned long long> render_skipped;      // [n_views]: faces with a vertex that is not usable
+    DeviceBuffer<int> vis_count;                  // [V]: views that see the vertex
+    DeviceBuffer<unsigned long long> vis_seen;    // [1]: vertices with a count > 0
+
+    // the mesh moves or changes: what was rendered from it is no longer its picture
+    void drop_views() { have_render = have_visibility = false; }
+
     // the mesh is about to be replaced: nothing derived from it stays
     void drop_mesh()
     {
         have_mesh = have_csr = have_pinned = have_labels = have_normals = false;
+        drop_views();
     }
 };
 

@@ -683,6 +683,54 @@ class Engine:
         out += [a for a in (nrm, lab) if a is not None]
         return tuple(out)
 
+    # -- rendering and visibility of the current mesh (csrc/amvs_mesh_render.hip) ----
+    def set_render_tuning(self, large_face_pixels=0):
+        """Performance only: faces whose clamped bounding box holds more pixels than this are drawn by a workgroup
+        instead of by one lane (0 = automatic).  The maps do not depend on it."""
+        self._chk(self._lib.amvs_set_render_tuning(self._h, int(large_face_pixels)))
+
+    def mesh_render(self, K, poses, near=1e-3, skipped=False, fetch=True):
+        """Z-buffer render of the current mesh into the cameras poses = list of (R, t) with the intrinsics K (3,3), both
+        used in float32 (include/amvs.h amvs_mesh_render): (depth (n,H,W) float32, 0 where nothing was drawn, face
+        (n,H,W) int32, -1 there)[, faces skipped per view (n,) int64 with skipped=True].  The maps stay on the device
+        for mesh_visibility until the mesh changes; fetch=False leaves them there and returns only the skipped counts
+        (mesh_render_fetch copies them later)."""
+        n = len(poses)
+        Kf = _r32(K, 9)
+        pp = _r32(_poses64(poses), n, 12) if n else np.zeros((0, 12), np.float32)
+        skip = np.zeros(max(n, 1), np.int64)
+        self._chk(self._lib.amvs_mesh_render(self._h, n, _p(Kf), _p(pp), float(np.float32(near)),
+                                             skip.ctypes.data_as(C.POINTER(C.c_int64))))
+        if not fetch:
+            return skip[:n]
+        out = self.mesh_render_fetch(0, n)
+        return out + (skip[:n],) if skipped else out
+
+    def mesh_render_fetch(self, first, count):
+        """(depth, face) of `count` views of the current render from view `first` on."""
+        depth = np.empty((count, self.H, self.W), np.float32)
+        face = np.empty((count, self.H, self.W), np.int32)
+        self._chk(self._lib.amvs_fetch_render(self._h, int(first), int(count), _p(depth), face.ctypes.data_as(i32p)))
+        return depth, face
+
+    def mesh_visibility(self, depth_tolerance):
+        """In how many of the rendered views every vertex of the current mesh is seen: in front of the render's near,
+        inside the image, and not behind the rendered depth at its nearest pixel by more than depth_tolerance
+        (include/amvs.h amvs_mesh_visibility).  Returns counts (V,) int32; needs mesh_render."""
+        seen = C.c_int64(0)
+        self._chk(self._lib.amvs_mesh_visibility(self._h, float(np.float32(depth_tolerance)), C.byref(seen)))
+        counts = np.empty(self._mesh_counts[0], np.int32)
+        self._chk(self._lib.amvs_fetch_mesh_visibility(self._h, counts.ctypes.data_as(i32p)))
+        return counts
+
+    def mesh_filter_visible(self, min_views=1):
+        """Keep the faces whose three vertices are each seen by at least min_views views (needs mesh_visibility).
+        Returns (vertices, faces) after it; drops the render, the counts, labels and normals."""
+        nv, nf = C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.amvs_mesh_filter_visible(self._h, int(min_views), C.byref(nv), C.byref(nf)))
+        self._mesh_counts = (nv.value, nf.value)
+        return nv.value, nf.value
+
     def knn_mean_distance(self, points, k=20):
         """Mean distance of every point to its k-1 nearest other points, bit-identical to
         np.mean(NearestNeighbors(n_neighbors=k).fit(p).kneighbors(p)[0][:, 1:], axis=1)."""

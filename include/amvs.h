@@ -339,9 +339,12 @@ int amvs_tsdf_set_volume(amvs_ctx *ctx, const float *tsdf, const float *weight, 
  * amvs_fetch_mesh returns the current mesh, cleaned or not.  No float atomics: every float sum runs in a fixed order
  * over the corners c = 3 * face + k that hold the vertex, in ascending c.  Limits: int32 vertex ids and
  * 3 * n_faces <= INT32_MAX.  Labels and normals are attributes of the current mesh: amvs_tsdf_integrate,
- * amvs_tsdf_set_volume, amvs_tsdf_extract, amvs_mesh_set, amvs_mesh_decimate and amvs_mesh_decimate_quadric drop both,
- * amvs_mesh_filter_components drops the normals and leaves fresh labels, amvs_mesh_smooth drops the normals and keeps
- * the labels.                                                                                                      */
+ * amvs_tsdf_set_volume, amvs_tsdf_extract, amvs_mesh_set, amvs_mesh_decimate, amvs_mesh_decimate_quadric and
+ * amvs_mesh_filter_visible drop both, amvs_mesh_filter_components drops the normals and leaves fresh labels,
+ * amvs_mesh_smooth drops the normals and keeps the labels.  The rendered maps and the visibility counts (below) are
+ * attributes too: every call of this list drops both, and so do amvs_mesh_filter_components and amvs_mesh_smooth,
+ * which replace or move the mesh; amvs_mesh_normals keeps them, and a decimation refused for a vertex outside the
+ * cluster grid changes nothing.                                                                                    */
 /* Replace the context's mesh by host arrays: n_vertices x 3 float32 positions, n_faces x 3 int32 vertex ids,
  * n_vertices x 3 uint8 RGB colours (NULL: zeros).  A test hook, and the way to clean a mesh made elsewhere.
  * Validated on the host before anything is copied -- finite positions, ids in [0, n_vertices), no face with a
@@ -418,6 +421,57 @@ int amvs_mesh_decimate_quadric(amvs_ctx *ctx, const float origin[3], float cell,
 /* n_vertices x 3 float32 normals (amvs_mesh_normals) and n_vertices int32 labels (amvs_mesh_filter_components) of
  * the current mesh.  NULL skips an output; asking for one that is not current is AMVS_EINVAL.                     */
 int amvs_fetch_mesh_attributes(amvs_ctx *ctx, float *normals, int32_t *labels);
+
+/* ---- rendering and visibility: the current mesh seen from given cameras (csrc/amvs_mesh_render.hip) -----------
+ * No reference counterpart (the reference has no mesh): judged against a NumPy restatement of the definitions below,
+ * bit for bit (tests/mesh_render_restatement.py, DESIGN.md section 8 "Rendering and visibility").  Images are the
+ * context's H x W; pixel centres sit at integer coordinates, as in amvs_tsdf_integrate (nearest pixel
+ * floorf(u + 0.5f)).  No float atomics and no dependence on execution order: integer coverage, and a 64-bit integer
+ * minimum per pixel.  The maps and the counts are attributes of the current mesh (the list above says what drops
+ * them); all calls synchronise.                                                                                    */
+/* Z-buffer rasteriser of the current mesh into n_views cameras with the float32 intrinsics K and poses (n_views x 12
+ * float32: R row-major, then t; world -> camera).  All float32 unless stated, every operation rounded on its own (no
+ * fused multiply-add), the divisions IEEE.
+ * a. Projection of vertex X, as amvs_tsdf_integrate forms it: zc = ((P[6]*X + P[7]*Y) + P[8]*Z) + P[11], xc and yc
+ *    likewise from rows 0 and 1; pu = (K0*xc + K1*yc) + K2*zc, pv and pw likewise from rows 1 and 2 of K; u = pu / pw,
+ *    v = pv / pw, iz = 1.0f / zc.  The vertex is usable iff zc > near, |u| <= 2^20 and |v| <= 2^20 (comparisons false
+ *    for NaN).  Its fixed-point screen position is sx = (int64)rintf(u * 256.0f), sy likewise (ties to even).
+ * b. Face set-up.  A face with a vertex that is not usable is skipped whole (no clipping) and counted in
+ *    n_skipped[view].  area = (x1-x0)*(y2-y0) - (y1-y0)*(x2-x0) in int64; area == 0 draws nothing; area < 0: the second
+ *    and third corner are exchanged and area negated, and everything below uses the exchanged order (both windings are
+ *    drawn, there is no back-face culling).
+ * c. Coverage, exact in int64, at the pixels (px, py) of the face's bounding box clamped to the image, P = (256 px,
+ *    256 py).  For the edges a -> b = v1 -> v2, v2 -> v0, v0 -> v1: w = (bx-ax)*(Py-ay) - (by-ay)*(Px-ax).  The pixel is
+ *    inside iff for all three w > 0, or w == 0 and (dy < 0 or (dy == 0 and dx > 0)) with dx = bx-ax, dy = by-ay: a
+ *    pixel centre on an edge two faces share belongs to exactly one of them.  (Coordinates <= 2^28 in magnitude,
+ *    differences <= 2^29, products < 2^58.)
+ * d. Depth, perspective-correct: b_i = (float)w_i / (float)area (int64 -> float32 rounds to nearest even),
+ *    z = 1.0f / ((b0*iz_0 + b1*iz_1) + b2*iz_2); the pixel is dropped unless z is finite and > 0.
+ * e. Resolve: key = (uint64)bits(z) << 32 | (uint32)face; the pixel keeps the minimum key over all faces (the nearest
+ *    surface, equal depth going to the smallest face index).  depth = the key's upper word as float, or 0.0f where
+ *    nothing was drawn; face = the key's lower word, or -1 there.
+ * AMVS_EINVAL: no current mesh, n_views < 1, near not finite or <= 0, non-finite K or poses, n_views * H * W >
+ * INT32_MAX.  An empty mesh renders empty maps.  n_skipped: NULL or [n_views].                                      */
+int amvs_mesh_render(amvs_ctx *ctx, int n_views, const float K[9], const float *poses, float near, int64_t *n_skipped);
+/* The maps of views first .. first + count - 1 of the current render: [count][H][W] float32 depth and int32 face ids.
+ * NULL skips an output; AMVS_EINVAL without a current render or for views that were not rendered.                   */
+int amvs_fetch_render(amvs_ctx *ctx, int first, int count, float *depth_out, int32_t *face_out);
+/* Visibility counts against the current render (AMVS_EINVAL without one; depth_tolerance finite and >= 0).  For every
+ * vertex and rendered view, with the projection (a) and the render's near: the vertex is seen iff zc > near,
+ * fx = floorf(u + 0.5f) and fy = floorf(v + 0.5f) fall inside the image, and the rendered depth d there is 0.0f
+ * (nothing drawn) or zc <= d + depth_tolerance.  counts[v] = the number of such views.  n_seen (optional): the
+ * vertices with a count > 0.                                                                                       */
+int amvs_mesh_visibility(amvs_ctx *ctx, float depth_tolerance, int64_t *n_seen);
+/* The n_vertices int32 counts of amvs_mesh_visibility; AMVS_EINVAL unless they are current.                        */
+int amvs_fetch_mesh_visibility(amvs_ctx *ctx, int32_t *counts);
+/* Keeps the faces whose three vertices each have counts >= min_views (min_views >= 1; the views need not be the same
+ * ones), compacted in their order; the vertices no face uses leave as in amvs_tsdf_extract's last pass.  Needs current
+ * counts, else AMVS_EINVAL.  n_vertices and n_faces are the mesh after it; a mesh that loses every face gives 0 / 0.
+ * Drops the maps, the counts, labels and normals.                                                                  */
+int amvs_mesh_filter_visible(amvs_ctx *ctx, int min_views, int64_t *n_vertices, int64_t *n_faces);
+/* Performance only, the maps do not depend on it: a face whose clamped bounding box holds more than large_face_pixels
+ * pixels is drawn by a workgroup instead of by one lane (0 = automatic; < 0 is AMVS_EINVAL).                        */
+int amvs_set_render_tuning(amvs_ctx *ctx, int large_face_pixels);
 
 /* ---- extended mode: what the reference's docstring names but does not implement ----------------
  * (mvs_patchmatch.py:1-13 lists plane hypotheses with normals and VIEW propagation; its code ignores

@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
-"""Device time of the surface-mesh kernels (csrc/amvs_mesh.hip, csrc/amvs_mesh_clean.hip, csrc/amvs_mesh_decimate.hip) at the CLI operating point (run on the GPU box):
+"""Device time of the surface-mesh kernels (csrc/amvs_mesh.hip, csrc/amvs_mesh_clean.hip, csrc/amvs_mesh_decimate.hip,
+csrc/amvs_mesh_render.hip) at the CLI operating point (run on the GPU box):
 16 views at 1008 x 756, patch 11, the maps of the extended mode (the reference's algorithm leaves too few correct
 depths for a surface) resident on the device, a 256^3 TSDF volume around the fused cloud.  Integration and extraction are timed separately with HIP events on the engine's stream (the extraction
 includes its two count read-backs); the first-order bounds of DESIGN.md section 8 are printed next to them.
 Then the clean-up stage on that mesh and on the mesh of a 256^3 sphere: the vertex -> corner index, labelling + filter,
 10 Taubin iterations and the normals, each the median of 5 after a warm-up, with a first-order byte estimate; the
 decimation of either mesh at a cell of 2 voxels with either placement of the clusters' vertices (the mean, the quadrics),
-likewise; and
+likewise; the render of either mesh into the views (the scene's cameras; a ring of as many round the sphere) and the
+visibility counts against it, before and after that decimation, next to a first-order estimate that prices the 64-bit
+minimum atomics at the rate measured for float adds, which nobody has measured for them; and
 the labelling of a shuffled strip of 100 000 faces next to a sphere of about as many.
 
     python tools/mesh_time.py [n_views W H dim]
@@ -155,12 +158,58 @@ def decimate_time(name, restore, grid_origin, cell):
     assert qcounts[:2] == counts
 
 
+def render_time(name, restore, K, cams, near, tolerance, grid_origin, cell):
+    """Render (csrc/amvs_mesh_render.hip) of the restored mesh into `cams` and the visibility counts, then the same on
+    the mesh decimated at 2 voxels: small faces first, faces of tens of pixels after.  The maps stay on the device."""
+    for stage in ("as extracted", "decimated at 2 voxels"):
+        tr, tv = [], []
+        for rep in range(REPS + 1):
+            V, F = restore()
+            if stage != "as extracted":
+                V, F = eng.mesh_decimate(grid_origin, cell)
+            r, _, skipped = timed(lambda: eng.mesh_render(K, cams, near=near, fetch=False))
+            v, _, counts = timed(lambda: eng.mesh_visibility(tolerance))
+            if rep:
+                tr.append(r); tv.append(v)
+        face = eng.mesh_render_fetch(0, len(cams))[1]
+        covered = int((face >= 0).sum())
+        pixels = face.size
+        # first order: every covered pixel is hit by a front and a back face (2 atomics of 8 B) at the chip-wide rate
+        # measured for FLOAT adds (about 1.3 TB/s of bytes; NOT measured for 64-bit integer minima), the key clear
+        # (8 B per pixel) and the split (8 B in, 8 B out) stream at 8 TB/s
+        est = 2 * covered * 8 / 1.3e12 * 1e3 + pixels * 24 / 8e12 * 1e3
+        vis = (V * (12 + 4) + V * len(cams) * 4) / 8e12 * 1e3
+        print(f"render of {name}, {stage}: {V:,} vertices, {F:,} faces into {len(cams)} views of {W}x{H}, {covered:,} of "
+              f"{pixels:,} pixels covered, {int(skipped.sum()):,} (view, face) pairs skipped; {int((counts > 0).sum()):,} vertices seen")
+        print(f"  render     median {np.median(tr):8.3f} ms device (min {min(tr):.3f}); first-order estimate {est:.4f} ms "
+              f"(atomics at the float-add rate, unmeasured for integer minima): {np.median(tr) / est:.1f} x")
+        print(f"  visibility median {np.median(tv):8.3f} ms device (min {min(tv):.3f}); first-order bytes (estimate) {vis:.4f} ms "
+              f"at 8 TB/s")
+
+
+def ring_of_cameras(n, distance=3.0):
+    """n cameras round the origin looking at it, on a tilted ring: (R, t) with R's rows the camera's axes."""
+    out = []
+    for a in np.arange(n) * 2 * np.pi / n:
+        eye = distance * np.array([np.cos(a) * 0.9, np.sin(a) * 0.9, np.sqrt(1 - 0.81) * np.cos(3 * a)])
+        z = -eye / np.linalg.norm(eye)
+        x = np.cross([0.0, 0.0, 1.0], z)
+        x /= np.linalg.norm(x)
+        R = np.stack([x, np.cross(z, x), z])
+        out.append((R, -R @ eye))
+    return out
+
+
 clean_times(f"the CLI operating point ({dim}^3)", restore_volume)
 decimate_time(f"the CLI operating point ({dim}^3)", restore_volume, origin, 2.0 * voxel)
+render_time(f"the CLI operating point ({dim}^3)", restore_volume, pm.K_scaled, poses, voxel, voxel, origin, 2.0 * voxel)
 sphere = mv.sphere_volume(256, radius=0.8)
 eng.tsdf_set_volume(*sphere.arrays())
 clean_times("the 256^3 sphere", restore_volume)
 decimate_time("the 256^3 sphere", restore_volume, sphere.origin, 2.0 * float(sphere.voxel))
+K_sphere = np.array([[0.9 * H, 0, W / 2.0], [0, 0.9 * H, H / 2.0], [0, 0, 1]])
+render_time("the 256^3 sphere", restore_volume, K_sphere, ring_of_cameras(len(poses)), 0.1, float(sphere.voxel), sphere.origin,
+            2.0 * float(sphere.voxel))
 
 
 def label_time(name, restore):
