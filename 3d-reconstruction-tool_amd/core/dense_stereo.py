@@ -23,6 +23,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from .camera import Camera, CameraPose
+from .utils import rows_matmul
 from .view_cache import ResidentViews
 from .. import parallel as _parallel
 
@@ -273,8 +274,8 @@ class DenseStereoReconstructor(ResidentViews):
         ys, xs = np.where(keep)
         K_inv = np.linalg.inv(self.K_scaled)
         pix = np.stack([xs, ys, np.ones_like(xs)], axis=-1).astype(np.float32)
-        cam_pts = (pix @ K_inv.T) * depth_map[keep][:, np.newaxis]
-        world = (cam_pts - pose.t) @ pose.R
+        cam_pts = rows_matmul(pix, K_inv.T) * depth_map[keep][:, np.newaxis]
+        world = rows_matmul(cam_pts - pose.t, pose.R)
         return world, color_map[ys, xs][:, ::-1]
 
     def _filter_outliers(self, points: np.ndarray, colors: np.ndarray, k: int = 20, std_ratio: float = 2.0):

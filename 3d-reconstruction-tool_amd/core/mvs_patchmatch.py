@@ -31,6 +31,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from .camera import Camera, CameraPose
+from .utils import rows_matmul
 from .view_cache import ResidentViews
 from .. import engine as _engine
 from .. import parallel as _parallel
@@ -707,8 +708,8 @@ class PatchMatchMVS(ResidentViews):
                 continue
             ys, xs = np.where(keep)
             pix = np.stack([xs, ys, np.ones_like(xs)], axis=-1)
-            cam_pts = (pix @ K_inv.T) * dm.depth[keep][:, np.newaxis]
-            clouds.append((cam_pts - poses[idx].t) @ poses[idx].R)
+            cam_pts = rows_matmul(pix, K_inv.T) * dm.depth[keep][:, np.newaxis]
+            clouds.append(rows_matmul(cam_pts - poses[idx].t, poses[idx].R))
             cloud_colors.append(images[idx]["color"][ys, xs][:, ::-1])      # BGR -> RGB
         if not clouds:
             return np.array([]).reshape(0, 3), np.array([]).reshape(0, 3)

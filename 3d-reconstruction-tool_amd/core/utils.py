@@ -13,6 +13,23 @@ import numpy as np
 from .. import _lib
 
 
+def rows_matmul(rows: np.ndarray, matrix: np.ndarray) -> np.ndarray:
+    """rows (m, 3) @ matrix (3, 3) with every row rounded alike: x*b0 + y*b1 + z*b2 as the left-to-right fused
+    chain, which is what the device computes (amvs_fusion.hip) and what the BLAS matrix-matrix kernels give.  NumPy
+    hands a product of ONE row to the matrix-vector routine instead, whose rounding differs, so a single row is
+    multiplied as two.
+
+    This is a deliberate departure from the reference, which writes a plain `@` and so gets the matrix-vector rounding
+    for a view with exactly one selected pixel: there the reference's point depends on how many OTHER pixels of the
+    view were selected.  The project defines a point by the fused chain alone, on host and device; for one-pixel
+    views both are therefore a last bit away from the reference, and equal to each other.  That a two-row product
+    rounds like an m-row one is a property of the BLAS in use, not a guarantee: test_cloud_restatement_cpu.py holds
+    the host path to the exact fused chain for 1, 2, 3 and 4 rows per view and fails where a BLAS does otherwise."""
+    if len(rows) == 1:
+        return (np.concatenate([rows, rows]) @ matrix)[:1]
+    return rows @ matrix
+
+
 def save_ply(points: np.ndarray, colors: np.ndarray, output_path: str):
     """Save an (N,3) cloud with (N,3) RGB colours as ASCII PLY."""
     output_path = Path(output_path)

@@ -276,7 +276,11 @@ int amvs_knn_mean_distance(amvs_ctx *ctx, const double *points, int64_t n, int k
  * ([n_maps][H][W][3], host) and leave as RGB.  With do_filter: 95th-percentile radius cut around
  * the per-axis median, then 1 cm voxel de-duplication keeping the first point of each voxel in
  * key order.  counts[0] = fused points, counts[1] = points kept; amvs_fetch_cloud copies the
- * counts[1] x 3 points (float64) and colours (uint8) to the host.                              */
+ * counts[1] x 3 points (float64) and colours (uint8) to the host.  An empty result (no pixel
+ * selected, or the strict cut removed every point, as it does for one point and for two at equal
+ * distance) leaves no resident cloud: counts[1] = 0.  Depths, confidences, K_inv and poses must be
+ * finite; what a NaN or an infinite depth of a selected pixel does to the median, the percentile
+ * and the voxel keys is not defined.                                                            */
 int amvs_fuse_filter(amvs_ctx *ctx, int n_maps, const void *depth, const void *conf, int maps_on_device,
                      const uint8_t *colors_bgr_host, const double K_inv[9], const double *poses,
                      float min_views, int do_filter, int64_t counts[2]);
