@@ -26,6 +26,25 @@ static int check_tsdf_grid(amvs_ctx *c, const std::string &who, const float orig
     return AMVS_OK;
 }
 
+// AMVS_OK, or the failure of entry point `name` with HIP's error string
+static int hip_rc(amvs_ctx *c, const char *name, hipError_t e)
+{
+    return e == hipSuccess ? AMVS_OK : fail(c, AMVS_EHIP, std::string(name) + ": " + hipGetErrorString(e));
+}
+
+// HIPCHK with the entry point's name in the message instead of the call's text
+#define MESH_HIPCHK(c, name, call)                                \
+    do {                                                          \
+        if (int rc_ = hip_rc((c), (name), (call))) return rc_;    \
+    } while (0)
+
+// AMVS_OK, or the failure of entry point `name` on a context without a current mesh
+static int need_mesh(amvs_ctx *c, const char *name)
+{
+    if (amvs::tsdf_has_mesh(c->tsdf.get())) return AMVS_OK;
+    return fail(c, AMVS_EINVAL, std::string(name) + ": no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+}
+
 int amvs_tsdf_integrate(amvs_ctx *c, int n_maps, const void *depth, const void *conf, int maps_on_device,
                         const int *view_ids, const uint8_t *colors_bgr_host, const float K[9], const float *poses,
                         float min_views, const float origin[3], float voxel, const int32_t dims[3], float trunc)
@@ -43,11 +62,9 @@ int amvs_tsdf_integrate(amvs_ctx *c, int n_maps, const void *depth, const void *
     for (int j = 0; j < n_maps; ++j) slots[j] = view_ids ? view_ids[j] : j;
     if ((rc = bind_device(c))) return rc;
     if (!c->tsdf) c->tsdf.reset(amvs::tsdf_state_new());
-    const hipError_t e = amvs::tsdf_integrate(c->tsdf.get(), c->cache, (const float *)depth, (const float *)conf, maps_on_device != 0,
-                                              n_maps, c->H, c->W, view_ids ? c->d_bgr.get() : colors_bgr_host, view_ids != nullptr,
-                                              view_ids ? c->n_views : n_maps, slots.data(), K, poses, min_views, origin, voxel,
-                                              dims, trunc, c->stream);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("tsdf_integrate: ") + hipGetErrorString(e));
+    MESH_HIPCHK(c, "tsdf_integrate", amvs::tsdf_integrate(c->tsdf.get(), c->cache, (const float *)depth, (const float *)conf,
+                maps_on_device != 0, n_maps, c->H, c->W, view_ids ? c->d_bgr.get() : colors_bgr_host, view_ids != nullptr,
+                view_ids ? c->n_views : n_maps, slots.data(), K, poses, min_views, origin, voxel, dims, trunc, c->stream));
     return checked(c, AMVS_OK);
 }
 
@@ -60,8 +77,8 @@ int amvs_tsdf_set_volume(amvs_ctx *c, const float *tsdf, const float *weight, co
     if (rc) return rc;
     if ((rc = bind_device(c))) return rc;
     if (!c->tsdf) c->tsdf.reset(amvs::tsdf_state_new());
-    const hipError_t e = amvs::tsdf_set_volume(c->tsdf.get(), c->cache, tsdf, weight, color_sum, origin, voxel, dims, c->stream);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("tsdf_set_volume: ") + hipGetErrorString(e));
+    MESH_HIPCHK(c, "tsdf_set_volume", amvs::tsdf_set_volume(c->tsdf.get(), c->cache, tsdf, weight, color_sum, origin, voxel, dims,
+                c->stream));
     return checked(c, AMVS_OK);
 }
 
@@ -73,8 +90,7 @@ int amvs_tsdf_extract(amvs_ctx *c, int64_t *n_vertices, int64_t *n_faces)
     int rc = bind_device(c);
     if (rc) return rc;
     long long nv = 0, nf = 0;
-    const hipError_t e = amvs::tsdf_extract(c->tsdf.get(), c->cache, &nv, &nf, c->stream);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("tsdf_extract: ") + hipGetErrorString(e));
+    MESH_HIPCHK(c, "tsdf_extract", amvs::tsdf_extract(c->tsdf.get(), c->cache, &nv, &nf, c->stream));
     *n_vertices = nv; *n_faces = nf;
     return checked(c, AMVS_OK);
 }
@@ -120,8 +136,8 @@ int amvs_mesh_set(amvs_ctx *c, const float *vertices, int64_t n_vertices, const 
     int rc = bind_device(c);
     if (rc) return rc;
     if (!c->tsdf) c->tsdf.reset(amvs::tsdf_state_new());
-    const hipError_t e = amvs::mesh_set(c->tsdf.get(), c->cache, vertices, n_vertices, faces, n_faces, colors_rgb, c->stream);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_set: ") + hipGetErrorString(e));
+    MESH_HIPCHK(c, "mesh_set", amvs::mesh_set(c->tsdf.get(), c->cache, vertices, n_vertices, faces, n_faces, colors_rgb,
+                c->stream));
     return checked(c, AMVS_OK);
 }
 
@@ -130,13 +146,12 @@ int amvs_mesh_filter_components(amvs_ctx *c, int64_t min_faces, int keep_largest
 {
     if (!c) return AMVS_EINVAL;
     if (!n_components || !n_vertices || !n_faces) return fail(c, AMVS_EINVAL, "mesh_filter_components: NULL output");
-    if (!amvs::tsdf_has_mesh(c->tsdf.get()))
-        return fail(c, AMVS_EINVAL, "mesh_filter_components: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    if (int rc = need_mesh(c, "mesh_filter_components")) return rc;
     int rc = bind_device(c);
     if (rc) return rc;
     long long nc = 0, nv = 0, nf = 0;
-    const hipError_t e = amvs::mesh_filter_components(c->tsdf.get(), c->cache, min_faces, keep_largest != 0, &nc, &nv, &nf, c->stream);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_filter_components: ") + hipGetErrorString(e));
+    MESH_HIPCHK(c, "mesh_filter_components", amvs::mesh_filter_components(c->tsdf.get(), c->cache, min_faces, keep_largest != 0,
+                &nc, &nv, &nf, c->stream));
     *n_components = nc; *n_vertices = nv; *n_faces = nf;
     return checked(c, AMVS_OK);
 }
@@ -147,22 +162,20 @@ int amvs_mesh_smooth(amvs_ctx *c, int iterations, float lambda, float mu, int fi
     if (iterations < 0 || iterations > 1000) return fail(c, AMVS_EINVAL, "mesh_smooth: iterations must lie in 0 .. 1000");
     if (!(lambda > 0.0f && lambda <= 1.0f)) return fail(c, AMVS_EINVAL, "mesh_smooth: lambda must lie in (0, 1]");
     if (!std::isfinite(mu)) return fail(c, AMVS_EINVAL, "mesh_smooth: mu must be finite");
-    if (!amvs::tsdf_has_mesh(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_smooth: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    if (int rc = need_mesh(c, "mesh_smooth")) return rc;
     int rc = bind_device(c);
     if (rc) return rc;
-    const hipError_t e = amvs::mesh_smooth(c->tsdf.get(), c->cache, iterations, lambda, mu, fix_boundary != 0, c->stream);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_smooth: ") + hipGetErrorString(e));
+    MESH_HIPCHK(c, "mesh_smooth", amvs::mesh_smooth(c->tsdf.get(), c->cache, iterations, lambda, mu, fix_boundary != 0, c->stream));
     return checked(c, AMVS_OK);
 }
 
 int amvs_mesh_normals(amvs_ctx *c)
 {
     if (!c) return AMVS_EINVAL;
-    if (!amvs::tsdf_has_mesh(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_normals: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    if (int rc = need_mesh(c, "mesh_normals")) return rc;
     int rc = bind_device(c);
     if (rc) return rc;
-    const hipError_t e = amvs::mesh_normals(c->tsdf.get(), c->cache, c->stream);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_normals: ") + hipGetErrorString(e));
+    MESH_HIPCHK(c, "mesh_normals", amvs::mesh_normals(c->tsdf.get(), c->cache, c->stream));
     return checked(c, AMVS_OK);
 }
 
@@ -174,12 +187,11 @@ int amvs_mesh_decimate(amvs_ctx *c, const float origin[3], float cell, int64_t *
     for (int a = 0; a < 3; ++a)
         if (!std::isfinite(origin[a])) return fail(c, AMVS_EINVAL, "mesh_decimate: origin must be finite");
     if (!(cell > 0.0f) || !std::isfinite(cell)) return fail(c, AMVS_EINVAL, "mesh_decimate: cell must be positive and finite");
-    if (!amvs::tsdf_has_mesh(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_decimate: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    if (int rc = need_mesh(c, "mesh_decimate")) return rc;
     int rc = bind_device(c);
     if (rc) return rc;
     long long bad = -1, nv = 0, nf = 0;
-    const hipError_t e = amvs::mesh_decimate(c->tsdf.get(), c->cache, origin, cell, &bad, &nv, &nf, c->stream);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_decimate: ") + hipGetErrorString(e));
+    MESH_HIPCHK(c, "mesh_decimate", amvs::mesh_decimate(c->tsdf.get(), c->cache, origin, cell, &bad, &nv, &nf, c->stream));
     if (bad >= 0) return fail(c, AMVS_EINVAL, "mesh_decimate: vertex " + std::to_string(bad) + " outside the cluster grid");
     *n_vertices = nv; *n_faces = nf;
     return checked(c, AMVS_OK);
@@ -196,13 +208,12 @@ int amvs_mesh_decimate_quadric(amvs_ctx *c, const float origin[3], float cell, f
     if (!(cell > 0.0f) || !std::isfinite(cell)) return fail(c, AMVS_EINVAL, "mesh_decimate_quadric: cell must be positive and finite");
     if (!(regularisation > 0.0f && regularisation <= 1.0f))
         return fail(c, AMVS_EINVAL, "mesh_decimate_quadric: regularisation must be in (0, 1]");
-    if (!amvs::tsdf_has_mesh(c->tsdf.get()))
-        return fail(c, AMVS_EINVAL, "mesh_decimate_quadric: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    if (int rc = need_mesh(c, "mesh_decimate_quadric")) return rc;
     int rc = bind_device(c);
     if (rc) return rc;
     long long bad = -1, nv = 0, nf = 0, nk = 0;
-    const hipError_t e = amvs::mesh_decimate_quadric(c->tsdf.get(), c->cache, origin, cell, regularisation, &bad, &nv, &nf, &nk, c->stream);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_decimate_quadric: ") + hipGetErrorString(e));
+    MESH_HIPCHK(c, "mesh_decimate_quadric", amvs::mesh_decimate_quadric(c->tsdf.get(), c->cache, origin, cell, regularisation, &bad,
+                &nv, &nf, &nk, c->stream));
     if (bad >= 0) return fail(c, AMVS_EINVAL, "mesh_decimate_quadric: vertex " + std::to_string(bad) + " outside the cluster grid");
     *n_vertices = nv; *n_faces = nf; *n_fallback = nk;
     return checked(c, AMVS_OK);
@@ -211,8 +222,7 @@ int amvs_mesh_decimate_quadric(amvs_ctx *c, const float origin[3], float cell, f
 int amvs_fetch_mesh_attributes(amvs_ctx *c, float *normals, int32_t *labels)
 {
     if (!c) return AMVS_EINVAL;
-    if (!amvs::tsdf_has_mesh(c->tsdf.get()))
-        return fail(c, AMVS_EINVAL, "fetch_mesh_attributes: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    if (int rc = need_mesh(c, "fetch_mesh_attributes")) return rc;
     if (normals && !amvs::mesh_has_normals(c->tsdf.get()))
         return fail(c, AMVS_EINVAL, "fetch_mesh_attributes: no current normals (amvs_mesh_normals)");
     if (labels && !amvs::mesh_has_labels(c->tsdf.get()))
@@ -236,7 +246,7 @@ int amvs_set_render_tuning(amvs_ctx *c, int large_face_pixels)
 int amvs_mesh_render(amvs_ctx *c, int n_views, const float K[9], const float *poses, float near, int64_t *n_skipped)
 {
     if (!c) return AMVS_EINVAL;
-    if (!amvs::tsdf_has_mesh(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_render: no mesh (amvs_tsdf_extract or amvs_mesh_set)");
+    if (int rc = need_mesh(c, "mesh_render")) return rc;
     if (n_views < 1) return fail(c, AMVS_EINVAL, "mesh_render: n_views must be >= 1");
     if (!K || !poses) return fail(c, AMVS_EINVAL, "mesh_render: NULL K or poses");
     if (!(near > 0.0f) || !std::isfinite(near)) return fail(c, AMVS_EINVAL, "mesh_render: near must be positive and finite");
@@ -250,9 +260,8 @@ int amvs_mesh_render(amvs_ctx *c, int n_views, const float K[9], const float *po
     int rc = bind_device(c);
     if (rc) return rc;
     std::vector<long long> skipped(n_skipped ? (size_t)n_views : 0);
-    const hipError_t e = amvs::mesh_render(c->tsdf.get(), c->cache, n_views, c->H, c->W, K, poses, near,
-                                           n_skipped ? skipped.data() : nullptr, c->stream);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_render: ") + hipGetErrorString(e));
+    MESH_HIPCHK(c, "mesh_render", amvs::mesh_render(c->tsdf.get(), c->cache, n_views, c->H, c->W, K, poses, near,
+                n_skipped ? skipped.data() : nullptr, c->stream));
     for (size_t m = 0; m < skipped.size(); ++m) n_skipped[m] = skipped[m];
     return checked(c, AMVS_OK);
 }
@@ -280,8 +289,7 @@ int amvs_mesh_visibility(amvs_ctx *c, float depth_tolerance, int64_t *n_seen)
     int rc = bind_device(c);
     if (rc) return rc;
     long long seen = 0;
-    const hipError_t e = amvs::mesh_visibility(c->tsdf.get(), c->cache, depth_tolerance, &seen, c->stream);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_visibility: ") + hipGetErrorString(e));
+    MESH_HIPCHK(c, "mesh_visibility", amvs::mesh_visibility(c->tsdf.get(), c->cache, depth_tolerance, &seen, c->stream));
     if (n_seen) *n_seen = seen;
     return checked(c, AMVS_OK);
 }
@@ -308,8 +316,7 @@ int amvs_mesh_filter_visible(amvs_ctx *c, int min_views, int64_t *n_vertices, in
     int rc = bind_device(c);
     if (rc) return rc;
     long long nv = 0, nf = 0;
-    const hipError_t e = amvs::mesh_filter_visible(c->tsdf.get(), c->cache, min_views, &nv, &nf, c->stream);
-    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("mesh_filter_visible: ") + hipGetErrorString(e));
+    MESH_HIPCHK(c, "mesh_filter_visible", amvs::mesh_filter_visible(c->tsdf.get(), c->cache, min_views, &nv, &nf, c->stream));
     *n_vertices = nv; *n_faces = nf;
     return checked(c, AMVS_OK);
 }

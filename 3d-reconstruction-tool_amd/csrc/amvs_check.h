@@ -10,7 +10,10 @@
 // the record.  In the shipped build the macros are the identity and cost nothing.
 //
 // A translation unit defines AMVS_TU_ID (a small integer, see amvs_context.hip: index_report) before including this
-// header and places AMVS_CHECK_TU(name) once at file scope (outside any namespace).
+// header and places AMVS_CHECK_TU(name) once at file scope (outside any namespace).  A violation is recorded with the
+// id of the unit that compiles the kernel and the __LINE__ of the file that holds the AMVS_IDX: a checked kernel
+// belongs in a .hip file, not in a header that several units include (the mesh units' shared kernels are in
+// amvs_mesh.hip for that reason).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -36,6 +36,8 @@
 #include "amvs_kernels.h"
 #include "amvs_mesh_state.h"
 
+#include <hipcub/hipcub.hpp>
+
 namespace amvs {
 
 namespace {
@@ -59,8 +61,6 @@ __constant__ unsigned char k_tet_c1[6] = {1, 1, 2, 2, 4, 4};
 __constant__ unsigned char k_tet_c2[6] = {3, 5, 3, 6, 5, 6};
 
 __device__ __forceinline__ int tri_count(unsigned c) { const int b = __popc(c); return b == 2 ? 2 : (b & 1); }
-
-struct Kmat { float k[9]; };
 
 __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const float *__restrict__ depth, const float *__restrict__ conf,
                                                              long long map_elems, const unsigned char *__restrict__ bgr,
@@ -261,9 +261,141 @@ __global__ __launch_bounds__(256) void face_kernel(const float *__restrict__ tsd
     }
 }
 
+// (d) drop the vertices no face uses (their edges are shared only by tetrahedra with an unobserved corner):
+// flag the used ones (every writer stores the same 1), scan, move the kept vertices down, renumber the faces
+__global__ __launch_bounds__(256) void vertex_used_kernel(const int *__restrict__ faces, long long n_ids, long long n_vertices,
+                                                          unsigned *__restrict__ used)
+{
+    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < n_ids) used[AMVS_IDX((long long)faces[f], n_vertices)] = 1u;
+}
+
+__global__ __launch_bounds__(256) void vertex_compact_kernel(const float *__restrict__ verts, const unsigned char *__restrict__ rgb,
+                                                             const unsigned *__restrict__ used, const unsigned *__restrict__ new_id,
+                                                             long long n_vertices, long long n_kept, float *__restrict__ verts_out,
+                                                             unsigned char *__restrict__ rgb_out)
+{
+    const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_vertices || !used[v]) return;
+    const long long o = AMVS_IDX((long long)new_id[v], n_kept);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { verts_out[3 * o + c] = verts[3 * v + c]; rgb_out[3 * o + c] = rgb[3 * v + c]; }
+}
+
+__global__ __launch_bounds__(256) void face_renumber_kernel(int *__restrict__ faces, long long n_ids, long long n_vertices,
+                                                            const unsigned *__restrict__ new_id)
+{
+    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < n_ids) faces[f] = (int)new_id[AMVS_IDX((long long)faces[f], n_vertices)];
+}
+
+// the kept faces in their order, each in its own corner order; MAPPED: the ids through vertex_map (n_vertices entries)
+template <bool MAPPED>
+__global__ __launch_bounds__(256) void face_compact_kernel(const int *__restrict__ faces, const unsigned *__restrict__ vertex_map,
+                                                           const unsigned *__restrict__ keep, const unsigned *__restrict__ new_id,
+                                                           long long n_faces, long long n_vertices, long long n_kept,
+                                                           int *__restrict__ out)
+{
+    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n_faces || !keep[f]) return;
+    const long long o = AMVS_IDX((long long)new_id[f], n_kept);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (MAPPED) out[3 * o + k] = (int)vertex_map[AMVS_IDX((long long)faces[3 * f + k], n_vertices)];
+        else out[3 * o + k] = faces[3 * f + k];
+    }
+}
+
 }  // namespace
 
-// TsdfState, the scans and pass (d): amvs_mesh_state.h
+// ---- what the mesh units share (amvs_mesh_state.h) -----------------------------------------------------------
+
+hipError_t exclusive_scan(TsdfState *s, ScratchCache &cache, const unsigned *in, unsigned *out, long long n, hipStream_t st)
+{
+    size_t bytes = 0;
+    MCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, st));
+    MCHK(s->scan_tmp.reserve(bytes > 0 ? bytes : 1, cache));
+    return hipcub::DeviceScan::ExclusiveSum(s->scan_tmp.get(), bytes, in, out, (int)n, st);
+}
+
+hipError_t scan_total(const unsigned *count, const unsigned *base, long long n, long long *total, hipStream_t st)
+{
+    unsigned h[2] = {0, 0};
+    MCHK(hipMemcpyAsync(&h[0], count + n - 1, 4, hipMemcpyDeviceToHost, st));
+    MCHK(hipMemcpyAsync(&h[1], base + n - 1, 4, hipMemcpyDeviceToHost, st));
+    MCHK(hipStreamSynchronize(st));
+    *total = (long long)h[0] + (long long)h[1];
+    return hipSuccess;
+}
+
+int bits_for(long long n)
+{
+    int bits = 1;
+    while (bits < 32 && (1ll << bits) < n) ++bits;
+    return bits;
+}
+
+template <class K>
+hipError_t sort_pairs(TsdfState *s, ScratchCache &cache, const K *key_in, K *key_out, const unsigned *val_in, unsigned *val_out,
+                      long long n, int bits, hipStream_t st)
+{
+    size_t bytes = 0;
+    MCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key_in, key_out, val_in, val_out, (int)n, 0, bits, st));
+    MCHK(s->scan_tmp.reserve(bytes > 0 ? bytes : 1, cache));
+    return hipcub::DeviceRadixSort::SortPairs(s->scan_tmp.get(), bytes, key_in, key_out, val_in, val_out, (int)n, 0, bits, st);
+}
+template hipError_t sort_pairs(TsdfState *, ScratchCache &, const unsigned *, unsigned *, const unsigned *, unsigned *, long long, int,
+                               hipStream_t);
+template hipError_t sort_pairs(TsdfState *, ScratchCache &, const unsigned long long *, unsigned long long *, const unsigned *,
+                               unsigned *, long long, int, hipStream_t);
+
+hipError_t compact_faces(TsdfState *s, ScratchCache &cache, long long nv, long long nf, const unsigned *vertex_map,
+                         long long *kept_f, hipStream_t st)
+{
+    *kept_f = 0;
+    if (nf == 0) return hipSuccess;
+    MCHK(s->fnew.reserve((size_t)nf, cache)); MCHK(s->faces2.reserve(3 * (size_t)nf, cache));
+    MCHK(exclusive_scan(s, cache, s->fkeep.get(), s->fnew.get(), nf, st));
+    MCHK(scan_total(s->fkeep.get(), s->fnew.get(), nf, kept_f, st));
+    if (*kept_f == nf && !vertex_map) return hipSuccess;      // every face stays as it is
+    s->topology_changed();
+    if (*kept_f == 0) return hipSuccess;
+    const auto kernel = vertex_map ? face_compact_kernel<true> : face_compact_kernel<false>;
+    MCHK(launch(kernel, nf, st, s->faces.get(), vertex_map, s->fkeep.get(), s->fnew.get(), nf, nv, *kept_f, s->faces2.get()));
+    std::swap(s->faces, s->faces2);
+    return hipSuccess;
+}
+
+hipError_t drop_unused_vertices(TsdfState *s, ScratchCache &cache, long long nv, long long nf, long long *kept_v, hipStream_t st)
+{
+    *kept_v = 0;
+    if (nv > 0 && nf > 0) {
+        MCHK(hipMemsetAsync(s->vused.get(), 0, 4 * (size_t)nv, st));
+        MCHK(launch(vertex_used_kernel, 3 * nf, st, s->faces.get(), 3 * nf, nv, s->vused.get()));
+        MCHK(exclusive_scan(s, cache, s->vused.get(), s->vnew.get(), nv, st));
+        MCHK(scan_total(s->vused.get(), s->vnew.get(), nv, kept_v, st));
+    }
+    if (*kept_v == nv) return hipSuccess;                     // every vertex is used: the new ids are the old ones
+    s->topology_changed();
+    if (*kept_v == 0) return hipSuccess;
+    MCHK(launch(vertex_compact_kernel, nv, st, s->verts.get(), s->rgb.get(), s->vused.get(), s->vnew.get(), nv, *kept_v,
+                s->verts2.get(), s->rgb2.get()));
+    MCHK(launch(face_renumber_kernel, 3 * nf, st, s->faces.get(), 3 * nf, nv, s->vnew.get()));
+    std::swap(s->verts, s->verts2);
+    std::swap(s->rgb, s->rgb2);
+    return hipSuccess;
+}
+
+hipError_t compact_mesh(TsdfState *s, ScratchCache &cache, Compaction *out, hipStream_t st)
+{
+    const long long nv = s->n_vertices, nf = s->n_faces;
+    MCHK(compact_faces(s, cache, nv, nf, nullptr, &out->kept_f, st));
+    MCHK(drop_unused_vertices(s, cache, nv, out->kept_f, &out->kept_v, st));
+    out->removed = out->kept_f < nf || out->kept_v < nv;
+    s->n_vertices = out->kept_v; s->n_faces = out->kept_f;
+    return hipSuccess;
+}
+
 TsdfState *tsdf_state_new() { return new TsdfState(); }
 
 void tsdf_state_free(TsdfState *s) { delete s; }
@@ -312,10 +444,8 @@ hipError_t tsdf_integrate(TsdfState *s, ScratchCache &cache, const float *depth,
     s->n = n;
     Kmat km;
     for (int q = 0; q < 9; ++q) km.k[q] = K[q];
-    hipLaunchKernelGGL(tsdf_integrate_kernel, grid_of(n), dim3(256), 0, st, depth, conf, (long long)nmap, bgr,
-                       (long long)(hw * (size_t)bgr_images), (const int *)s->slots.get(), (const float *)s->cams.get(), km, n_maps,
-                       H, W, min_views, trunc, s->g, s->tsdf.get(), s->weight.get(), s->color.get());
-    MCHK(hipGetLastError());
+    MCHK(launch(tsdf_integrate_kernel, n, st, depth, conf, (long long)nmap, bgr, (long long)(hw * (size_t)bgr_images), s->slots.get(),
+                s->cams.get(), km, n_maps, H, W, min_views, trunc, s->g, s->tsdf.get(), s->weight.get(), s->color.get()));
     MCHK(hipStreamSynchronize(st));
     s->have_volume = true;
     return hipSuccess;
@@ -343,9 +473,7 @@ hipError_t tsdf_extract(TsdfState *s, ScratchCache &cache, long long *n_vertices
     s->drop_mesh();
     const long long n = s->n;
     // (a) vertices
-    hipLaunchKernelGGL(edge_mask_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf.get(), (const float *)s->weight.get(),
-                       s->g, s->mask.get(), s->vcount.get());
-    MCHK(hipGetLastError());
+    MCHK(launch(edge_mask_kernel, n, st, s->tsdf.get(), s->weight.get(), s->g, s->mask.get(), s->vcount.get()));
     MCHK(exclusive_scan(s, cache, s->vcount.get(), s->vbase.get(), n, st));
     long long nv = 0;
     MCHK(scan_total(s->vcount.get(), s->vbase.get(), n, &nv, st));
@@ -353,28 +481,20 @@ hipError_t tsdf_extract(TsdfState *s, ScratchCache &cache, long long *n_vertices
     MCHK(s->verts.reserve(3 * m, cache)); MCHK(s->rgb.reserve(3 * m, cache));
     MCHK(s->verts2.reserve(3 * m, cache)); MCHK(s->rgb2.reserve(3 * m, cache));
     MCHK(s->vused.reserve(m, cache)); MCHK(s->vnew.reserve(m, cache));
-    hipLaunchKernelGGL(vertex_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf.get(), (const float *)s->weight.get(),
-                       (const float *)s->color.get(), s->g, (const unsigned char *)s->mask.get(), (const unsigned *)s->vbase.get(), nv,
-                       s->verts.get(), s->rgb.get());
-    MCHK(hipGetLastError());
+    MCHK(launch(vertex_kernel, n, st, s->tsdf.get(), s->weight.get(), s->color.get(), s->g, s->mask.get(), s->vbase.get(), nv,
+                s->verts.get(), s->rgb.get()));
     // (b) triangle counts
-    hipLaunchKernelGGL(tri_count_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf.get(), (const float *)s->weight.get(),
-                       s->g, s->tcount.get());
-    MCHK(hipGetLastError());
+    MCHK(launch(tri_count_kernel, n, st, s->tsdf.get(), s->weight.get(), s->g, s->tcount.get()));
     MCHK(exclusive_scan(s, cache, s->tcount.get(), s->tbase.get(), n, st));
     long long nf = 0;
     MCHK(scan_total(s->tcount.get(), s->tbase.get(), n, &nf, st));
     MCHK(s->faces.reserve(3 * (size_t)(nf > 0 ? nf : 1), cache));
     // (c) faces
-    hipLaunchKernelGGL(face_kernel, grid_of(n), dim3(256), 0, st, (const float *)s->tsdf.get(), (const float *)s->weight.get(), s->g,
-                       (const unsigned char *)s->mask.get(), (const unsigned *)s->vbase.get(), nv, (const unsigned *)s->tcount.get(),
-                       (const unsigned *)s->tbase.get(), nf, s->faces.get());
-    MCHK(hipGetLastError());
+    MCHK(launch(face_kernel, n, st, s->tsdf.get(), s->weight.get(), s->g, s->mask.get(), s->vbase.get(), nv, s->tcount.get(),
+                s->tbase.get(), nf, s->faces.get()));
     // (d) keep the vertices the faces use, in their order
     long long kept = 0;
-    if (nv > 0 && nf > 0) {
-        MCHK(drop_unused_vertices(s, cache, nv, nf, &kept, st));
-    }
+    MCHK(drop_unused_vertices(s, cache, nv, nf, &kept, st));
     nv = kept;
     MCHK(hipStreamSynchronize(st));
     s->n_vertices = nv; s->n_faces = nf; s->have_mesh = true;

@@ -150,17 +150,6 @@ __global__ __launch_bounds__(256) void face_keep_kernel(const int *__restrict__ 
     keep[f] = k ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(256) void face_compact_kernel(const int *__restrict__ faces, const unsigned *__restrict__ keep,
-                                                           const unsigned *__restrict__ new_id, long long n_faces, long long n_kept,
-                                                           int *__restrict__ out)
-{
-    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= n_faces || !keep[f]) return;
-    const long long o = AMVS_IDX((long long)new_id[f], n_kept);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[3 * o + k] = faces[3 * f + k];
-}
-
 // after the vertices moved (order kept): the label of a kept vertex is the new id of its old label vertex
 __global__ __launch_bounds__(256) void relabel_kernel(const int *__restrict__ labels, const unsigned *__restrict__ used,
                                                       const unsigned *__restrict__ new_id, long long n_vertices, long long n_kept,
@@ -259,11 +248,9 @@ __global__ __launch_bounds__(256) void vertex_normal_kernel(const float *__restr
     normals[3 * v + 2] = ok ? sz / l : 0.0f;
 }
 
-// ---- host --------------------------------------------------------------------------------------------------
-
-inline size_t at_least_one(long long n) { return (size_t)(n > 0 ? n : 1); }
-
 }  // namespace
+
+// ---- host --------------------------------------------------------------------------------------------------
 
 // (a): row_start[0 .. V] and corners[0 .. 3 F) of the current faces
 hipError_t ensure_index(TsdfState *s, ScratchCache &cache, hipStream_t st)
@@ -275,20 +262,12 @@ hipError_t ensure_index(TsdfState *s, ScratchCache &cache, hipStream_t st)
     MCHK(s->corner_id.reserve(at_least_one(nc), cache)); MCHK(s->corners.reserve(at_least_one(nc), cache));
     MCHK(hipMemsetAsync(s->row_count.get(), 0, 4 * ((size_t)nv + 1), st));
     if (nc > 0) {
-        hipLaunchKernelGGL(corner_count_kernel, grid_of(nc), dim3(256), 0, st, (const int *)s->faces.get(), nc, nv, s->row_count.get(),
-                           s->corner_key.get(), s->corner_id.get());
-        MCHK(hipGetLastError());
+        MCHK(launch(corner_count_kernel, nc, st, s->faces.get(), nc, nv, s->row_count.get(), s->corner_key.get(), s->corner_id.get()));
     }
     MCHK(exclusive_scan(s, cache, s->row_count.get(), s->row_start.get(), nv + 1, st));
     if (nc > 0) {
-        int bits = 1;
-        while (bits < 32 && (1ll << bits) < nv) ++bits;
-        size_t bytes = 0;
-        MCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const unsigned *)s->corner_key.get(), s->corner_key2.get(),
-                                                (const unsigned *)s->corner_id.get(), s->corners.get(), (int)nc, 0, bits, st));
-        MCHK(s->scan_tmp.reserve(bytes > 0 ? bytes : 1, cache));
-        MCHK(hipcub::DeviceRadixSort::SortPairs(s->scan_tmp.get(), bytes, (const unsigned *)s->corner_key.get(), s->corner_key2.get(),
-                                                (const unsigned *)s->corner_id.get(), s->corners.get(), (int)nc, 0, bits, st));
+        MCHK(sort_pairs(s, cache, (const unsigned *)s->corner_key.get(), s->corner_key2.get(), (const unsigned *)s->corner_id.get(),
+                        s->corners.get(), nc, bits_for(nv), st));
     }
     s->have_csr = true;
     return hipSuccess;
@@ -300,9 +279,7 @@ hipError_t mesh_face_normals(TsdfState *s, ScratchCache &cache, hipStream_t st)
     const long long nv = s->n_vertices, nf = s->n_faces;
     MCHK(s->face_normal.reserve(3 * at_least_one(nf), cache));
     if (nf > 0) {
-        hipLaunchKernelGGL(face_normal_kernel, grid_of(nf), dim3(256), 0, st, (const float *)s->verts.get(), (const int *)s->faces.get(), nf,
-                           nv, s->face_normal.get());
-        MCHK(hipGetLastError());
+        MCHK(launch(face_normal_kernel, nf, st, s->verts.get(), s->faces.get(), nf, nv, s->face_normal.get()));
     }
     return hipSuccess;
 }
@@ -317,9 +294,7 @@ hipError_t ensure_pinned(TsdfState *s, ScratchCache &cache, hipStream_t st)
     MCHK(s->pinned.reserve(at_least_one(nv), cache));
     if (nv > 0) MCHK(hipMemsetAsync(s->pinned.get(), 0, (size_t)nv, st));
     if (nc > 0) {
-        hipLaunchKernelGGL(pinned_kernel, grid_of(nc), dim3(256), 0, st, (const int *)s->faces.get(), (const unsigned *)s->row_start.get(),
-                           (const unsigned *)s->corners.get(), nc, nv, s->pinned.get());
-        MCHK(hipGetLastError());
+        MCHK(launch(pinned_kernel, nc, st, s->faces.get(), s->row_start.get(), s->corners.get(), nc, nv, s->pinned.get()));
     }
     s->have_pinned = true;
     return hipSuccess;
@@ -335,19 +310,13 @@ hipError_t label_components(TsdfState *s, ScratchCache &cache, long long *n_comp
     *n_components = 0;
     if (nv == 0) return hipSuccess;
     MCHK(hipMemsetAsync(s->comp_faces.get(), 0, 4 * (size_t)nv, st));
-    hipLaunchKernelGGL(iota_kernel, grid_of(nv), dim3(256), 0, st, s->parent.get(), nv);
-    MCHK(hipGetLastError());
+    MCHK(launch(iota_kernel, nv, st, s->parent.get(), nv));
     if (nf > 0) {
-        hipLaunchKernelGGL(uf_hook_kernel, grid_of(nf), dim3(256), 0, st, (const int *)s->faces.get(), nf, nv, s->parent.get());
-        MCHK(hipGetLastError());
+        MCHK(launch(uf_hook_kernel, nf, st, s->faces.get(), nf, nv, s->parent.get()));
     }
-    hipLaunchKernelGGL(uf_flatten_kernel, grid_of(nv), dim3(256), 0, st, (const int *)s->parent.get(), nv, s->labels.get(),
-                       s->comp_stat.get());
-    MCHK(hipGetLastError());
+    MCHK(launch(uf_flatten_kernel, nv, st, s->parent.get(), nv, s->labels.get(), s->comp_stat.get()));
     if (nf > 0) {
-        hipLaunchKernelGGL(comp_faces_kernel, grid_of(nf), dim3(256), 0, st, (const int *)s->faces.get(), (const int *)s->labels.get(), nf,
-                           nv, s->comp_faces.get());
-        MCHK(hipGetLastError());
+        MCHK(launch(comp_faces_kernel, nf, st, s->faces.get(), s->labels.get(), nf, nv, s->comp_faces.get()));
     }
     unsigned long long h = 0;
     MCHK(hipMemcpyAsync(&h, s->comp_stat.get(), 8, hipMemcpyDeviceToHost, st));
@@ -381,8 +350,8 @@ hipError_t mesh_set(TsdfState *s, ScratchCache &cache, const float *verts, long 
 hipError_t mesh_filter_components(TsdfState *s, ScratchCache &cache, long long min_faces, bool keep_largest, long long *n_components,
                                   long long *n_vertices, long long *n_faces, hipStream_t st)
 {
-    s->have_labels = s->have_normals = false;
-    s->drop_views();
+    s->have_labels = false;
+    s->positions_changed();           // nothing moves, but normals and render do not outlive a labelling
     const long long nv = s->n_vertices, nf = s->n_faces;
     MCHK(label_components(s, cache, n_components, st));
     *n_vertices = nv; *n_faces = nf;
@@ -390,61 +359,35 @@ hipError_t mesh_filter_components(TsdfState *s, ScratchCache &cache, long long m
     if ((min_faces <= 0 && !keep_largest) || nv == 0) return hipSuccess;
     int only_label = -1;
     if (keep_largest) {
-        hipLaunchKernelGGL(comp_largest_kernel, grid_of(nv), dim3(256), 0, st, (const int *)s->labels.get(),
-                           (const unsigned *)s->comp_faces.get(), nv, s->comp_stat.get());
-        MCHK(hipGetLastError());
+        MCHK(launch(comp_largest_kernel, nv, st, s->labels.get(), s->comp_faces.get(), nv, s->comp_stat.get()));
         unsigned long long h = 0;
         MCHK(hipMemcpyAsync(&h, s->comp_stat.get() + 1, 8, hipMemcpyDeviceToHost, st));
         MCHK(hipStreamSynchronize(st));
         only_label = (int)(0xFFFFFFFFull - (h & 0xFFFFFFFFull));
     }
-    s->have_labels = false;
-    long long kept_f = 0, kept_v = 0;
+    s->have_labels = false;           // until they are in the numbering of what stays
     if (nf > 0) {
-        MCHK(s->fkeep.reserve((size_t)nf, cache)); MCHK(s->fnew.reserve((size_t)nf, cache)); MCHK(s->faces2.reserve(3 * (size_t)nf, cache));
-        hipLaunchKernelGGL(face_keep_kernel, grid_of(nf), dim3(256), 0, st, (const int *)s->faces.get(), (const int *)s->labels.get(),
-                           (const unsigned *)s->comp_faces.get(), nf, nv, min_faces, only_label, s->fkeep.get());
-        MCHK(hipGetLastError());
-        MCHK(exclusive_scan(s, cache, s->fkeep.get(), s->fnew.get(), nf, st));
-        MCHK(scan_total(s->fkeep.get(), s->fnew.get(), nf, &kept_f, st));
+        MCHK(s->fkeep.reserve((size_t)nf, cache));
+        MCHK(launch(face_keep_kernel, nf, st, s->faces.get(), s->labels.get(), s->comp_faces.get(), nf, nv, min_faces, only_label,
+                    s->fkeep.get()));
     }
-    if (kept_f == nf && nf > 0) {
-        // every face stays; vertices leave only if some are isolated
-        MCHK(hipMemsetAsync(s->vused.get(), 0, 4 * (size_t)nv, st));
-        hipLaunchKernelGGL(vertex_used_kernel, grid_of(3 * nf), dim3(256), 0, st, (const int *)s->faces.get(), 3 * nf, nv, s->vused.get());
-        MCHK(hipGetLastError());
-        MCHK(exclusive_scan(s, cache, s->vused.get(), s->vnew.get(), nv, st));
-        MCHK(scan_total(s->vused.get(), s->vnew.get(), nv, &kept_v, st));
-        if (kept_v == nv) { s->have_labels = true; return hipSuccess; }      // nothing to remove: the index stays too
-    }
-    s->have_csr = s->have_pinned = false;
-    if (kept_f > 0) {
-        if (kept_f < nf) {
-            hipLaunchKernelGGL(face_compact_kernel, grid_of(nf), dim3(256), 0, st, (const int *)s->faces.get(),
-                               (const unsigned *)s->fkeep.get(), (const unsigned *)s->fnew.get(), nf, kept_f, s->faces2.get());
-            MCHK(hipGetLastError());
-            std::swap(s->faces, s->faces2);
-        }
-        MCHK(drop_unused_vertices(s, cache, nv, kept_f, &kept_v, st));
+    Compaction k;
+    MCHK(compact_mesh(s, cache, &k, st));
+    if (!k.removed) { s->have_labels = true; return hipSuccess; }        // the mesh is as it was: the index stays too
+    if (k.kept_f > 0) {
         // labels into the new numbering (parent serves as the second buffer)
-        hipLaunchKernelGGL(relabel_kernel, grid_of(nv), dim3(256), 0, st, (const int *)s->labels.get(), (const unsigned *)s->vused.get(),
-                           (const unsigned *)s->vnew.get(), nv, kept_v, s->parent.get());
-        MCHK(hipGetLastError());
+        MCHK(launch(relabel_kernel, nv, st, s->labels.get(), s->vused.get(), s->vnew.get(), nv, k.kept_v, s->parent.get()));
         std::swap(s->labels, s->parent);
-    } else {
-        kept_v = 0;
     }
     MCHK(hipStreamSynchronize(st));
-    s->n_vertices = kept_v; s->n_faces = kept_f;
     s->have_labels = true;
-    *n_vertices = kept_v; *n_faces = kept_f;
+    *n_vertices = k.kept_v; *n_faces = k.kept_f;
     return hipSuccess;
 }
 
 hipError_t mesh_smooth(TsdfState *s, ScratchCache &cache, int iterations, float lambda, float mu, bool fix_boundary, hipStream_t st)
 {
-    s->have_normals = false;
-    s->drop_views();
+    s->positions_changed();
     const long long nv = s->n_vertices, nc = 3 * s->n_faces;
     if (iterations > 0 && nv > 0) {
         MCHK(ensure_index(s, cache, st));
@@ -454,10 +397,8 @@ hipError_t mesh_smooth(TsdfState *s, ScratchCache &cache, int iterations, float 
         for (int it = 0; it < iterations; ++it)
             for (int half = 0; half < 2; ++half) {
                 if (half == 1 && mu == 0.0f) continue;
-                hipLaunchKernelGGL(umbrella_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->verts.get(), (const int *)s->faces.get(),
-                                   (const unsigned *)s->row_start.get(), (const unsigned *)s->corners.get(), pin, nc, nv,
-                                   half == 0 ? lambda : mu, s->verts2.get());
-                MCHK(hipGetLastError());
+                MCHK(launch(umbrella_kernel, nv, st, s->verts.get(), s->faces.get(), s->row_start.get(), s->corners.get(), pin, nc, nv,
+                            half == 0 ? lambda : mu, s->verts2.get()));
                 std::swap(s->verts, s->verts2);
             }
     }
@@ -472,9 +413,8 @@ hipError_t mesh_normals(TsdfState *s, ScratchCache &cache, hipStream_t st)
     MCHK(s->normals.reserve(3 * at_least_one(nv), cache));
     MCHK(mesh_face_normals(s, cache, st));
     if (nv > 0) {
-        hipLaunchKernelGGL(vertex_normal_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->face_normal.get(),
-                           (const unsigned *)s->row_start.get(), (const unsigned *)s->corners.get(), 3 * nf, nv, s->normals.get());
-        MCHK(hipGetLastError());
+        MCHK(launch(vertex_normal_kernel, nv, st, s->face_normal.get(), s->row_start.get(), s->corners.get(), 3 * nf, nv,
+                    s->normals.get()));
     }
     MCHK(hipStreamSynchronize(st));
     s->have_normals = true;

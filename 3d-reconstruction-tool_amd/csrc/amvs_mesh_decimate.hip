@@ -182,19 +182,6 @@ __global__ __launch_bounds__(256) void group_decide_kernel(const unsigned *__res
     else if (net < 0) keep[first_odd] = 1u;
 }
 
-// (4) the kept faces in their order, in cluster ids and their own corner order
-__global__ __launch_bounds__(256) void face_keep_mapped_kernel(const int *__restrict__ faces, const unsigned *__restrict__ cluster_of,
-                                                               const unsigned *__restrict__ keep, const unsigned *__restrict__ new_id,
-                                                               long long n_faces, long long n_vertices, long long n_kept,
-                                                               int *__restrict__ out)
-{
-    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= n_faces || !keep[f]) return;
-    const long long o = AMVS_IDX((long long)new_id[f], n_kept);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[3 * o + k] = (int)cluster_of[AMVS_IDX((long long)faces[3 * f + k], n_vertices)];
-}
-
 // quadric placement: one thread per old vertex walks its row of the vertex -> corner index; mean = the representatives
 __global__ __launch_bounds__(256) void vertex_quadric_kernel(const float *__restrict__ verts, const int *__restrict__ faces,
                                                              const float *__restrict__ fn, const unsigned *__restrict__ row_start,
@@ -261,24 +248,6 @@ __global__ __launch_bounds__(256) void cluster_solve_kernel(const float *__restr
     if (kept && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)kept) - 1)) atomicAdd(n_fallback, (unsigned)__popcll(kept));
 }
 
-inline int bits_for(long long n)
-{
-    int bits = 1;
-    while (bits < 32 && (1ll << bits) < n) ++bits;
-    return bits;
-}
-
-// stable sort of (key, value) pairs on the low `bits` bits of the key
-template <class K>
-hipError_t sort_pairs(TsdfState *s, ScratchCache &cache, const K *key_in, K *key_out, const unsigned *val_in, unsigned *val_out,
-                      long long n, int bits, hipStream_t st)
-{
-    size_t bytes = 0;
-    MCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key_in, key_out, val_in, val_out, (int)n, 0, bits, st));
-    MCHK(s->scan_tmp.reserve(bytes > 0 ? bytes : 1, cache));
-    return hipcub::DeviceRadixSort::SortPairs(s->scan_tmp.get(), bytes, key_in, key_out, val_in, val_out, (int)n, 0, bits, st);
-}
-
 // both placements: quadric == false is mesh_decimate, launch for launch
 hipError_t decimate(TsdfState *s, ScratchCache &cache, const float origin[3], float cell, bool quadric, float regularisation,
                     long long *bad_vertex, long long *n_vertices, long long *n_faces, long long *n_fallback, hipStream_t st)
@@ -296,24 +265,19 @@ hipError_t decimate(TsdfState *s, ScratchCache &cache, const float origin[3], fl
         MCHK(s->dec_cluster.reserve((size_t)nv, cache)); MCHK(s->dec_start.reserve((size_t)nv + 1, cache));
         MCHK(s->dec_flag.reserve(2, cache));
         MCHK(hipMemsetAsync(s->dec_flag.get(), 0xFF, 4, st));
-        hipLaunchKernelGGL(cell_key_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->verts.get(), nv,
-                           Cells{origin[0], origin[1], origin[2], cell}, s->dec_key.get(), s->dec_id.get(), s->dec_flag.get());
-        MCHK(hipGetLastError());
+        MCHK(launch(cell_key_kernel, nv, st, s->verts.get(), nv, Cells{origin[0], origin[1], origin[2], cell}, s->dec_key.get(),
+                    s->dec_id.get(), s->dec_flag.get()));
         unsigned bad = DEC_NONE;
         MCHK(hipMemcpyAsync(&bad, s->dec_flag.get(), 4, hipMemcpyDeviceToHost, st));
         MCHK(hipStreamSynchronize(st));
         if (bad != DEC_NONE) { *bad_vertex = (long long)bad; return hipSuccess; }
         MCHK(sort_pairs(s, cache, (const unsigned long long *)s->dec_key.get(), s->dec_key2.get(), (const unsigned *)s->dec_id.get(),
                         s->dec_id2.get(), nv, 63, st));
-        hipLaunchKernelGGL(key_head_kernel, grid_of(nv), dim3(256), 0, st, (const unsigned long long *)s->dec_key2.get(), nv,
-                           s->dec_head.get());
-        MCHK(hipGetLastError());
+        MCHK(launch(key_head_kernel, nv, st, s->dec_key2.get(), nv, s->dec_head.get()));
         MCHK(exclusive_scan(s, cache, s->dec_head.get(), s->dec_before.get(), nv, st));
         MCHK(scan_total(s->dec_head.get(), s->dec_before.get(), nv, &nc, st));
-        hipLaunchKernelGGL(cluster_map_kernel, grid_of(nv), dim3(256), 0, st, (const unsigned *)s->dec_id2.get(),
-                           (const unsigned *)s->dec_head.get(), (const unsigned *)s->dec_before.get(), nv, nc, s->dec_cluster.get(),
-                           s->dec_start.get());
-        MCHK(hipGetLastError());
+        MCHK(launch(cluster_map_kernel, nv, st, s->dec_id2.get(), s->dec_head.get(), s->dec_before.get(), nv, nc, s->dec_cluster.get(),
+                    s->dec_start.get()));
         if (place) {
             // the index and the face normals of the mesh as it still is
             MCHK(ensure_index(s, cache, st));
@@ -322,8 +286,7 @@ hipError_t decimate(TsdfState *s, ScratchCache &cache, const float origin[3], fl
         }
     }
     const int *const old_faces = s->faces.get();
-    s->have_csr = s->have_pinned = s->have_labels = s->have_normals = false;
-    s->drop_views();
+    s->topology_changed();
     long long kept_f = 0, kept_v = 0;
     if (nf > 0 && nv > 0) {
         // (4) before (3): the faces still hold the old ids
@@ -331,75 +294,54 @@ hipError_t decimate(TsdfState *s, ScratchCache &cache, const float origin[3], fl
         MCHK(s->dec_even.reserve((size_t)nf, cache));
         MCHK(s->dec_fkey.reserve((size_t)nf, cache)); MCHK(s->dec_fkey2.reserve((size_t)nf, cache));
         MCHK(s->dec_perm.reserve((size_t)nf, cache)); MCHK(s->dec_perm2.reserve((size_t)nf, cache));
-        MCHK(s->fkeep.reserve((size_t)nf, cache)); MCHK(s->fnew.reserve((size_t)nf, cache)); MCHK(s->faces2.reserve(3 * (size_t)nf, cache));
-        hipLaunchKernelGGL(face_triple_kernel, grid_of(nf), dim3(256), 0, st, (const int *)s->faces.get(),
-                           (const unsigned *)s->dec_cluster.get(), nf, nv, s->dec_ta.get(), s->dec_tlo.get(), s->dec_thi.get(),
-                           s->dec_even.get(), s->fkeep.get());
-        MCHK(hipGetLastError());
+        MCHK(s->fkeep.reserve((size_t)nf, cache)); MCHK(s->fnew.reserve((size_t)nf, cache));
+        MCHK(launch(face_triple_kernel, nf, st, s->faces.get(), s->dec_cluster.get(), nf, nv, s->dec_ta.get(), s->dec_tlo.get(),
+                    s->dec_thi.get(), s->dec_even.get(), s->fkeep.get()));
         long long n_live = 0;
         MCHK(exclusive_scan(s, cache, s->fkeep.get(), s->fnew.get(), nf, st));
         MCHK(scan_total(s->fkeep.get(), s->fnew.get(), nf, &n_live, st));
         if (n_live > 0) {
             const int bits = bits_for(nc);
-            hipLaunchKernelGGL(live_list_kernel, grid_of(nf), dim3(256), 0, st, (const unsigned *)s->fkeep.get(),
-                               (const unsigned *)s->fnew.get(), (const unsigned *)s->dec_thi.get(), nf, n_live, s->dec_perm.get(),
-                               s->dec_fkey.get());
-            MCHK(hipGetLastError());
+            MCHK(launch(live_list_kernel, nf, st, s->fkeep.get(), s->fnew.get(), s->dec_thi.get(), nf, n_live, s->dec_perm.get(),
+                        s->dec_fkey.get()));
             MCHK(sort_pairs(s, cache, (const unsigned *)s->dec_fkey.get(), s->dec_fkey2.get(), (const unsigned *)s->dec_perm.get(),
                             s->dec_perm2.get(), n_live, bits, st));
             const unsigned *const fields[2] = {s->dec_tlo.get(), s->dec_ta.get()};
             for (const unsigned *field : fields) {
                 std::swap(s->dec_perm, s->dec_perm2);
-                hipLaunchKernelGGL(gather_key_kernel, grid_of(n_live), dim3(256), 0, st, (const unsigned *)s->dec_perm.get(), field, n_live,
-                                   nf, s->dec_fkey.get());
-                MCHK(hipGetLastError());
+                MCHK(launch(gather_key_kernel, n_live, st, s->dec_perm.get(), field, n_live, nf, s->dec_fkey.get()));
                 MCHK(sort_pairs(s, cache, (const unsigned *)s->dec_fkey.get(), s->dec_fkey2.get(), (const unsigned *)s->dec_perm.get(),
                                 s->dec_perm2.get(), n_live, bits, st));
             }
             MCHK(hipMemsetAsync(s->fkeep.get(), 0, 4 * (size_t)nf, st));
-            hipLaunchKernelGGL(group_decide_kernel, grid_of(n_live), dim3(256), 0, st, (const unsigned *)s->dec_perm2.get(),
-                               (const unsigned *)s->dec_ta.get(), (const unsigned *)s->dec_tlo.get(), (const unsigned *)s->dec_thi.get(),
-                               (const unsigned char *)s->dec_even.get(), n_live, nf, s->fkeep.get());
-            MCHK(hipGetLastError());
-            MCHK(exclusive_scan(s, cache, s->fkeep.get(), s->fnew.get(), nf, st));
-            MCHK(scan_total(s->fkeep.get(), s->fnew.get(), nf, &kept_f, st));
-        }
-        if (kept_f > 0) {
-            hipLaunchKernelGGL(face_keep_mapped_kernel, grid_of(nf), dim3(256), 0, st, (const int *)s->faces.get(),
-                               (const unsigned *)s->dec_cluster.get(), (const unsigned *)s->fkeep.get(), (const unsigned *)s->fnew.get(),
-                               nf, nv, kept_f, s->faces2.get());
-            MCHK(hipGetLastError());
-            std::swap(s->faces, s->faces2);
+            MCHK(launch(group_decide_kernel, n_live, st, s->dec_perm2.get(), s->dec_ta.get(), s->dec_tlo.get(), s->dec_thi.get(),
+                        s->dec_even.get(), n_live, nf, s->fkeep.get()));
+            // the kept faces in their order, in cluster ids and their own corner order
+            MCHK(compact_faces(s, cache, nv, nf, s->dec_cluster.get(), &kept_f, st));
         }
     }
     unsigned fallback = 0;
     if (kept_f > 0 || place) {
         // (3) into the second buffers
-        hipLaunchKernelGGL(representative_kernel, grid_of(nc), dim3(256), 0, st, (const float *)s->verts.get(),
-                           (const unsigned char *)s->rgb.get(), (const unsigned *)s->dec_id2.get(), (const unsigned *)s->dec_start.get(),
-                           nv, nc, s->verts2.get(), s->rgb2.get());
-        MCHK(hipGetLastError());
+        MCHK(launch(representative_kernel, nc, st, s->verts.get(), s->rgb.get(), s->dec_id2.get(), s->dec_start.get(), nv, nc,
+                    s->verts2.get(), s->rgb2.get()));
     }
     if (place) {
         // the quadrics read the old faces (step (4) may have swapped them away) and the old positions; the count comes
         // back with the next read-back
         MCHK(hipMemsetAsync(s->dec_flag.get() + 1, 0, 4, st));
-        hipLaunchKernelGGL(vertex_quadric_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->verts.get(), old_faces,
-                           (const float *)s->face_normal.get(), (const unsigned *)s->row_start.get(), (const unsigned *)s->corners.get(),
-                           (const unsigned *)s->dec_cluster.get(), (const float *)s->verts2.get(), 3 * nf, nv, nc, s->dec_quadric.get());
-        MCHK(hipGetLastError());
-        hipLaunchKernelGGL(cluster_solve_kernel, grid_of(nc), dim3(256), 0, st, (const float *)s->dec_quadric.get(),
-                           (const unsigned *)s->dec_id2.get(), (const unsigned *)s->dec_start.get(), nv, nc, regularisation, cell,
-                           s->verts2.get(), s->dec_flag.get() + 1);
-        MCHK(hipGetLastError());
+        MCHK(launch(vertex_quadric_kernel, nv, st, s->verts.get(), old_faces, s->face_normal.get(), s->row_start.get(),
+                    s->corners.get(), s->dec_cluster.get(), s->verts2.get(), 3 * nf, nv, nc, s->dec_quadric.get()));
+        MCHK(launch(cluster_solve_kernel, nc, st, s->dec_quadric.get(), s->dec_id2.get(), s->dec_start.get(), nv, nc, regularisation,
+                    cell, s->verts2.get(), s->dec_flag.get() + 1));
         MCHK(hipMemcpyAsync(&fallback, s->dec_flag.get() + 1, 4, hipMemcpyDeviceToHost, st));
     }
     if (kept_f > 0) {
         // (5) back into the first buffers
         std::swap(s->verts, s->verts2);
         std::swap(s->rgb, s->rgb2);
-        MCHK(drop_unused_vertices(s, cache, nc, kept_f, &kept_v, st));
     }
+    MCHK(drop_unused_vertices(s, cache, nc, kept_f, &kept_v, st));
     MCHK(hipStreamSynchronize(st));
     s->n_vertices = kept_v; s->n_faces = kept_f;
     *n_vertices = kept_v; *n_faces = kept_f;

@@ -45,8 +45,6 @@ constexpr int AUTO_LARGE_PIXELS = 256;        // box size from which a face goes
 constexpr int LARGE_GRID = 1024;              // workgroups per view of the large-face kernel
 constexpr int MAX_GRID_Y = 65535;
 
-struct Kmat { float k[9]; };
-
 // (a) of the definition: camera depth and image position of a world point, every operation rounded on its own
 struct Projected { float zc, u, v; };
 
@@ -241,25 +239,12 @@ __global__ __launch_bounds__(256) void visible_keep_kernel(const int *__restrict
     keep[f] = k ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(256) void visible_compact_kernel(const int *__restrict__ faces, const unsigned *__restrict__ keep,
-                                                              const unsigned *__restrict__ new_id, long long n_faces, long long n_kept,
-                                                              int *__restrict__ out)
-{
-    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= n_faces || !keep[f]) return;
-    const long long o = AMVS_IDX((long long)new_id[f], n_kept);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[3 * o + k] = faces[3 * f + k];
-}
-
 inline Kmat kmat_of(const float K[9])
 {
     Kmat k;
     for (int i = 0; i < 9; ++i) k.k[i] = K[i];
     return k;
 }
-
-inline size_t at_least_one(long long n) { return (size_t)(n > 0 ? n : 1); }
 
 }  // namespace
 
@@ -295,9 +280,7 @@ hipError_t mesh_render(TsdfState *s, ScratchCache &cache, int n_views, int H, in
             MCHK(hipGetLastError());
         }
     }
-    hipLaunchKernelGGL(split_kernel, grid_of(n), dim3(256), 0, st, (const unsigned long long *)s->render_keys.get(), n,
-                       s->render_depth.get(), s->render_face.get());
-    MCHK(hipGetLastError());
+    MCHK(launch(split_kernel, n, st, s->render_keys.get(), n, s->render_depth.get(), s->render_face.get()));
     std::vector<unsigned long long> skipped(n_skipped_h ? (size_t)n_views : 0);
     if (n_skipped_h) MCHK(hipMemcpyAsync(skipped.data(), s->render_skipped.get(), 8 * (size_t)n_views, hipMemcpyDeviceToHost, st));
     MCHK(hipStreamSynchronize(st));
@@ -328,11 +311,9 @@ hipError_t mesh_visibility(TsdfState *s, ScratchCache &cache, float tolerance, l
     MCHK(s->vis_seen.reserve(1, cache));
     MCHK(hipMemsetAsync(s->vis_seen.get(), 0, 8, st));
     if (nv > 0) {
-        hipLaunchKernelGGL(visibility_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->verts.get(), nv,
-                           (const float *)s->render_cams.get(), kmat_of(s->render_K), s->render_views, s->render_H, s->render_W,
-                           s->render_near, tolerance, (const float *)s->render_depth.get(),
-                           (long long)s->render_views * s->render_H * s->render_W, s->vis_count.get(), s->vis_seen.get());
-        MCHK(hipGetLastError());
+        MCHK(launch(visibility_kernel, nv, st, s->verts.get(), nv, s->render_cams.get(), kmat_of(s->render_K), s->render_views,
+                    s->render_H, s->render_W, s->render_near, tolerance, s->render_depth.get(),
+                    (long long)s->render_views * s->render_H * s->render_W, s->vis_count.get(), s->vis_seen.get()));
     }
     unsigned long long seen = 0;
     MCHK(hipMemcpyAsync(&seen, s->vis_seen.get(), 8, hipMemcpyDeviceToHost, st));
@@ -352,30 +333,16 @@ hipError_t mesh_filter_visible(TsdfState *s, ScratchCache &cache, int min_views,
                                hipStream_t st)
 {
     const long long nv = s->n_vertices, nf = s->n_faces;
-    long long kept_f = 0, kept_v = 0;
     if (nf > 0) {
-        MCHK(s->fkeep.reserve((size_t)nf, cache)); MCHK(s->fnew.reserve((size_t)nf, cache)); MCHK(s->faces2.reserve(3 * (size_t)nf, cache));
-        hipLaunchKernelGGL(visible_keep_kernel, grid_of(nf), dim3(256), 0, st, (const int *)s->faces.get(), (const int *)s->vis_count.get(),
-                           nf, nv, min_views, s->fkeep.get());
-        MCHK(hipGetLastError());
-        MCHK(exclusive_scan(s, cache, s->fkeep.get(), s->fnew.get(), nf, st));
-        MCHK(scan_total(s->fkeep.get(), s->fnew.get(), nf, &kept_f, st));
+        MCHK(s->fkeep.reserve((size_t)nf, cache));
+        MCHK(launch(visible_keep_kernel, nf, st, s->faces.get(), s->vis_count.get(), nf, nv, min_views, s->fkeep.get()));
     }
-    // the mesh changes from here on: nothing derived from it stays
-    s->have_csr = s->have_pinned = s->have_labels = s->have_normals = false;
-    s->drop_views();
-    if (kept_f > 0) {
-        if (kept_f < nf) {
-            hipLaunchKernelGGL(visible_compact_kernel, grid_of(nf), dim3(256), 0, st, (const int *)s->faces.get(),
-                               (const unsigned *)s->fkeep.get(), (const unsigned *)s->fnew.get(), nf, kept_f, s->faces2.get());
-            MCHK(hipGetLastError());
-            std::swap(s->faces, s->faces2);
-        }
-        MCHK(drop_unused_vertices(s, cache, nv, kept_f, &kept_v, st));
-    }
+    // the call counts as a change of the mesh also when every face stays: nothing derived from it is current
+    s->topology_changed();
+    Compaction k;
+    MCHK(compact_mesh(s, cache, &k, st));
     MCHK(hipStreamSynchronize(st));
-    s->n_vertices = kept_v; s->n_faces = kept_f;
-    *n_vertices = kept_v; *n_faces = kept_f;
+    *n_vertices = k.kept_v; *n_faces = k.kept_f;
     return hipSuccess;
 }
 

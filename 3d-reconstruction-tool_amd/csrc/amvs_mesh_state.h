@@ -1,14 +1,12 @@
 // amvs_mesh_state.h -- what the surface-mesh translation units share: the context's volume-and-mesh state
 // (amvs_mesh.hip builds the mesh, amvs_mesh_clean.hip and amvs_mesh_decimate.hip work on it in place,
-// amvs_mesh_render.hip draws it into views and filters it by what they see), the hipCUB scan
-// with its read-back, and the kernels of extraction pass (d) that drop unused vertices, which the component filter and
-// the decimation run again.
-// Include after defining AMVS_TU_ID (amvs_check.h): the kernels here are compiled into each including unit.
+// amvs_mesh_render.hip draws it into views and filters it by what they see), the rule of what goes stale when the
+// mesh changes, and the declarations of the device code they share: the scans and the sort with their scratch, and
+// the compaction of the kept faces and the used vertices (extraction pass (d)).  That code is compiled once, in
+// amvs_mesh.hip: an index violation in it is reported with that unit's id and a line of that file.
 #pragma once
 #include "amvs_check.h"
 #include "amvs_buffer.h"
-
-#include <hipcub/hipcub.hpp>
 
 #include <cstdint>
 #include <utility>
@@ -82,90 +80,94 @@ struct TsdfState {
     DeviceBuffer<int> vis_count;                  // [V]: views that see the vertex
     DeviceBuffer<unsigned long long> vis_seen;    // [1]: vertices with a count > 0
 
-    // the mesh moves or changes: what was rendered from it is no longer its picture
+    // What is still current after every operation (anything else of the mesh's attributes is stale):
+    //
+    //   operation                                          still current afterwards        set by it
+    //   tsdf_integrate, tsdf_set_volume, tsdf_extract,     nothing                         the mesh (extract, set)
+    //     mesh_set
+    //   mesh_filter_components, label only or nothing      index, pinned                   labels; normals and render are
+    //     removed                                                                          dropped although the mesh is unchanged
+    //   mesh_filter_components, something removed          nothing                         labels, in the new numbering
+    //   mesh_smooth, any iteration count, 0 included       index, pinned, labels           nothing; normals and render dropped
+    //   mesh_normals                                       everything                      normals
+    //   mesh_decimate, mesh_decimate_quadric               nothing                         nothing
+    //   the same, refused for a vertex outside the grid    everything, mesh untouched      nothing
+    //   mesh_render                                        index, pinned, labels, normals  render; visibility dropped
+    //   mesh_visibility                                    all of these and the render     visibility
+    //   mesh_filter_visible, also when nothing is removed  nothing                         nothing
+    //
+    // Every function that changes the mesh calls the one of these that applies, and so does the shared compaction
+    // (amvs_mesh.hip) before it moves a face or a vertex.
+
+    // the mesh is drawn again or differs from its picture: the maps and the counts are stale
     void drop_views() { have_render = have_visibility = false; }
+
+    // vertices moved, faces and ids as they were: what was computed from the positions is stale
+    void positions_changed()
+    {
+        have_normals = false;
+        drop_views();
+    }
+
+    // faces or vertex ids changed: so is everything that is indexed by them
+    void topology_changed()
+    {
+        have_csr = have_pinned = have_labels = false;
+        positions_changed();
+    }
 
     // the mesh is about to be replaced: nothing derived from it stays
     void drop_mesh()
     {
-        have_mesh = have_csr = have_pinned = have_labels = have_normals = false;
-        drop_views();
+        have_mesh = false;
+        topology_changed();
     }
 };
 
-namespace {
-
-// (d) drop the vertices no face uses (their edges are shared only by tetrahedra with an unobserved corner):
-// flag the used ones (every writer stores the same 1), scan, move the kept vertices down, renumber the faces
-__global__ __launch_bounds__(256) void vertex_used_kernel(const int *__restrict__ faces, long long n_ids, long long n_vertices,
-                                                          unsigned *__restrict__ used)
-{
-    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f < n_ids) used[AMVS_IDX((long long)faces[f], n_vertices)] = 1u;
-}
-
-__global__ __launch_bounds__(256) void vertex_compact_kernel(const float *__restrict__ verts, const unsigned char *__restrict__ rgb,
-                                                             const unsigned *__restrict__ used, const unsigned *__restrict__ new_id,
-                                                             long long n_vertices, long long n_kept, float *__restrict__ verts_out,
-                                                             unsigned char *__restrict__ rgb_out)
-{
-    const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= n_vertices || !used[v]) return;
-    const long long o = AMVS_IDX((long long)new_id[v], n_kept);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { verts_out[3 * o + c] = verts[3 * v + c]; rgb_out[3 * o + c] = rgb[3 * v + c]; }
-}
-
-__global__ __launch_bounds__(256) void face_renumber_kernel(int *__restrict__ faces, long long n_ids, long long n_vertices,
-                                                            const unsigned *__restrict__ new_id)
-{
-    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f < n_ids) faces[f] = (int)new_id[AMVS_IDX((long long)faces[f], n_vertices)];
-}
-
 inline dim3 grid_of(long long n) { return dim3((unsigned)((n + 255) / 256)); }
 
-inline hipError_t exclusive_scan(TsdfState *s, ScratchCache &cache, const unsigned *in, unsigned *out, long long n, hipStream_t st)
+// one thread per element, 256 to a workgroup, on `st`; n > 0 is the caller's business, as with the launch itself
+template <class... P, class... A>
+inline hipError_t launch(void (*kernel)(P...), long long n, hipStream_t st, A... args)
 {
-    size_t bytes = 0;
-    MCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, st));
-    MCHK(s->scan_tmp.reserve(bytes > 0 ? bytes : 1, cache));
-    return hipcub::DeviceScan::ExclusiveSum(s->scan_tmp.get(), bytes, in, out, (int)n, st);
+    hipLaunchKernelGGL(kernel, grid_of(n), dim3(256), 0, st, static_cast<P>(args)...);
+    return hipGetLastError();
 }
+inline size_t at_least_one(long long n) { return (size_t)(n > 0 ? n : 1); }
 
-// total of an exclusive scan: base[n-1] + count[n-1]
-inline hipError_t scan_total(const unsigned *count, const unsigned *base, long long n, long long *total, hipStream_t st)
-{
-    unsigned h[2] = {0, 0};
-    MCHK(hipMemcpyAsync(&h[0], count + n - 1, 4, hipMemcpyDeviceToHost, st));
-    MCHK(hipMemcpyAsync(&h[1], base + n - 1, 4, hipMemcpyDeviceToHost, st));
-    MCHK(hipStreamSynchronize(st));
-    *total = (long long)h[0] + (long long)h[1];
-    return hipSuccess;
-}
-
-// the vertices no face uses leave the mesh: the kept ones keep their order, the faces are renumbered.  nv, nf > 0.
-inline hipError_t drop_unused_vertices(TsdfState *s, ScratchCache &cache, long long nv, long long nf, long long *kept,
-                                       hipStream_t st)
-{
-    MCHK(hipMemsetAsync(s->vused.get(), 0, 4 * (size_t)nv, st));
-    hipLaunchKernelGGL(vertex_used_kernel, grid_of(3 * nf), dim3(256), 0, st, (const int *)s->faces.get(), 3 * nf, nv,
-                       s->vused.get());
-    MCHK(hipGetLastError());
-    MCHK(exclusive_scan(s, cache, s->vused.get(), s->vnew.get(), nv, st));
-    MCHK(scan_total(s->vused.get(), s->vnew.get(), nv, kept, st));
-    hipLaunchKernelGGL(vertex_compact_kernel, grid_of(nv), dim3(256), 0, st, (const float *)s->verts.get(),
-                       (const unsigned char *)s->rgb.get(), (const unsigned *)s->vused.get(), (const unsigned *)s->vnew.get(), nv,
-                       *kept, s->verts2.get(), s->rgb2.get());
-    MCHK(hipGetLastError());
-    hipLaunchKernelGGL(face_renumber_kernel, grid_of(3 * nf), dim3(256), 0, st, s->faces.get(), 3 * nf, nv,
-                       (const unsigned *)s->vnew.get());
-    MCHK(hipGetLastError());
-    std::swap(s->verts, s->verts2);
-    std::swap(s->rgb, s->rgb2);
-    return hipSuccess;
-}
-
+namespace {
+// intrinsics as a kernel argument.  Per unit on purpose: the symbol names of the kernels that take one carry it.
+struct Kmat { float k[9]; };
 }  // namespace
+
+// ---- amvs_mesh.hip: device code every mesh unit uses, compiled there once -----------------------------------
+
+// exclusive sum of in[0 .. n) into out; the scratch is the state's
+hipError_t exclusive_scan(TsdfState *s, ScratchCache &cache, const unsigned *in, unsigned *out, long long n, hipStream_t st);
+// total of an exclusive scan, read back: base[n-1] + count[n-1].  n > 0.  Synchronises.
+hipError_t scan_total(const unsigned *count, const unsigned *base, long long n, long long *total, hipStream_t st);
+// key bits that tell n values apart, 1 .. 32
+int bits_for(long long n);
+// stable sort of (key, value) pairs on the low `bits` bits of the key; K = unsigned or unsigned long long
+template <class K>
+hipError_t sort_pairs(TsdfState *s, ScratchCache &cache, const K *key_in, K *key_out, const unsigned *val_in, unsigned *val_out,
+                      long long n, int bits, hipStream_t st);
+
+// The faces f with fkeep[f] != 0 stay, in their order; with `vertex_map` their ids go through it (its extent: nv).
+// Scans fkeep into fnew, reads the total back (one synchronisation) and, unless every face stays as it is, writes the
+// kept ones into faces2 and swaps.  nf == 0 and *kept_f == 0 launch nothing.
+hipError_t compact_faces(TsdfState *s, ScratchCache &cache, long long nv, long long nf, const unsigned *vertex_map,
+                         long long *kept_f, hipStream_t st);
+// Extraction pass (d): of nv vertices those that none of the first nf faces uses leave, the others keep their order and
+// the faces are renumbered.  Leaves the used flags in vused and the new ids in vnew; one synchronisation.  Nothing
+// moves when every vertex is used; nv == 0 or nf == 0 launch nothing and keep nothing.
+hipError_t drop_unused_vertices(TsdfState *s, ScratchCache &cache, long long nv, long long nf, long long *kept_v, hipStream_t st);
+
+struct Compaction {
+    long long kept_f = 0, kept_v = 0;
+    bool removed = false;             // a face or a vertex left
+};
+// compact_faces without a map, then drop_unused_vertices, then the counts of the state; the caller synchronises
+hipError_t compact_mesh(TsdfState *s, ScratchCache &cache, Compaction *out, hipStream_t st);
 
 }  // namespace amvs

@@ -9,6 +9,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mesh_restatement as mr  # noqa: E402
+from mesh_hip_common import _same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -31,12 +32,6 @@ def _world_points(depth, K, R, t):
     rays = np.stack([xs, ys, np.ones_like(xs)], -1).reshape(-1, 3) @ np.linalg.inv(K).T
     Xc = rays * depth.reshape(-1, 1)
     return (Xc - t) @ R
-
-
-def _same_bits(a, b):
-    a = np.ascontiguousarray(a, np.float32)
-    b = np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def _check_volume(eng, depth, conf, colors, K, poses, min_views, origin, voxel, dims, trunc, what):

@@ -19,23 +19,12 @@ import mesh_decimate_restatement as dr  # noqa: E402
 import mesh_quadric_inputs as qi  # noqa: E402
 import mesh_quadric_restatement as qr  # noqa: E402
 import mesh_volumes as mv  # noqa: E402
+from mesh_hip_common import K_ANY, _engine, _same_bits, _scene_a_inputs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-K_ANY = np.array([[30.0, 0, 16.0], [0, 30.0, 12.0], [0, 0, 1]], np.float32)
 REGS = (1e-3, 0.1)
-
-
-def _engine(H=24, W=32, n=1, K=K_ANY):
-    import amvs
-    return amvs.Engine(H, W, n, K)
-
-
-def _same_bits(a, b):
-    a = np.ascontiguousarray(a, np.float32)
-    b = np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def _assert_mesh_equal(mesh, ref, what):
@@ -256,17 +245,6 @@ def test_state_rules_and_errors():
         assert eng.mesh_decimate_quadric(origin, 0.3) == (0, 0, ref[3]) and ref[3] >= 2
         from amvs import _lib
         assert _lib.index_check()[0] == 0
-
-
-def _scene_a_inputs(scene_a):
-    """Images, poses and sparse points (the ground-truth depth of view 0, every 8th pixel) of the committed scene."""
-    import amvs
-    images = [{"image": np.ascontiguousarray(c)} for c in scene_a.colors]
-    d = scene_a.gt_depth[0][::8, ::8].astype(np.float64)
-    ys, xs = np.mgrid[0:scene_a.H:8, 0:scene_a.W:8]
-    rays = np.stack([xs, ys, np.ones_like(xs)], -1).reshape(-1, 3) @ np.linalg.inv(scene_a.K).T
-    sparse = (rays * d.reshape(-1, 1) - scene_a.t[0]) @ scene_a.R[0]
-    return amvs.Camera(K=scene_a.K.copy(), dist=np.zeros(5)), images, scene_a.poses(), sparse
 
 
 @pytest.mark.parametrize("mode", ["exact", "fast"])

@@ -17,6 +17,7 @@ import mesh_clean_restatement as cr  # noqa: E402
 import mesh_render_inputs as ri  # noqa: E402
 import mesh_render_restatement as rr  # noqa: E402
 import mesh_volumes as mv  # noqa: E402
+from mesh_hip_common import _scene_a_inputs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -308,17 +309,6 @@ def _render_raw(eng, n_views, K, near):
     poses = np.ascontiguousarray(ri.IDENTITY, F32)
     f32p = C.POINTER(C.c_float)
     return eng._lib.amvs_mesh_render(eng._h, n_views, Kf.ctypes.data_as(f32p), poses.ctypes.data_as(f32p), float(near), None)
-
-
-def _scene_a_inputs(scene_a):
-    """Images, poses and sparse points (the ground-truth depth of view 0, every 8th pixel) of the committed scene."""
-    import amvs
-    images = [{"image": np.ascontiguousarray(c)} for c in scene_a.colors]
-    d = scene_a.gt_depth[0][::8, ::8].astype(np.float64)
-    ys, xs = np.mgrid[0:scene_a.H:8, 0:scene_a.W:8]
-    rays = np.stack([xs, ys, np.ones_like(xs)], -1).reshape(-1, 3) @ np.linalg.inv(scene_a.K).T
-    sparse = (rays * d.reshape(-1, 1) - scene_a.t[0]) @ scene_a.R[0]
-    return amvs.Camera(K=scene_a.K.copy(), dist=np.zeros(5)), images, scene_a.poses(), sparse
 
 
 def test_reconstruct_mesh_visibility_culling(scene_a, capsys):
