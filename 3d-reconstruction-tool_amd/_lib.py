@@ -140,6 +140,9 @@ SIGNATURES = {
     "amvs_fetch_mesh_visibility": (C.c_int, [C.c_void_p, i32p]),
     "amvs_mesh_filter_visible": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "amvs_set_render_tuning": (C.c_int, [C.c_void_p, C.c_int]),
+    "amvs_mesh_color_views": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_uint8), C.c_float, C.c_float, C.c_int,
+                                        C.POINTER(C.c_int64)]),
+    "amvs_fetch_render_color": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "amvs_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "amvs_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "amvs_allgather_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),

@@ -124,7 +124,8 @@ class PatchMatchMVS(ResidentViews):
                          fix_boundary: bool = True, with_normals: bool = False,
                          decimate_voxels: float = 0.0, decimate_placement: str = "mean",
                          decimate_regularisation: float = 1e-3, min_visible_views: int = 0,
-                         visibility_tolerance_voxels: float = 1.0) -> Tuple[np.ndarray, ...]:
+                         visibility_tolerance_voxels: float = 1.0, color_from_views: bool = False,
+                         color_min_cos: float = 0.2, color_best_view: bool = False) -> Tuple[np.ndarray, ...]:
         """Surface mesh of the scene: reconstruct()'s preparation, sweep and fusion, then the per-view depth maps
         fused into a truncated signed distance volume and its zero level set extracted by marching tetrahedra on
         the GPU (csrc/amvs_mesh.hip; no reference counterpart).  Returns (vertices (V,3) float32, faces (F,3) int32,
@@ -148,6 +149,11 @@ class PatchMatchMVS(ResidentViews):
         decimate_placement="mean" puts that vertex at the mean of the cell's vertices, "quadric" where the planes of
         their faces meet best (Engine.mesh_decimate_quadric with decimate_regularisation; same faces and colours, a
         smaller error on curved surfaces and at edges);
+        color_from_views=True then colours the final mesh from the images (csrc/amvs_mesh_color.hip): the normals, a
+        render into the fused views with near plane one voxel, and for every vertex the bilinear samples of the views that
+        see it within float32(visibility_tolerance_voxels) * float32(voxel_size) at a cosine above color_min_cos, blended
+        with the cosine as weight or, with color_best_view, taken from the most frontal view; a vertex no view reaches
+        keeps the volume's colour;
         with_normals=True appends area-weighted vertex normals (V,3) float32 to the result, a 4-tuple then.  With the
         defaults none of it runs.  The grid of the last call is kept in last_mesh_grid (origin, voxel, dims, trunc), the views
         it fused in last_mesh_views."""
@@ -171,6 +177,15 @@ class PatchMatchMVS(ResidentViews):
             raise ValueError("min_visible_views must be an integer and not negative")
         if not (np.isfinite(visibility_tolerance_voxels) and visibility_tolerance_voxels >= 0):
             raise ValueError("visibility_tolerance_voxels must be finite and not negative")
+        for name, flag in (("color_from_views", color_from_views), ("color_best_view", color_best_view)):
+            if not isinstance(flag, (bool, np.bool_)):
+                raise ValueError(f"{name} must be a bool")
+        try:
+            cos_ok = not isinstance(color_min_cos, bool) and 0.0 <= float(color_min_cos) < 1.0
+        except (TypeError, ValueError):
+            cos_ok = False
+        if not cos_ok:
+            raise ValueError("color_min_cos must lie in [0, 1)")
         points, _, maps = self._reconstruct_maps(images, poses, sparse_points)
         do_filter = min_component_faces > 0 or keep_largest
         empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), np.zeros((0, 3), np.uint8))
@@ -192,7 +207,7 @@ class PatchMatchMVS(ResidentViews):
         print(f"  Mesh: {len(verts):,} vertices, {len(faces):,} faces ({time.time() - t0:.2f}s)")
         decimate = decimate_voxels > 0
         cull = min_visible_views > 0
-        if not (cull or do_filter or smooth_iterations > 0 or with_normals or decimate):
+        if not (cull or do_filter or smooth_iterations > 0 or with_normals or decimate or color_from_views):
             return verts, faces, colors
         t0 = time.time()
         eng = self._engine
@@ -216,8 +231,13 @@ class PatchMatchMVS(ResidentViews):
                                                       decimate_regularisation)[2]
             else:
                 eng.mesh_decimate(np.asarray(origin, np.float64).astype(np.float32), cell)
-        if with_normals:
+        if with_normals or color_from_views:
             eng.mesh_normals()
+        if color_from_views:
+            eng.mesh_render(self.K_scaled, fused, near=np.float32(voxel), fetch=False)
+            images_of = {k: src[k] for k in ("view_ids", "colors_bgr") if k in src}
+            n_colored = eng.mesh_color_views(np.float32(visibility_tolerance_voxels) * np.float32(voxel), color_min_cos,
+                                             color_best_view, **images_of)
         out = eng.mesh_fetch(normals=with_normals, labels=do_filter and not decimate)
         line = [culled] if cull else []
         if do_filter and decimate:
@@ -230,6 +250,8 @@ class PatchMatchMVS(ResidentViews):
         if decimate:
             how = f", quadric placement ({kept_mean:,} kept the mean)" if decimate_placement == "quadric" else ""
             line.append(f"decimation at {decimate_voxels:g} voxels{how}: {filtered[1]:,} faces -> {len(out[1]):,}")
+        if color_from_views:
+            line.append(f"colours from {len(fused)} views: {n_colored:,} of {len(out[0]):,} vertices")
         if with_normals:
             line.append("normals")
         print(f"  Clean-up: {', '.join(line)} ({time.time() - t0:.2f}s)")

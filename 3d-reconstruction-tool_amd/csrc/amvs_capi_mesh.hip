@@ -1,5 +1,5 @@
 // amvs_capi_mesh.hip -- the TSDF and mesh entry points of the C ABI (include/amvs.h; amvs_mesh.hip,
-// amvs_mesh_clean.hip, amvs_mesh_decimate.hip, amvs_mesh_render.hip).
+// amvs_mesh_clean.hip, amvs_mesh_decimate.hip, amvs_mesh_render.hip, amvs_mesh_color.hip).
 #include "amvs_ctx.h"
 
 #include <cmath>
@@ -318,6 +318,52 @@ int amvs_mesh_filter_visible(amvs_ctx *c, int min_views, int64_t *n_vertices, in
     long long nv = 0, nf = 0;
     MESH_HIPCHK(c, "mesh_filter_visible", amvs::mesh_filter_visible(c->tsdf.get(), c->cache, min_views, &nv, &nf, c->stream));
     *n_vertices = nv; *n_faces = nf;
+    return checked(c, AMVS_OK);
+}
+
+// ---- colours from the views (amvs_mesh_color.hip) ----
+int amvs_mesh_color_views(amvs_ctx *c, const int *view_ids, const uint8_t *colors_bgr_host, float depth_tolerance, float min_cos,
+                          int best_view, int64_t *n_colored)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::mesh_has_render(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_color_views: no current render (amvs_mesh_render)");
+    if (!amvs::mesh_has_normals(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_color_views: no current normals (amvs_mesh_normals)");
+    if ((view_ids != nullptr) == (colors_bgr_host != nullptr))
+        return fail(c, AMVS_EINVAL, "mesh_color_views: give exactly one colour source (view_ids or colors_bgr_host)");
+    if (!(depth_tolerance >= 0.0f) || !std::isfinite(depth_tolerance))
+        return fail(c, AMVS_EINVAL, "mesh_color_views: depth_tolerance must be finite and not negative");
+    if (!(min_cos >= 0.0f && min_cos < 1.0f)) return fail(c, AMVS_EINVAL, "mesh_color_views: min_cos must lie in [0, 1)");
+    const int n = amvs::mesh_render_views(c->tsdf.get());
+    int rc;
+    if (view_ids && (rc = check_colour_views(c, n, view_ids))) {
+        c->err = "mesh_color_views: " + c->err;
+        return rc;
+    }
+    std::vector<int> slots(n);
+    for (int j = 0; j < n; ++j) slots[j] = view_ids ? view_ids[j] : j;
+    if ((rc = bind_device(c))) return rc;
+    long long colored = 0;
+    MESH_HIPCHK(c, "mesh_color_views", amvs::mesh_color_views(c->tsdf.get(), c->cache, view_ids ? c->d_bgr.get() : colors_bgr_host,
+                view_ids != nullptr, view_ids ? c->n_views : n, slots.data(), depth_tolerance, min_cos, best_view != 0, &colored,
+                c->stream));
+    if (n_colored) *n_colored = colored;
+    return checked(c, AMVS_OK);
+}
+
+int amvs_fetch_render_color(amvs_ctx *c, int first, int count, uint8_t *rgb_out)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::mesh_has_render(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "fetch_render_color: no current render (amvs_mesh_render)");
+    const int n = amvs::mesh_render_views(c->tsdf.get());
+    if (first < 0 || count < 1 || first > n - count)
+        return fail(c, AMVS_EINVAL, "fetch_render_color: views " + std::to_string(first) + " .. " +
+                                        std::to_string((long long)first + count - 1) + " are not among the " + std::to_string(n) +
+                                        " rendered");
+    if (!rgb_out) return fail(c, AMVS_EINVAL, "fetch_render_color: NULL output");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    MESH_HIPCHK(c, "fetch_render_color", amvs::mesh_fetch_render_color(c->tsdf.get(), c->cache, first, count, rgb_out, c->stream));
     return checked(c, AMVS_OK);
 }
 

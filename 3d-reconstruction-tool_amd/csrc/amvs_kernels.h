@@ -311,4 +311,13 @@ hipError_t mesh_fetch_visibility(TsdfState *s, int *counts, hipStream_t st);
 hipError_t mesh_filter_visible(TsdfState *s, ScratchCache &cache, int min_views, long long *n_vertices, long long *n_faces,
                                hipStream_t st);
 
+// amvs_mesh_color.hip: the current mesh coloured from the images of the rendered views, and the current render shaded
+// with the vertex colours (include/amvs.h amvs_mesh_color_views, amvs_fetch_render_color).  Both need the current render,
+// the first the current normals too; the caller has validated the arguments.  Both synchronise and change no flag.
+// bgr: [bgr_images][H*W][3] BGR (host or device), rendered view j takes its colours from image slots_h[j].
+hipError_t mesh_color_views(TsdfState *s, ScratchCache &cache, const unsigned char *bgr, bool bgr_on_device, long long bgr_images,
+                            const int *slots_h, float tolerance, float min_cos, bool best_view, long long *n_colored, hipStream_t st);
+// rgb_out: [count][H][W][3] RGB on the host, computed into a leased block
+hipError_t mesh_fetch_render_color(TsdfState *s, ScratchCache &cache, int first, int count, unsigned char *rgb_out, hipStream_t st);
+
 }  // namespace amvs

@@ -1,6 +1,7 @@
 // amvs_mesh_state.h -- what the surface-mesh translation units share: the context's volume-and-mesh state
 // (amvs_mesh.hip builds the mesh, amvs_mesh_clean.hip and amvs_mesh_decimate.hip work on it in place,
-// amvs_mesh_render.hip draws it into views and filters it by what they see), the rule of what goes stale when the
+// amvs_mesh_render.hip draws it into views and filters it by what they see, amvs_mesh_color.hip colours it from the
+// views' images and shades the render), the rule of what goes stale when the
 // mesh changes, and the declarations of the device code they share: the scans and the sort with their scratch, and
 // the compaction of the kept faces and the used vertices (extraction pass (d)).  That code is compiled once, in
 // amvs_mesh.hip: an index violation in it is reported with that unit's id and a line of that file.
@@ -95,6 +96,10 @@ struct TsdfState {
     //   mesh_render                                        index, pinned, labels, normals  render; visibility dropped
     //   mesh_visibility                                    all of these and the render     visibility
     //   mesh_filter_visible, also when nothing is removed  nothing                         nothing
+    //   mesh_color_views (needs render and normals)        everything: positions, faces,   the colours of the vertices a
+    //                                                      index, pinned, labels, normals, view reached
+    //                                                      render, visibility
+    //   fetch_render_color                                 everything                      nothing
     //
     // Every function that changes the mesh calls the one of these that applies, and so does the shared compaction
     // (amvs_mesh.hip) before it moves a face or a vertex.

@@ -100,6 +100,7 @@ class Engine:
         if rc != 0:
             raise AmvsError(f"amvs_create failed ({rc}): {self._lib.amvs_last_error(None).decode()}")
         self._h = h
+        self._render_views = 0           # views of the last mesh_render: the image count mesh_color_views expects
         if mode != "exact":
             self.set_mode(mode)
 
@@ -701,6 +702,7 @@ class Engine:
         skip = np.zeros(max(n, 1), np.int64)
         self._chk(self._lib.amvs_mesh_render(self._h, n, _p(Kf), _p(pp), float(np.float32(near)),
                                              skip.ctypes.data_as(C.POINTER(C.c_int64))))
+        self._render_views = n
         if not fetch:
             return skip[:n]
         out = self.mesh_render_fetch(0, n)
@@ -730,6 +732,38 @@ class Engine:
         self._chk(self._lib.amvs_mesh_filter_visible(self._h, int(min_views), C.byref(nv), C.byref(nf)))
         self._mesh_counts = (nv.value, nf.value)
         return nv.value, nf.value
+
+    # -- colours from the views and the render in colour (csrc/amvs_mesh_color.hip) ----
+    def mesh_color_views(self, depth_tolerance, min_cos=0.2, best_view=False, view_ids=None, colors_bgr=None):
+        """Recolour the current mesh's vertices from the images of the rendered views (include/amvs.h
+        amvs_mesh_color_views): a view contributes where the vertex's 2 x 2 footprint lies in the image and on the
+        rendered surface within depth_tolerance, and the cosine between the normal and the direction to the camera
+        exceeds min_cos; the bilinear samples are blended with the cosine as weight, or with best_view the view with the
+        largest cosine is taken.  Image j belongs to rendered view j: view_ids (resident colour images) or colors_bgr
+        (n,H,W,3) uint8 BGR, exactly one of them.  Needs mesh_render and mesh_normals.  Returns the number of vertices
+        recoloured; the others keep their colour."""
+        n = self._render_views           # whether that render is still current is the library's check
+        idp, colp = None, None
+        if view_ids is not None:
+            ids, idp = _ids(view_ids)
+            if ids.shape != (n,):
+                raise ValueError(f"{ids.size} view ids for {n} rendered views")
+        if colors_bgr is not None:
+            cols = np.ascontiguousarray(colors_bgr, dtype=np.uint8)
+            if cols.shape != (n, self.H, self.W, 3):
+                raise ValueError(f"colors_bgr must be ({n}, {self.H}, {self.W}, 3)")
+            colp = _u8(cols)
+        done = C.c_int64(0)
+        self._chk(self._lib.amvs_mesh_color_views(self._h, idp, colp, float(np.float32(depth_tolerance)),
+                                                  float(np.float32(min_cos)), int(bool(best_view)), C.byref(done)))
+        return done.value
+
+    def mesh_render_color(self, first, count):
+        """The current render of `count` views from view `first` on, shaded with the current vertex colours
+        (include/amvs.h amvs_fetch_render_color): (count,H,W,3) uint8 RGB, 0 where nothing was drawn."""
+        out = np.empty((max(int(count), 0), self.H, self.W, 3), np.uint8)
+        self._chk(self._lib.amvs_fetch_render_color(self._h, int(first), int(count), _u8(out)))
+        return out
 
     def knn_mean_distance(self, points, k=20):
         """Mean distance of every point to its k-1 nearest other points, bit-identical to

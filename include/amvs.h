@@ -348,7 +348,8 @@ int amvs_tsdf_set_volume(amvs_ctx *ctx, const float *tsdf, const float *weight, 
  * amvs_mesh_smooth drops the normals and keeps the labels.  The rendered maps and the visibility counts (below) are
  * attributes too: every call of this list drops both, and so do amvs_mesh_filter_components and amvs_mesh_smooth,
  * which replace or move the mesh; amvs_mesh_normals keeps them, and a decimation refused for a vertex outside the
- * cluster grid changes nothing.                                                                                    */
+ * cluster grid changes nothing.  amvs_mesh_color_views writes colours only: positions, faces, labels, normals, the
+ * maps and the counts all stay current after it; amvs_fetch_render_color changes nothing.                          */
 /* Replace the context's mesh by host arrays: n_vertices x 3 float32 positions, n_faces x 3 int32 vertex ids,
  * n_vertices x 3 uint8 RGB colours (NULL: zeros).  A test hook, and the way to clean a mesh made elsewhere.
  * Validated on the host before anything is copied -- finite positions, ids in [0, n_vertices), no face with a
@@ -476,6 +477,49 @@ int amvs_mesh_filter_visible(amvs_ctx *ctx, int min_views, int64_t *n_vertices, 
 /* Performance only, the maps do not depend on it: a face whose clamped bounding box holds more than large_face_pixels
  * pixels is drawn by a workgroup instead of by one lane (0 = automatic; < 0 is AMVS_EINVAL).                        */
 int amvs_set_render_tuning(amvs_ctx *ctx, int large_face_pixels);
+
+/* ---- colours from the views, and the render in colour (csrc/amvs_mesh_color.hip) -------------------------------
+ * No reference counterpart: judged against a NumPy restatement of the definitions below, bit for bit
+ * (tests/mesh_color_restatement.py, DESIGN.md section 8 "Colours from the views").  All float32, every operation
+ * rounded on its own (no fused multiply-add), the divisions and sqrtf IEEE.  No float atomics and no dependence on
+ * execution order: a vertex walks the views in ascending order.  Both calls synchronise.                            */
+/* Recolours the vertices of the current mesh from the images of the rendered views.  Needs the current render and the
+ * current normals (amvs_mesh_normals keeps the render and amvs_mesh_render keeps the normals, so either order works).
+ * Image j belongs to rendered view j, for as many images as views were rendered, at the context's H x W.  Exactly one
+ * of view_ids (resident prepared images, each with a colour image: amvs_set_view_bgr8) and colors_bgr_host
+ * ([n][H][W][3] uint8 BGR, staged as amvs_tsdf_integrate's) is non-NULL.  For every vertex X with normal n, the rendered
+ * views in ascending order:
+ * a. Projection (a) of amvs_mesh_render with the render's K, poses and near, keeping xc, yc, zc, u, v.  The view is
+ *    skipped unless zc > near.
+ * b. Footprint: x0 = floorf(u), y0 = floorf(v); skipped unless x0 >= 0, x0 < W - 1, y0 >= 0 and y0 < H - 1 (comparisons
+ *    false for NaN).  ax = u - x0, ay = v - y0.
+ * c. Occlusion and silhouettes: at each of the four pixels (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1), d the
+ *    rendered depth there, the view is skipped unless d > 0, zc <= d + depth_tolerance and d <= zc + depth_tolerance
+ *    hold at all four: an undrawn pixel shows background, a nearer surface occludes the vertex, a farther one means
+ *    that the footprint straddles this surface's outline.
+ * d. Weight: ncx = (P0*nx + P1*ny) + P2*nz, ncy and ncz likewise from rows 1 and 2 of R;
+ *    dot = (ncx*xc + ncy*yc) + ncz*zc; len = sqrtf((xc*xc + yc*yc) + zc*zc); c = (-dot) / len.  Skipped unless
+ *    c > min_cos (false for NaN; a zero normal never passes).  w = c.
+ * e. Sample, for each of the B, G, R bytes, f the bytes as float with the first index x:
+ *    top = f00 + ax*(f10 - f00); bot = f01 + ax*(f11 - f01); val = top + ay*(bot - top).
+ * f. Combine.  best_view == 0: S_ch += w*val and Wsum += w, both from 0.0f, in view order.  Otherwise the val of the view
+ *    with the largest w is kept; only a strictly greater w replaces it, so a tie goes to the lowest view index.
+ * g. Write: q = S_ch / Wsum, or the best view's val; colour = floorf(q + 0.5f) clamped to 0 .. 255, written in the
+ *    mesh's RGB order.  A vertex that no view reached keeps its colour.  n_colored (optional) counts the vertices
+ *    written.
+ * AMVS_EINVAL: no current render or no current normals; both image arguments or neither; a view id out of range or
+ * without a resident colour image; depth_tolerance not finite or < 0; min_cos not finite or outside [0, 1).
+ * Positions, faces, index, labels, normals, the render and the counts all stay current.                            */
+int amvs_mesh_color_views(amvs_ctx *ctx, const int *view_ids, const uint8_t *colors_bgr_host, float depth_tolerance,
+                          float min_cos, int best_view, int64_t *n_colored);
+/* The current render of views first .. first + count - 1 shaded with the current vertex colours: [count][H][W][3] uint8
+ * RGB.  A pixel whose face id is -1 gives 0, 0, 0.  Otherwise the face is set up again as in (b) of amvs_mesh_render, the
+ * pixel's three edge functions w_i are evaluated as in (c), b_i = (float)w_i / (float)area, z is the pixel's rendered
+ * depth, and per channel q = z * ((b0*iz_0*c0 + b1*iz_1*c1) + b2*iz_2*c2) with c_i the corners' colours as float in the
+ * exchanged corner order and every product taken left to right; the byte is floorf(q + 0.5f) clamped to 0 .. 255.
+ * AMVS_EINVAL without a current render or for views that were not rendered.  Keeps no state: the picture is computed
+ * into scratch memory and copied out.                                                                               */
+int amvs_fetch_render_color(amvs_ctx *ctx, int first, int count, uint8_t *rgb_out);
 
 /* ---- extended mode: what the reference's docstring names but does not implement ----------------
  * (mvs_patchmatch.py:1-13 lists plane hypotheses with normals and VIEW propagation; its code ignores

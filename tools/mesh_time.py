@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Device time of the surface-mesh kernels (csrc/amvs_mesh.hip, csrc/amvs_mesh_clean.hip, csrc/amvs_mesh_decimate.hip,
-csrc/amvs_mesh_render.hip) at the CLI operating point (run on the GPU box):
+csrc/amvs_mesh_render.hip, csrc/amvs_mesh_color.hip) at the CLI operating point (run on the GPU box):
 16 views at 1008 x 756, patch 11, the maps of the extended mode (the reference's algorithm leaves too few correct
 depths for a surface) resident on the device, a 256^3 TSDF volume around the fused cloud.  Integration and extraction are timed separately with HIP events on the engine's stream (the extraction
 includes its two count read-backs); the first-order bounds of DESIGN.md section 8 are printed next to them.
@@ -9,7 +9,10 @@ Then the clean-up stage on that mesh and on the mesh of a 256^3 sphere: the vert
 decimation of either mesh at a cell of 2 voxels with either placement of the clusters' vertices (the mean, the quadrics),
 likewise; the render of either mesh into the views (the scene's cameras; a ring of as many round the sphere) and the
 visibility counts against it, before and after that decimation, next to a first-order estimate that prices the 64-bit
-minimum atomics at the rate measured for float adds, which nobody has measured for them; and
+minimum atomics at the rate measured for float adds, which nobody has measured for them; the colours from the views
+in both combine modes and the colour render against those maps (resident images, so no upload is timed: the scene's
+own; noise round the sphere), next to
+a first-order byte estimate (no time gate: there is no earlier code to compare with); and
 the labelling of a shuffled strip of 100 000 faces next to a sphere of about as many.
 
     python tools/mesh_time.py [n_views W H dim]
@@ -158,11 +161,11 @@ def decimate_time(name, restore, grid_origin, cell):
     assert qcounts[:2] == counts
 
 
-def render_time(name, restore, K, cams, near, tolerance, grid_origin, cell):
+def render_time(name, restore, K, cams, near, tolerance, grid_origin, cell, colours):
     """Render (csrc/amvs_mesh_render.hip) of the restored mesh into `cams` and the visibility counts, then the same on
     the mesh decimated at 2 voxels: small faces first, faces of tens of pixels after.  The maps stay on the device."""
     for stage in ("as extracted", "decimated at 2 voxels"):
-        tr, tv = [], []
+        tr, tv, tb, tk, tc = [], [], [], [], []
         for rep in range(REPS + 1):
             V, F = restore()
             if stage != "as extracted":
@@ -171,6 +174,15 @@ def render_time(name, restore, K, cams, near, tolerance, grid_origin, cell):
             v, _, counts = timed(lambda: eng.mesh_visibility(tolerance))
             if rep:
                 tr.append(r); tv.append(v)
+        # the colours in a loop of their own, on the maps of the last round: the calls keep everything current, and the
+        # colour render's 36 MB copy to the host stays out of the rounds that time the render and the counts
+        eng.mesh_normals()                                            # keeps the maps
+        for rep in range(REPS + 1):
+            b, _, n_blend = timed(lambda: eng.mesh_color_views(tolerance, 0.2, False, **colours))
+            k, _, n_best = timed(lambda: eng.mesh_color_views(tolerance, 0.2, True, **colours))
+            c, _, _ = timed(lambda: eng.mesh_render_color(0, len(cams)))
+            if rep:
+                tb.append(b); tk.append(k); tc.append(c)
         face = eng.mesh_render_fetch(0, len(cams))[1]
         covered = int((face >= 0).sum())
         pixels = face.size
@@ -185,6 +197,25 @@ def render_time(name, restore, K, cams, near, tolerance, grid_origin, cell):
               f"(atomics at the float-add rate, unmeasured for integer minima): {np.median(tr) / est:.1f} x")
         print(f"  visibility median {np.median(tv):8.3f} ms device (min {min(tv):.3f}); first-order bytes (estimate) {vis:.4f} ms "
               f"at 8 TB/s")
+        # first order, per (vertex, view): the projection is arithmetic, four 4-byte depths and twelve colour bytes are
+        # read, as if every pair passed every test; per vertex position, normal and colour.  An ESTIMATE at 8 TB/s.
+        col = (V * (12 + 12 + 3) + V * len(cams) * (4 * 4 + 12)) / 8e12 * 1e3
+        # the colour render: face id and depth in, three corners' positions and colours gathered, 3 bytes out; the
+        # picture then crosses to the host (included in the time, not in the estimate)
+        pic = (pixels * (4 + 4 + 3) + covered * (12 + 3 * (12 + 3))) / 8e12 * 1e3
+        for label, t, n in (("blend", tb, n_blend), ("best view", tk, n_best)):
+            print(f"  colours, {label:9s} median {np.median(t):8.3f} ms device (min {min(t):.3f}), {n:,} of {V:,} vertices recoloured; "
+                  f"first-order bytes (estimate) {col:.4f} ms at 8 TB/s")
+        print(f"  colour render      median {np.median(tc):8.3f} ms device with the copy of {pixels * 3 / 1e6:.1f} MB to the host "
+              f"(min {min(tc):.3f}); first-order device bytes (estimate) {pic:.4f} ms at 8 TB/s")
+
+
+def resident_images(images_bgr):
+    """The images into the engine's colour slots 0 .. n-1 (outside any timed call): mesh_color_views then reads resident
+    images and its time holds no host-to-device copy."""
+    for j, img in enumerate(images_bgr):
+        eng.set_view_colors(j, img)
+    return dict(view_ids=list(range(len(images_bgr))))
 
 
 def ring_of_cameras(n, distance=3.0):
@@ -202,14 +233,16 @@ def ring_of_cameras(n, distance=3.0):
 
 clean_times(f"the CLI operating point ({dim}^3)", restore_volume)
 decimate_time(f"the CLI operating point ({dim}^3)", restore_volume, origin, 2.0 * voxel)
-render_time(f"the CLI operating point ({dim}^3)", restore_volume, pm.K_scaled, poses, voxel, voxel, origin, 2.0 * voxel)
+scene_colours = dict(view_ids=src["view_ids"]) if "view_ids" in src else resident_images(src["colors_bgr"])
+render_time(f"the CLI operating point ({dim}^3)", restore_volume, pm.K_scaled, poses, voxel, voxel, origin, 2.0 * voxel, scene_colours)
 sphere = mv.sphere_volume(256, radius=0.8)
 eng.tsdf_set_volume(*sphere.arrays())
 clean_times("the 256^3 sphere", restore_volume)
 decimate_time("the 256^3 sphere", restore_volume, sphere.origin, 2.0 * float(sphere.voxel))
 K_sphere = np.array([[0.9 * H, 0, W / 2.0], [0, 0.9 * H, H / 2.0], [0, 0, 1]])
+noise = resident_images(np.random.default_rng(1).integers(0, 256, (len(poses), H, W, 3), dtype=np.uint8))
 render_time("the 256^3 sphere", restore_volume, K_sphere, ring_of_cameras(len(poses)), 0.1, float(sphere.voxel), sphere.origin,
-            2.0 * float(sphere.voxel))
+            2.0 * float(sphere.voxel), noise)
 
 
 def label_time(name, restore):
