@@ -143,6 +143,10 @@ SIGNATURES = {
     "amvs_mesh_color_views": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_uint8), C.c_float, C.c_float, C.c_int,
                                         C.POINTER(C.c_int64)]),
     "amvs_fetch_render_color": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
+    "amvs_mesh_texture": (C.c_int, [C.c_void_p, i32p, C.POINTER(C.c_uint8), C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "amvs_fetch_mesh_texture": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), f32p]),
+    "amvs_fetch_render_texture": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "amvs_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "amvs_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "amvs_allgather_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),

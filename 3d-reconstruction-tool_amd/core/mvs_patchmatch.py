@@ -125,7 +125,8 @@ class PatchMatchMVS(ResidentViews):
                          decimate_voxels: float = 0.0, decimate_placement: str = "mean",
                          decimate_regularisation: float = 1e-3, min_visible_views: int = 0,
                          visibility_tolerance_voxels: float = 1.0, color_from_views: bool = False,
-                         color_min_cos: float = 0.2, color_best_view: bool = False) -> Tuple[np.ndarray, ...]:
+                         color_min_cos: float = 0.2, color_best_view: bool = False,
+                         texture_texels: int = 0) -> Tuple[np.ndarray, ...]:
         """Surface mesh of the scene: reconstruct()'s preparation, sweep and fusion, then the per-view depth maps
         fused into a truncated signed distance volume and its zero level set extracted by marching tetrahedra on
         the GPU (csrc/amvs_mesh.hip; no reference counterpart).  Returns (vertices (V,3) float32, faces (F,3) int32,
@@ -154,6 +155,11 @@ class PatchMatchMVS(ResidentViews):
         see it within float32(visibility_tolerance_voxels) * float32(voxel_size) at a cosine above color_min_cos, blended
         with the cosine as weight or, with color_best_view, taken from the most frontal view; a vertex no view reaches
         keeps the volume's colour;
+        texture_texels=N > 0 (an integer up to 64) then textures the final mesh (csrc/amvs_mesh_texture.hip): a render into
+        the fused views with near plane one voxel, and a per-face atlas with N texel intervals per triangle leg, every
+        texel coloured like a vertex above, with the same tolerance, images, color_min_cos and color_best_view, and from
+        the vertex colours where no view reaches it; uv (F,3,2) float32 and atlas (Ht,Wt,3) uint8 RGB are appended to the
+        result, after the normals if those were asked for (core.utils.save_mesh_obj writes them);
         with_normals=True appends area-weighted vertex normals (V,3) float32 to the result, a 4-tuple then.  With the
         defaults none of it runs.  The grid of the last call is kept in last_mesh_grid (origin, voxel, dims, trunc), the views
         it fused in last_mesh_views."""
@@ -186,11 +192,21 @@ class PatchMatchMVS(ResidentViews):
             cos_ok = False
         if not cos_ok:
             raise ValueError("color_min_cos must lie in [0, 1)")
+        try:
+            texels_ok = (not isinstance(texture_texels, (bool, np.bool_)) and int(texture_texels) == texture_texels
+                         and 0 <= texture_texels <= 64)
+        except (TypeError, ValueError, OverflowError):
+            texels_ok = False
+        if not texels_ok:
+            raise ValueError("texture_texels must be an integer in 0 .. 64")
+        texture = int(texture_texels) > 0
         points, _, maps = self._reconstruct_maps(images, poses, sparse_points)
         do_filter = min_component_faces > 0 or keep_largest
         empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), np.zeros((0, 3), np.uint8))
         if with_normals:
             empty += (np.zeros((0, 3), np.float32),)
+        if texture:
+            empty += (np.zeros((0, 3, 2), np.float32), np.zeros((0, 0, 3), np.uint8))
         if maps is None or (bounds is None and len(points) == 0):
             return empty
         origin, voxel, dims, trunc = self._mesh_grid(points, bounds, voxel_size, trunc_voxels, max_dim)
@@ -207,7 +223,7 @@ class PatchMatchMVS(ResidentViews):
         print(f"  Mesh: {len(verts):,} vertices, {len(faces):,} faces ({time.time() - t0:.2f}s)")
         decimate = decimate_voxels > 0
         cull = min_visible_views > 0
-        if not (cull or do_filter or smooth_iterations > 0 or with_normals or decimate or color_from_views):
+        if not (cull or do_filter or smooth_iterations > 0 or with_normals or decimate or color_from_views or texture):
             return verts, faces, colors
         t0 = time.time()
         eng = self._engine
@@ -238,6 +254,12 @@ class PatchMatchMVS(ResidentViews):
             images_of = {k: src[k] for k in ("view_ids", "colors_bgr") if k in src}
             n_colored = eng.mesh_color_views(np.float32(visibility_tolerance_voxels) * np.float32(voxel), color_min_cos,
                                              color_best_view, **images_of)
+        if texture:
+            if not color_from_views:
+                eng.mesh_render(self.K_scaled, fused, near=np.float32(voxel), fetch=False)
+            images_of = {k: src[k] for k in ("view_ids", "colors_bgr") if k in src}
+            atlas, uv, n_textured = eng.mesh_texture(np.float32(visibility_tolerance_voxels) * np.float32(voxel), int(texture_texels),
+                                                     color_min_cos, color_best_view, **images_of)
         out = eng.mesh_fetch(normals=with_normals, labels=do_filter and not decimate)
         line = [culled] if cull else []
         if do_filter and decimate:
@@ -252,6 +274,10 @@ class PatchMatchMVS(ResidentViews):
             line.append(f"decimation at {decimate_voxels:g} voxels{how}: {filtered[1]:,} faces -> {len(out[1]):,}")
         if color_from_views:
             line.append(f"colours from {len(fused)} views: {n_colored:,} of {len(out[0]):,} vertices")
+        if texture:
+            line.append(f"texture {int(texture_texels)} texels, {atlas.shape[1]} x {atlas.shape[0]}: {n_textured:,} of "
+                        f"{eng.last_texture_texels:,} texels from the views")
+            out = out + (uv, atlas)
         if with_normals:
             line.append("normals")
         print(f"  Clean-up: {', '.join(line)} ({time.time() - t0:.2f}s)")

@@ -87,6 +87,65 @@ def save_mesh_ply(vertices: np.ndarray, faces: np.ndarray, colors: np.ndarray, o
     print(f"Saved mesh with {n_v:,} vertices and {len(tris):,} faces to {output_path}")
 
 
+def _png_rgb8(image: np.ndarray) -> bytes:
+    """An (H,W,3) uint8 RGB image as a PNG file's bytes: 8-bit truecolour, no interlace, every row with filter 0."""
+    import struct
+    import zlib
+    h, w = image.shape[:2]
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+    rows = np.zeros((h, 1 + 3 * w), np.uint8)
+    rows[:, 1:] = image.reshape(h, 3 * w)
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) +
+            chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
+def save_mesh_obj(vertices: np.ndarray, faces: np.ndarray, uv: np.ndarray, atlas: np.ndarray, output_path: str,
+                  normals: np.ndarray = None):
+    """Save a textured triangle mesh as Wavefront OBJ with its material and texture: name.obj, name.mtl and name.png beside
+    each other, `name` being output_path without its suffix.  vertices (V,3), faces (F,3) vertex ids, uv (F,3,2) per corner
+    with v up (Engine.mesh_texture's), atlas (Ht,Wt,3) uint8 RGB with row 0 on top.  The OBJ has `v`, one `vt` per corner,
+    `vn` with normals (V,3), and `f a/ta` or `f a/ta/na` with ids from 1; the MTL names the PNG as map_Kd.  The PNG is
+    written with the standard library alone (8-bit RGB, filter 0)."""
+    output_path = Path(output_path)
+    output_path.parent.mkdir(parents=True, exist_ok=True)
+    stem = output_path.with_suffix("")
+    name = stem.name
+    verts = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
+    tris = np.asarray(faces).reshape(-1, 3)
+    uvs = np.asarray(uv, dtype=np.float32).reshape(-1, 3, 2)
+    img = np.asarray(atlas)
+    if tris.size and (tris.min() < 0 or tris.max() >= len(verts)):
+        raise ValueError("face vertex ids out of range")
+    if len(uvs) != len(tris):
+        raise ValueError(f"uv must be ({len(tris)}, 3, 2)")
+    if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
+        raise ValueError("atlas must be (Ht, Wt, 3) uint8")
+    if len(tris) and img.size == 0:
+        raise ValueError("a mesh with faces needs an atlas that is not empty")
+    if img.size == 0:
+        img = np.zeros((1, 1, 3), np.uint8)                      # a PNG has at least one pixel
+    lines = [f"mtllib {name}.mtl", f"usemtl {name}"]
+    lines += ["v %.9g %.9g %.9g" % tuple(p) for p in verts.tolist()]
+    lines += ["vt %.9g %.9g" % tuple(t) for t in uvs.reshape(-1, 2).tolist()]
+    if normals is not None:
+        nrm = np.asarray(normals, dtype=np.float32).reshape(len(verts), 3)
+        lines += ["vn %.9g %.9g %.9g" % tuple(n) for n in nrm.tolist()]
+    for f, (a, b, c) in enumerate(tris.tolist()):
+        t = 3 * f + 1
+        if normals is None:
+            lines.append(f"f {a + 1}/{t} {b + 1}/{t + 1} {c + 1}/{t + 2}")
+        else:
+            lines.append(f"f {a + 1}/{t}/{a + 1} {b + 1}/{t + 1}/{b + 1} {c + 1}/{t + 2}/{c + 1}")
+    stem.with_suffix(".obj").write_text("\n".join(lines) + "\n")
+    stem.with_suffix(".mtl").write_text(f"newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n")
+    stem.with_suffix(".png").write_bytes(_png_rgb8(np.ascontiguousarray(img)))
+    print(f"Saved textured mesh with {len(verts):,} vertices, {len(tris):,} faces and a {img.shape[1]} x {img.shape[0]} texture "
+          f"to {stem.with_suffix('.obj')}")
+
+
 def compute_scene_bounds(points: np.ndarray) -> dict:
     """Axis-aligned bounds, centre and extent of a cloud (reference utils.py:72-86)."""
     lo, hi = points.min(axis=0), points.max(axis=0)

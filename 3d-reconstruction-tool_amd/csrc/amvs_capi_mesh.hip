@@ -1,5 +1,5 @@
 // amvs_capi_mesh.hip -- the TSDF and mesh entry points of the C ABI (include/amvs.h; amvs_mesh.hip,
-// amvs_mesh_clean.hip, amvs_mesh_decimate.hip, amvs_mesh_render.hip, amvs_mesh_color.hip).
+// amvs_mesh_clean.hip, amvs_mesh_decimate.hip, amvs_mesh_render.hip, amvs_mesh_color.hip, amvs_mesh_texture.hip).
 #include "amvs_ctx.h"
 
 #include <cmath>
@@ -364,6 +364,76 @@ int amvs_fetch_render_color(amvs_ctx *c, int first, int count, uint8_t *rgb_out)
     int rc = bind_device(c);
     if (rc) return rc;
     MESH_HIPCHK(c, "fetch_render_color", amvs::mesh_fetch_render_color(c->tsdf.get(), c->cache, first, count, rgb_out, c->stream));
+    return checked(c, AMVS_OK);
+}
+
+// ---- texture from the views (amvs_mesh_texture.hip) ----
+int amvs_mesh_texture(amvs_ctx *c, const int *view_ids, const uint8_t *colors_bgr_host, float depth_tolerance, float min_cos,
+                      int best_view, int texels, int cells_per_row, int *width, int *height, int64_t *n_texels,
+                      int64_t *n_textured)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::mesh_has_render(c->tsdf.get())) return fail(c, AMVS_EINVAL, "mesh_texture: no current render (amvs_mesh_render)");
+    if ((view_ids != nullptr) == (colors_bgr_host != nullptr))
+        return fail(c, AMVS_EINVAL, "mesh_texture: give exactly one colour source (view_ids or colors_bgr_host)");
+    if (!(depth_tolerance >= 0.0f) || !std::isfinite(depth_tolerance))
+        return fail(c, AMVS_EINVAL, "mesh_texture: depth_tolerance must be finite and not negative");
+    if (!(min_cos >= 0.0f && min_cos < 1.0f)) return fail(c, AMVS_EINVAL, "mesh_texture: min_cos must lie in [0, 1)");
+    if (texels < 1 || texels > AMVS_TEXTURE_MAX_TEXELS)
+        return fail(c, AMVS_EINVAL, "mesh_texture: texels must lie in 1 .. " + std::to_string(AMVS_TEXTURE_MAX_TEXELS));
+    if (cells_per_row < 0) return fail(c, AMVS_EINVAL, "mesh_texture: cells_per_row must be >= 0 (0 = automatic)");
+    const int n = amvs::mesh_render_views(c->tsdf.get());
+    int rc;
+    if (view_ids && (rc = check_colour_views(c, n, view_ids))) {
+        c->err = "mesh_texture: " + c->err;
+        return rc;
+    }
+    long long nf = 0, cols = 0, wt = 0, ht = 0;
+    amvs::mesh_texture_layout(c->tsdf.get(), texels, cells_per_row, &nf, &cols, &wt, &ht);
+    if (wt > AMVS_TEXTURE_MAX_SIDE || ht > AMVS_TEXTURE_MAX_SIDE)
+        return fail(c, AMVS_EINVAL, "mesh_texture: an atlas of " + std::to_string(wt) + " x " + std::to_string(ht) + " texels for " +
+                                        std::to_string(nf) + " faces is over the limit of " + std::to_string(AMVS_TEXTURE_MAX_SIDE) +
+                                        " a side (AMVS_TEXTURE_MAX_SIDE)");
+    std::vector<int> slots(n);
+    for (int j = 0; j < n; ++j) slots[j] = view_ids ? view_ids[j] : j;
+    if ((rc = bind_device(c))) return rc;
+    long long textured = 0;
+    MESH_HIPCHK(c, "mesh_texture", amvs::mesh_texture(c->tsdf.get(), c->cache, view_ids ? c->d_bgr.get() : colors_bgr_host,
+                view_ids != nullptr, view_ids ? c->n_views : n, slots.data(), depth_tolerance, min_cos, best_view != 0, texels,
+                (int)cols, (int)wt, (int)ht, &textured, c->stream));
+    if (width) *width = (int)wt;
+    if (height) *height = (int)ht;
+    if (n_texels) *n_texels = nf * ((long long)(texels + 1) * (texels + 2) / 2 + texels);
+    if (n_textured) *n_textured = textured;
+    return checked(c, AMVS_OK);
+}
+
+int amvs_fetch_mesh_texture(amvs_ctx *c, uint8_t *atlas_rgb, float *uv)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::mesh_has_texture(c->tsdf.get())) return fail(c, AMVS_EINVAL, "fetch_mesh_texture: no current texture (amvs_mesh_texture)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    HIPCHK(c, amvs::mesh_fetch_texture(c->tsdf.get(), atlas_rgb, uv, c->stream));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_fetch_render_texture(amvs_ctx *c, int first, int count, uint8_t *rgb_out)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::mesh_has_render(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "fetch_render_texture: no current render (amvs_mesh_render)");
+    if (!amvs::mesh_has_texture(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "fetch_render_texture: no current texture (amvs_mesh_texture)");
+    const int n = amvs::mesh_render_views(c->tsdf.get());
+    if (first < 0 || count < 1 || first > n - count)
+        return fail(c, AMVS_EINVAL, "fetch_render_texture: views " + std::to_string(first) + " .. " +
+                                        std::to_string((long long)first + count - 1) + " are not among the " + std::to_string(n) +
+                                        " rendered");
+    if (!rgb_out) return fail(c, AMVS_EINVAL, "fetch_render_texture: NULL output");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    MESH_HIPCHK(c, "fetch_render_texture", amvs::mesh_fetch_render_texture(c->tsdf.get(), c->cache, first, count, rgb_out, c->stream));
     return checked(c, AMVS_OK);
 }
 

@@ -320,4 +320,23 @@ hipError_t mesh_color_views(TsdfState *s, ScratchCache &cache, const unsigned ch
 // rgb_out: [count][H][W][3] RGB on the host, computed into a leased block
 hipError_t mesh_fetch_render_color(TsdfState *s, ScratchCache &cache, int first, int count, unsigned char *rgb_out, hipStream_t st);
 
+// amvs_mesh_texture.hip: the texture atlas of the current mesh from the images of the rendered views, its UVs and the
+// current render shaded with it (include/amvs.h amvs_mesh_texture, amvs_fetch_mesh_texture, amvs_fetch_render_texture).
+// The caller has validated the arguments; all synchronise.
+bool mesh_has_texture(const TsdfState *s);
+// the layout of the current mesh's n_faces faces at `texels` intervals per leg: cells per row (cells_per_row, or the
+// automatic value for 0) and the atlas's sides, which the caller compares with AMVS_TEXTURE_MAX_SIDE.  No faces: all zero.
+void mesh_texture_layout(const TsdfState *s, int texels, int cells_per_row, long long *n_faces, long long *cols, long long *width,
+                         long long *height);
+// of the current texture
+void mesh_texture_size(const TsdfState *s, int *texels, int *width, int *height);
+// images as mesh_color_views; cols, width, height from mesh_texture_layout.  Sets the texture, changes no other flag.
+hipError_t mesh_texture(TsdfState *s, ScratchCache &cache, const unsigned char *bgr, bool bgr_on_device, long long bgr_images,
+                        const int *slots_h, float tolerance, float min_cos, bool best_view, int texels, int cols, int width,
+                        int height, long long *n_textured, hipStream_t st);
+// atlas_rgb: [height][width][3], uv: [n_faces][3][2] on the host; NULL skips one
+hipError_t mesh_fetch_texture(TsdfState *s, unsigned char *atlas_rgb, float *uv, hipStream_t st);
+// rgb_out: [count][H][W][3] RGB on the host, computed into a leased block
+hipError_t mesh_fetch_render_texture(TsdfState *s, ScratchCache &cache, int first, int count, unsigned char *rgb_out, hipStream_t st);
+
 }  // namespace amvs

@@ -170,6 +170,7 @@ hipError_t mesh_color_views(TsdfState *s, ScratchCache &cache, const unsigned ch
     MCHK(hipMemcpyAsync(&colored, count.get(), 8, hipMemcpyDeviceToHost, st));
     MCHK(hipStreamSynchronize(st));
     if (n_colored) *n_colored = (long long)colored;
+    s->have_texture = false;          // the atlas falls back to the vertex colours where no view reaches
     return hipSuccess;
 }
 

@@ -1,7 +1,7 @@
 // amvs_mesh_state.h -- what the surface-mesh translation units share: the context's volume-and-mesh state
 // (amvs_mesh.hip builds the mesh, amvs_mesh_clean.hip and amvs_mesh_decimate.hip work on it in place,
 // amvs_mesh_render.hip draws it into views and filters it by what they see, amvs_mesh_color.hip colours it from the
-// views' images and shades the render), the rule of what goes stale when the
+// views' images and shades the render, amvs_mesh_texture.hip textures it from them), the rule of what goes stale when the
 // mesh changes, and the declarations of the device code they share: the scans and the sort with their scratch, and
 // the compaction of the kept faces and the used vertices (extraction pass (d)).  That code is compiled once, in
 // amvs_mesh.hip: an index violation in it is reported with that unit's id and a line of that file.
@@ -81,6 +81,12 @@ struct TsdfState {
     DeviceBuffer<int> vis_count;                  // [V]: views that see the vertex
     DeviceBuffer<unsigned long long> vis_seen;    // [1]: vertices with a count > 0
 
+    // ---- texture (amvs_mesh_texture.hip): the atlas and the UVs are attributes of the current mesh and its colours ----
+    bool have_texture = false;
+    int tex_N = 0, tex_cols = 0, tex_W = 0, tex_H = 0;    // texel intervals per leg, cells per row, atlas width and height
+    DeviceBuffer<unsigned char> tex_atlas;        // [tex_H][tex_W][3] RGB
+    DeviceBuffer<float> tex_uv;                   // [F][3][2]
+
     // What is still current after every operation (anything else of the mesh's attributes is stale):
     //
     //   operation                                          still current afterwards        set by it
@@ -99,7 +105,15 @@ struct TsdfState {
     //   mesh_color_views (needs render and normals)        everything: positions, faces,   the colours of the vertices a
     //                                                      index, pinned, labels, normals, view reached
     //                                                      render, visibility
+    //                                                                                      the texture is dropped: its
+    //                                                                                      fall-back colours changed
     //   fetch_render_color                                 everything                      nothing
+    //   mesh_texture (needs render)                        everything                      texture
+    //   fetch_mesh_texture, fetch_render_texture           everything                      nothing
+    //
+    // The texture outlives what does not touch positions, faces or colours: mesh_normals, mesh_render (the mesh may be
+    // drawn again from other cameras and shaded with the atlas), mesh_visibility and every fetch keep it.  Every other
+    // row of the table drops it, through positions_changed().
     //
     // Every function that changes the mesh calls the one of these that applies, and so does the shared compaction
     // (amvs_mesh.hip) before it moves a face or a vertex.
@@ -110,7 +124,7 @@ struct TsdfState {
     // vertices moved, faces and ids as they were: what was computed from the positions is stale
     void positions_changed()
     {
-        have_normals = false;
+        have_normals = have_texture = false;
         drop_views();
     }
 

@@ -765,6 +765,44 @@ class Engine:
         self._chk(self._lib.amvs_fetch_render_color(self._h, int(first), int(count), _u8(out)))
         return out
 
+    # -- texture from the views and the render shaded with it (csrc/amvs_mesh_texture.hip) ----
+    def mesh_texture(self, depth_tolerance, texels=8, min_cos=0.2, best_view=False, cells_per_row=0, view_ids=None,
+                     colors_bgr=None):
+        """A per-face texture atlas of the current mesh from the images of the rendered views (include/amvs.h
+        amvs_mesh_texture): every face gets a right triangle of `texels` texel intervals per leg, two faces to a square
+        cell, cells_per_row cells to a row (0 = a square atlas).  A texel is coloured as mesh_color_views colours a
+        vertex, at its point on the face with the face's normal, and falls back to the interpolated vertex colours where
+        no view reaches it.  Image j belongs to rendered view j: view_ids or colors_bgr, exactly one.  Needs mesh_render.
+        Returns (atlas (Ht,Wt,3) uint8 RGB, uv (F,3,2) float32 with v up, texels a view reached); n_texels of the last
+        call is kept in last_texture_texels."""
+        n = self._render_views           # whether that render is still current is the library's check
+        idp, colp = None, None
+        if view_ids is not None:
+            ids, idp = _ids(view_ids)
+            if ids.shape != (n,):
+                raise ValueError(f"{ids.size} view ids for {n} rendered views")
+        if colors_bgr is not None:
+            cols = np.ascontiguousarray(colors_bgr, dtype=np.uint8)
+            if cols.shape != (n, self.H, self.W, 3):
+                raise ValueError(f"colors_bgr must be ({n}, {self.H}, {self.W}, 3)")
+            colp = _u8(cols)
+        wt, ht, total, done = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.amvs_mesh_texture(self._h, idp, colp, float(np.float32(depth_tolerance)), float(np.float32(min_cos)),
+                                              int(bool(best_view)), int(texels), int(cells_per_row), C.byref(wt), C.byref(ht),
+                                              C.byref(total), C.byref(done)))
+        self.last_texture_texels = total.value
+        atlas = np.empty((ht.value, wt.value, 3), np.uint8)
+        uv = np.empty((self._mesh_counts[1], 3, 2), np.float32)
+        self._chk(self._lib.amvs_fetch_mesh_texture(self._h, _u8(atlas) if atlas.size else None, _p(uv) if uv.size else None))
+        return atlas, uv, done.value
+
+    def mesh_render_texture(self, first, count):
+        """The current render of `count` views from view `first` on, shaded with the current texture (include/amvs.h
+        amvs_fetch_render_texture): (count,H,W,3) uint8 RGB, 0 where nothing was drawn."""
+        out = np.empty((max(int(count), 0), self.H, self.W, 3), np.uint8)
+        self._chk(self._lib.amvs_fetch_render_texture(self._h, int(first), int(count), _u8(out)))
+        return out
+
     def knn_mean_distance(self, points, k=20):
         """Mean distance of every point to its k-1 nearest other points, bit-identical to
         np.mean(NearestNeighbors(n_neighbors=k).fit(p).kneighbors(p)[0][:, 1:], axis=1)."""

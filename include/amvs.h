@@ -349,7 +349,10 @@ int amvs_tsdf_set_volume(amvs_ctx *ctx, const float *tsdf, const float *weight, 
  * attributes too: every call of this list drops both, and so do amvs_mesh_filter_components and amvs_mesh_smooth,
  * which replace or move the mesh; amvs_mesh_normals keeps them, and a decimation refused for a vertex outside the
  * cluster grid changes nothing.  amvs_mesh_color_views writes colours only: positions, faces, labels, normals, the
- * maps and the counts all stay current after it; amvs_fetch_render_color changes nothing.                          */
+ * maps and the counts all stay current after it; amvs_fetch_render_color changes nothing.  The texture
+ * (amvs_mesh_texture, below) is an attribute as well: every call that drops the maps because it replaces or moves the
+ * mesh drops it, and so does amvs_mesh_color_views, whose colours it falls back to; amvs_mesh_normals, amvs_mesh_render,
+ * amvs_mesh_visibility and every fetch keep it, and amvs_mesh_texture itself leaves everything else current.       */
 /* Replace the context's mesh by host arrays: n_vertices x 3 float32 positions, n_faces x 3 int32 vertex ids,
  * n_vertices x 3 uint8 RGB colours (NULL: zeros).  A test hook, and the way to clean a mesh made elsewhere.
  * Validated on the host before anything is copied -- finite positions, ids in [0, n_vertices), no face with a
@@ -509,7 +512,8 @@ int amvs_set_render_tuning(amvs_ctx *ctx, int large_face_pixels);
  *    written.
  * AMVS_EINVAL: no current render or no current normals; both image arguments or neither; a view id out of range or
  * without a resident colour image; depth_tolerance not finite or < 0; min_cos not finite or outside [0, 1).
- * Positions, faces, index, labels, normals, the render and the counts all stay current.                            */
+ * Positions, faces, index, labels, normals, the render and the counts all stay current; a texture (amvs_mesh_texture)
+ * does not, since its fall-back colours changed.                                                                    */
 int amvs_mesh_color_views(amvs_ctx *ctx, const int *view_ids, const uint8_t *colors_bgr_host, float depth_tolerance,
                           float min_cos, int best_view, int64_t *n_colored);
 /* The current render of views first .. first + count - 1 shaded with the current vertex colours: [count][H][W][3] uint8
@@ -520,6 +524,74 @@ int amvs_mesh_color_views(amvs_ctx *ctx, const int *view_ids, const uint8_t *col
  * AMVS_EINVAL without a current render or for views that were not rendered.  Keeps no state: the picture is computed
  * into scratch memory and copied out.                                                                               */
 int amvs_fetch_render_color(amvs_ctx *ctx, int first, int count, uint8_t *rgb_out);
+
+/* ---- texture from the views, and the render shaded with it (csrc/amvs_mesh_texture.hip) --------------------------
+ * A per-face texture atlas of the current mesh, the carrier of colour for a decimated mesh whose faces span many image
+ * pixels.  No reference counterpart: judged against a NumPy restatement of the definitions below, bit for bit
+ * (tests/mesh_texture_restatement.py, DESIGN.md section 8 "Texture").  All float32, every operation rounded on its own
+ * (no fused multiply-add), the divisions and sqrtf IEEE.  No float atomics and nothing depends on execution order.  All
+ * three calls synchronise.
+ *
+ * Layout.  N = texels is the number of texel intervals along a leg, 1 <= N <= AMVS_TEXTURE_MAX_TEXELS; C = N + 3.  Faces
+ * 2c and 2c+1 share cell c.  With cols cells per row, cols is cells_per_row if that is positive; if it is 0, cols is the
+ * smallest integer with cols*cols >= n_cells, n_cells = (F+1)/2.  rows = ceil(n_cells / cols).  The origin of cell c is
+ * (cx, cy) = ((c % cols)*C, (c / cols)*C).  The atlas is Ht = rows*C by Wt = cols*C texels, uint8 RGB, row 0 on top.
+ * Either side above AMVS_TEXTURE_MAX_SIDE is AMVS_EINVAL, before anything is allocated; a mesh with no faces gives a
+ * 0 x 0 atlas and success.  The texel set of a face is {(i, j): 0 <= i, j <= N, i + j <= N + 1}; the diagonal
+ * i + j = N + 1 is the gutter that a bilinear lookup inside the triangle can touch.  Texel (i, j) of an even face sits
+ * at atlas (cx + i, cy + j), of an odd face at (cx + C-1-i, cy + C-1-j).  The two sets of a cell are disjoint, the
+ * diagonal between them stays unused.  Corners 0, 1, 2 of a face are its texels (0,0), (N,0), (0,N).  Every atlas texel
+ * in no set is 0, 0, 0; this includes the odd half of a last cell that has no second face.
+ *
+ * UVs.  [F][3][2] float32 per corner, with (X, Y) the corner's atlas texel: u = ((float)X + 0.5f) / (float)Wt,
+ * v = 1.0f - ((float)Y + 0.5f) / (float)Ht (OBJ convention, v up).
+ *
+ * Colour of texel (i, j) of face f with corners p0, p1, p2 in the face's own order:
+ * a. b1 = (float)i / (float)N, b2 = (float)j / (float)N, b0 = (1.0f - b1) - b2.  In the gutter b0 is -1/N, so the point
+ *    lies just outside the face on its plane.
+ * b. The point, per axis: X = (b0*x0 + b1*x1) + b2*x2.
+ * c. The normal is the face's: n = cross(p1 - p0, p2 - p0) formed as amvs_mesh_normals forms it
+ *    (ay*bz - az*by, az*bx - ax*bz, ax*by - ay*bx with a = p1 - p0, b = p2 - p0); l = sqrtf((nx*nx + ny*ny) + nz*nz);
+ *    n / l per component if l > 0, else (0, 0, 0).  No current vertex normals are needed.
+ * d. Steps a to f of amvs_mesh_color_views, word for word, for this point and this normal: projection with the render's
+ *    K, poses and near, the 2 x 2 footprint, the four-depth occlusion and outline test with depth_tolerance, the cosine
+ *    against min_cos, the bilinear sample, and blend or best_view.
+ * e. If a view was reached, q = S_ch / Wsum or the best view's val, and the byte is floorf(q + 0.5f) clamped to 0 .. 255,
+ *    in RGB order.
+ * f. Otherwise the texel falls back to the vertex colours: per channel q = (b0*c0 + b1*c1) + b2*c2 of the corners'
+ *    current colours as float, rounded and clamped the same way.  The atlas then has no holes.
+ * g. n_texels counts the texels in some face's set, F * ((N+1)*(N+2)/2 + N); n_textured counts those of them a view
+ *    reached.
+ * The image arguments and their rules are amvs_mesh_color_views's.  width, height, n_texels and n_textured are optional.
+ * AMVS_EINVAL: no current mesh or render; both image arguments or neither; a view id out of range or without a resident
+ * colour image; depth_tolerance not finite or < 0; min_cos not finite or outside [0, 1); texels outside
+ * 1 .. AMVS_TEXTURE_MAX_TEXELS; cells_per_row < 0; an atlas side above AMVS_TEXTURE_MAX_SIDE.
+ * Needs the current render and nothing else, and leaves everything else current.  What keeps the texture current:
+ * amvs_mesh_normals, amvs_mesh_render (the mesh may be rendered again from other cameras and shaded with the atlas),
+ * amvs_mesh_visibility and every fetch.  What drops it: every operation that replaces or moves the mesh
+ * (amvs_tsdf_integrate, amvs_tsdf_set_volume, amvs_tsdf_extract, amvs_mesh_set, amvs_mesh_filter_components,
+ * amvs_mesh_smooth with any iteration count, amvs_mesh_decimate and amvs_mesh_decimate_quadric unless refused,
+ * amvs_mesh_filter_visible), and amvs_mesh_color_views, because the fall-back colours changed.                       */
+#define AMVS_TEXTURE_MAX_TEXELS 64
+#define AMVS_TEXTURE_MAX_SIDE 16384
+int amvs_mesh_texture(amvs_ctx *ctx, const int *view_ids, const uint8_t *colors_bgr_host, float depth_tolerance, float min_cos,
+                      int best_view, int texels, int cells_per_row, int *width, int *height, int64_t *n_texels,
+                      int64_t *n_textured);
+/* The current texture: atlas_rgb [Ht][Wt][3] uint8 and uv [F][3][2] float32; NULL skips an output.  AMVS_EINVAL
+ * without a current texture.                                                                                        */
+int amvs_fetch_mesh_texture(amvs_ctx *ctx, uint8_t *atlas_rgb, float *uv);
+/* The current render of views first .. first + count - 1 shaded with the atlas: [count][H][W][3] uint8 RGB.  A pixel
+ * whose face id is -1 gives 0, 0, 0.  Otherwise the face is set up again as amvs_fetch_render_color does, the three edge
+ * functions w_k are evaluated and b_k = (float)w_k / (float)area; z is the pixel's rendered depth.
+ * g_k = z * (b_k * iz_k) in the exchanged corner order; if the set-up exchanged corners 1 and 2, g_1 and g_2 are
+ * exchanged back.  x = fminf(fmaxf(g_1 * (float)N, 0.0f), (float)N), and y likewise from g_2.
+ * i = min((int)floorf(x), N-1), j likewise; ax = x - (float)i, ay = y - (float)j.  If i + j >= N the pixel is on the
+ * hypotenuse within rounding, and j = N - 1 - i, ay = 1.0f.  The four taps (i,j), (i+1,j), (i,j+1), (i+1,j+1) are then in
+ * the face's set; per channel, f the taps' bytes as float with the first index i:
+ * top = f00 + ax*(f10 - f00); bot = f01 + ax*(f11 - f01); q = top + ay*(bot - top); the byte is floorf(q + 0.5f) clamped
+ * to 0 .. 255.  AMVS_EINVAL without a current render or a current texture, or for views that were not rendered.  Keeps
+ * no state: the picture is computed into scratch memory and copied out.                                             */
+int amvs_fetch_render_texture(amvs_ctx *ctx, int first, int count, uint8_t *rgb_out);
 
 /* ---- extended mode: what the reference's docstring names but does not implement ----------------
  * (mvs_patchmatch.py:1-13 lists plane hypotheses with normals and VIEW propagation; its code ignores

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Device time of the surface-mesh kernels (csrc/amvs_mesh.hip, csrc/amvs_mesh_clean.hip, csrc/amvs_mesh_decimate.hip,
-csrc/amvs_mesh_render.hip, csrc/amvs_mesh_color.hip) at the CLI operating point (run on the GPU box):
+csrc/amvs_mesh_render.hip, csrc/amvs_mesh_color.hip, csrc/amvs_mesh_texture.hip) at the CLI operating point (run on the GPU box):
 16 views at 1008 x 756, patch 11, the maps of the extended mode (the reference's algorithm leaves too few correct
 depths for a surface) resident on the device, a 256^3 TSDF volume around the fused cloud.  Integration and extraction are timed separately with HIP events on the engine's stream (the extraction
 includes its two count read-backs); the first-order bounds of DESIGN.md section 8 are printed next to them.
@@ -12,7 +12,8 @@ visibility counts against it, before and after that decimation, next to a first-
 minimum atomics at the rate measured for float adds, which nobody has measured for them; the colours from the views
 in both combine modes and the colour render against those maps (resident images, so no upload is timed: the scene's
 own; noise round the sphere), next to
-a first-order byte estimate (no time gate: there is no earlier code to compare with); and
+a first-order byte estimate (no time gate: there is no earlier code to compare with); the texture at 8 texels per leg in
+both combine modes (the call alone, the atlas stays on the device) and the textured render, likewise; and
 the labelling of a shuffled strip of 100 000 faces next to a sphere of about as many.
 
     python tools/mesh_time.py [n_views W H dim]
@@ -183,6 +184,17 @@ def render_time(name, restore, K, cams, near, tolerance, grid_origin, cell, colo
             c, _, _ = timed(lambda: eng.mesh_render_color(0, len(cams)))
             if rep:
                 tb.append(b); tk.append(k); tc.append(c)
+        # the texture likewise, after the colours (which drop it): N = 8, or the largest N whose atlas fits
+        N = 8
+        while N > 1 and int(np.ceil(np.sqrt((F + 1) // 2))) * (N + 3) > 16384:
+            N -= 1
+        tt, tu, tp = [], [], []
+        for rep in range(REPS + 1):
+            b, _, tex_blend = timed(lambda: texture_call(tolerance, N, False, colours))
+            k, _, tex_best = timed(lambda: texture_call(tolerance, N, True, colours))
+            c, _, _ = timed(lambda: eng.mesh_render_texture(0, len(cams)))
+            if rep:
+                tt.append(b); tu.append(k); tp.append(c)
         face = eng.mesh_render_fetch(0, len(cams))[1]
         covered = int((face >= 0).sum())
         pixels = face.size
@@ -208,6 +220,28 @@ def render_time(name, restore, K, cams, near, tolerance, grid_origin, cell, colo
                   f"first-order bytes (estimate) {col:.4f} ms at 8 TB/s")
         print(f"  colour render      median {np.median(tc):8.3f} ms device with the copy of {pixels * 3 / 1e6:.1f} MB to the host "
               f"(min {min(tc):.3f}); first-order device bytes (estimate) {pic:.4f} ms at 8 TB/s")
+        # first order, per texel: the face's ids, three corner positions and colours (served by the cache within a face, priced
+        # as if not) and 3 bytes out; per (texel, view) pair the 28 B the colours count; per atlas slot 3 bytes.  An ESTIMATE.
+        wt, ht, T = tex_blend[0], tex_blend[1], tex_blend[2]
+        tex = (T * (12 + 3 * (12 + 3) + 3) + T * len(cams) * (4 * 4 + 12) + wt * ht * 3) / 8e12 * 1e3
+        # the textured render: face id and depth in, three corners' positions gathered, four texels of 3 bytes, 3 bytes out
+        tpic = (pixels * (4 + 4 + 3) + covered * (12 + 3 * 12 + 4 * 3)) / 8e12 * 1e3
+        for label, t, r in (("blend", tt, tex_blend), ("best view", tu, tex_best)):
+            print(f"  texture N={N}, {label:9s} median {np.median(t):8.3f} ms device (min {min(t):.3f}), atlas {wt} x {ht}, {r[3]:,} of "
+                  f"{T:,} texels from the views; first-order bytes (estimate) {tex:.4f} ms at 8 TB/s")
+        print(f"  textured render    median {np.median(tp):8.3f} ms device with the copy of {pixels * 3 / 1e6:.1f} MB to the host "
+              f"(min {min(tp):.3f}); first-order device bytes (estimate) {tpic:.4f} ms at 8 TB/s")
+
+
+def texture_call(tolerance, N, best, colours):
+    """amvs_mesh_texture alone, from resident images: the atlas and the UVs stay on the device.  Returns (width, height,
+    n_texels, n_textured)."""
+    import ctypes as C
+    ids = np.ascontiguousarray(colours["view_ids"], np.int32)
+    wt, ht, total, done = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_int64(0)
+    eng._chk(eng._lib.amvs_mesh_texture(eng._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), None, float(np.float32(tolerance)), 0.2,
+                                        int(best), N, 0, C.byref(wt), C.byref(ht), C.byref(total), C.byref(done)))
+    return wt.value, ht.value, total.value, done.value
 
 
 def resident_images(images_bgr):
