@@ -125,6 +125,8 @@ SIGNATURES = {
     "amvs_fetch_mesh": (C.c_int, [C.c_void_p, f32p, i32p, C.POINTER(C.c_uint8)]),
     "amvs_tsdf_fetch_volume": (C.c_int, [C.c_void_p, f32p, f32p, f32p]),
     "amvs_tsdf_set_volume": (C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p, C.c_float, i32p]),
+    "amvs_tsdf_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "amvs_tsdf_fetch_fill": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8)]),
     "amvs_mesh_set": (C.c_int, [C.c_void_p, f32p, C.c_int64, i32p, C.c_int64, C.POINTER(C.c_uint8)]),
     "amvs_mesh_filter_components": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                               C.POINTER(C.c_int64)]),

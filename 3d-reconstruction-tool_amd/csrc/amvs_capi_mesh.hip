@@ -1,5 +1,6 @@
 // amvs_capi_mesh.hip -- the TSDF and mesh entry points of the C ABI (include/amvs.h; amvs_mesh.hip,
-// amvs_mesh_clean.hip, amvs_mesh_decimate.hip, amvs_mesh_render.hip, amvs_mesh_color.hip, amvs_mesh_texture.hip).
+// amvs_mesh_fill.hip, amvs_mesh_clean.hip, amvs_mesh_decimate.hip, amvs_mesh_render.hip, amvs_mesh_color.hip,
+// amvs_mesh_texture.hip).
 #include "amvs_ctx.h"
 
 #include <cmath>
@@ -112,6 +113,39 @@ int amvs_tsdf_fetch_volume(amvs_ctx *c, float *tsdf, float *weight, float *color
     int rc = bind_device(c);
     if (rc) return rc;
     HIPCHK(c, amvs::tsdf_fetch_volume(c->tsdf.get(), tsdf, weight, color_sum, c->stream));
+    return checked(c, AMVS_OK);
+}
+
+// ---- hole filling (amvs_mesh_fill.hip): in place on the context's current volume ----
+int amvs_tsdf_fill(amvs_ctx *c, int steps, int min_neighbours, int64_t *filled_per_step, int64_t *n_filled)
+{
+    if (!c) return AMVS_EINVAL;
+    if (steps < 1 || steps > AMVS_FILL_MAX_STEPS)
+        return fail(c, AMVS_EINVAL, "tsdf_fill: steps must lie in 1 .. " + std::to_string(AMVS_FILL_MAX_STEPS));
+    if (min_neighbours < 1 || min_neighbours > 6) return fail(c, AMVS_EINVAL, "tsdf_fill: min_neighbours must lie in 1 .. 6");
+    if (!amvs::tsdf_has_volume(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "tsdf_fill: no volume (amvs_tsdf_integrate or amvs_tsdf_set_volume)");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    std::vector<long long> per_step((size_t)steps, 0);
+    long long total = 0;
+    MESH_HIPCHK(c, "tsdf_fill", amvs::tsdf_fill(c->tsdf.get(), c->cache, steps, min_neighbours, per_step.data(), &total,
+                c->stream));
+    if (filled_per_step)
+        for (int s = 0; s < steps; ++s) filled_per_step[s] = per_step[(size_t)s];
+    if (n_filled) *n_filled = total;
+    return checked(c, AMVS_OK);
+}
+
+int amvs_tsdf_fetch_fill(amvs_ctx *c, uint8_t *gen)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!amvs::tsdf_has_fill(c->tsdf.get()))
+        return fail(c, AMVS_EINVAL, "tsdf_fetch_fill: no fill of the current volume (amvs_tsdf_fill)");
+    if (!gen) return fail(c, AMVS_EINVAL, "tsdf_fetch_fill: NULL output");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    HIPCHK(c, amvs::tsdf_fetch_fill(c->tsdf.get(), gen, c->stream));
     return checked(c, AMVS_OK);
 }
 

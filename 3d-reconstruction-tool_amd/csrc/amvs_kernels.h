@@ -267,6 +267,14 @@ bool tsdf_has_mesh(const TsdfState *s);
 hipError_t tsdf_fetch_mesh(TsdfState *s, float *verts, int *faces, unsigned char *rgb, hipStream_t st);
 hipError_t tsdf_fetch_volume(TsdfState *s, float *tsdf, float *weight, float *color_sum, hipStream_t st);
 
+// amvs_mesh_fill.hip: hole filling in the state's current volume (include/amvs.h amvs_tsdf_fill, amvs_tsdf_fetch_fill).
+// steps in 1 .. AMVS_FILL_MAX_STEPS and min_neighbours in 1 .. 6 are the caller's business.  Drops the mesh; filled_per_step
+// ([steps]) and n_filled may be NULL.  Synchronises.
+hipError_t tsdf_fill(TsdfState *s, ScratchCache &cache, int steps, int min_neighbours, long long *filled_per_step,
+                     long long *n_filled, hipStream_t st);
+bool tsdf_has_fill(const TsdfState *s);          // a fill ran on the current volume
+hipError_t tsdf_fetch_fill(TsdfState *s, unsigned char *gen, hipStream_t st);
+
 // amvs_mesh_clean.hip: clean-up of the state's current mesh in place (include/amvs.h amvs_mesh_*).  All synchronise.
 // replaces the mesh by host arrays the caller has validated (copies only); rgb NULL: zeros
 hipError_t mesh_set(TsdfState *s, ScratchCache &cache, const float *verts, long long nv, const int *faces, long long nf,

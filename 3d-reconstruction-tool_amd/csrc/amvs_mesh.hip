@@ -419,7 +419,7 @@ hipError_t tsdf_integrate(TsdfState *s, ScratchCache &cache, const float *depth,
                           const int *slots_h, const float K[9], const float *poses_h, float min_views, const float origin[3],
                           float voxel, const int dims[3], float trunc, hipStream_t st)
 {
-    s->have_volume = false;
+    s->have_volume = s->have_fill = false;
     s->drop_mesh();
     const long long n = (long long)dims[0] * dims[1] * dims[2];
     const size_t hw = (size_t)H * W, nmap = hw * (size_t)n_maps;
@@ -454,7 +454,7 @@ hipError_t tsdf_integrate(TsdfState *s, ScratchCache &cache, const float *depth,
 hipError_t tsdf_set_volume(TsdfState *s, ScratchCache &cache, const float *tsdf, const float *weight, const float *color_sum,
                            const float origin[3], float voxel, const int dims[3], hipStream_t st)
 {
-    s->have_volume = false;
+    s->have_volume = s->have_fill = false;
     s->drop_mesh();
     const long long n = (long long)dims[0] * dims[1] * dims[2];
     MCHK(reserve_volume(s, cache, n));

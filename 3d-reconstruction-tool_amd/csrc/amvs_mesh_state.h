@@ -1,5 +1,6 @@
 // amvs_mesh_state.h -- what the surface-mesh translation units share: the context's volume-and-mesh state
-// (amvs_mesh.hip builds the mesh, amvs_mesh_clean.hip and amvs_mesh_decimate.hip work on it in place,
+// (amvs_mesh.hip builds the mesh, amvs_mesh_fill.hip grows the volume into unobserved space, amvs_mesh_clean.hip and
+// amvs_mesh_decimate.hip work on the mesh in place,
 // amvs_mesh_render.hip draws it into views and filters it by what they see, amvs_mesh_color.hip colours it from the
 // views' images and shades the render, amvs_mesh_texture.hip textures it from them), the rule of what goes stale when the
 // mesh changes, and the declarations of the device code they share: the scans and the sort with their scratch, and
@@ -32,6 +33,8 @@ struct TsdfState {
     bool have_volume = false, have_mesh = false;
     DeviceBuffer<float> tsdf, weight, color;      // [n], [n], [n][3]
     DeviceBuffer<unsigned char> mask;
+    bool have_fill = false;                       // fill_gen holds the generations of a fill of the current volume
+    DeviceBuffer<unsigned char> fill_gen;         // [n] (amvs_mesh_fill.hip)
     DeviceBuffer<unsigned> vcount, vbase, tcount, tbase;
     DeviceBuffer<unsigned char> scan_tmp;
     DeviceBuffer<float> cams;                     // [n_maps][12] R, t
@@ -92,6 +95,7 @@ struct TsdfState {
     //   operation                                          still current afterwards        set by it
     //   tsdf_integrate, tsdf_set_volume, tsdf_extract,     nothing                         the mesh (extract, set)
     //     mesh_set
+    //   tsdf_fill (changes the volume, not its grid)       nothing                         nothing
     //   mesh_filter_components, label only or nothing      index, pinned                   labels; normals and render are
     //     removed                                                                          dropped although the mesh is unchanged
     //   mesh_filter_components, something removed          nothing                         labels, in the new numbering

@@ -611,6 +611,30 @@ class Engine:
                                                  float(np.float32(voxel)), dmp))
         self._tsdf_dims = (nx, ny, nz)
 
+    def tsdf_fill(self, steps, min_neighbours=1):
+        """Hole filling in the current volume (include/amvs.h amvs_tsdf_fill): `steps` times (1 .. 64) every unobserved grid
+        point with at least `min_neighbours` (1 .. 6) observed or already filled 6-neighbours becomes their mean, in signed
+        distance and colour, with weight 1.  Drops the mesh: tsdf_extract() then meshes the filled volume.  Returns the
+        number of points filled; the per-step counts are kept in last_fill_counts."""
+        counts = np.zeros(max(int(steps), 1), np.int64)
+        total = C.c_int64(0)
+        self.last_fill_counts = None
+        self._chk(self._lib.amvs_tsdf_fill(self._h, int(steps), int(min_neighbours), counts.ctypes.data_as(C.POINTER(C.c_int64)),
+                                           C.byref(total)))
+        self.last_fill_counts = [int(c) for c in counts]
+        return total.value
+
+    def tsdf_fill_generations(self):
+        """Test hook (include/amvs.h amvs_tsdf_fetch_fill): the generations of the last tsdf_fill on the current volume,
+        (nz,ny,nx) uint8 -- 0 still unobserved, 1 observed before the call, s + 1 filled by step s."""
+        dims = getattr(self, "_tsdf_dims", None)
+        if dims is None:
+            raise AmvsError("no TSDF volume: call tsdf_integrate first")
+        nx, ny, nz = dims
+        gen = np.empty((nz, ny, nx), np.uint8)
+        self._chk(self._lib.amvs_tsdf_fetch_fill(self._h, gen.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return gen
+
     # -- mesh clean-up (components, Taubin smoothing, decimation, normals), in place on the context's current mesh ----
     def mesh_set(self, vertices, faces, colors=None):
         """Make host arrays the context's mesh (include/amvs.h amvs_mesh_set): vertices (V,3) float32, faces (F,3)

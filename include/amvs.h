@@ -335,6 +335,44 @@ int amvs_tsdf_fetch_volume(amvs_ctx *ctx, float *tsdf, float *weight, float *col
  * which is NOT checked.  Synchronises.                                                                      */
 int amvs_tsdf_set_volume(amvs_ctx *ctx, const float *tsdf, const float *weight, const float *color_sum,
                          const float origin[3], float voxel, const int32_t dims[3]);
+/* Hole filling (csrc/amvs_mesh_fill.hip): grow the signed distance of the context's current volume -- the one
+ * amvs_tsdf_integrate or amvs_tsdf_set_volume made -- from its observed grid points into the unobserved ones next to
+ * them, `steps` layers deep, so that amvs_tsdf_extract closes the holes the unobserved points left.  Judged against
+ * tests/mesh_fill_restatement.py, bit for bit (DESIGN.md section 8 "Hole filling").
+ *
+ * Every call starts with a generation per grid point, gen (uint8, the layout of weight): 1 where weight > 0, else 0.
+ * Then the steps s = 1 .. steps run.  A point is KNOWN AT STEP s if 1 <= gen <= s.  For every point p with
+ * gen[p] == 0, decided from the state before the step (all points of a step at once):
+ *  1. its in-grid neighbours are visited in the fixed order (i-1), (i+1), (j-1), (j+1), (k-1), (k+1); c is the number
+ *     of those known at step s;
+ *  2. if c >= min_neighbours:
+ *       tsdf[p] = acc / (float)c, where acc starts at +0.0f and takes acc = acc + tsdf[q] over the known neighbours q
+ *       in that order;
+ *       color_sum[3p + ch] = cacc_ch / (float)c with cacc_ch = cacc_ch + color_sum[3q + ch] / weight[q], from +0.0f,
+ *       over the same neighbours in the same order (the mean of their mean colours);
+ *       weight[p] = 1.0f and gen[p] = s + 1.
+ * All arithmetic is float32, every operation rounded on its own, every division IEEE.  Nothing of a neighbour that is
+ * not known is read but its generation: its tsdf and colour sums may be NaN or garbage.  A point once filled never
+ * changes, an observed point never changes, and a point with fewer than min_neighbours known neighbours stays
+ * unobserved and may be filled by a later step.  Because acc starts at +0.0f, a single neighbour of -0.0f gives +0.0f,
+ * which amvs_tsdf_extract takes for outside.
+ *
+ * All `steps` steps run, without a read-back between them.  filled_per_step[s - 1] (may be NULL) is the number of
+ * points step s filled, *n_filled (may be NULL) their sum.  steps outside 1 .. AMVS_FILL_MAX_STEPS or min_neighbours
+ * outside 1 .. 6: AMVS_EINVAL before any work; without a current volume: AMVS_EINVAL, as amvs_tsdf_extract.  Drops
+ * the mesh and every attribute of it, as amvs_tsdf_set_volume does.  Synchronises.
+ *
+ * Afterwards the volume is the filled one (amvs_tsdf_fetch_volume: a filled point has weight 1 and its colour sums are
+ * its mean colour), and a second call takes the points the first filled for observed.  Hence amvs_tsdf_fill(a) followed
+ * by amvs_tsdf_fill(b) leaves the same tsdf, weight and colour sums as one amvs_tsdf_fill(a + b) with the same
+ * min_neighbours (the generations differ: those of the second call count from its start).                     */
+#define AMVS_FILL_MAX_STEPS 64
+int amvs_tsdf_fill(amvs_ctx *ctx, int steps, int min_neighbours, int64_t *filled_per_step /* [steps], may be NULL */,
+                   int64_t *n_filled);
+/* Test hook: the generations of the last amvs_tsdf_fill on the current volume, dims[2] x dims[1] x dims[0] uint8 (0: still
+ * unobserved, 1: observed before the call, s + 1: filled by step s).  AMVS_EINVAL if there was no amvs_tsdf_fill since
+ * the volume was made.                                                                                       */
+int amvs_tsdf_fetch_fill(amvs_ctx *ctx, uint8_t *gen /* dims[2] x dims[1] x dims[0] */);
 
 /* ---- mesh clean-up: components, Taubin smoothing, vertex normals, decimation (csrc/amvs_mesh_clean.hip) ------
  * No reference counterpart (the reference has no mesh): judged against a NumPy restatement of the definitions below,

@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
-"""Device time of the surface-mesh kernels (csrc/amvs_mesh.hip, csrc/amvs_mesh_clean.hip, csrc/amvs_mesh_decimate.hip,
-csrc/amvs_mesh_render.hip, csrc/amvs_mesh_color.hip, csrc/amvs_mesh_texture.hip) at the CLI operating point (run on the GPU box):
+"""Device time of the surface-mesh kernels (csrc/amvs_mesh.hip, csrc/amvs_mesh_fill.hip, csrc/amvs_mesh_clean.hip,
+csrc/amvs_mesh_decimate.hip, csrc/amvs_mesh_render.hip, csrc/amvs_mesh_color.hip, csrc/amvs_mesh_texture.hip) at the CLI
+operating point (run on the GPU box):
 16 views at 1008 x 756, patch 11, the maps of the extended mode (the reference's algorithm leaves too few correct
 depths for a surface) resident on the device, a 256^3 TSDF volume around the fused cloud.  Integration and extraction are timed separately with HIP events on the engine's stream (the extraction
 includes its two count read-backs); the first-order bounds of DESIGN.md section 8 are printed next to them.
+Then the hole filling (amvs_tsdf_fill) at 2 and 8 steps on that volume and on a 256^3 sphere with a tube unobserved, each the
+median of 5 after a warm-up on a volume integrated or set again before every call, next to a first-order byte estimate (no
+time gate: there is no earlier code to compare with).
 Then the clean-up stage on that mesh and on the mesh of a 256^3 sphere: the vertex -> corner index, labelling + filter,
 10 Taubin iterations and the normals, each the median of 5 after a warm-up, with a first-order byte estimate; the
 decimation of either mesh at a cell of 2 voxels with either placement of the clusters' vertices (the mean, the quadrics),
@@ -91,7 +95,38 @@ print(f"  bounds (estimates): integrate VALU {valu_ms:.3f} ms / bytes {gather_ms
 # ---- clean-up (csrc/amvs_mesh_clean.hip) ----
 sys.path.insert(0, "tests")
 import mesh_clean_inputs as ci  # noqa: E402
+import mesh_fill_inputs as fi  # noqa: E402
 import mesh_volumes as mv  # noqa: E402
+
+
+def fill_time(name, restore, n_points):
+    """Hole filling (csrc/amvs_mesh_fill.hip) of the volume restore() makes, the whole call: the memset, the generations,
+    the steps and the read-back of the counts."""
+    for steps in (2, 8):
+        ts = []
+        for rep in range(REPS + 1):
+            restore()
+            ms, _, total = timed(lambda: eng.tsdf_fill(steps))
+            if rep:
+                ts.append(ms)
+        frontier = sum(eng.last_fill_counts)
+        # first order: the generations written once (4 B of weight in, 1 B out), then per step 1 B per point and about 50 B
+        # per point filled (6 neighbour bytes, 5 floats of up to 6 neighbours served mostly by the cache, 21 B out).  An ESTIMATE.
+        est = n_points * 5 + steps * n_points + frontier * 50
+        print(f"hole filling of {name}, {steps} steps: {total:,} points filled {eng.last_fill_counts}: "
+              f"median {np.median(ts):.3f} ms device (min {min(ts):.3f}); first-order bytes (estimate) {est / 1e6:.1f} MB = "
+              f"{est / 8e12 * 1e3:.4f} ms at 8 TB/s, {est / 6.29e12 * 1e3:.4f} ms at the 6.29 TB/s a copy reaches")
+
+
+def restore_scene_volume():
+    eng.tsdf_integrate(pm.K_scaled, poses, pm.min_views, origin, voxel, dims, trunc, **src)
+
+
+fill_time(f"the CLI operating point ({dim}^3)", restore_scene_volume, n_pts)
+tube = fi.sphere_with_tube(256)[0]
+fill_time("the 256^3 sphere without a tube", lambda: eng.tsdf_set_volume(*tube.arrays()), 256 ** 3)
+del tube
+restore_scene_volume()
 
 
 def clean_times(name, restore, min_faces=8):
