@@ -119,6 +119,15 @@ SIGNATURES = {
                                       C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "amvs_set_view_colors": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint8)]),
     "amvs_fetch_cloud": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8)]),
+    "amvs_depth_normals": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.c_float, C.c_int, C.c_float, C.c_int, C.c_int,
+                                     C.POINTER(C.c_int64)]),
+    "amvs_fetch_depth_normals": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p]),
+    "amvs_cloud_normals": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int,
+                                     C.POINTER(C.c_int64)]),
+    "amvs_fetch_cloud_normals": (C.c_int, [C.c_void_p, f32p, i32p]),
+    "amvs_cloud_set": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int64]),
     "amvs_tsdf_integrate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, i32p, C.POINTER(C.c_uint8),
                                       f32p, f32p, C.c_float, f32p, C.c_float, i32p, C.c_float]),
     "amvs_tsdf_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -154,6 +163,7 @@ SIGNATURES = {
     "amvs_allgather_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "amvs_comm_destroy": (C.c_int, [C.c_void_p]),
     "amvs_write_ply": (C.c_int, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int64]),
+    "amvs_write_ply_normals": (C.c_int, [C.c_char_p, C.POINTER(C.c_double), f32p, C.POINTER(C.c_int64), C.c_int64]),
     "amvs_knn_mean_distance": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.c_int, C.POINTER(C.c_double)]),
     "amvs_selftest_lean_math": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "amvs_index_check": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),

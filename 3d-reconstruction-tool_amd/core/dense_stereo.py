@@ -57,12 +57,31 @@ class DenseStereoReconstructor(ResidentViews):
         for r, c in ((0, 0), (1, 1), (0, 2), (1, 2)):
             self.K_scaled[r, c] *= scale
         self._subsample_on_host = False  # test switch: sub-sample clouds above 500 000 points as the host path does
+        self._cloud_resident = False     # the engine holds the final cloud
 
     def _engine_mode(self) -> str:
         return self.mode                 # the engine is created in this object's mode (no mode per call here)
 
     def reconstruct(self, images: List[dict], poses: Dict[int, CameraPose],
-                    max_pairs: int = 30) -> Tuple[np.ndarray, np.ndarray]:
+                    max_pairs: int = 30, *, with_normals: bool = False, normal_radius: int = 2,
+                    normal_jump: float = 0.05, normal_depth_tolerance: float = 0.01) -> Tuple[np.ndarray, ...]:
+        """(points, colors) as the reference returns them.  with_normals=True appends oriented unit normals (N,3) float32
+        of the final cloud (csrc/amvs_cloud_normals.hip, include/amvs.h amvs_cloud_normals; no reference counterpart),
+        fitted to the inverse depths of the sweep's maps over the pixels the back-projection selects (confidence >=
+        min_views - 0.5) and collected per point from the views that see it; a point no view gives one keeps (0, 0, 0)."""
+        if with_normals:
+            _, world = _parallel.rank_world(self.process_group)
+            if world > 1:
+                raise NotImplementedError("with_normals runs on one process: normals with a process group of "
+                                          f"{world} ranks are not implemented (call it without a process group)")
+        fit = (normal_radius, normal_jump, normal_depth_tolerance) if with_normals else None
+        points, colors, normals = self._reconstruct(images, poses, max_pairs, fit)
+        return (points, colors, normals) if with_normals else (points, colors)
+
+    def _reconstruct(self, images, poses, max_pairs, fit):
+        """reconstruct() and its progress lines; fit = None or (radius, jump, depth tolerance) of the normals, which are
+        computed on the final cloud before the closing line."""
+        no_normals = np.zeros((0, 3), np.float32)
         print("\n" + "=" * 60)
         print("GPU DENSE STEREO")
         print(f"  Scale: {self.scale}x, Depths: {self.num_depths}, Min views: {self.min_views}")
@@ -72,7 +91,7 @@ class DenseStereoReconstructor(ResidentViews):
         n_cameras = len(camera_indices)
         if n_cameras < 3:                                       # reference :77-79
             print("Need at least 3 cameras for multi-view stereo")
-            return np.array([]), np.array([])
+            return np.array([]), np.array([]), no_normals
 
         print("\nPreparing images...")
         if self.device_prep:
@@ -97,28 +116,46 @@ class DenseStereoReconstructor(ResidentViews):
                 jobs.append((ref_idx, neighbors))
         if not jobs:
             print("No points reconstructed!")
-            return np.array([]), np.array([])
+            return np.array([]), np.array([]), no_normals
 
         H, W = processed[camera_indices[0]]["shape"]
         depths = 1.0 / np.linspace(1 / depth_max, 1 / depth_min, self.num_depths)      # reference :204-205
         eng = self._ensure_engine(processed, poses)
-        counts, total, resident = self._sweep_and_backproject(eng, jobs, processed, poses, depths, H, W)
+        counts, total, maps = self._sweep_and_backproject(eng, jobs, processed, poses, depths, H, W, want_maps=fit is not None)
         per_view = (time.time() - t1) / len(jobs)
         for i, ((ref_idx, _), cnt) in enumerate(zip(jobs, counts)):
             print(f"  [{i+1}/{len(jobs)}] Cam {ref_idx}: {cnt:,} pts ({per_view:.1f}s)")
         if total == 0:
             print("No points reconstructed!")
-            return np.array([]), np.array([])
+            return np.array([]), np.array([]), no_normals
         print("\nMerging point clouds...")
         print(f"  Raw points: {total:,}")
         points, colors = self._filter_and_downsample_device(eng, total, voxel_size=0.02)
+        normals = self._cloud_normals(eng, points, colors, maps, *fit) if fit is not None else None
         print(f"\nDense stereo completed in {time.time() - t0:.1f}s")
-        return points, colors
+        return points, colors, normals
 
-    def _sweep_and_backproject(self, eng, jobs, processed, poses, depths, H, W):
+    def _cloud_normals(self, eng, points, colors, maps, radius, jump, depth_tolerance):
+        """Normals of the final cloud from the maps _sweep_and_backproject(want_maps=True) returned: their poses and, unless
+        they are the engine's resident sweep batch, host arrays or device tensors.  The cloud is the engine's resident one
+        unless the filter took the host path; that one is uploaded first."""
+        if len(points) == 0:
+            return np.zeros((0, 3), np.float32)
+        t0 = time.time()
+        if not self._cloud_resident:
+            eng.cloud_set(points, colors)
+        where = {k: maps[k] for k in ("depth", "conf", "device_ptrs") if k in maps}
+        _, n_points = eng.cloud_normals(self.K_scaled, maps["poses"], self.min_views - 0.5, radius, jump, 3, depth_tolerance, 1,
+                                        **where)
+        normals, _ = eng.fetch_cloud_normals(len(points))
+        print(f"  Normals: {n_points:,} of {len(points):,} points from {len(maps['poses'])} views ({time.time() - t0:.2f}s)")
+        return normals
+
+    def _sweep_and_backproject(self, eng, jobs, processed, poses, depths, H, W, want_maps=False):
         """Batched plane sweep of this rank's reference views (maps stay on the GPU), all-gather of
         the maps when ranks share the work, back-projection on the device.  Returns the per-view
-        point counts, their sum, and whether the cloud is resident (always, here)."""
+        point counts, their sum, and -- with want_maps, else None -- where _cloud_normals finds the maps
+        that were back-projected and their poses."""
         rank, world = _parallel.rank_world(self.process_group)
         mine = _parallel.shard(len(jobs), rank, world)
         groups = {}
@@ -137,7 +174,7 @@ class DenseStereoReconstructor(ResidentViews):
             else:
                 cols = np.stack([processed[jobs[j][0]]["color"] for j in js])
                 counts, total = eng.stereo_backproject(cols, K_inv, view_poses, min_conf)
-            return counts, total, True
+            return counts, total, dict(poses=view_poses) if want_maps else None      # (the resident maps of the sweep)
         # several batches and / or several ranks: the maps of every view are collected first -- in
         # device tensors when torch-ROCm is there (job j in row j; the sweeps write their rows, RCCL
         # gathers the rank blocks in place, the back-projection reads them: nothing crosses PCIe)
@@ -172,7 +209,10 @@ class DenseStereoReconstructor(ResidentViews):
             first = 0 if world > 1 else mine[0]
             counts, total = eng.stereo_backproject(cols, K_inv, view_poses, min_conf,
                                                    device_ptrs=(dmaps[first].data_ptr(), cmaps[first].data_ptr()))
-            return counts, total, True
+            if not want_maps:
+                return counts, total, None
+            return counts, total, dict(poses=view_poses, device_ptrs=(dmaps[first].data_ptr(), cmaps[first].data_ptr()),
+                                       tensors=(dmaps[first:first + len(order)], cmaps[first:first + len(order)]))
         dmaps = np.zeros((len(mine), H, W), np.float32)
         cmaps = np.zeros((len(mine), H, W), np.float32)
         row = {j: n for n, j in enumerate(mine)}
@@ -182,7 +222,7 @@ class DenseStereoReconstructor(ResidentViews):
             for n, j in enumerate(js):
                 dmaps[row[j]], cmaps[row[j]] = d[n], c[n]
         counts, total = eng.stereo_backproject(cols, K_inv, view_poses, min_conf, depth=dmaps, conf=cmaps)
-        return counts, total, True
+        return counts, total, dict(poses=view_poses, depth=dmaps, conf=cmaps) if want_maps else None
 
     def _filter_and_downsample_device(self, eng, total, voxel_size, k=20, std_ratio=2.0):
         """_filter_outliers (:439-473) + _voxel_down_sample (:475-492) on the resident cloud.  The
@@ -192,6 +232,7 @@ class DenseStereoReconstructor(ResidentViews):
         same draw on the device (amvs_cloud_take); neighbour counts the device search is not compiled for take
         the host path."""
         host_path = not self.device_filter or not eng.knn_supported(k) or k >= min(total, 500000) // 2
+        self._cloud_resident = True
         if total < k + 1:
             keep = None
         elif total > 500000 and not host_path and not self._subsample_on_host:
@@ -203,6 +244,7 @@ class DenseStereoReconstructor(ResidentViews):
             mean_d = eng.cloud_knn_mean_distance(total, k)
             keep = mean_d < np.mean(mean_d) + std_ratio * np.std(mean_d)
         elif total > 500000 or host_path:
+            self._cloud_resident = False
             points, colors = eng.fetch_cloud(total)
             points, colors = self._filter_outliers(points, colors, k, std_ratio)
             print(f"  After outlier removal: {len(points):,}")

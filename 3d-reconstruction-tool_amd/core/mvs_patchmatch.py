@@ -110,12 +110,53 @@ class PatchMatchMVS(ResidentViews):
         # as well; how the RCCL calls are rehearsed on a one-GPU box
         self.exercise_exchange = False
         self._streams = None             # (device, sweep stream, exchange stream) of _exchange_streams
+        self._cloud_resident = False
 
     # ------------------------------------------------------------------ public ----
     def reconstruct(self, images: List[dict], poses: Dict[int, CameraPose],
-                    sparse_points: np.ndarray = None) -> Tuple[np.ndarray, np.ndarray]:
-        points, colors, _ = self._reconstruct_maps(images, poses, sparse_points)
-        return points, colors
+                    sparse_points: np.ndarray = None, *, with_normals: bool = False, normal_radius: int = 2,
+                    normal_jump: float = 0.05, normal_depth_tolerance: float = 0.01) -> Tuple[np.ndarray, ...]:
+        """(points, colors) as the reference returns them.  with_normals=True appends oriented unit normals (N,3) float32
+        of the final cloud (csrc/amvs_cloud_normals.hip, include/amvs.h amvs_cloud_normals; no reference counterpart): per
+        view a plane is fitted to the inverse depths in a window of normal_radius pixels around every pixel with
+        confidence >= min_views, over the neighbours whose depth is within normal_jump of the centre's, and every point
+        takes the cosine-weighted mean of the normals of the views that see it within normal_depth_tolerance (relative).
+        A point no view gives a normal keeps (0, 0, 0)."""
+        if with_normals:
+            _, world = _parallel.rank_world(self.process_group)
+            if world > 1:
+                raise NotImplementedError("with_normals runs on one process: normals with a process group of "
+                                          f"{world} ranks are not implemented (call it without a process group)")
+        points, colors, maps = self._reconstruct_maps(images, poses, sparse_points)
+        if not with_normals:
+            return points, colors
+        return points, colors, self._cloud_normals(points, colors, maps, poses, normal_radius, normal_jump, normal_depth_tolerance)
+
+    def _cloud_normals(self, points, colors, maps, poses, radius, jump, depth_tolerance):
+        """Normals of the final cloud from the maps _reconstruct_maps returned.  The cloud is the engine's resident one
+        wherever the fusion ran on the device; the host fusion's cloud is uploaded first."""
+        if maps is None or len(points) == 0:
+            return np.zeros((len(points), 3), np.float32)       # (one row per point, whatever the early exit)
+        t0 = time.time()
+        kind, data, _ = maps
+        if kind == "resident":
+            ids = list(data.ref_ids)
+            import torch
+            torch.cuda.synchronize(data.depth.device)
+            where = dict(device_ptrs=(data.depth.data_ptr(), data.confidence.data_ptr()))
+        else:
+            ids = list(data)
+            where = dict(depth=np.stack([data[i].depth for i in ids]), conf=np.stack([data[i].confidence for i in ids])) if ids else {}
+        if not ids:
+            return np.zeros((len(points), 3), np.float32)
+        eng = self._engine
+        if not self._cloud_resident:
+            eng.cloud_set(points, colors)
+        _, n_points = eng.cloud_normals(self.K_scaled, [(poses[i].R, poses[i].t) for i in ids], self.min_views, radius, jump, 3,
+                                        depth_tolerance, 1, **where)
+        normals, _ = eng.fetch_cloud_normals(len(points))
+        print(f"  Normals: {n_points:,} of {len(points):,} points from {len(ids)} views ({time.time() - t0:.2f}s)")
+        return normals
 
     def reconstruct_mesh(self, images: List[dict], poses: Dict[int, CameraPose], sparse_points: np.ndarray = None, *,
                          voxel_size: Optional[float] = None, bounds=None, trunc_voxels: float = 4.0,
@@ -401,16 +442,19 @@ class PatchMatchMVS(ResidentViews):
         else:
             torch = _parallel._torch_cuda() if self.device_fusion and jobs else None
             sweep = self._sweep_resident
+        self._cloud_resident = False     # the engine holds the final cloud (what _cloud_normals works on)
         if torch is not None:
             resident = sweep(torch, jobs, proc_images, poses, cam_indices)
             print("\nFusing depth maps...")
             points, colors, raw = self._fuse_filter_resident(resident, proc_images, poses)
+            self._cloud_resident = len(resident.ref_ids) > 0
             maps = ("resident", resident, proc_images)
         else:
             depth_maps = self._sweep(jobs, proc_images, poses, cam_indices)
             print("\nFusing depth maps...")
             if self.device_fusion and self._engine is not None and depth_maps:
                 points, colors, raw = self._fuse_filter_device(depth_maps, proc_images, poses)
+                self._cloud_resident = raw > 0
             else:
                 points, colors = self._fuse_depth_maps(depth_maps, proc_images, poses)
                 raw = len(points)

@@ -1,6 +1,6 @@
 """Output helpers around the dense stage (reference: src/core/utils.py).
 
-`save_ply` has the reference's signature and writes the same bytes (utils.py:8-37); the per-point
+`save_ply` has the reference's signature (plus optional normals) and writes the same bytes (utils.py:8-37); the per-point
 Python `f.write` loop there dominates wall time for multi-million-point clouds, so the formatting
 runs in the native library (`amvs_write_ply`, host-only).  `save_mesh_ply` writes the surface mesh of
 PatchMatchMVS.reconstruct_mesh as binary little-endian PLY (no reference counterpart).
@@ -30,18 +30,27 @@ def rows_matmul(rows: np.ndarray, matrix: np.ndarray) -> np.ndarray:
     return rows @ matrix
 
 
-def save_ply(points: np.ndarray, colors: np.ndarray, output_path: str):
-    """Save an (N,3) cloud with (N,3) RGB colours as ASCII PLY."""
+def save_ply(points: np.ndarray, colors: np.ndarray, output_path: str, normals: np.ndarray = None):
+    """Save an (N,3) cloud with (N,3) RGB colours as ASCII PLY.  With normals (N,3) float32 every vertex is
+    x y z nx ny nz red green blue (`amvs_write_ply_normals`; no reference counterpart); without, the file is the
+    reference's byte for byte."""
     output_path = Path(output_path)
     output_path.parent.mkdir(parents=True, exist_ok=True)
     n = len(points)
     pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(n, 3))
     cols = np.ascontiguousarray(np.asarray(colors).reshape(n, 3).astype(int).astype(np.int64))
     lib = _lib.load()
-    rc = lib.amvs_write_ply(str(output_path).encode(), pts.ctypes.data_as(C.POINTER(C.c_double)),
-                            cols.ctypes.data_as(C.POINTER(C.c_int64)), n)
+    if normals is None:
+        name = "amvs_write_ply"
+        rc = lib.amvs_write_ply(str(output_path).encode(), pts.ctypes.data_as(C.POINTER(C.c_double)),
+                                cols.ctypes.data_as(C.POINTER(C.c_int64)), n)
+    else:
+        name = "amvs_write_ply_normals"
+        nrm = np.ascontiguousarray(np.asarray(normals, dtype=np.float32).reshape(n, 3))
+        rc = lib.amvs_write_ply_normals(str(output_path).encode(), pts.ctypes.data_as(C.POINTER(C.c_double)),
+                                        nrm.ctypes.data_as(_lib.f32p), cols.ctypes.data_as(C.POINTER(C.c_int64)), n)
     if rc != 0:
-        raise _lib.AmvsError(f"amvs_write_ply failed ({rc}): {lib.amvs_last_error(None).decode()}")
+        raise _lib.AmvsError(f"{name} failed ({rc}): {lib.amvs_last_error(None).decode()}")
     print(f"Saved {n:,} points to {output_path}")
 
 

@@ -1,7 +1,8 @@
 // amvs_capi_cloud.hip -- the point-cloud entry points of the C ABI (include/amvs.h): back-projection, fusion, the
-// steps on the resident cloud, the neighbour statistic and the PLY writer.
+// steps on the resident cloud, its normals from the depth maps, the neighbour statistic and the PLY writers.
 #include "amvs_ctx.h"
 
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <utility>
@@ -172,6 +173,121 @@ int amvs_fetch_cloud(amvs_ctx *c, double *points, uint8_t *colors)
     return checked(c, AMVS_OK);
 }
 
+// the parameters amvs_depth_normals and amvs_cloud_normals share, and where the maps are; NULL = fine
+static const char *normal_args_error(const amvs_ctx *c, int n_maps, const void *depth, const void *conf, int maps_where,
+                                     const double *K, const double *poses, int radius, float jump, int min_points)
+{
+    if (n_maps < 1 || maps_where < 0 || maps_where > 2) return "bad argument";
+    if (!K || !poses) return "NULL K / poses";
+    if (radius < 1 || radius > 4) return "radius outside 1 .. 4";
+    if (min_points < 3) return "min_points below 3";
+    if (!(jump > 0.0f && jump <= FLT_MAX)) return "jump must be positive and finite";
+    if (maps_where == 2 ? n_maps != c->n_sweep : (!depth || !conf))
+        return maps_where == 2 ? "n_maps differs from the resident plane-sweep batch" : "NULL maps";
+    if ((long long)n_maps * c->H * c->W > 0x7FFFFFFFll) return "more than 2^31 - 1 pixels";
+    return nullptr;
+}
+
+int amvs_depth_normals(amvs_ctx *c, int n_maps, const void *depth, const void *conf, int maps_where, const double K[9],
+                       const double *poses, float min_confidence, int radius, float jump, int min_points, int world,
+                       int64_t *n_normals)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!n_normals) return fail(c, AMVS_EINVAL, "NULL output");
+    if (const char *why = normal_args_error(c, n_maps, depth, conf, maps_where, K, poses, radius, jump, min_points))
+        return fail(c, AMVS_EINVAL, why);
+    int rc = bind_device(c);
+    if (rc) return rc;
+    const size_t n = (size_t)c->H * c->W * (size_t)n_maps;
+    amvs::DeviceBuffer<float> copy[2];
+    const float *dd = maps_where == 2 ? c->d_sweep_depth.get() : (const float *)depth;
+    const float *dc = maps_where == 2 ? c->d_sweep_conf.get() : (const float *)conf;
+    if (maps_where == 0 && (rc = stage_maps(c, n, dd, dc, copy))) return rc;
+    c->depth_normal_maps = 0;
+    long long cnt = 0;
+    const hipError_t e = amvs::depth_normals(dd, dc, n_maps, c->H, c->W, K, poses, min_confidence, radius, jump, min_points,
+                                             world != 0, c->cache, c->d_depth_normals, &cnt, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("depth_normals: ") + hipGetErrorString(e));
+    c->depth_normal_maps = n_maps;
+    *n_normals = cnt;
+    return checked(c, AMVS_OK);
+}
+
+int amvs_fetch_depth_normals(amvs_ctx *c, int first, int count, float *out)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!out || first < 0 || count < 1 || (long long)first + count > c->depth_normal_maps)
+        return fail(c, AMVS_EINVAL, "NULL output / maps outside the last amvs_depth_normals");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    const size_t per = 3 * (size_t)c->H * c->W;
+    HIPCHK(c, hipMemcpyAsync(out, c->d_depth_normals.get() + per * first, sizeof(float) * per * count, hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_cloud_normals(amvs_ctx *c, int n_maps, const void *depth, const void *conf, int maps_where, const double K[9],
+                       const double *poses, float min_confidence, int radius, float jump, int min_points,
+                       float depth_tolerance, int min_views, int64_t counts[2])
+{
+    if (!c) return AMVS_EINVAL;
+    if (!counts) return fail(c, AMVS_EINVAL, "NULL output");
+    if (const char *why = normal_args_error(c, n_maps, depth, conf, maps_where, K, poses, radius, jump, min_points))
+        return fail(c, AMVS_EINVAL, why);
+    if (!(depth_tolerance > 0.0f && depth_tolerance <= FLT_MAX)) return fail(c, AMVS_EINVAL, "depth_tolerance must be positive and finite");
+    if (min_views < 1) return fail(c, AMVS_EINVAL, "min_views below 1");
+    if (c->cloud.n < 1) return fail(c, AMVS_EINVAL, "no resident cloud");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    const size_t n = (size_t)c->H * c->W * (size_t)n_maps;
+    amvs::DeviceBuffer<float> copy[2];
+    const float *dd = maps_where == 2 ? c->d_sweep_depth.get() : (const float *)depth;
+    const float *dc = maps_where == 2 ? c->d_sweep_conf.get() : (const float *)conf;
+    if (maps_where == 0 && (rc = stage_maps(c, n, dd, dc, copy))) return rc;
+    c->depth_normal_maps = 0;
+    c->cloud.have_normals = false;
+    long long cnt[2] = {0, 0};
+    const hipError_t e = amvs::cloud_normals(c->cloud.pts.get(), c->cloud.n, dd, dc, n_maps, c->H, c->W, K, poses, min_confidence,
+                                             radius, jump, min_points, depth_tolerance, min_views, c->cache, c->d_depth_normals,
+                                             c->cloud.nrm, c->cloud.seen, cnt, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("cloud_normals: ") + hipGetErrorString(e));
+    c->depth_normal_maps = n_maps;
+    c->cloud.have_normals = true;
+    counts[0] = cnt[0]; counts[1] = cnt[1];
+    return checked(c, AMVS_OK);
+}
+
+int amvs_fetch_cloud_normals(amvs_ctx *c, float *normals, int32_t *seen)
+{
+    if (!c) return AMVS_EINVAL;
+    if (c->cloud.n < 1 || !c->cloud.have_normals) return fail(c, AMVS_EINVAL, "the resident cloud has no normals");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    static_assert(sizeof(int) == sizeof(int32_t), "count width");
+    if (normals)
+        HIPCHK(c, hipMemcpyAsync(normals, c->cloud.nrm.get(), sizeof(float) * 3 * c->cloud.n, hipMemcpyDeviceToHost, c->stream));
+    if (seen) HIPCHK(c, hipMemcpyAsync(seen, c->cloud.seen.get(), sizeof(int32_t) * c->cloud.n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return checked(c, AMVS_OK);
+}
+
+int amvs_cloud_set(amvs_ctx *c, const double *points, const uint8_t *colors_rgb, int64_t n)
+{
+    if (!c) return AMVS_EINVAL;
+    if (n < 0 || n > 0x7FFFFFFFll || (n > 0 && (!points || !colors_rgb))) return fail(c, AMVS_EINVAL, "bad argument");
+    int rc = bind_device(c);
+    if (rc) return rc;
+    Cloud next;
+    if (n > 0) {
+        if ((rc = upload(c, points, 3 * (size_t)n, next.pts)) || (rc = upload(c, colors_rgb, 3 * (size_t)n, next.rgb))) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        next.n = n;
+    }
+    c->cloud = std::move(next);
+    return checked(c, AMVS_OK);
+}
+
 int amvs_knn_mean_distance(amvs_ctx *c, const double *points, int64_t n, int k, double *mean_out)
 {
     if (!c) return AMVS_EINVAL;
@@ -224,22 +340,22 @@ static inline char *put_i64(char *o, long long v)
     return put_u64(o, (uint64_t)v);
 }
 
-// utils.save_ply (utils.py:8-37): ASCII PLY, "%.6f %.6f %.6f %d %d %d" per vertex.  Host-only:
-// formats into a 1 MiB buffer instead of one Python f.write per point.
-int amvs_write_ply(const char *path, const double *points, const int64_t *colors, int64_t n)
+// utils.save_ply (utils.py:8-37): ASCII PLY, "%.6f %.6f %.6f %d %d %d" per vertex; with normals (float32, widened)
+// three more "%.6f" between the position and the colour.  Host-only: formats into a 1 MiB buffer instead of one Python
+// f.write per point.
+static int write_ply(const char *path, const double *points, const float *normals, const int64_t *colors, int64_t n)
 {
-    if (!path || n < 0 || (n > 0 && (!points || !colors))) return fail(nullptr, AMVS_EINVAL, "bad argument");
     FILE *f = std::fopen(path, "w");
     if (!f) return fail(nullptr, AMVS_EINVAL, std::string("cannot open ") + path);
     std::vector<char> buf(1 << 20);
     size_t used = (size_t)std::snprintf(buf.data(), buf.size(),
                                         "ply\nformat ascii 1.0\nelement vertex %lld\nproperty float x\n"
-                                        "property float y\nproperty float z\nproperty uchar red\n"
+                                        "property float y\nproperty float z\n%sproperty uchar red\n"
                                         "property uchar green\nproperty uchar blue\nend_header\n",
-                                        (long long)n);
+                                        (long long)n, normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "");
     bool ok = true;
     for (int64_t i = 0; i < n && ok; ++i) {
-        if (used + 1400 > buf.size()) {              // (a "%.6f" of the largest double is 316 characters)
+        if (used + 1400 > buf.size()) {              // (a "%.6f" of the largest double is 316 characters, of a float 46)
             ok = std::fwrite(buf.data(), 1, used, f) == used;
             used = 0;
         }
@@ -247,6 +363,8 @@ int amvs_write_ply(const char *path, const double *points, const int64_t *colors
         o = put_f6(o, points[3 * i]); *o++ = ' ';
         o = put_f6(o, points[3 * i + 1]); *o++ = ' ';
         o = put_f6(o, points[3 * i + 2]); *o++ = ' ';
+        if (normals)
+            for (int k = 0; k < 3; ++k) { o = put_f6(o, (double)normals[3 * i + k]); *o++ = ' '; }
         o = put_i64(o, (long long)colors[3 * i]); *o++ = ' ';
         o = put_i64(o, (long long)colors[3 * i + 1]); *o++ = ' ';
         o = put_i64(o, (long long)colors[3 * i + 2]); *o++ = '\n';
@@ -255,6 +373,18 @@ int amvs_write_ply(const char *path, const double *points, const int64_t *colors
     if (ok && used) ok = std::fwrite(buf.data(), 1, used, f) == used;
     ok = (std::fclose(f) == 0) && ok;
     return ok ? AMVS_OK : fail(nullptr, AMVS_EINVAL, std::string("write failed: ") + path);
+}
+
+int amvs_write_ply(const char *path, const double *points, const int64_t *colors, int64_t n)
+{
+    if (!path || n < 0 || (n > 0 && (!points || !colors))) return fail(nullptr, AMVS_EINVAL, "bad argument");
+    return write_ply(path, points, nullptr, colors, n);
+}
+
+int amvs_write_ply_normals(const char *path, const double *points, const float *normals, const int64_t *colors, int64_t n)
+{
+    if (!path || !normals || n < 0 || (n > 0 && (!points || !colors))) return fail(nullptr, AMVS_EINVAL, "bad argument");
+    return write_ply(path, points, normals, colors, n);
 }
 
 }  // extern "C"

@@ -40,11 +40,16 @@ struct FastStats {
     std::vector<char> done;
 };
 
-// a point cloud on the device: float64 xyz, uint8 rgb
+// a point cloud on the device: float64 xyz, uint8 rgb; after amvs_cloud_normals also float32 normals and the int32 counts
+// of the views that gave them.  Every step that makes a cloud assigns a fresh Cloud, so the normals never outlive the
+// points they were computed for.
 struct Cloud {
     amvs::DeviceBuffer<double> pts;
     amvs::DeviceBuffer<unsigned char> rgb;
     long long n = 0;
+    amvs::DeviceBuffer<float> nrm;
+    amvs::DeviceBuffer<int> seen;
+    bool have_normals = false;
 };
 
 }  // namespace host
@@ -89,6 +94,8 @@ struct amvs_ctx {
     amvs::DeviceBuffer<float> d_sweep_depth, d_sweep_conf;     // maps of the last amvs_plane_sweep_batch
     int n_sweep = 0;
     amvs::host::Cloud cloud;             // result of the last fusion / back-projection and the steps after it
+    amvs::DeviceBuffer<float> d_depth_normals;   // [depth_normal_maps][H*W][3] of the last amvs_depth_normals / amvs_cloud_normals
+    int depth_normal_maps = 0;           // (grown only; 0 = none to fetch)
     // volume, scans and mesh of amvs_tsdf_* (amvs_mesh.hip), lazily created
     std::unique_ptr<amvs::TsdfState, void (*)(amvs::TsdfState *)> tsdf{nullptr, amvs::tsdf_state_free};
     // split schedule (amvs_pm_params.schedule == AMVS_SCHEDULE_SPLIT): sample maps (its streams and token events are

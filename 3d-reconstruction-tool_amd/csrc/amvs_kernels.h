@@ -245,6 +245,18 @@ hipError_t voxel_downsample(const double *pts, const unsigned char *rgb, long lo
                             double voxel, ScratchCache &cache, DeviceBuffer<double> &pts_out,
                             DeviceBuffer<unsigned char> &rgb_out, long long *m_out, hipStream_t st);
 
+// amvs_cloud_normals.hip: per-view normal maps fitted to the inverse depths, and the normals of a cloud from them
+// (include/amvs.h amvs_depth_normals, amvs_cloud_normals).  depth / conf: [n_maps][H*W] float32 on the device; K_h: 9
+// doubles row-major, poses_h: n_maps x 12 doubles (host).  The caller has validated the parameters.  `normals` /
+// `map_normals` ([n_maps][H*W][3]), nrm_out ([n_pts][3]) and seen_out ([n_pts]) are grown as needed.  Both synchronise.
+hipError_t depth_normals(const float *depth, const float *conf, int n_maps, int H, int W, const double *K_h, const double *poses_h,
+                         float min_confidence, int radius, float jump, int min_points, bool world, ScratchCache &cache,
+                         DeviceBuffer<float> &normals, long long *n_normals, hipStream_t st);
+// counts[0] = pixels with a normal (world frame), counts[1] = points with a normal
+hipError_t cloud_normals(const double *pts, long long n_pts, const float *depth, const float *conf, int n_maps, int H, int W,
+                         const double *K_h, const double *poses_h, float min_confidence, int radius, float jump, int min_points,
+                         float depth_tolerance, int min_views, ScratchCache &cache, DeviceBuffer<float> &map_normals,
+                         DeviceBuffer<float> &nrm_out, DeviceBuffer<int> &seen_out, long long counts[2], hipStream_t st);
 
 // amvs_mesh.hip: TSDF fusion of the per-view maps and marching-tetrahedra extraction (include/amvs.h
 // amvs_tsdf_*).  The state (volume, scans, mesh) is owned by a context and freed with it; its buffers are

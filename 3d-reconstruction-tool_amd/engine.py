@@ -416,6 +416,63 @@ class Engine:
     def knn_supported(self, k):
         return bool(self._lib.amvs_knn_supported(int(k)))
 
+    # -- normals from the depth maps (include/amvs.h amvs_depth_normals ...) --
+    def _normal_maps(self, poses, depth, conf, device_ptrs):
+        """(n maps, depth pointer, confidence pointer, maps_where, poses array, keep) of the three ways the maps reach
+        amvs_depth_normals / amvs_cloud_normals: host arrays (n,H,W), device_ptrs=(depth_ptr, conf_ptr), or neither --
+        the resident maps of the last plane_sweep_batch."""
+        pp = _poses64(poses)
+        n = pp.shape[0]
+        if device_ptrs is not None:
+            return n, C.c_void_p(device_ptrs[0]), C.c_void_p(device_ptrs[1]), 1, pp, None
+        if depth is None:
+            return n, C.c_void_p(0), C.c_void_p(0), 2, pp, None
+        depth, conf = _f32(depth, (n, self.H, self.W)), _f32(conf, (n, self.H, self.W))
+        return n, depth.ctypes.data_as(C.c_void_p), conf.ctypes.data_as(C.c_void_p), 0, pp, (depth, conf)
+
+    def depth_normals(self, K, poses, min_confidence, radius=2, jump=0.05, min_points=3, world=False, depth=None, conf=None,
+                      device_ptrs=None, fetch=True):
+        """Per-view normal maps fitted to the inverse depths (include/amvs.h amvs_depth_normals): K (3,3) float64, poses =
+        list of (R, t) float64, maps as _normal_maps takes them.  Returns (normals (n,H,W,3) float32 -- zero where a pixel
+        has none --, pixels with a normal), or the count alone with fetch=False (the maps stay on the device)."""
+        n, dptr, cptr, where, pp, keep = self._normal_maps(poses, depth, conf, device_ptrs)
+        Kd = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+        cnt = C.c_int64(0)
+        self._chk(self._lib.amvs_depth_normals(self._h, n, dptr, cptr, where, _f64(Kd), _f64(pp), float(min_confidence),
+                                               int(radius), float(jump), int(min_points), int(bool(world)), C.byref(cnt)))
+        if not fetch:
+            return int(cnt.value)
+        out = np.empty((n, self.H, self.W, 3), np.float32)
+        self._chk(self._lib.amvs_fetch_depth_normals(self._h, 0, n, _p(out)))
+        return out, int(cnt.value)
+
+    def cloud_normals(self, K, poses, min_confidence, radius=2, jump=0.05, min_points=3, depth_tolerance=0.01, min_views=1,
+                      depth=None, conf=None, device_ptrs=None):
+        """Normals of the resident cloud from the views that see it (include/amvs.h amvs_cloud_normals).  Returns (pixels
+        with a normal, points with a normal); fetch_cloud_normals copies the result."""
+        n, dptr, cptr, where, pp, keep = self._normal_maps(poses, depth, conf, device_ptrs)
+        Kd = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+        counts = (C.c_int64 * 2)()
+        self._chk(self._lib.amvs_cloud_normals(self._h, n, dptr, cptr, where, _f64(Kd), _f64(pp), float(min_confidence),
+                                               int(radius), float(jump), int(min_points), float(depth_tolerance),
+                                               int(min_views), counts))
+        return int(counts[0]), int(counts[1])
+
+    def fetch_cloud_normals(self, m):
+        """(normals (m,3) float32, seen (m,) int32) of the m points of the resident cloud."""
+        nrm = np.empty((m, 3), np.float32)
+        seen = np.empty(m, np.int32)
+        self._chk(self._lib.amvs_fetch_cloud_normals(self._h, _p(nrm), seen.ctypes.data_as(i32p)))
+        return nrm, seen
+
+    def cloud_set(self, points, colors=None):
+        """Replace the resident cloud by host arrays (test hook; colours default to zero).  Returns the point count."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        m = len(pts)
+        rgb = np.zeros((m, 3), np.uint8) if colors is None else np.ascontiguousarray(colors, dtype=np.uint8).reshape(m, 3)
+        self._chk(self._lib.amvs_cloud_set(self._h, _f64(pts), _u8(rgb), m))
+        return m
+
     # -- single steps (parity tests) ----------------------------------------
     def eval_cost(self, ref, src_ids, patch_size, depth):
         src, srcp = _ids(src_ids)

@@ -297,6 +297,87 @@ int amvs_fuse_filter_views(amvs_ctx *ctx, int n_maps, const int *view_ids, const
                            int64_t counts[2]);
 int amvs_fetch_cloud(amvs_ctx *ctx, double *points_out, uint8_t *colors_out);
 
+/* ---- oriented normals for the cloud, fitted from the depth maps (csrc/amvs_cloud_normals.hip) ---------------------
+ * The reference's cloud has no normals; no counterpart, hence no parity: judged against tests/cloud_normals_restatement.py,
+ * written from the text below, bit for bit, and against the analytic normals of a synthetic height field (DESIGN.md
+ * section 9).  Per view a least-squares plane is fitted to the INVERSE depths of a small window -- inverse depth is linear
+ * in the pixel coordinates on a plane, so the fit is a 3 x 3 system with an integer matrix, solved in closed form: no
+ * eigen-decomposition, no iteration, and a normal that faces its camera by construction.  Each cloud point then collects
+ * the normals of the views that see it.
+ *
+ * All arithmetic below is float64 unless stated: one rounding per operation, nothing contracted, in exactly the written
+ * order; an integer that meets a float64 is converted first (exactly: every integer here is below 2^53).
+ *
+ * Pixel validity.  Pixel p of map j is VALID iff, in float32, depth > 0, depth <= FLT_MAX and conf >= min_confidence.
+ * NaN fails each comparison.
+ *
+ * Window fit.  Parameters: radius r in 1 .. 4, jump (float32, positive and finite), min_points (>= 3).  A valid centre
+ * pixel (x0, y0) has float32 depth dc.  Walk dy = -r .. r in the outer loop and dx = -r .. r in the inner loop; skip
+ * positions outside the image.  A neighbour with depth dn is USED iff it is valid and
+ *     fabs((double)dn - (double)dc) <= (double)jump * (double)dc.
+ * The centre always uses itself.  Over the used neighbours accumulate
+ *     exact integers:            n, sx = sum dx, sy = sum dy, sxx = sum dx*dx, sxy = sum dx*dy, syy = sum dy*dy;
+ *     float64, in walk order:    q = 1.0 / (double)dn;  Sq += q;  Sxq += (double)dx * q;  Syq += (double)dy * q.
+ * M = [[sxx, sxy, sx], [sxy, syy, sy], [sx, sy, n]].  Its determinant det and its adjugate C (symmetric) are computed in
+ * 64-bit integers:
+ *     C00 = syy*n - sy*sy    C01 = sx*sy - sxy*n     C02 = sxy*sy - sx*syy
+ *     C11 = sxx*n - sx*sx    C12 = sxy*sx - sxx*sy   C22 = sxx*syy - sxy*sxy      det = sxx*C00 + sxy*C01 + sx*C02.
+ * The pixel has NO NORMAL if n < min_points or det == 0 (exactly collinear used points).  Otherwise M is a Gram matrix,
+ * det > 0, and the numerators of the solution need no division:
+ *     a = (C00*Sxq + C01*Syq) + C02*Sq
+ *     b = (C01*Sxq + C11*Syq) + C12*Sq
+ *     c = (C02*Sxq + C12*Syq) + C22*Sq
+ * The pixel has no normal unless c > 0 (the fitted inverse depth at the centre is positive).  Then, with K row-major:
+ *     c' = (c - a*(double)x0) - b*(double)y0
+ *     m_i = (K[0][i]*a + K[1][i]*b) + K[2][i]*c'            i = 0, 1, 2
+ *     len = sqrt((m0*m0 + m1*m1) + m2*m2)
+ * The pixel has no normal unless len > 0 and len is finite.  The camera-frame normal is n_cam_i = (-m_i) / len; it faces
+ * the camera: n_cam . P < 0 for the pixel's point P.  With world != 0:
+ *     n_w[i] = (R[0][i]*n0 + R[1][i]*n1) + R[2][i]*n2
+ * where R comes from poses[j] in the fusion's layout (12 doubles: R row-major, then t; X_cam = R X_world + t).  Each
+ * component is rounded once to float32 and stored in [n_maps][H][W][3]; a pixel with no normal stores (0, 0, 0).
+ *
+ * Cloud normals.  Each resident cloud point X (float64) visits the maps in ascending j, using WORLD-frame normal maps:
+ *   1. Xc_i = ((R[i][0]*X0 + R[i][1]*X1) + R[i][2]*X2) + t_i.
+ *   2. uvw_i = (K[i][0]*Xc0 + K[i][1]*Xc1) + K[i][2]*Xc2.  Skip the map unless uvw2 > 0 and Xc2 > 0.
+ *   3. px = floor(uvw0/uvw2 + 0.5), py = floor(uvw1/uvw2 + 0.5).  Skip unless 0 <= px < W and 0 <= py < H, compared in
+ *      float64 before any integer conversion (NaN fails).
+ *   4. Skip unless the stored normal n (float32, widened) at the pixel has a non-zero component.
+ *   5. Skip unless fabs((double)d - Xc2) <= (double)depth_tolerance * (double)d, d the pixel's float32 depth.
+ *   6. nc_i = (R[i][0]*n0 + R[i][1]*n1) + R[i][2]*n2 and
+ *      w = (-((nc0*Xc0 + nc1*Xc1) + nc2*Xc2)) / sqrt((Xc0*Xc0 + Xc1*Xc1) + Xc2*Xc2).  Skip unless w > 0.
+ *   7. s_i = s_i + w*n_i (i = 0, 1, 2) and seen += 1.
+ * After the last map, with L = sqrt((s0*s0 + s1*s1) + s2*s2): the point's normal is s_i / L, each rounded to float32, iff
+ * seen >= min_views (>= 1) and L > 0; otherwise it is (0, 0, 0).  seen (int32) is kept either way.  The sums live in
+ * registers with a fixed map order; there are no atomics on them.
+ *
+ * Lifetime.  The normals belong to the resident cloud they were computed for: every step that makes a cloud
+ * (amvs_fuse_filter*, amvs_stereo_backproject*, amvs_cloud_voxel_downsample, amvs_cloud_take, amvs_cloud_set) drops them,
+ * and amvs_fetch_cloud_normals then returns AMVS_EINVAL until amvs_cloud_normals ran again.
+ *
+ * Errors (AMVS_EINVAL before anything is allocated): radius outside 1 .. 4, min_points < 3, jump or depth_tolerance not
+ * positive and finite, min_views < 1, NULL K or poses, more than 2^31 - 1 pixels; amvs_cloud_normals without a resident
+ * cloud.
+ *
+ * amvs_depth_normals: maps_where as in amvs_stereo_backproject (0 host arrays, 1 device pointers, 2 the resident maps of
+ * the last amvs_plane_sweep_batch).  The normal maps stay on the device in a grow-only buffer of the context, which the
+ * next amvs_depth_normals or amvs_cloud_normals overwrites; *n_normals = pixels with a normal.                          */
+int amvs_depth_normals(amvs_ctx *ctx, int n_maps, const void *depth, const void *conf, int maps_where, const double K[9],
+                       const double *poses, float min_confidence, int radius, float jump, int min_points, int world,
+                       int64_t *n_normals);
+/* maps first .. first + count - 1 of the last amvs_depth_normals / amvs_cloud_normals: out is [count][H][W][3] float32. */
+int amvs_fetch_depth_normals(amvs_ctx *ctx, int first, int count, float *out);
+/* The fit with world = 1, then the cloud normals of the resident cloud.  counts[0] = pixels with a normal, counts[1] =
+ * points with a normal.                                                                                                 */
+int amvs_cloud_normals(amvs_ctx *ctx, int n_maps, const void *depth, const void *conf, int maps_where, const double K[9],
+                       const double *poses, float min_confidence, int radius, float jump, int min_points,
+                       float depth_tolerance, int min_views, int64_t counts[2]);
+/* normals: [n][3] float32, seen: [n] int32 for the n points of the resident cloud; either may be NULL.                  */
+int amvs_fetch_cloud_normals(amvs_ctx *ctx, float *normals, int32_t *seen);
+/* Test hook in the spirit of amvs_tsdf_set_volume and amvs_mesh_set: replaces the resident cloud by host arrays (copies
+ * only; n x 3 float64 points, n x 3 uint8 RGB colours).  n = 0 leaves no resident cloud.                                */
+int amvs_cloud_set(amvs_ctx *ctx, const double *points, const uint8_t *colors_rgb, int64_t n);
+
 /* ---- surface mesh: TSDF fusion + marching tetrahedra (csrc/amvs_mesh.hip) ------------------------
  * The reference stops at the point cloud; no counterpart, hence no parity: judged against synthetic ground
  * truth and a NumPy restatement of the same float32 operations (tests/mesh_restatement.py).
@@ -743,6 +824,9 @@ int amvs_comm_destroy(amvs_ctx *ctx);
  * bytes as the reference writes, through one buffered native writer (no GPU involved; ctx-free).
  * points: n x 3 float64, colors: n x 3 int64 (the reference casts with .astype(int)).          */
 int amvs_write_ply(const char *path, const double *points, const int64_t *colors, int64_t n);
+/* The same with normals (n x 3 float32, not NULL; no reference counterpart): the header gains `property float nx`, `ny`,
+ * `nz` between z and red, and each line is "x y z nx ny nz r g b" with the normals as "%.6f" of the widened float32.   */
+int amvs_write_ply_normals(const char *path, const double *points, const float *normals, const int64_t *colors, int64_t n);
 
 /* Index-checked build (csrc/amvs_check.h, -DAMVS_CHECK_INDICES; amvs_version() then ends in "+index-checks"): the
  * GPU-side substitute for an address sanitizer, which this pool does not offer for device code.  Every
