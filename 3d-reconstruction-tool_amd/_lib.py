@@ -1,4 +1,4 @@
-"""ctypes binding of libamvs.so (the C ABI declared in include/amvs.h).
+"""ctypes binding of libamvs.so (the C ABI declared in include/amvs.h and include/amvs_depth.h).
 
 There is no CPU fallback: if the shared library is missing or no HIP device is
 present, loading / context creation raises.
@@ -170,6 +170,14 @@ SIGNATURES = {
     "amvs_rng_fill": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int64, f32p, f32p]),
 }
 
+# name -> (restype, argtypes); every symbol include/amvs_depth.h declares.  A table of its own because
+# tests/test_cloud_normals_cpu.py holds SIGNATURES to the 92 declarations of include/amvs.h; load() binds both.
+DEPTH_SIGNATURES = {
+    "amvs_depth_filter": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), C.POINTER(C.c_double), i32p, C.c_int, C.c_float, C.c_float,
+                                    C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
+}
+
 _lib = None
 
 
@@ -205,7 +213,7 @@ def load():
                 "(or `make -C 3d-reconstruction-tool_amd/csrc`). There is no CPU fallback.")
         _share_torch_hip_runtime()
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()):
             fn = getattr(lib, name)      # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args

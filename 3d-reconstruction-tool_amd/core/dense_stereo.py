@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from .camera import Camera, CameraPose
-from .utils import rows_matmul
+from .utils import nearest_map_neighbours, rows_matmul
 from .view_cache import ResidentViews
 from .. import parallel as _parallel
 
@@ -58,29 +58,68 @@ class DenseStereoReconstructor(ResidentViews):
             self.K_scaled[r, c] *= scale
         self._subsample_on_host = False  # test switch: sub-sample clouds above 500 000 points as the host path does
         self._cloud_resident = False     # the engine holds the final cloud
+        self._filter_threshold = None    # filter_min_views while the maps of the last call are the geometric filter's
+
+    def _map_threshold(self):
+        """What a pixel's confidence must reach to be back-projected and to take part in the normals: min_views - 0.5
+        (reference :121), or -- when the maps at hand are the (depth, count) of the geometric filter -- filter_min_views."""
+        held = getattr(self, "_filter_threshold", None)
+        return self.min_views - 0.5 if held is None else held
 
     def _engine_mode(self) -> str:
         return self.mode                 # the engine is created in this object's mode (no mode per call here)
 
     def reconstruct(self, images: List[dict], poses: Dict[int, CameraPose],
                     max_pairs: int = 30, *, with_normals: bool = False, normal_radius: int = 2,
-                    normal_jump: float = 0.05, normal_depth_tolerance: float = 0.01) -> Tuple[np.ndarray, ...]:
+                    normal_jump: float = 0.05, normal_depth_tolerance: float = 0.01, geometric_filter: bool = False,
+                    filter_px: float = 1.0, filter_rel: Optional[float] = None, filter_min_views: int = 2,
+                    filter_refine: bool = True, filter_neighbours: Optional[int] = None) -> Tuple[np.ndarray, ...]:
         """(points, colors) as the reference returns them.  with_normals=True appends oriented unit normals (N,3) float32
         of the final cloud (csrc/amvs_cloud_normals.hip, include/amvs.h amvs_cloud_normals; no reference counterpart),
         fitted to the inverse depths of the sweep's maps over the pixels the back-projection selects (confidence >=
-        min_views - 0.5) and collected per point from the views that see it; a point no view gives one keeps (0, 0, 0)."""
+        min_views - 0.5) and collected per point from the views that see it; a point no view gives one keeps (0, 0, 0).
+
+        geometric_filter=True (off by default: the call is then exactly what it was) checks the depth maps against each
+        other between the sweep and the back-projection (csrc/amvs_depth_filter.hip, include/amvs_depth.h
+        amvs_depth_filter; no reference counterpart): a pixel with confidence >= min_views - 0.5 keeps its depth only if at
+        least filter_min_views other maps agree with it after forward-backward reprojection -- the reprojected pixel
+        within filter_px pixels, the reprojected depth within filter_rel (relative) -- and with filter_refine it becomes
+        the mean of its own and the agreeing depths.  The sweep's depths are quantised to the num_depths planes, so two
+        views of one surface point disagree by up to a plane spacing and filter_rel HAS TO COVER a plane spacing: its
+        default (None) is the largest relative spacing of adjacent planes, max((d[k] - d[k+1]) / d[k+1]) over the plane
+        list d (far to near), which is the spacing at the far end.  filter_neighbours: None compares every map with every
+        other one, an int k with the k nearest camera centres among the views that have a map (the rule and the order of
+        _find_neighbors).  The back-projection and the normals then read the filtered depths and the counts, with
+        filter_min_views as their threshold in place of min_views - 0.5."""
+        gfilter = None
+        if geometric_filter:
+            _, world = _parallel.rank_world(self.process_group)
+            if world > 1:
+                raise NotImplementedError("geometric_filter runs on one process: filtering across a process group of "
+                                          f"{world} ranks is not implemented (call it without a process group)")
+            if isinstance(filter_min_views, (bool, np.bool_)) or int(filter_min_views) != filter_min_views or filter_min_views < 1:
+                raise ValueError("filter_min_views must be an integer of at least 1")
+            gfilter = (float(filter_px), None if filter_rel is None else float(filter_rel), int(filter_min_views),
+                       bool(filter_refine), filter_neighbours)
         if with_normals:
             _, world = _parallel.rank_world(self.process_group)
             if world > 1:
                 raise NotImplementedError("with_normals runs on one process: normals with a process group of "
                                           f"{world} ranks are not implemented (call it without a process group)")
         fit = (normal_radius, normal_jump, normal_depth_tolerance) if with_normals else None
-        points, colors, normals = self._reconstruct(images, poses, max_pairs, fit)
+        points, colors, normals = self._reconstruct(images, poses, max_pairs, fit, gfilter)
         return (points, colors, normals) if with_normals else (points, colors)
 
-    def _reconstruct(self, images, poses, max_pairs, fit):
+    @staticmethod
+    def plane_spacing(depths) -> float:
+        """The largest relative spacing of adjacent planes of the plane list: the default filter_rel."""
+        d = np.asarray(depths, np.float64)
+        return float(np.max(np.abs(d[:-1] - d[1:]) / np.minimum(d[:-1], d[1:]))) if len(d) > 1 else 0.01
+
+    def _reconstruct(self, images, poses, max_pairs, fit, gfilter=None):
         """reconstruct() and its progress lines; fit = None or (radius, jump, depth tolerance) of the normals, which are
-        computed on the final cloud before the closing line."""
+        computed on the final cloud before the closing line; gfilter = None or (px, rel or None, min views, refine,
+        neighbours) of the geometric filter."""
         no_normals = np.zeros((0, 3), np.float32)
         print("\n" + "=" * 60)
         print("GPU DENSE STEREO")
@@ -121,7 +160,10 @@ class DenseStereoReconstructor(ResidentViews):
         H, W = processed[camera_indices[0]]["shape"]
         depths = 1.0 / np.linspace(1 / depth_max, 1 / depth_min, self.num_depths)      # reference :204-205
         eng = self._ensure_engine(processed, poses)
-        counts, total, maps = self._sweep_and_backproject(eng, jobs, processed, poses, depths, H, W, want_maps=fit is not None)
+        if gfilter is not None and gfilter[1] is None:
+            gfilter = (gfilter[0], self.plane_spacing(depths)) + gfilter[2:]
+        counts, total, maps = self._sweep_and_backproject(eng, jobs, processed, poses, depths, H, W, want_maps=fit is not None,
+                                                          gfilter=gfilter)
         per_view = (time.time() - t1) / len(jobs)
         for i, ((ref_idx, _), cnt) in enumerate(zip(jobs, counts)):
             print(f"  [{i+1}/{len(jobs)}] Cam {ref_idx}: {cnt:,} pts ({per_view:.1f}s)")
@@ -145,13 +187,27 @@ class DenseStereoReconstructor(ResidentViews):
         if not self._cloud_resident:
             eng.cloud_set(points, colors)
         where = {k: maps[k] for k in ("depth", "conf", "device_ptrs") if k in maps}
-        _, n_points = eng.cloud_normals(self.K_scaled, maps["poses"], self.min_views - 0.5, radius, jump, 3, depth_tolerance, 1,
+        _, n_points = eng.cloud_normals(self.K_scaled, maps["poses"], self._map_threshold(), radius, jump, 3, depth_tolerance, 1,
                                         **where)
         normals, _ = eng.fetch_cloud_normals(len(points))
         print(f"  Normals: {n_points:,} of {len(points):,} points from {len(maps['poses'])} views ({time.time() - t0:.2f}s)")
         return normals
 
-    def _sweep_and_backproject(self, eng, jobs, processed, poses, depths, H, W, want_maps=False):
+    def _geometric_filter(self, eng, view_poses, min_conf, gfilter, **maps):
+        """Engine.depth_filter on the maps about to be back-projected (resident with in_place, device tensors with
+        out_ptrs, or host arrays); returns what it returns."""
+        t0 = time.time()
+        px, rel, min_views, refine, k = gfilter
+        centers = [-np.asarray(R, np.float64).T @ np.asarray(t, np.float64).reshape(3) for R, t in view_poses]
+        out = eng.depth_filter(self.K_scaled, view_poses, min_conf, px, rel, min_views, refine,
+                               neighbours=nearest_map_neighbours(centers, k), **maps)
+        n_valid, n_kept = out if len(out) == 2 else out[2]
+        self._filter_threshold = min_views
+        print(f"  Geometric filter: {n_kept:,} of {n_valid:,} valid pixels agree with {min_views} views or more "
+              f"(relative depth {rel:.4g}, {time.time() - t0:.2f}s)")
+        return out
+
+    def _sweep_and_backproject(self, eng, jobs, processed, poses, depths, H, W, want_maps=False, gfilter=None):
         """Batched plane sweep of this rank's reference views (maps stay on the GPU), all-gather of
         the maps when ranks share the work, back-projection on the device.  Returns the per-view
         point counts, their sum, and -- with want_maps, else None -- where _cloud_normals finds the maps
@@ -162,13 +218,17 @@ class DenseStereoReconstructor(ResidentViews):
         for j in mine:                                     # a batch has one neighbour count
             groups.setdefault(len(jobs[j][1]), []).append(j)
         K_inv = np.linalg.inv(self.K_scaled)
-        min_conf = self.min_views - 0.5                    # reference :121
+        self._filter_threshold = None
+        min_conf = self._map_threshold()                   # reference :121
         single = world == 1 and len(groups) == 1
         if single:
             js = next(iter(groups.values()))
             refs, nbrs = self._job_slots(jobs, js)
             eng.plane_sweep_batch(refs, nbrs, depths, self.patch_size, self.consistency_thresh)
             view_poses = [(poses[jobs[j][0]].R, poses[jobs[j][0]].t) for j in js]
+            if gfilter is not None:                        # the resident maps become (filtered depth, count)
+                self._geometric_filter(eng, view_poses, min_conf, gfilter, in_place=True)
+                min_conf = self._map_threshold()
             if self._resident_colors and processed is self._engine_images:
                 counts, total = eng.stereo_backproject_views(refs, K_inv, view_poses, min_conf)
             else:
@@ -207,6 +267,13 @@ class DenseStereoReconstructor(ResidentViews):
                         t.copy_(full)
                 torch.cuda.synchronize(dev)
             first = 0 if world > 1 else mine[0]
+            if gfilter is not None:
+                fd, fc = torch.empty_like(dmaps), torch.empty_like(cmaps)
+                torch.cuda.synchronize(dev)
+                self._geometric_filter(eng, view_poses, min_conf, gfilter,
+                                       device_ptrs=(dmaps[first].data_ptr(), cmaps[first].data_ptr()),
+                                       out_ptrs=(fd[first].data_ptr(), fc[first].data_ptr()))
+                dmaps, cmaps, min_conf = fd, fc, self._map_threshold()
             counts, total = eng.stereo_backproject(cols, K_inv, view_poses, min_conf,
                                                    device_ptrs=(dmaps[first].data_ptr(), cmaps[first].data_ptr()))
             if not want_maps:
@@ -221,6 +288,9 @@ class DenseStereoReconstructor(ResidentViews):
             d, c = eng.fetch_sweep_maps(0, len(js))
             for n, j in enumerate(js):
                 dmaps[row[j]], cmaps[row[j]] = d[n], c[n]
+        if gfilter is not None:
+            dmaps, cmaps, _ = self._geometric_filter(eng, view_poses, min_conf, gfilter, depth=dmaps, conf=cmaps)
+            min_conf = self._map_threshold()
         counts, total = eng.stereo_backproject(cols, K_inv, view_poses, min_conf, depth=dmaps, conf=cmaps)
         return counts, total, dict(poses=view_poses, depth=dmaps, conf=cmaps) if want_maps else None
 

@@ -31,7 +31,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from .camera import Camera, CameraPose
-from .utils import rows_matmul
+from .utils import nearest_map_neighbours, rows_matmul
 from .view_cache import ResidentViews
 from .. import engine as _engine
 from .. import parallel as _parallel
@@ -111,26 +111,59 @@ class PatchMatchMVS(ResidentViews):
         self.exercise_exchange = False
         self._streams = None             # (device, sweep stream, exchange stream) of _exchange_streams
         self._cloud_resident = False
+        self._filter_threshold = None    # filter_min_views while the maps of the last call are the geometric filter's
+
+    def _threshold(self):
+        """What a pixel's confidence must reach to be used by the fusion, the TSDF and the normals: min_views, or -- when the
+        maps at hand are the (depth, count) of the geometric filter -- its filter_min_views."""
+        held = getattr(self, "_filter_threshold", None)
+        return self.min_views if held is None else held
 
     # ------------------------------------------------------------------ public ----
     def reconstruct(self, images: List[dict], poses: Dict[int, CameraPose],
                     sparse_points: np.ndarray = None, *, with_normals: bool = False, normal_radius: int = 2,
-                    normal_jump: float = 0.05, normal_depth_tolerance: float = 0.01) -> Tuple[np.ndarray, ...]:
+                    normal_jump: float = 0.05, normal_depth_tolerance: float = 0.01, geometric_filter: bool = False,
+                    filter_px: float = 1.0, filter_rel: float = 0.01, filter_min_views: int = 2, filter_refine: bool = True,
+                    filter_neighbours: Optional[int] = None) -> Tuple[np.ndarray, ...]:
         """(points, colors) as the reference returns them.  with_normals=True appends oriented unit normals (N,3) float32
         of the final cloud (csrc/amvs_cloud_normals.hip, include/amvs.h amvs_cloud_normals; no reference counterpart): per
         view a plane is fitted to the inverse depths in a window of normal_radius pixels around every pixel with
         confidence >= min_views, over the neighbours whose depth is within normal_jump of the centre's, and every point
         takes the cosine-weighted mean of the normals of the views that see it within normal_depth_tolerance (relative).
-        A point no view gives a normal keeps (0, 0, 0)."""
+        A point no view gives a normal keeps (0, 0, 0).
+
+        geometric_filter=True (off by default: the call is then exactly what it was) checks the depth maps against each
+        other between the sweep and the fusion (csrc/amvs_depth_filter.hip, include/amvs_depth.h amvs_depth_filter; no
+        reference counterpart): a pixel with confidence >= min_views keeps its depth only if at least filter_min_views other
+        maps agree with it after forward-backward reprojection -- the reprojected pixel within filter_px pixels, the
+        reprojected depth within filter_rel (relative) -- and with filter_refine it becomes the mean of its own and the
+        agreeing depths.  filter_neighbours: None compares every map with every other one, an int k with the k nearest
+        camera centres among the views that have a map (core.utils.nearest_map_neighbours).  The fusion and the normals then
+        read the filtered depths and the counts, with filter_min_views as their threshold in place of min_views.  In the
+        extended mode the filter runs after that mode's own consistency step, on its maps."""
         if with_normals:
             _, world = _parallel.rank_world(self.process_group)
             if world > 1:
                 raise NotImplementedError("with_normals runs on one process: normals with a process group of "
                                           f"{world} ranks are not implemented (call it without a process group)")
-        points, colors, maps = self._reconstruct_maps(images, poses, sparse_points)
+        gfilter = self._filter_arguments(geometric_filter, filter_px, filter_rel, filter_min_views, filter_refine, filter_neighbours)
+        points, colors, maps = self._reconstruct_maps(images, poses, sparse_points, gfilter)
         if not with_normals:
             return points, colors
         return points, colors, self._cloud_normals(points, colors, maps, poses, normal_radius, normal_jump, normal_depth_tolerance)
+
+    def _filter_arguments(self, geometric_filter, px, rel, min_views, refine, neighbours):
+        """None, or (filter_px, filter_rel, filter_min_views, filter_refine, filter_neighbours) of a call with
+        geometric_filter=True, which runs on one process."""
+        if not geometric_filter:
+            return None
+        _, world = _parallel.rank_world(self.process_group)
+        if world > 1:
+            raise NotImplementedError("geometric_filter runs on one process: filtering across a process group of "
+                                      f"{world} ranks is not implemented (call it without a process group)")
+        if isinstance(min_views, (bool, np.bool_)) or int(min_views) != min_views or min_views < 1:
+            raise ValueError("filter_min_views must be an integer of at least 1")
+        return float(px), float(rel), int(min_views), bool(refine), neighbours
 
     def _cloud_normals(self, points, colors, maps, poses, radius, jump, depth_tolerance):
         """Normals of the final cloud from the maps _reconstruct_maps returned.  The cloud is the engine's resident one
@@ -152,7 +185,7 @@ class PatchMatchMVS(ResidentViews):
         eng = self._engine
         if not self._cloud_resident:
             eng.cloud_set(points, colors)
-        _, n_points = eng.cloud_normals(self.K_scaled, [(poses[i].R, poses[i].t) for i in ids], self.min_views, radius, jump, 3,
+        _, n_points = eng.cloud_normals(self.K_scaled, [(poses[i].R, poses[i].t) for i in ids], self._threshold(), radius, jump, 3,
                                         depth_tolerance, 1, **where)
         normals, _ = eng.fetch_cloud_normals(len(points))
         print(f"  Normals: {n_points:,} of {len(points):,} points from {len(ids)} views ({time.time() - t0:.2f}s)")
@@ -168,7 +201,9 @@ class PatchMatchMVS(ResidentViews):
                          visibility_tolerance_voxels: float = 1.0, color_from_views: bool = False,
                          color_min_cos: float = 0.2, color_best_view: bool = False,
                          texture_texels: int = 0, fill_holes_voxels: int = 0,
-                         fill_min_neighbours: int = 1) -> Tuple[np.ndarray, ...]:
+                         fill_min_neighbours: int = 1, geometric_filter: bool = False, filter_px: float = 1.0,
+                         filter_rel: float = 0.01, filter_min_views: int = 2, filter_refine: bool = True,
+                         filter_neighbours: Optional[int] = None) -> Tuple[np.ndarray, ...]:
         """Surface mesh of the scene: reconstruct()'s preparation, sweep and fusion, then the per-view depth maps
         fused into a truncated signed distance volume and its zero level set extracted by marching tetrahedra on
         the GPU (csrc/amvs_mesh.hip; no reference counterpart).  Returns (vertices (V,3) float32, faces (F,3) int32,
@@ -217,7 +252,9 @@ class PatchMatchMVS(ResidentViews):
         the vertex colours where no view reaches it; uv (F,3,2) float32 and atlas (Ht,Wt,3) uint8 RGB are appended to the
         result, after the normals if those were asked for (core.utils.save_mesh_obj writes them);
         with_normals=True appends area-weighted vertex normals (V,3) float32 to the result, a 4-tuple then.  With the
-        defaults none of it runs.  The grid of the last call is kept in last_mesh_grid (origin, voxel, dims, trunc), the views
+        defaults none of it runs.  geometric_filter and the filter_* keywords are reconstruct()'s: the cloud that sizes the
+        volume and the maps the volume fuses are then the filtered ones, with filter_min_views as the TSDF's threshold.
+        The grid of the last call is kept in last_mesh_grid (origin, voxel, dims, trunc), the views
         it fused in last_mesh_views."""
         rank, world = _parallel.rank_world(self.process_group)
         if world > 1:
@@ -265,7 +302,8 @@ class PatchMatchMVS(ResidentViews):
             if not ok:
                 raise ValueError(f"{name} must be an integer in {lo} .. {hi}")
         fill = int(fill_holes_voxels)
-        points, _, maps = self._reconstruct_maps(images, poses, sparse_points)
+        gfilter = self._filter_arguments(geometric_filter, filter_px, filter_rel, filter_min_views, filter_refine, filter_neighbours)
+        points, _, maps = self._reconstruct_maps(images, poses, sparse_points, gfilter)
         do_filter = min_component_faces > 0 or keep_largest
         empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), np.zeros((0, 3), np.uint8))
         if with_normals:
@@ -284,11 +322,11 @@ class PatchMatchMVS(ResidentViews):
         fused = [(poses[i].R, poses[i].t) for i in ids]
         self.last_mesh_views = None
         if fill > 0:
-            self._engine.tsdf_integrate(self.K_scaled, fused, self.min_views, origin, voxel, dims, trunc, **src)
+            self._engine.tsdf_integrate(self.K_scaled, fused, self._threshold(), origin, voxel, dims, trunc, **src)
             n_filled = self._engine.tsdf_fill(fill, int(fill_min_neighbours))
             verts, faces, colors = self._engine.tsdf_extract()
         else:
-            verts, faces, colors = self._engine.tsdf_mesh(self.K_scaled, fused, self.min_views, origin, voxel, dims, trunc, **src)
+            verts, faces, colors = self._engine.tsdf_mesh(self.K_scaled, fused, self._threshold(), origin, voxel, dims, trunc, **src)
         self.last_mesh_views = list(ids)
         print(f"  Mesh: {len(verts):,} vertices, {len(faces):,} faces ({time.time() - t0:.2f}s)")
         decimate = decimate_voxels > 0
@@ -402,8 +440,10 @@ class PatchMatchMVS(ResidentViews):
         dims = tuple(max(2, int(np.ceil((hi[a] - lo[a]) / voxel - 1e-6)) + 1) for a in range(3))
         return lo, voxel, dims, tv * voxel
 
-    def _reconstruct_maps(self, images: List[dict], poses: Dict[int, CameraPose], sparse_points: np.ndarray = None):
-        """reconstruct(): preparation, sweep, fusion and its progress lines.  Returns (points, colors, maps) where maps
+    def _reconstruct_maps(self, images: List[dict], poses: Dict[int, CameraPose], sparse_points: np.ndarray = None,
+                          gfilter=None):
+        """reconstruct(): preparation, sweep, fusion and its progress lines; with gfilter (_filter_arguments) the geometric
+        filter between the sweep and the fusion, and its (depth, count) maps in place of the sweep's from there on.  Returns (points, colors, maps) where maps
         is None (fewer than 3 cameras, no views) or (kind, per-view maps, prepared images): kind "resident" with the
         device tensors of _sweep_resident / _sweep_extended, or "host" with the DepthNormalMap dict of _sweep."""
         print("\n" + "=" * 60)
@@ -443,14 +483,19 @@ class PatchMatchMVS(ResidentViews):
             torch = _parallel._torch_cuda() if self.device_fusion and jobs else None
             sweep = self._sweep_resident
         self._cloud_resident = False     # the engine holds the final cloud (what _cloud_normals works on)
+        self._filter_threshold = None
         if torch is not None:
             resident = sweep(torch, jobs, proc_images, poses, cam_indices)
+            if gfilter is not None:
+                resident = self._geometric_filter_resident(torch, resident, poses, gfilter)
             print("\nFusing depth maps...")
             points, colors, raw = self._fuse_filter_resident(resident, proc_images, poses)
             self._cloud_resident = len(resident.ref_ids) > 0
             maps = ("resident", resident, proc_images)
         else:
             depth_maps = self._sweep(jobs, proc_images, poses, cam_indices)
+            if gfilter is not None:
+                depth_maps = self._geometric_filter_host(depth_maps, poses, gfilter)
             print("\nFusing depth maps...")
             if self.device_fusion and self._engine is not None and depth_maps:
                 points, colors, raw = self._fuse_filter_device(depth_maps, proc_images, poses)
@@ -788,6 +833,43 @@ class PatchMatchMVS(ResidentViews):
         return _ResidentMaps(ref_ids=[jobs[j][0] for j in range(len(jobs))], depth=depth[slots_all].contiguous(),
                              normal=normal[slots_all].contiguous(), confidence=conf.contiguous(), shape=(H, W))
 
+    # ------------------------------------------------------------ geometric filter --
+    def _filter_rows(self, ids, poses, gfilter):
+        return nearest_map_neighbours([poses[i].center for i in ids], gfilter[4])
+
+    def _geometric_filter_resident(self, torch, maps: "_ResidentMaps", poses, gfilter) -> "_ResidentMaps":
+        """The maps of _sweep_resident / _sweep_extended through Engine.depth_filter, device to device: new tensors take
+        the filtered depths and the counts (the normal maps are the sweep's)."""
+        ids = list(maps.ref_ids)
+        if not ids:
+            return maps
+        t0 = time.time()
+        px, rel, min_views, refine, _ = gfilter
+        depth, count = torch.empty_like(maps.depth), torch.empty_like(maps.confidence)
+        torch.cuda.synchronize(maps.depth.device)
+        n_valid, n_kept = self._engine.depth_filter(self.K_scaled, [(poses[i].R, poses[i].t) for i in ids], self.min_views, px, rel,
+                                                    min_views, refine, neighbours=self._filter_rows(ids, poses, gfilter),
+                                                    device_ptrs=(maps.depth.data_ptr(), maps.confidence.data_ptr()),
+                                                    out_ptrs=(depth.data_ptr(), count.data_ptr()))
+        self._filter_threshold = min_views
+        print(f"\nGeometric filter: {n_kept:,} of {n_valid:,} valid pixels agree with {min_views} views or more ({time.time() - t0:.2f}s)")
+        return _ResidentMaps(ref_ids=ids, depth=depth, normal=maps.normal, confidence=count, shape=maps.shape)
+
+    def _geometric_filter_host(self, depth_maps: Dict[int, DepthNormalMap], poses, gfilter) -> Dict[int, DepthNormalMap]:
+        """The host maps of _sweep through Engine.depth_filter."""
+        ids = list(depth_maps)
+        if not ids:
+            return depth_maps
+        t0 = time.time()
+        px, rel, min_views, refine, _ = gfilter
+        depth, count, (n_valid, n_kept) = self._engine.depth_filter(
+            self.K_scaled, [(poses[i].R, poses[i].t) for i in ids], self.min_views, px, rel, min_views, refine,
+            neighbours=self._filter_rows(ids, poses, gfilter), depth=np.stack([depth_maps[i].depth for i in ids]),
+            conf=np.stack([depth_maps[i].confidence for i in ids]))
+        self._filter_threshold = min_views
+        print(f"\nGeometric filter: {n_kept:,} of {n_valid:,} valid pixels agree with {min_views} views or more ({time.time() - t0:.2f}s)")
+        return {i: DepthNormalMap(depth=depth[n], normal=depth_maps[i].normal, confidence=count[n]) for n, i in enumerate(ids)}
+
     # ------------------------------------------------------------ fusion / filter --
     def _fuse_filter_resident(self, maps: "_ResidentMaps", images: Dict, poses: Dict[int, CameraPose]):
         """Fusion + filter straight from the device tensors of _sweep_resident."""
@@ -800,18 +882,18 @@ class PatchMatchMVS(ResidentViews):
         if self._resident_colors and images is self._engine_images:
             return self._engine.fuse_filter_views([self._slot[i] for i in maps.ref_ids], maps.depth.data_ptr(),
                                                   maps.confidence.data_ptr(), K_inv,
-                                                  [(poses[i].R, poses[i].t) for i in maps.ref_ids], self.min_views,
+                                                  [(poses[i].R, poses[i].t) for i in maps.ref_ids], self._threshold(),
                                                   do_filter=True)
         cols = np.stack([images[i]["color"] for i in maps.ref_ids])
         return self._engine.fuse_filter(None, None, cols, K_inv, [(poses[i].R, poses[i].t) for i in maps.ref_ids],
-                                        self.min_views, do_filter=True,
+                                        self._threshold(), do_filter=True,
                                         device_ptrs=(maps.depth.data_ptr(), maps.confidence.data_ptr(), n))
 
     def _fuse_filter_device(self, depth_maps: Dict[int, "DepthNormalMap"], images: Dict,
                             poses: Dict[int, CameraPose]):
         """_fuse_depth_maps + _filter_points on the GPU (amvs_fuse_filter): float64, same order,
         bit-identical clouds; returns (points, colors, raw point count)."""
-        ids = [idx for idx, dm in depth_maps.items() if np.any(dm.confidence >= self.min_views)]
+        ids = [idx for idx, dm in depth_maps.items() if np.any(dm.confidence >= self._threshold())]
         if not ids:
             return np.array([]).reshape(0, 3), np.array([]).reshape(0, 3), 0
         depth = np.stack([depth_maps[i].depth for i in ids])
@@ -819,7 +901,7 @@ class PatchMatchMVS(ResidentViews):
         cols = np.stack([images[i]["color"] for i in ids])
         K_inv = np.linalg.inv(self.K_scaled)
         return self._engine.fuse_filter(depth, conf, cols, K_inv, [(poses[i].R, poses[i].t) for i in ids],
-                                        self.min_views, do_filter=True)
+                                        self._threshold(), do_filter=True)
 
 
     def _fuse_depth_maps(self, depth_maps: Dict[int, DepthNormalMap], images: Dict,
@@ -828,7 +910,7 @@ class PatchMatchMVS(ResidentViews):
         K_inv = np.linalg.inv(self.K_scaled)
         clouds, cloud_colors = [], []
         for idx, dm in depth_maps.items():
-            keep = dm.confidence >= self.min_views
+            keep = dm.confidence >= self._threshold()
             if not np.any(keep):
                 continue
             ys, xs = np.where(keep)

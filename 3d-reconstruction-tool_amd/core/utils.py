@@ -30,6 +30,25 @@ def rows_matmul(rows: np.ndarray, matrix: np.ndarray) -> np.ndarray:
     return rows @ matrix
 
 
+def nearest_map_neighbours(centers: np.ndarray, k) -> np.ndarray:
+    """Neighbour rows of the cross-view depth-map filter (Engine.depth_filter): for each of the n maps the k nearest camera
+    centres among the other maps -- the rule and the stable order of DenseStereoReconstructor._find_neighbors (distance
+    ascending, ties in map order).  k = None, or a single map: None (every other map in ascending index).  Otherwise
+    (n, min(k, n - 1)) int32."""
+    centers = np.asarray(centers, np.float64).reshape(-1, 3)
+    n = len(centers)
+    if k is None or n < 2:
+        return None
+    k = int(k)
+    if k < 1:
+        raise ValueError("filter_neighbours must be None or a positive integer")
+    rows = []
+    for j in range(n):
+        ranked = sorted(((i, np.linalg.norm(centers[i] - centers[j])) for i in range(n) if i != j), key=lambda item: item[1])
+        rows.append([i for i, _ in ranked[:k]])
+    return np.asarray(rows, np.int32)
+
+
 def save_ply(points: np.ndarray, colors: np.ndarray, output_path: str, normals: np.ndarray = None):
     """Save an (N,3) cloud with (N,3) RGB colours as ASCII PLY.  With normals (N,3) float32 every vertex is
     x y z nx ny nz red green blue (`amvs_write_ply_normals`; no reference counterpart); without, the file is the

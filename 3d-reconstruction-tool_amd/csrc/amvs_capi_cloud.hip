@@ -1,11 +1,15 @@
 // amvs_capi_cloud.hip -- the point-cloud entry points of the C ABI (include/amvs.h): back-projection, fusion, the
-// steps on the resident cloud, its normals from the depth maps, the neighbour statistic and the PLY writers.
+// steps on the resident cloud, its normals from the depth maps, the neighbour statistic and the PLY writers; and the
+// cross-view depth-map filter of include/amvs_depth.h, whose maps those steps consume.
 #include "amvs_ctx.h"
+#include "../../include/amvs_depth.h"
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <utility>
+#include <vector>
 
 using namespace amvs::host;
 
@@ -285,6 +289,94 @@ int amvs_cloud_set(amvs_ctx *c, const double *points, const uint8_t *colors_rgb,
         next.n = n;
     }
     c->cloud = std::move(next);
+    return checked(c, AMVS_OK);
+}
+
+// do the byte ranges [a, a + n) and [b, b + n) share a byte
+static bool ranges_overlap(const void *a, const void *b, size_t n)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + n && y < x + n;
+}
+
+int amvs_depth_filter(amvs_ctx *c, int n_maps, const void *depth, const void *conf, int maps_where, const double K[9],
+                      const double K_inv[9], const double *poses, const int32_t *neighbours, int n_nbr, float min_confidence,
+                      float max_px, float max_rel, int min_consistent, int refine, void *depth_out, void *count_out,
+                      int out_where, int64_t counts[2])
+{
+    if (!c) return AMVS_EINVAL;
+    if (!counts) return fail(c, AMVS_EINVAL, "NULL output");
+    if (n_maps < 1 || maps_where < 0 || maps_where > 2 || out_where < 0 || out_where > 2) return fail(c, AMVS_EINVAL, "bad argument");
+    if (!K || !K_inv || !poses) return fail(c, AMVS_EINVAL, "NULL K / K_inv / poses");
+    if (out_where == 2 && maps_where != 2) return fail(c, AMVS_EINVAL, "out_where 2 replaces the resident maps: it needs maps_where 2");
+    if (maps_where == 2 ? n_maps != c->n_sweep : (!depth || !conf))
+        return fail(c, AMVS_EINVAL, maps_where == 2 ? "n_maps differs from the resident plane-sweep batch" : "NULL maps");
+    if (out_where != 2 && (!depth_out || !count_out)) return fail(c, AMVS_EINVAL, "NULL output maps");
+    if (!(max_px > 0.0f && max_px <= FLT_MAX) || !(max_rel > 0.0f && max_rel <= FLT_MAX))
+        return fail(c, AMVS_EINVAL, "max_px and max_rel must be positive and finite");
+    if (min_consistent < 1) return fail(c, AMVS_EINVAL, "min_consistent below 1");
+    if ((long long)n_maps * c->H * c->W > 0x7FFFFFFFll) return fail(c, AMVS_EINVAL, "more than 2^31 - 1 pixels");
+    const size_t n = (size_t)c->H * c->W * (size_t)n_maps;
+    if (maps_where == 1 && out_where == 1) {
+        const void *in[2] = {depth, conf}, *out[2] = {depth_out, count_out};
+        for (int a = 0; a < 2; ++a)
+            for (int b = 0; b < 2; ++b)
+                if (ranges_overlap(in[a], out[b], sizeof(float) * n)) return fail(c, AMVS_EINVAL, "the outputs overlap the inputs");
+    }
+    if (out_where == 1 && ranges_overlap(depth_out, count_out, sizeof(float) * n)) return fail(c, AMVS_EINVAL, "the outputs overlap");
+    // the neighbour rows: the caller's, checked, or every other map in ascending index
+    std::vector<int> rows;
+    if (neighbours) {
+        if (n_nbr < 1) return fail(c, AMVS_EINVAL, "n_nbr below 1");
+        std::vector<char> seen((size_t)n_maps);
+        for (int j = 0; j < n_maps; ++j) {
+            std::fill(seen.begin(), seen.end(), 0);
+            for (int k = 0; k < n_nbr; ++k) {
+                const int i = neighbours[(size_t)j * n_nbr + k];
+                if (i == -1) continue;
+                if (i < 0 || i >= n_maps) return fail(c, AMVS_EINVAL, "a neighbour outside -1 .. n_maps - 1");
+                if (i == j) return fail(c, AMVS_EINVAL, "a map is its own neighbour");
+                if (seen[i]) return fail(c, AMVS_EINVAL, "a neighbour repeated within a row");
+                seen[i] = 1;
+            }
+        }
+        rows.assign(neighbours, neighbours + (size_t)n_maps * n_nbr);
+    } else {
+        n_nbr = n_maps - 1;
+        rows.reserve((size_t)n_maps * n_nbr);
+        for (int j = 0; j < n_maps; ++j)
+            for (int i = 0; i < n_maps; ++i)
+                if (i != j) rows.push_back(i);
+    }
+    int rc = bind_device(c);
+    if (rc) return rc;
+    amvs::DeviceBuffer<float> copy[2];
+    const float *dd = maps_where == 2 ? c->d_sweep_depth.get() : (const float *)depth;
+    const float *dc = maps_where == 2 ? c->d_sweep_conf.get() : (const float *)conf;
+    if (maps_where == 0 && (rc = stage_maps(c, n, dd, dc, copy))) return rc;
+    // device outputs are written where the caller wants them; host outputs and the resident maps get scratch first
+    amvs::ScratchCache::Lease scratch;
+    float *od = (float *)depth_out, *oc = (float *)count_out;
+    if (out_where != 1) {
+        HIPCHK(c, c->cache.lease(scratch, 2 * sizeof(float) * n));
+        od = scratch.get<float>();
+        oc = od + n;
+    }
+    long long cnt[2] = {0, 0};
+    const hipError_t e = amvs::depth_filter(dd, dc, n_maps, c->H, c->W, K, K_inv, poses, rows.data(), n_nbr, min_confidence, max_px,
+                                            max_rel, min_consistent, refine != 0, c->cache, od, oc, cnt, c->stream);
+    if (e != hipSuccess) return fail(c, AMVS_EHIP, std::string("depth_filter: ") + hipGetErrorString(e));
+    if (out_where != 1) {
+        void *to_d = out_where == 2 ? (void *)c->d_sweep_depth.get() : depth_out;
+        void *to_c = out_where == 2 ? (void *)c->d_sweep_conf.get() : count_out;
+        const hipMemcpyKind kind = out_where == 2 ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        hipError_t e2 = hipMemcpyAsync(to_d, od, sizeof(float) * n, kind, c->stream);
+        if (e2 == hipSuccess) e2 = hipMemcpyAsync(to_c, oc, sizeof(float) * n, kind, c->stream);
+        const hipError_t e3 = hipStreamSynchronize(c->stream);      // (also on failure: the lease goes back with nothing in flight)
+        if (e2 != hipSuccess || e3 != hipSuccess)
+            return fail(c, AMVS_EHIP, std::string("depth_filter copy: ") + hipGetErrorString(e2 != hipSuccess ? e2 : e3));
+    }
+    counts[0] = cnt[0]; counts[1] = cnt[1];
     return checked(c, AMVS_OK);
 }
 

@@ -257,6 +257,14 @@ hipError_t cloud_normals(const double *pts, long long n_pts, const float *depth,
                          const double *K_h, const double *poses_h, float min_confidence, int radius, float jump, int min_points,
                          float depth_tolerance, int min_views, ScratchCache &cache, DeviceBuffer<float> &map_normals,
                          DeviceBuffer<float> &nrm_out, DeviceBuffer<int> &seen_out, long long counts[2], hipStream_t st);
+// amvs_depth_filter.hip: the cross-view depth-map filter (include/amvs_depth.h amvs_depth_filter).  depth / conf and the
+// two outputs: [n_maps][H*W] float32 on the device, the outputs apart from the inputs; K_h, Ki_h: 9 doubles row-major,
+// poses_h: n_maps x 12 doubles, nbr_h: [n_maps][n_nbr] int32 map indices or -1 (host; n_nbr may be 0).  The caller has
+// validated the parameters.  counts[0] = valid input pixels, counts[1] = pixels kept.  Synchronises.
+hipError_t depth_filter(const float *depth, const float *conf, int n_maps, int H, int W, const double *K_h, const double *Ki_h,
+                        const double *poses_h, const int *nbr_h, int n_nbr, float min_confidence, float max_px, float max_rel,
+                        int min_consistent, bool refine, ScratchCache &cache, float *depth_out, float *count_out,
+                        long long counts[2], hipStream_t st);
 
 // amvs_mesh.hip: TSDF fusion of the per-view maps and marching-tetrahedra extraction (include/amvs.h
 // amvs_tsdf_*).  The state (volume, scans, mesh) is owned by a context and freed with it; its buffers are

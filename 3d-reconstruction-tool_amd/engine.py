@@ -473,6 +473,44 @@ class Engine:
         self._chk(self._lib.amvs_cloud_set(self._h, _f64(pts), _u8(rgb), m))
         return m
 
+    # -- cross-view depth-map filter (include/amvs_depth.h amvs_depth_filter) --
+    def depth_filter(self, K, poses, min_confidence, max_px=1.0, max_rel=0.01, min_consistent=2, refine=True, neighbours=None,
+                     depth=None, conf=None, device_ptrs=None, out_ptrs=None, in_place=False):
+        """Consistent-view counts and fused depths of n depth maps (include/amvs_depth.h amvs_depth_filter): K (3,3) float64
+        (K_inv is np.linalg.inv(K)), poses = list of (R, t) float64, maps as _normal_maps takes them.  neighbours: None --
+        every other map in ascending index -- or (n, n_nbr) int32 map indices, -1 for none.  Returns (depth (n,H,W) float32,
+        count (n,H,W) float32, (valid input pixels, pixels kept)); a pixel with fewer than min_consistent agreeing
+        neighbours has depth 0, a kept one its input depth or, with refine, the mean of its own and the agreeing depths.
+        With out_ptrs=(depth_ptr, count_ptr) -- device memory apart from the inputs -- or in_place=True -- the resident maps
+        of the last plane_sweep_batch are replaced by (depth, count) -- the maps stay on the device and the counts alone
+        are returned."""
+        n, dptr, cptr, where, pp, keep = self._normal_maps(poses, depth, conf, device_ptrs)
+        Kd = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        Ki = np.ascontiguousarray(np.linalg.inv(Kd)).reshape(9)
+        Kd = Kd.reshape(9)
+        nbr, nbrp, n_nbr = None, None, 0
+        if neighbours is not None:
+            nbr = np.ascontiguousarray(neighbours, dtype=np.int32)
+            if nbr.ndim != 2 or nbr.shape[0] != n:
+                raise ValueError(f"expected neighbours of shape ({n}, n_nbr), got {nbr.shape}")
+            nbrp, n_nbr = nbr.ctypes.data_as(i32p), nbr.shape[1]
+        if in_place and out_ptrs is not None:
+            raise ValueError("in_place and out_ptrs exclude each other")
+        counts = (C.c_int64 * 2)()
+        out = None
+        if in_place:
+            optr, kptr, out_where = C.c_void_p(0), C.c_void_p(0), 2
+        elif out_ptrs is not None:
+            optr, kptr, out_where = C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]), 1
+        else:
+            out = np.empty((2, n, self.H, self.W), np.float32)
+            optr, kptr, out_where = out[0].ctypes.data_as(C.c_void_p), out[1].ctypes.data_as(C.c_void_p), 0
+        self._chk(self._lib.amvs_depth_filter(self._h, n, dptr, cptr, where, _f64(Kd), _f64(Ki), _f64(pp), nbrp, n_nbr,
+                                              float(min_confidence), float(max_px), float(max_rel), int(min_consistent),
+                                              int(bool(refine)), optr, kptr, out_where, counts))
+        totals = (int(counts[0]), int(counts[1]))
+        return totals if out is None else (out[0], out[1], totals)
+
     # -- single steps (parity tests) ----------------------------------------
     def eval_cost(self, ref, src_ids, patch_size, depth):
         src, srcp = _ids(src_ids)
