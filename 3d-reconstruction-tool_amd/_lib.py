@@ -1,4 +1,4 @@
-"""ctypes binding of libamvs.so (the C ABI declared in include/amvs.h and include/amvs_depth.h).
+"""ctypes binding of libamvs.so (the C ABI declared in include/amvs.h, include/amvs_depth.h and include/amvs_lens.h).
 
 There is no CPU fallback: if the shared library is missing or no HIP device is
 present, loading / context creation raises.
@@ -178,6 +178,15 @@ DEPTH_SIGNATURES = {
                                     C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
 }
 
+# name -> (restype, argtypes); every symbol include/amvs_lens.h declares (a table of its own for the same reason)
+LENS_SIGNATURES = {
+    "amvs_undistort_bgr8": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int64)]),
+    "amvs_set_view_bgr8_undistorted": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_int,
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, f32p, f32p,
+                                                 C.POINTER(C.c_uint8)]),
+}
+
 _lib = None
 
 
@@ -213,7 +222,7 @@ def load():
                 "(or `make -C 3d-reconstruction-tool_amd/csrc`). There is no CPU fallback.")
         _share_torch_hip_runtime()
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(LENS_SIGNATURES.items()):
             fn = getattr(lib, name)      # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args

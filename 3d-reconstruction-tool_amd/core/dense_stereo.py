@@ -37,9 +37,11 @@ class DenseStereoReconstructor(ResidentViews):
     def __init__(self, camera: Camera, scale: float = 0.25, num_depths: int = 64,
                  patch_size: int = 5, min_views: int = 3, consistency_thresh: float = 0.8, *,
                  device: Optional[int] = None, device_filter: bool = True, mode: str = "exact",
-                 process_group=None, device_prep: Optional[bool] = None):
-        super().__init__(device_prep)            # the resident-view cache and the device_prep default
+                 process_group=None, device_prep: Optional[bool] = None, undistort: bool = False):
+        super().__init__(device_prep, undistort)     # the resident-view cache, the device_prep default, the lens switch
         self.camera = camera
+        if self.undistort:
+            self._lens()                         # (an unsupported distortion model is refused here, not at the first call)
         self.scale = scale
         self.num_depths = num_depths
         self.patch_size = patch_size

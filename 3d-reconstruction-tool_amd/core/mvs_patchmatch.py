@@ -73,9 +73,12 @@ class PatchMatchMVS(ResidentViews):
                  depth_min: float = 0.1, depth_max: float = 100.0, *,
                  seed: int = 0, device: Optional[int] = None, views_per_batch: int = 16,
                  process_group=None, device_fusion: bool = True, mode: str = "exact",
-                 device_prep: Optional[bool] = None, extended: bool = False, gather_normals: bool = True):
-        super().__init__(device_prep)            # the resident-view cache and the device_prep default
+                 device_prep: Optional[bool] = None, extended: bool = False, gather_normals: bool = True,
+                 undistort: bool = False):
+        super().__init__(device_prep, undistort)     # the resident-view cache, the device_prep default, the lens switch
         self.camera = camera
+        if self.undistort:
+            self._lens()                         # (an unsupported distortion model is refused here, not at the first call)
         self.scale = scale
         self.patch_size = patch_size
         self.num_iterations = num_iterations

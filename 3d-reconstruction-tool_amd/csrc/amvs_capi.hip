@@ -6,6 +6,7 @@
 // a scene are uploaded once and stay resident; a batch of reference views is swept
 // together, one kernel launch per cost-evaluation step over the whole batch.
 #include "amvs_ctx.h"
+#include "../../include/amvs_lens.h"
 
 #include <cmath>
 #include <cstring>
@@ -538,13 +539,31 @@ static void resize_axis_tables(int n_dst, int n_src, std::vector<int> &ofs, std:
     }
 }
 
-int amvs_set_view_bgr8(amvs_ctx *c, int view, const uint8_t *bgr_host, int src_h, int src_w, const float R[9],
-                       const float t[3], uint8_t *scaled_bgr_out)
+// The lens of include/amvs_lens.h as the kernel takes it: K and k1, k2, p1, p2, k3, k4, k5, k6 (absent ones 0).
+struct Lens {
+    double K[9], dist8[8];
+};
+
+// the header's "Errors": NULL = fine (lens filled), else what is wrong
+static const char *lens_arguments(int h, int w, const double *K, const double *dist, int n_dist, Lens &lens)
 {
-    if (c) c->pm_resumable = false;
-    if (!c) return AMVS_EINVAL;
-    if (view < 0 || view >= c->n_views || !bgr_host || !R || !t || src_h < 1 || src_w < 1)
-        return fail(c, AMVS_EINVAL, "bad view argument");
+    if (!K || !dist) return "NULL K / dist";
+    if (h < 1 || w < 1 || h > (1 << 24) || w > (1 << 24)) return "image side outside 1 .. 2^24";
+    if (n_dist != 4 && n_dist != 5 && n_dist != 8) return "n_dist must be 4, 5 or 8";
+    for (int k = 0; k < 9; ++k) if (!std::isfinite(K[k])) return "K is not finite";
+    for (int k = 0; k < n_dist; ++k) if (!std::isfinite(dist[k])) return "a distortion coefficient is not finite";
+    if (!(K[0] > 0.0) || !(K[4] > 0.0)) return "fx and fy must be positive";
+    if (K[1] != 0.0 || K[3] != 0.0 || K[6] != 0.0 || K[7] != 0.0 || K[8] != 1.0) return "K must be [fx 0 cx; 0 fy cy; 0 0 1]";
+    std::memcpy(lens.K, K, sizeof(lens.K));
+    for (int k = 0; k < 8; ++k) lens.dist8[k] = k < n_dist ? dist[k] : 0.0;
+    return nullptr;
+}
+
+// amvs_set_view_bgr8, and with `lens` amvs_set_view_bgr8_undistorted: the same copies and launches in the same order, with
+// the undistortion of the staged source (into d_prep_undist, which the resize then reads) behind its upload.
+static int set_view_bgr8(amvs_ctx *c, int view, const uint8_t *bgr_host, int src_h, int src_w, const Lens *lens, const float R[9],
+                         const float t[3], uint8_t *scaled_bgr_out)
+{
     int rc = bind_device(c);
     if (rc) return rc;
     const size_t n_src = (size_t)src_h * src_w, n_dst = (size_t)c->H * c->W;
@@ -563,6 +582,11 @@ int amvs_set_view_bgr8(amvs_ctx *c, int view, const uint8_t *bgr_host, int src_h
     int *d_xofs = c->d_prep_tab.get(), *d_yofs = d_xofs + c->W;
     short *d_ialpha = (short *)(d_xofs + tab_ints), *d_ibeta = d_ialpha + 2 * c->W;
     HIPCHK(c, hipMemcpyAsync(d_src, bgr_host, 3 * n_src, hipMemcpyHostToDevice, c->stream));
+    if (lens) {
+        HIPCHK(c, c->d_prep_undist.reserve(3 * n_src, c->cache));
+        HIPCHK(c, amvs::launch_undistort_bgr8(d_src, src_h, src_w, lens->K, lens->dist8, c->d_prep_undist.get(), nullptr, c->stream));
+        d_src = c->d_prep_undist.get();
+    }
     HIPCHK(c, hipMemcpyAsync(d_xofs, xofs.data(), 4 * (size_t)c->W, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_yofs, yofs.data(), 4 * (size_t)c->H, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_ialpha, ialpha.data(), 4 * (size_t)c->W, hipMemcpyHostToDevice, c->stream));
@@ -572,6 +596,66 @@ int amvs_set_view_bgr8(amvs_ctx *c, int view, const uint8_t *bgr_host, int src_h
     if (scaled_bgr_out) HIPCHK(c, hipMemcpyAsync(scaled_bgr_out, d_scaled, 3 * n_dst, hipMemcpyDeviceToHost, c->stream));
     if ((rc = view_uploaded(c, view, R, t, true))) return rc;
     c->have_bgr[view] = 1;
+    return checked(c, AMVS_OK);
+}
+
+int amvs_set_view_bgr8(amvs_ctx *c, int view, const uint8_t *bgr_host, int src_h, int src_w, const float R[9],
+                       const float t[3], uint8_t *scaled_bgr_out)
+{
+    if (c) c->pm_resumable = false;
+    if (!c) return AMVS_EINVAL;
+    if (view < 0 || view >= c->n_views || !bgr_host || !R || !t || src_h < 1 || src_w < 1)
+        return fail(c, AMVS_EINVAL, "bad view argument");
+    return set_view_bgr8(c, view, bgr_host, src_h, src_w, nullptr, R, t, scaled_bgr_out);
+}
+
+int amvs_set_view_bgr8_undistorted(amvs_ctx *c, int view, const uint8_t *bgr_host, int src_h, int src_w, const double K_src[9],
+                                   const double *dist, int n_dist, const float R[9], const float t[3], uint8_t *scaled_bgr_out)
+{
+    if (c) c->pm_resumable = false;
+    if (!c) return AMVS_EINVAL;
+    if (view < 0 || view >= c->n_views || !bgr_host || !R || !t) return fail(c, AMVS_EINVAL, "bad view argument");
+    Lens lens;
+    if (const char *bad = lens_arguments(src_h, src_w, K_src, dist, n_dist, lens)) return fail(c, AMVS_EINVAL, bad);
+    return set_view_bgr8(c, view, bgr_host, src_h, src_w, &lens, R, t, scaled_bgr_out);
+}
+
+int amvs_undistort_bgr8(amvs_ctx *c, const uint8_t *bgr_host, int h, int w, const double K[9], const double *dist, int n_dist,
+                        uint8_t *out_host, int64_t *n_outside)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!bgr_host || !out_host) return fail(c, AMVS_EINVAL, "NULL image");
+    Lens lens;
+    if (const char *bad = lens_arguments(h, w, K, dist, n_dist, lens)) return fail(c, AMVS_EINVAL, bad);
+    int rc = bind_device(c);
+    if (rc) return rc;
+    const size_t bytes = 3 * (size_t)h * (size_t)w;
+    HIPCHK(c, c->d_prep_src.reserve(bytes, c->cache));
+    HIPCHK(c, c->d_prep_undist.reserve(bytes, c->cache));
+    amvs::ScratchCache::Lease counter;
+    if (n_outside) HIPCHK(c, c->cache.lease(counter, sizeof(unsigned long long)));
+    // amvs_get_timing after this call: init_ms = the upload (and the counter's reset), sweep_ms = the kernel,
+    // confidence_ms = the download (as amvs_plane_sweep_device fills the same three)
+    resolve_timing(c);
+    c->timing = amvs_timing{};
+    c->timing_groups = 0;
+    c->n_step_events = 0;
+    HIPCHK(c, hipEventRecord(c->ev[0].get(), c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_prep_src.get(), bgr_host, bytes, hipMemcpyHostToDevice, c->stream));
+    if (n_outside) HIPCHK(c, hipMemsetAsync(counter.get(), 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipEventRecord(c->ev[1].get(), c->stream));
+    HIPCHK(c, amvs::launch_undistort_bgr8(c->d_prep_src.get(), h, w, lens.K, lens.dist8, c->d_prep_undist.get(),
+                                          counter.get<unsigned long long>(), c->stream));
+    HIPCHK(c, hipEventRecord(c->ev[2].get(), c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_host, c->d_prep_undist.get(), bytes, hipMemcpyDeviceToHost, c->stream));
+    unsigned long long outside = 0;
+    if (n_outside) HIPCHK(c, hipMemcpyAsync(&outside, counter.get(), sizeof(outside), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev[3].get(), c->stream));
+    c->timing.sweep_launches = 1;
+    c->timing_pending = true;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    resolve_timing(c);
+    if (n_outside) *n_outside = (int64_t)outside;
     return checked(c, AMVS_OK);
 }
 

@@ -28,6 +28,7 @@ void check_fetch_mesh_texture(unsigned long long out[4], bool reset);
 void check_fetch_mesh_fill(unsigned long long out[4], bool reset);
 void check_fetch_cloud_normals(unsigned long long out[4], bool reset);
 void check_fetch_depth_filter(unsigned long long out[4], bool reset);
+void check_fetch_undistort(unsigned long long out[4], bool reset);
 }  // namespace amvs
 #endif
 
@@ -42,7 +43,7 @@ std::string g_create_error;
 // (out[1] = translation unit << 32 | source line: 1 amvs_kernels, 2 amvs_kernels_fast, 3 amvs_sweep_fast,
 // 4 amvs_sweep_exact, 5 amvs_generic, 6 amvs_extended, 7 amvs_fusion, 8 amvs_knn, 9 amvs_mesh, 10 amvs_mesh_clean,
 // 11 amvs_mesh_decimate, 12 amvs_mesh_render, 13 amvs_mesh_color, 14 amvs_mesh_texture, 15 amvs_mesh_fill,
-// 16 amvs_cloud_normals, 17 amvs_depth_filter;
+// 16 amvs_cloud_normals, 17 amvs_depth_filter, 18 amvs_undistort;
 // out[2] = the index, out[3] = the extent it was compared with).  Zeros in the shipped build.
 void index_report(uint64_t out[4], bool reset)
 {
@@ -54,7 +55,8 @@ void index_report(uint64_t out[4], bool reset)
         amvs::check_fetch_generic, amvs::check_fetch_extended, amvs::check_fetch_fusion, amvs::check_fetch_knn,
         amvs::check_fetch_mesh, amvs::check_fetch_mesh_clean, amvs::check_fetch_mesh_decimate,
         amvs::check_fetch_mesh_render, amvs::check_fetch_mesh_color, amvs::check_fetch_mesh_texture,
-        amvs::check_fetch_mesh_fill, amvs::check_fetch_cloud_normals, amvs::check_fetch_depth_filter};
+        amvs::check_fetch_mesh_fill, amvs::check_fetch_cloud_normals, amvs::check_fetch_depth_filter,
+        amvs::check_fetch_undistort};
     for (auto f : fetch) {
         unsigned long long r[4] = {0, 0, 0, 0};
         f(r, reset);

@@ -73,6 +73,7 @@ struct amvs_ctx {
     amvs::DeviceBuffer<unsigned char> d_bgr;      // [n_views][H*W*3] prepared colour images (amvs_set_view_bgr8), lazily allocated
     amvs::DeviceBuffer<unsigned char> d_prep_src; // staging of one uploaded source image + the resize tables (amvs_set_view_bgr8):
     amvs::DeviceBuffer<int> d_prep_tab;           // kept across calls -- an allocation per view cost more than the copy
+    amvs::DeviceBuffer<unsigned char> d_prep_undist;   // the staged image undistorted at its own size (include/amvs_lens.h), grown only
     std::vector<char> have_bgr;
     amvs::DeviceBuffer<int> d_flag;     // [n_views] 1 = the view did not quantise to 8 bits losslessly
     mutable std::vector<char> exact8;    // host copy of !d_flag, refreshed lazily (flags_dirty)

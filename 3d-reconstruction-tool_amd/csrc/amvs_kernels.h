@@ -234,6 +234,12 @@ hipError_t launch_prep_bgr8(const unsigned char *src, int sh, int sw, int dh, in
                             const short *ialpha, const int *yofs, const short *ibeta, unsigned char *scaled,
                             float *gray, hipStream_t st);
 
+// amvs_undistort.hip: lens undistortion of one [h][w][3] image at its own resolution (include/amvs_lens.h): K, 9 doubles
+// row-major, and dist8 = k1, k2, p1, p2, k3, k4, k5, k6 on the host, validated by the caller; src and dst on the device,
+// apart; n_outside NULL or a device counter the OUTSIDE pixels are added to.  Does not synchronise.
+hipError_t launch_undistort_bgr8(const unsigned char *src, int h, int w, const double K[9], const double dist8[8],
+                                 unsigned char *dst, unsigned long long *n_outside, hipStream_t st);
+
 // amvs_fusion.hip: the stereo path's post-steps (dense_stereo.py:407-437, 475-492)
 hipError_t stereo_backproject(const float *depth, const float *conf, const unsigned char *bgr, int n_maps, int H, int W,
                               const double *Kinv_h, const double *poses_h, float min_confidence, ScratchCache &cache,

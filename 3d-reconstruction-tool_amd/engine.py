@@ -52,6 +52,30 @@ def _kinv64(K_inv64):
     return np.ascontiguousarray(K_inv64, dtype=np.float64).reshape(9)
 
 
+def lens_coefficients(dist):
+    """The distortion coefficients as include/amvs_lens.h takes them: float64 k1, k2, p1, p2, k3, k4, k5, k6 with the
+    trailing zeros trimmed to 8, 5 or 4 entries.  The model ends at the rational one: a non-zero coefficient beyond the
+    eighth (thin prism s1 .. s4, tilt tau_x, tau_y) is refused, not ignored."""
+    d = np.asarray(dist, np.float64).reshape(-1)
+    if np.any(d[8:] != 0.0):
+        raise ValueError("unsupported distortion model: thin-prism / tilt coefficients (beyond k6, the eighth) are "
+                         "non-zero; the undistortion knows k1, k2, p1, p2, k3, k4, k5, k6")
+    d = np.concatenate([d[:8], np.zeros(max(0, 8 - d.size))])
+    n = 8 if np.any(d[5:] != 0.0) else (5 if d[4] != 0.0 else 4)
+    return np.ascontiguousarray(d[:n])
+
+
+def _lens(K, dist):
+    return np.ascontiguousarray(K, dtype=np.float64).reshape(9), lens_coefficients(dist)
+
+
+def _bgr8(image):
+    img = np.ascontiguousarray(image, dtype=np.uint8)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("expected an (h, w, 3) uint8 BGR image")
+    return img
+
+
 def _job_ids(ref_ids, src_ids):
     """(n jobs, reference id pointer, source id pointer, sources per job, keep) of n reference views and their
     (n, S) source views; keep holds the two int32 arrays the pointers point into."""
@@ -243,6 +267,32 @@ class Engine:
         out = np.empty((self.H, self.W, 3), np.uint8) if want_color else None
         self._chk(self._lib.amvs_set_view_bgr8(
             self._h, int(view), _u8(img), img.shape[0], img.shape[1], _p(R), _p(t), _u8(out) if want_color else None))
+        return out
+
+    # -- lens undistortion (include/amvs_lens.h) --
+    def undistort_bgr8(self, image, K, dist):
+        """(image undistorted at its own size (h, w, 3) uint8, number of pixels whose source lies outside the image and
+        which are zero) of an 8-bit BGR image (include/amvs_lens.h amvs_undistort_bgr8): K (3,3) float64 of that image,
+        dist as lens_coefficients takes it.  Touches no view."""
+        img = _bgr8(image)
+        K9, d = _lens(K, dist)
+        out = np.empty_like(img)
+        n_outside = C.c_int64(0)
+        self._chk(self._lib.amvs_undistort_bgr8(self._h, _u8(img), img.shape[0], img.shape[1], _f64(K9), _f64(d), d.size,
+                                                _u8(out), C.byref(n_outside)))
+        return out, int(n_outside.value)
+
+    def set_view_bgr8_undistorted(self, view, image, K_src, dist, R, t, want_color=True):
+        """set_view_bgr8 with the lens undistortion on the device between the upload and the resize (include/amvs_lens.h
+        amvs_set_view_bgr8_undistorted): K_src (3,3) float64 is the calibration's matrix at the image's own resolution,
+        not the engine's scaled K."""
+        img = _bgr8(image)
+        K9, d = _lens(K_src, dist)
+        R, t = _pose32(R, t)
+        out = np.empty((self.H, self.W, 3), np.uint8) if want_color else None
+        self._chk(self._lib.amvs_set_view_bgr8_undistorted(
+            self._h, int(view), _u8(img), img.shape[0], img.shape[1], _f64(K9), _f64(d), d.size, _p(R), _p(t),
+            _u8(out) if want_color else None))
         return out
 
     def set_view_colors(self, view, image_bgr_u8):
