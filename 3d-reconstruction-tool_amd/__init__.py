@@ -10,7 +10,7 @@ repository root.
 from .core.camera import Camera, CameraPose, load_calibration  # noqa: F401
 
 __all__ = ["Camera", "CameraPose", "load_calibration", "PatchMatchMVS", "DepthNormalMap",
-           "DenseStereoReconstructor", "Engine", "AmvsError", "save_ply", "save_mesh_ply"]
+           "DenseStereoReconstructor", "DenseReconstructor", "Engine", "AmvsError", "save_ply", "save_mesh_ply"]
 
 
 def __getattr__(name):
@@ -22,6 +22,9 @@ def __getattr__(name):
     if name == "DenseStereoReconstructor":
         from .core import dense_stereo
         return dense_stereo.DenseStereoReconstructor
+    if name == "DenseReconstructor":
+        from .core import dense
+        return dense.DenseReconstructor
     if name == "Engine":
         from .engine import Engine
         return Engine

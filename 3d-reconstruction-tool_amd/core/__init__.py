@@ -1,0 +1,13 @@
+"""The reconstruction classes.  DenseReconstructor and the method it is built on are resolved lazily, so importing
+the package for the camera types does not import the engine."""
+__all__ = ["DenseReconstructor", "reconstruct_from_features"]
+
+
+def __getattr__(name):
+    if name == "DenseReconstructor":
+        from .dense import DenseReconstructor
+        return DenseReconstructor
+    if name == "reconstruct_from_features":
+        from .dense import DenseReconstructor
+        return DenseReconstructor.reconstruct_from_features
+    raise AttributeError(name)

@@ -131,6 +131,24 @@ __global__ __launch_bounds__(256) void voxel_key_kernel(const double *__restrict
     }
 }
 
+// voxel key of the grid anchored at `origin` (include/amvs_match.h amvs_cloud_voxel_downsample_grid): the indices
+// floor((p - origin) / voxel) per axis, folded in lexicographic order over the index box [lo, lo + ext) of the kept points
+struct GridKey { double origin[3]; long long lo[3], ext[3]; };
+
+__global__ __launch_bounds__(256) void grid_key_kernel(const double *__restrict__ pts, const long long *__restrict__ sel,
+                                                       long long m, long long m_src, double voxel, const GridKey g,
+                                                       long long *__restrict__ keys)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < m;
+         i += (long long)gridDim.x * blockDim.x) {
+        const long long s = AMVS_IDX(sel[i], m_src);
+        const long long ix = (long long)floor((pts[3 * s] - g.origin[0]) / voxel) - g.lo[0];
+        const long long iy = (long long)floor((pts[3 * s + 1] - g.origin[1]) / voxel) - g.lo[1];
+        const long long iz = (long long)floor((pts[3 * s + 2] - g.origin[2]) / voxel) - g.lo[2];
+        keys[i] = (ix * g.ext[1] + iy) * g.ext[2] + iz;
+    }
+}
+
 __global__ __launch_bounds__(256) void run_head_kernel(const long long *__restrict__ keys, long long m,
                                                        unsigned char *__restrict__ flag)
 {
@@ -203,14 +221,17 @@ hipError_t sort_keys(double *in, double *out, long long n, ScratchCache &cache, 
 hipError_t voxel_first_of_key(const double *pts, const unsigned char *rgb, long long m_src, const long long *sel, long long m2,
                               double voxel, ScratchCache &cache, Lease &tmp, Lease &flag, Lease &cnt,
                               DeviceBuffer<double> &pts_out, DeviceBuffer<unsigned char> &rgb_out, long long *m3_out,
-                              hipStream_t st)
+                              hipStream_t st, const GridKey *grid = nullptr)
 {
     *m3_out = 0;
     Lease keysA, keysB, idxA, idxB, pick;
     FCHK(cache.lease(keysA, 8 * m2)); FCHK(cache.lease(keysB, 8 * m2)); FCHK(cache.lease(idxA, 8 * m2));
     FCHK(cache.lease(idxB, 8 * m2)); FCHK(cache.lease(pick, 8 * m2));
     FCHK(cache.lease(flag, m2));
-    hipLaunchKernelGGL(voxel_key_kernel, grid_for(m2), dim3(256), 0, st, pts, sel, m2, m_src, voxel, keysA.get<long long>());
+    if (grid)
+        hipLaunchKernelGGL(grid_key_kernel, grid_for(m2), dim3(256), 0, st, pts, sel, m2, m_src, voxel, *grid, keysA.get<long long>());
+    else
+        hipLaunchKernelGGL(voxel_key_kernel, grid_for(m2), dim3(256), 0, st, pts, sel, m2, m_src, voxel, keysA.get<long long>());
     hipLaunchKernelGGL(iota_kernel, grid_for(m2), dim3(256), 0, st, idxA.get<long long>(), m2);
     {
         size_t bytes = 0;
@@ -413,6 +434,36 @@ hipError_t voxel_downsample(const double *pts, const unsigned char *rgb, long lo
     if (m2 == 0) return hipSuccess;
     return voxel_first_of_key(pts, rgb, m, (const long long *)sel.get(), m2, voxel, cache, tmp, flag, cnt, pts_out, rgb_out,
                               m_out, st);
+}
+
+// The voxel grid of include/amvs_match.h (the reference's dense mode: voxels anchored at `origin`, survivors in
+// lexicographic voxel order): voxel_downsample with another key.  lo / ext: the index box of the kept points per axis,
+// which the caller derived from their bounds (floor((x - origin) / voxel) is monotone in x) and checked to hold fewer
+// than 2^62 voxels.
+hipError_t voxel_downsample_grid(const double *pts, const unsigned char *rgb, long long m, const unsigned char *keep_h,
+                                 const double origin[3], double voxel, const long long lo[3], const long long ext[3],
+                                 ScratchCache &cache, DeviceBuffer<double> &pts_out, DeviceBuffer<unsigned char> &rgb_out,
+                                 long long *m_out, hipStream_t st)
+{
+    *m_out = 0;
+    if (m <= 0) return hipSuccess;
+    if (m > 0x7FFFFFFFll) return hipErrorInvalidValue;
+    GridKey g;
+    for (int a = 0; a < 3; ++a) { g.origin[a] = origin[a]; g.lo[a] = lo[a]; g.ext[a] = ext[a]; }
+    Lease tmp, flag, sel, cnt;
+    FCHK(cache.lease(flag, m));
+    FCHK(cache.lease(sel, sizeof(long long) * m));
+    FCHK(cache.lease(cnt, sizeof(long long)));
+    long long m2 = m;
+    if (keep_h) {
+        FCHK(hipMemcpyAsync(flag.get(), keep_h, m, hipMemcpyHostToDevice, st));
+        FCHK(select_indices(flag.get<unsigned char>(), m, sel.get<long long>(), cnt.get<long long>(), &m2, cache, tmp, st));
+    } else {
+        hipLaunchKernelGGL(iota_kernel, grid_for(m), dim3(256), 0, st, sel.get<long long>(), m);
+    }
+    if (m2 == 0) return hipSuccess;
+    return voxel_first_of_key(pts, rgb, m, (const long long *)sel.get(), m2, voxel, cache, tmp, flag, cnt, pts_out, rgb_out,
+                              m_out, st, &g);
 }
 
 }  // namespace amvs

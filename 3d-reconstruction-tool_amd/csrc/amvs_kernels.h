@@ -250,6 +250,11 @@ hipError_t cloud_take(const double *pts, const unsigned char *rgb, long long n, 
 hipError_t voxel_downsample(const double *pts, const unsigned char *rgb, long long m, const unsigned char *keep_h,
                             double voxel, ScratchCache &cache, DeviceBuffer<double> &pts_out,
                             DeviceBuffer<unsigned char> &rgb_out, long long *m_out, hipStream_t st);
+// the grid anchored at `origin` of include/amvs_match.h; lo / ext: the voxel-index box of the kept points
+hipError_t voxel_downsample_grid(const double *pts, const unsigned char *rgb, long long m, const unsigned char *keep_h,
+                                 const double origin[3], double voxel, const long long lo[3], const long long ext[3],
+                                 ScratchCache &cache, DeviceBuffer<double> &pts_out, DeviceBuffer<unsigned char> &rgb_out,
+                                 long long *m_out, hipStream_t st);
 
 // amvs_cloud_normals.hip: per-view normal maps fitted to the inverse depths, and the normals of a cloud from them
 // (include/amvs.h amvs_depth_normals, amvs_cloud_normals).  depth / conf: [n_maps][H*W] float32 on the device; K_h: 9

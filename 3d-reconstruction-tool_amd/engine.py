@@ -125,6 +125,7 @@ class Engine:
             raise AmvsError(f"amvs_create failed ({rc}): {self._lib.amvs_last_error(None).decode()}")
         self._h = h
         self._render_views = 0           # views of the last mesh_render: the image count mesh_color_views expects
+        self._desc_rows = {}             # rows of every descriptor slot that was set: the sizes of knn2's outputs
         if mode != "exact":
             self.set_mode(mode)
 
@@ -522,6 +523,96 @@ class Engine:
         rgb = np.zeros((m, 3), np.uint8) if colors is None else np.ascontiguousarray(colors, dtype=np.uint8).reshape(m, 3)
         self._chk(self._lib.amvs_cloud_set(self._h, _f64(pts), _u8(rgb), m))
         return m
+
+    # -- dense-SIFT mode (include/amvs_match.h): exact descriptor matching, pair triangulation, grid voxels --
+    def set_descriptors(self, slot, descriptors):
+        """One image's descriptors, (n, 128) uint8, into the resident slot `slot` (amvs_desc_set).  Returns n."""
+        d = np.ascontiguousarray(descriptors)
+        if d.dtype != np.uint8 or d.ndim != 2:
+            raise ValueError("descriptors must be a 2-D uint8 array")
+        self._chk(self._lib.amvs_desc_set(self._h, int(slot), _u8(d) if d.size else None, d.shape[0], d.shape[1]))
+        self._desc_rows[int(slot)] = d.shape[0]
+        return d.shape[0]
+
+    def _slot_rows(self, slot):
+        if int(slot) not in self._desc_rows:
+            raise AmvsError(f"descriptor slot {slot} was never set")
+        return self._desc_rows[int(slot)]
+
+    def knn2(self, slot_q, slot_t):
+        """(idx (n_q, 2) int32, dist2 (n_q, 2) int32): for every query row the two train rows smallest under (s, j), s the
+        exact squared distance, j the train index (amvs_desc_knn2)."""
+        n_q = self._slot_rows(slot_q)
+        idx = np.empty((n_q, 2), np.int32)
+        d2 = np.empty((n_q, 2), np.int32)
+        self._chk(self._lib.amvs_desc_knn2(self._h, int(slot_q), int(slot_t), idx.ctypes.data_as(i32p), d2.ctypes.data_as(i32p)))
+        return idx, d2
+
+    def match_descriptors(self, slot_q, slot_t, ratio=0.85, cross_check=False):
+        """(q_idx, t_idx, dist2), int32 each, in query order: the matches that pass Lowe's ratio test on the exact
+        squared distances and, with cross_check, the symmetric filter (amvs_desc_match)."""
+        n_q = self._slot_rows(slot_q)
+        out = np.empty((3, max(n_q, 1)), np.int32)
+        m = C.c_int64(0)
+        self._chk(self._lib.amvs_desc_match(self._h, int(slot_q), int(slot_t), float(np.float32(ratio)), int(bool(cross_check)),
+                                            out[0].ctypes.data_as(i32p), out[1].ctypes.data_as(i32p),
+                                            out[2].ctypes.data_as(i32p), C.byref(m)))
+        k = int(m.value)
+        return out[0, :k].copy(), out[1, :k].copy(), out[2, :k].copy()
+
+    def pair_cloud_begin(self):
+        self._chk(self._lib.amvs_pair_cloud_begin(self._h))
+
+    def pair_triangulate(self, K, R1, t1, R2, t2, pts1, pts2, rgb, depth_min=0.1, depth_max=50.0, cos_min_parallax=None,
+                         max_reproj=6.0):
+        """Triangulates the candidates (pts1, pts2: (m, 2) float32; rgb: (m, 3) uint8, the colour of every candidate) of
+        one pair, appends the accepted ones to the accumulating cloud and returns their number (amvs_pair_triangulate).
+        cos_min_parallax defaults to cos(0.3 degrees), the reference's floor."""
+        if cos_min_parallax is None:
+            cos_min_parallax = float(np.cos(np.deg2rad(0.3)))
+        a = [np.ascontiguousarray(x, dtype=np.float64).reshape(n) for x, n in ((K, 9), (R1, 9), (t1, 3), (R2, 9), (t2, 3))]
+        p1 = np.ascontiguousarray(pts1, dtype=np.float32).reshape(-1, 2)
+        p2 = np.ascontiguousarray(pts2, dtype=np.float32).reshape(-1, 2)
+        m = len(p1)
+        col = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1, 3)
+        if len(p2) != m or len(col) != m:
+            raise ValueError("pts1, pts2 and rgb must have one row per candidate")
+        k = C.c_int64(0)
+        self._chk(self._lib.amvs_pair_triangulate(self._h, *[_f64(x) for x in a], _p(p1) if m else None, _p(p2) if m else None,
+                                                  _u8(col) if m else None, m, float(depth_min), float(depth_max),
+                                                  float(cos_min_parallax), float(max_reproj), C.byref(k)))
+        return int(k.value)
+
+    def pair_cloud_finish(self):
+        """The accumulated cloud becomes the resident cloud; returns its point count."""
+        total = C.c_int64(0)
+        self._chk(self._lib.amvs_pair_cloud_finish(self._h, C.byref(total)))
+        return int(total.value)
+
+    def cloud_bounds(self, keep_mask=None):
+        """(min (3,), max (3,)) float64 of the resident cloud's kept points (amvs_cloud_bounds)."""
+        km = None if keep_mask is None else np.ascontiguousarray(keep_mask, dtype=np.uint8)
+        mn, mx = np.empty(3, np.float64), np.empty(3, np.float64)
+        self._chk(self._lib.amvs_cloud_bounds(self._h, None if km is None else _u8(km), _f64(mn), _f64(mx)))
+        return mn, mx
+
+    def cloud_voxel_downsample_grid(self, origin, voxel_size, keep_mask=None):
+        """The voxel de-duplication of the reference's dense mode on the resident cloud: voxels anchored at `origin`, the
+        first point of every voxel in lexicographic voxel order (amvs_cloud_voxel_downsample_grid).  Returns the count."""
+        km = None if keep_mask is None else np.ascontiguousarray(keep_mask, dtype=np.uint8)
+        o = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        cnt = C.c_int64(0)
+        self._chk(self._lib.amvs_cloud_voxel_downsample_grid(self._h, None if km is None else _u8(km), _f64(o), float(voxel_size),
+                                                             C.byref(cnt)))
+        return int(cnt.value)
+
+    def selftest_sqrt(self, values):
+        """sqrt of float64 values on the device (amvs_match_selftest_sqrt)."""
+        v = np.ascontiguousarray(values, dtype=np.float64).ravel()
+        out = np.empty_like(v)
+        if v.size:
+            self._chk(self._lib.amvs_match_selftest_sqrt(self._h, _f64(v), v.size, _f64(out)))
+        return out
 
     # -- cross-view depth-map filter (include/amvs_depth.h amvs_depth_filter) --
     def depth_filter(self, K, poses, min_confidence, max_px=1.0, max_rel=0.01, min_consistent=2, refine=True, neighbours=None,
