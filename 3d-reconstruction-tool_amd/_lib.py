@@ -1,5 +1,5 @@
-"""ctypes binding of libamvs.so (the C ABI declared in include/amvs.h, include/amvs_depth.h, include/amvs_lens.h and
-include/amvs_match.h).
+"""ctypes binding of libamvs.so (the C ABI declared in include/amvs.h, include/amvs_depth.h, include/amvs_lens.h,
+include/amvs_match.h and include/amvs_epipolar.h).
 
 There is no CPU fallback: if the shared library is missing or no HIP device is
 present, loading / context creation raises.
@@ -206,6 +206,19 @@ MATCH_SIGNATURES = {
 DESC_DIM, DESC_TILE, DESC_CHUNK, DESC_QUERY_BLOCK = 128, 32, 256, 512
 DESC_MAX_ROWS, DESC_MAX_SLOTS = 1 << 20, 1 << 16
 
+# name -> (restype, argtypes); every symbol include/amvs_epipolar.h declares (a table of its own for the same reason)
+u8p, i64p = C.POINTER(C.c_uint8), C.POINTER(C.c_int64)
+EPIPOLAR_SIGNATURES = {
+    "amvs_fmat_hypotheses": (C.c_int, [C.c_void_p, f32p, f32p, C.c_int, C.c_uint64, C.c_int, C.c_int, i32p, f64p]),
+    "amvs_fmat_score": (C.c_int, [C.c_void_p, f64p, C.c_int, f32p, f32p, C.c_int, C.c_double, i32p]),
+    "amvs_fmat_inliers": (C.c_int, [C.c_void_p, f64p, f32p, f32p, C.c_int, C.c_double, u8p, i64p]),
+    "amvs_fmat_fit": (C.c_int, [C.c_void_p, f32p, f32p, u8p, C.c_int, f64p, i64p]),
+    "amvs_fmat_ransac": (C.c_int, [C.c_void_p, f32p, f32p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64, f64p, u8p, i64p,
+                                   i32p]),
+}
+# include/amvs_epipolar.h: hypotheses per RANSAC batch, matches per block of a sum, and the limits
+FMAT_BATCH, FMAT_BLOCK, FMAT_MAX_MATCHES, FMAT_MAX_HYP = 1024, 64, 1 << 20, 1 << 20
+
 _lib = None
 
 
@@ -242,7 +255,7 @@ def load():
         _share_torch_hip_runtime()
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(LENS_SIGNATURES.items()) \
-                + list(MATCH_SIGNATURES.items()):
+                + list(MATCH_SIGNATURES.items()) + list(EPIPOLAR_SIGNATURES.items()):
             fn = getattr(lib, name)      # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args

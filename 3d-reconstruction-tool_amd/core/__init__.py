@@ -1,6 +1,6 @@
 """The reconstruction classes.  DenseReconstructor and the method it is built on are resolved lazily, so importing
 the package for the camera types does not import the engine."""
-__all__ = ["DenseReconstructor", "reconstruct_from_features"]
+__all__ = ["DenseReconstructor", "reconstruct_from_features", "FeatureMatcher", "ImageFeatures", "FeatureMatch"]
 
 
 def __getattr__(name):
@@ -10,4 +10,7 @@ def __getattr__(name):
     if name == "reconstruct_from_features":
         from .dense import DenseReconstructor
         return DenseReconstructor.reconstruct_from_features
+    if name in ("FeatureMatcher", "ImageFeatures", "FeatureMatch"):
+        from . import features
+        return getattr(features, name)
     raise AttributeError(name)

@@ -614,6 +614,70 @@ class Engine:
             self._chk(self._lib.amvs_match_selftest_sqrt(self._h, _f64(v), v.size, _f64(out)))
         return out
 
+    # -- geometric verification (include/amvs_epipolar.h): fundamental-matrix RANSAC on the matches of two views --
+    @staticmethod
+    def _match_points(pts1, pts2):
+        p1 = np.ascontiguousarray(pts1, dtype=np.float32).reshape(-1, 2)
+        p2 = np.ascontiguousarray(pts2, dtype=np.float32).reshape(-1, 2)
+        if len(p1) != len(p2):
+            raise ValueError("pts1 and pts2 must have one row per match")
+        return p1, p2, len(p1)
+
+    def fmat_hypotheses(self, pts1, pts2, seed=0, first=0, count=_lib.FMAT_BATCH):
+        """(idx (count, 8) int32, F (count, 3, 3) float64): the samples of hypotheses first .. first + count - 1 in draw
+        order and their 8-point fits, not forced to rank 2 (amvs_fmat_hypotheses)."""
+        p1, p2, m = self._match_points(pts1, pts2)
+        n = max(int(count), 1)
+        idx = np.empty((n, 8), np.int32)
+        F = np.empty((n, 3, 3), np.float64)
+        self._chk(self._lib.amvs_fmat_hypotheses(self._h, _p(p1), _p(p2), m, int(seed) & (2 ** 64 - 1), int(first), int(count),
+                                                 idx.ctypes.data_as(i32p), _f64(F)))
+        return idx, F
+
+    def fmat_score(self, F, pts1, pts2, threshold=2.0):
+        """Inlier counts (n,) int32 of n fundamental matrices F (n, 3, 3) among the matches (amvs_fmat_score)."""
+        p1, p2, m = self._match_points(pts1, pts2)
+        Fs = np.ascontiguousarray(F, dtype=np.float64).reshape(-1, 9)
+        counts = np.empty(max(len(Fs), 1), np.int32)
+        self._chk(self._lib.amvs_fmat_score(self._h, _f64(Fs), len(Fs), _p(p1), _p(p2), m, float(threshold),
+                                            counts.ctypes.data_as(i32p)))
+        return counts[:len(Fs)]
+
+    def fmat_inliers(self, F, pts1, pts2, threshold=2.0):
+        """The inlier mask (m,) bool of one F (amvs_fmat_inliers)."""
+        p1, p2, m = self._match_points(pts1, pts2)
+        F9 = np.ascontiguousarray(F, dtype=np.float64).reshape(9)
+        mask = np.zeros(max(m, 1), np.uint8)
+        k = C.c_int64(0)
+        self._chk(self._lib.amvs_fmat_inliers(self._h, _f64(F9), _p(p1), _p(p2), m, float(threshold), _u8(mask), C.byref(k)))
+        return mask[:m].astype(bool)
+
+    def fmat_fit(self, pts1, pts2, mask=None):
+        """F (3, 3) float64 fitted to the matches of `mask` (None: all): normalised 8-point, rank 2, unit Frobenius norm, the
+        entry of largest magnitude positive (amvs_fmat_fit)."""
+        p1, p2, m = self._match_points(pts1, pts2)
+        km = None if mask is None else np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+        if km is not None and len(km) != m:
+            raise ValueError("mask must have one entry per match")
+        F = np.empty((3, 3), np.float64)
+        used = C.c_int64(0)
+        self._chk(self._lib.amvs_fmat_fit(self._h, _p(p1), _p(p2), None if km is None else _u8(km), m, _f64(F), C.byref(used)))
+        return F
+
+    def fundamental_ransac(self, pts1, pts2, threshold=2.0, confidence=0.999, max_hypotheses=4096, seed=0):
+        """(F (3, 3) float64 or None, mask (m,) bool, info): the fundamental matrix of the matches by RANSAC and its inliers
+        (amvs_fmat_ransac).  info = {"hypotheses", "best_hypothesis", "best_count", "n_inliers"}; F is None when no
+        hypothesis kept 8 matches or the refit kept fewer."""
+        p1, p2, m = self._match_points(pts1, pts2)
+        F = np.zeros((3, 3), np.float64)
+        mask = np.zeros(max(m, 1), np.uint8)
+        k = C.c_int64(0)
+        info = np.zeros(3, np.int32)
+        self._chk(self._lib.amvs_fmat_ransac(self._h, _p(p1), _p(p2), m, float(threshold), float(confidence), int(max_hypotheses),
+                                             int(seed) & (2 ** 64 - 1), _f64(F), _u8(mask), C.byref(k), info.ctypes.data_as(i32p)))
+        out = {"hypotheses": int(info[0]), "best_hypothesis": int(info[1]), "best_count": int(info[2]), "n_inliers": int(k.value)}
+        return (F if k.value >= 8 else None), mask[:m].astype(bool), out
+
     # -- cross-view depth-map filter (include/amvs_depth.h amvs_depth_filter) --
     def depth_filter(self, K, poses, min_confidence, max_px=1.0, max_rel=0.01, min_consistent=2, refine=True, neighbours=None,
                      depth=None, conf=None, device_ptrs=None, out_ptrs=None, in_place=False):
