@@ -219,6 +219,13 @@ EPIPOLAR_SIGNATURES = {
 # include/amvs_epipolar.h: hypotheses per RANSAC batch, matches per block of a sum, and the limits
 FMAT_BATCH, FMAT_BLOCK, FMAT_MAX_MATCHES, FMAT_MAX_HYP = 1024, 64, 1 << 20, 1 << 20
 
+# name -> (restype, argtypes); every symbol include/amvs_step.h declares (a table of its own for the same reason)
+STEP_SIGNATURES = {
+    "amvs_set_step_sources": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "amvs_get_step_sources": (C.c_int, [C.c_void_p, C.c_int, i32p, i32p]),
+    "amvs_step_sources_max_patch": (C.c_int, []),
+}
+
 _lib = None
 
 
@@ -255,7 +262,7 @@ def load():
         _share_torch_hip_runtime()
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(LENS_SIGNATURES.items()) \
-                + list(MATCH_SIGNATURES.items()) + list(EPIPOLAR_SIGNATURES.items()):
+                + list(MATCH_SIGNATURES.items()) + list(EPIPOLAR_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
             fn = getattr(lib, name)      # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args

@@ -7,6 +7,7 @@
 // together, one kernel launch per cost-evaluation step over the whole batch.
 #include "amvs_ctx.h"
 #include "../../include/amvs_lens.h"
+#include "../../include/amvs_step.h"
 
 #include <cmath>
 #include <cstring>
@@ -115,6 +116,9 @@ amvs::StepArgs base_args(const amvs_ctx *c, int patch, int n_jobs, int TH)
     a.pair_stride = c->pstride;
     a.jobs = c->d_jobs.get();
     a.aux = c->d_aux.get();
+    const StepRegs regs = step_regs(c, patch);             // (read by the fast step only; upload_jobs skips the maps to match)
+    a.ref_in_kernel = regs.stats ? 1 : 0;
+    a.depth_hist = regs.hist ? 1 : 0;
     return a;
 }
 
@@ -450,7 +454,7 @@ int one_step_begin(amvs_ctx *c, int ref, const int *src_ids, int n_src, int patc
     if ((rc = ensure_slots(c, 1))) return rc;
     int fast = 0;
     if ((rc = resolve_fast(c, AMVS_MODE_DEFAULT, &fast))) return rc;
-    if ((rc = upload_jobs(c, 1, &ref, src_ids, n_src, fast ? patch : 0))) return rc;
+    if ((rc = upload_jobs(c, 1, &ref, src_ids, n_src, fast ? patch : 0, false, !step_regs(c, patch).stats))) return rc;
     c->pm_resumable = false;                    // the single-step entry points overwrite the state of slot 0
     o.c = c; o.patch = patch; o.n_src = n_src; o.hw = (size_t)c->H * c->W;
     o.a = base_args(c, patch, 1, pick_tile_rows(c, patch, n_src, 1, 0, 64, fast != 0));
@@ -698,7 +702,9 @@ static int patchmatch_core(amvs_ctx *c, int n_ref, const int *ref_ids, const int
     if ((rc = ensure_slots(c, n_ref))) return rc;
     int fast = 0;
     if ((rc = resolve_fast(c, p->mode, &fast))) return rc;
-    if ((rc = upload_jobs(c, n_ref, ref_ids, src_ids, n_src, fast ? p->patch_size : 0))) return rc;
+    // (the (mean1, var1) maps only if the steps of this call read them)
+    if ((rc = upload_jobs(c, n_ref, ref_ids, src_ids, n_src, fast ? p->patch_size : 0, false, !step_regs(c, p->patch_size).stats)))
+        return rc;
 
     const size_t hw = (size_t)c->H * c->W;
     if (p->schedule < 0 || p->schedule > AMVS_SCHEDULE_PAIRED) return fail(c, AMVS_EINVAL, "unknown schedule");
@@ -820,6 +826,28 @@ int amvs_set_launch_order(amvs_ctx *c, int edge_first, int group_overlap)
     c->group_overlap = group_overlap < 0 ? AMVS_DEFAULT_GROUP_OVERLAP : group_overlap;
     return AMVS_OK;
 }
+
+int amvs_set_step_sources(amvs_ctx *c, int ref_stats, int centre_depth)
+{
+    if (!c) return AMVS_EINVAL;
+    if (ref_stats < -1 || ref_stats > 1 || centre_depth < -1 || centre_depth > 1)
+        return fail(c, AMVS_EINVAL, "step sources: ref_stats and centre_depth in -1..1");
+    c->ref_stats_source = ref_stats < 0 ? AMVS_DEFAULT_REF_STATS_SOURCE : ref_stats;
+    c->depth_source = centre_depth < 0 ? AMVS_DEFAULT_DEPTH_SOURCE : centre_depth;
+    return AMVS_OK;
+}
+
+int amvs_get_step_sources(amvs_ctx *c, int patch_size, int *ref_stats, int *centre_depth)
+{
+    if (!c) return AMVS_EINVAL;
+    if (!ref_stats || !centre_depth) return fail(c, AMVS_EINVAL, "step sources: NULL output");
+    const StepRegs regs = step_regs(c, patch_size);
+    *ref_stats = regs.stats ? 1 : 0;
+    *centre_depth = regs.hist ? 1 : 0;
+    return AMVS_OK;
+}
+
+int amvs_step_sources_max_patch(void) { return amvs::step_fast_regs_max_patch(); }
 
 int amvs_sweep_order(int n_jobs, int tiles_x, int tiles_y, int band_major, int paired, int edge_first,
                      int64_t capacity, int32_t *out, int32_t *n_blocks)

@@ -32,6 +32,7 @@ void check_fetch_undistort(unsigned long long out[4], bool reset);
 void check_fetch_match(unsigned long long out[4], bool reset);
 void check_fetch_triangulate(unsigned long long out[4], bool reset);
 void check_fetch_fmat(unsigned long long out[4], bool reset);
+void check_fetch_kernels_fast_regs(unsigned long long out[4], bool reset);
 }  // namespace amvs
 #endif
 
@@ -46,7 +47,8 @@ std::string g_create_error;
 // (out[1] = translation unit << 32 | source line: 1 amvs_kernels, 2 amvs_kernels_fast, 3 amvs_sweep_fast,
 // 4 amvs_sweep_exact, 5 amvs_generic, 6 amvs_extended, 7 amvs_fusion, 8 amvs_knn, 9 amvs_mesh, 10 amvs_mesh_clean,
 // 11 amvs_mesh_decimate, 12 amvs_mesh_render, 13 amvs_mesh_color, 14 amvs_mesh_texture, 15 amvs_mesh_fill,
-// 16 amvs_cloud_normals, 17 amvs_depth_filter, 18 amvs_undistort, 19 amvs_match, 20 amvs_triangulate, 21 amvs_fmat;
+// 16 amvs_cloud_normals, 17 amvs_depth_filter, 18 amvs_undistort, 19 amvs_match, 20 amvs_triangulate, 21 amvs_fmat,
+// 22 amvs_kernels_fast_regs (lines of amvs_kernels_fast.hip);
 // out[2] = the index, out[3] = the extent it was compared with).  Zeros in the shipped build.
 void index_report(uint64_t out[4], bool reset)
 {
@@ -60,7 +62,7 @@ void index_report(uint64_t out[4], bool reset)
         amvs::check_fetch_mesh_render, amvs::check_fetch_mesh_color, amvs::check_fetch_mesh_texture,
         amvs::check_fetch_mesh_fill, amvs::check_fetch_cloud_normals, amvs::check_fetch_depth_filter,
         amvs::check_fetch_undistort, amvs::check_fetch_match, amvs::check_fetch_triangulate,
-        amvs::check_fetch_fmat};
+        amvs::check_fetch_fmat, amvs::check_fetch_kernels_fast_regs};
     for (auto f : fetch) {
         unsigned long long r[4] = {0, 0, 0, 0};
         f(r, reset);
@@ -167,13 +169,36 @@ int ensure_fast_stats(amvs_ctx *c, int patch)
     return AMVS_OK;
 }
 
+// Where the fast sweep steps of this context take the reference statistics and the centre depth from
+// (amvs_set_step_sources).  The automatic choice is a table by patch size, like the `paired` rule of
+// run_fused_schedule: the registers where they were measured faster by the rule of DESIGN.md section 5 (round 9; bench.py
+// main line at that patch size, ms per step, medians of five alternating runs, maps and loads / statistics in the kernel
+// / both): 3x3 51.24 / 47.08 / 45.64 (three runs), 5x5 54.25 / 51.35 / 49.96, 7x7 58.42 / 55.71 / 54.27 (a second
+// session 58.87 / 55.61 / 54.17), 9x9 68.18 / 66.02 / 64.72, 11x11 73.76 / 72.47 / 71.16 -- and 13x13 80.85 / 82.33 /
+// 80.64, 15x15 86.81 / 89.80 / 88.25: there the 2 (k - 1) more cross-lane adds cost more than the load saves.
+// The statistics entry meets that rule against the maps at every size up to 11x11.  The HISTORY entry does not meet
+// it as worded -- alone against the maps and loads it gains 1.2 - 1.7 %, below three parent spreads at 7x7 (2.6 -
+// 3.1 %) and 3x3 (1.3 %) --: it rests on the stacked comparison, "both" against "statistics" (7x7: 2.6 % in both
+// sessions against three spreads of 1.1 %, every run below every run).  Sizes other than 7x7: one session.
+// 13x13 and 15x15 stay compiled although the table never picks them: they are the measurements that place the
+// table's edge, and the switch lets that edge be measured again on another image size or source count with one build.
+// The run-time-k kernels and patches above step_fast_regs_max_patch() always read the maps.
+StepRegs step_regs(const amvs_ctx *c, int patch)
+{
+    if (!amvs::step_fast_regs_supported(patch)) return StepRegs{false, false};
+    const bool auto_stats = patch <= 11, auto_hist = patch <= 11;
+    return StepRegs{c->ref_stats_source < 0 ? auto_stats : c->ref_stats_source != 0,
+                    c->depth_source < 0 ? auto_hist : c->depth_source != 0};
+}
+
 // `fast_patch` > 0: also fill the fast-mode records (precomposed projections, ref statistics of
-// that patch size)
-int upload_jobs(amvs_ctx *c, int n_ref, const int *ref_ids, const int *src_ids, int n_src, int fast_patch, bool compose_only)
+// that patch size -- unless `ref_maps` is false: no kernel of the call reads the maps, see step_regs)
+int upload_jobs(amvs_ctx *c, int n_ref, const int *ref_ids, const int *src_ids, int n_src, int fast_patch, bool compose_only,
+                bool ref_maps)
 {
     if (n_ref <= 0 || !ref_ids || !src_ids) return fail(c, AMVS_EINVAL, "empty batch");
     const float2 *fmaps = nullptr;
-    if (fast_patch > 0) {
+    if (fast_patch > 0 && ref_maps) {
         int rc = ensure_fast_stats(c, fast_patch);
         if (rc) return rc;
         fmaps = c->fstats[fast_patch].maps.get();

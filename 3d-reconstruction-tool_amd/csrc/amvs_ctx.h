@@ -24,6 +24,14 @@
 #define AMVS_DEFAULT_GROUP_OVERLAP 1
 #endif
 
+// Defaults of amvs_set_step_sources (-1 = the automatic table of step_regs, amvs_context.hip).
+#ifndef AMVS_DEFAULT_REF_STATS_SOURCE
+#define AMVS_DEFAULT_REF_STATS_SOURCE -1
+#endif
+#ifndef AMVS_DEFAULT_DEPTH_SOURCE
+#define AMVS_DEFAULT_DEPTH_SOURCE -1
+#endif
+
 // the communicator of amvs_comm.hip, the only file that sees RCCL (as rccl.h declares it)
 struct ncclComm;
 typedef ncclComm *ncclComm_t;
@@ -129,6 +137,9 @@ struct amvs_ctx {
     // edge to its centre (amvs_strip_order.h; -1: where the groups overlap, else top to bottom); group_overlap -- the view groups of a batch dealt to two streams of the
     // context (run_fused_schedule): 0 one stream, 1 two streams of equal priority, 2 a high / low pair
     int edge_first = AMVS_DEFAULT_EDGE_FIRST, group_overlap = AMVS_DEFAULT_GROUP_OVERLAP;
+    // Where the fast sweep step takes the reference window's statistics and the centre depth from (amvs_set_step_sources;
+    // resolved per call by step_regs): -1 the automatic table, 0 the (mean1, var1) maps / a second load, 1 the registers
+    int ref_stats_source = AMVS_DEFAULT_REF_STATS_SOURCE, depth_source = AMVS_DEFAULT_DEPTH_SOURCE;
     // -DAMVS_STEP_TRACE: [launch][trace_stride blocks][4] workgroup timeline of the last PatchMatch call
     amvs::DeviceBuffer<unsigned long long> d_trace;
     long long trace_stride = 0, trace_launches = 0;
@@ -168,8 +179,10 @@ int check_patch_src(amvs_ctx *c, int patch, int n_src);
 int ensure_slots(amvs_ctx *c, int n);
 int ensure_stats(amvs_ctx *c, int patch);
 int ensure_fast_stats(amvs_ctx *c, int patch);
+struct StepRegs { bool stats, hist; };      // StepArgs::ref_in_kernel / depth_hist of the fast sweep steps of `c`
+StepRegs step_regs(const amvs_ctx *c, int patch);
 int upload_jobs(amvs_ctx *c, int n_ref, const int *ref_ids, const int *src_ids, int n_src, int fast_patch = 0,
-                bool compose_only = false);
+                bool compose_only = false, bool ref_maps = true);
 const uint16_t *usable_pairs(const amvs_ctx *c);
 int resolve_fast(amvs_ctx *c, int requested, int *fast);
 void resolve_timing(amvs_ctx *c);

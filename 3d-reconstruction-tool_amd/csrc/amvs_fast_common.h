@@ -55,6 +55,50 @@ AMVS_DEV float ref_bytes_get(const uint32_t (&rb)[RefBytes<K>::NB], int i)
     return (float)((rb[j >> 2] >> (8 * (j & 3))) & 0xFFu);          // v_cvt_f32_ubyteN
 }
 
+// The sweep step can form the reference window's (mean1, var1) from the packed codes it carries (ref_window_stats)
+// instead of loading them from the (mean1, var1) maps.  The window sums are integers; both paths convert them to
+// float32 once, and that conversion is exact while k^2 * 255^2 < 2^24, i.e. up to 15 x 15 (15^2 * 65025 =
+// 14 630 625, 17^2 * 65025 = 18 792 225): the patch sizes the in-kernel form is compiled for.
+constexpr bool window_sums_exact_in_f32(int K) { return (long long)K * K * 65025ll < (1ll << 24); }
+constexpr int AMVS_REF_IN_KERNEL_MAX_PATCH = 15;
+constexpr bool ref_in_kernel_compiled(int K) { return K <= AMVS_REF_IN_KERNEL_MAX_PATCH; }
+static_assert(window_sums_exact_in_f32(AMVS_REF_IN_KERNEL_MAX_PATCH) && !window_sums_exact_in_f32(AMVS_REF_IN_KERNEL_MAX_PATCH + 2),
+              "AMVS_REF_IN_KERNEL_MAX_PATCH is the largest odd patch whose window sums of squares fit 24 bits");
+
+AMVS_DEV uint32_t wave_shl1_u(uint32_t x)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x130, 0xf, 0xf, true);
+}
+
+// (mean1, var1) of the k x k reference window whose left column is this lane's, from the last K codes of the
+// columns (rb of lanes i .. i+K-1): column sums of r and r^2 with one byte-sum and one byte-dot per packed register,
+// row sums as K-1 wave shifts -- integers, so in any order the values of fast_stats_kernel, which also counts the
+// out-of-image part of a window as zeros (out-of-image rows and lanes push code 0); then its two operations.
+template <int K>
+AMVS_DEV void ref_window_stats(const uint32_t (&rb)[RefBytes<K>::NB], float &m1, float &v1)
+{
+    static_assert(ref_in_kernel_compiled(K) && window_sums_exact_in_f32(K), "patch size beyond the in-kernel statistics");
+    constexpr int NB = RefBytes<K>::NB, FIRST = RefBytes<K>::FIRST;
+    constexpr float C1 = (float)(1.0 / ((double)(K * K) * 255.0));
+    constexpr float C2 = (float)(1.0 / ((double)(K * K) * 65025.0));
+    uint32_t cr = 0u, crr = 0u;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+        // (the bytes of rb[0] below the window still hold older rows)
+        const uint32_t w = (i == 0 && FIRST > 0) ? (rb[0] & (0xFFFFFFFFu << (8 * FIRST))) : rb[i];
+        cr = __builtin_amdgcn_sad_u8(w, 0u, cr);
+        crr = __builtin_amdgcn_udot4(w, w, crr, false);
+    }
+    uint32_t sr = cr, srr = crr;
+#pragma unroll
+    for (int j = 1; j < K; ++j) {
+        sr = wave_shl1_u(sr) + cr;
+        srr = wave_shl1_u(srr) + crr;
+    }
+    m1 = (float)(int)sr * C1;
+    v1 = __builtin_fmaf(-m1, m1, (float)(int)srr * C2);
+}
+
 // wave-uniform constants of the fast sampler
 struct FastConsts {
     float flo;                    // lower validity bound lo (patch half, or 0 for the confidence pass)

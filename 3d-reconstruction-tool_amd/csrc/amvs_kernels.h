@@ -106,6 +106,11 @@ struct StepArgs : StepArgsBase {
     // Dispatch order inside every XCD's range: 1 = each view's bands from the image edge towards its centre
     // (amvs_strip_order.h), 0 = top to bottom.  Performance only.
     int edge_first;
+    // Fast step, compiled patch sizes up to 15 x 15 (step_fast_regs_supported).  ref_in_kernel: the reference window's
+    // (mean1, var1) are formed in the kernel from the codes it carries; Job::ref_stats is not read (and may be 0).
+    // depth_hist: the centre pixel's / the propagation neighbour's depth is kept from the load that sampled it.
+    // Performance only: the maps are the same bit for bit.
+    int ref_in_kernel, depth_hist;
     // -DAMVS_STEP_TRACE builds: [grid][4] workgroup timeline of this launch (amvs_kernel_common.h), or NULL
     unsigned long long *trace;
 };
@@ -161,6 +166,11 @@ int step_fast_waves_per_cu(int K, int S, int wg_cap = 0);
 // the paired-band schedule is compiled for this patch / source count: fast arithmetic, exact arithmetic (packed 8-bit maps)
 bool step_fast_pair_supported(int K, int S);
 bool step_pair_supported(int K, int S);
+// StepArgs::ref_in_kernel / depth_hist are compiled for this patch size (the largest such: step_fast_regs_max_patch)
+bool step_fast_regs_supported(int K);
+int step_fast_regs_max_patch();
+// amvs_kernels_fast_regs.hip: the launches of launch_step_fast with one of the two set (it forwards them)
+hipError_t launch_step_fast_regs(int K, int S, const StepArgs &a, hipStream_t st);
 // test hook: per-source samples [S][H*W] and validity bits [H*W] of job 0 at the depth map a.d_in;
 // a.TH carries k/2, a.mode selects the bounds (MODE_EVAL patch bounds, MODE_CONF image bounds,
 // MODE_EVAL + 100 depth test only = plane sweep)

@@ -16,9 +16,16 @@
 //     (0..255), the 1/255 and 1/k^2 factors are folded into two constants of the NCC epilogue;
 //   * the reference image's window sums are exact integers, precomputed once per view and patch
 //     size as (mean1, var1) maps (launch_fast_stats): no ref sums, and no ref ring in LDS -- the
-//     last k reference codes of a column travel as packed bytes in 2-3 VGPRs;
+//     last k reference codes of a column travel as packed bytes in 1-8 VGPRs; up to 11 x 11 the sweep step
+//     forms the same two values from those bytes instead of loading them (STATS below; amvs_set_step_sources);
 //   * NCC epilogue: cov * RN(1/den) (no quotient refinement).
+// The sweep step's variants that take the reference statistics or the centre depth from registers (StepArgs::
+// ref_in_kernel / depth_hist) are compiled from this file by a translation unit of their own, so that they build
+// beside the others: amvs_kernels_fast_regs.hip defines AMVS_FAST_STEP_REGS_TU and includes this file, which then
+// compiles the step kernel, launch_step_fast_v and launch_step_fast_regs only.
+#ifndef AMVS_FAST_STEP_REGS_TU
 #define AMVS_TU_ID 2
+#endif
 #include "amvs_fast_common.h"
 
 namespace amvs {
@@ -126,11 +133,18 @@ __global__ __launch_bounds__(AMVS_WAVE * AMVS_WG_WAVES) void pm_sample_fast_kern
 // and finish their last K/2 output rows from the partner's samples instead of sampling a halo of their own:
 // K/2 halo rows per strip instead of K - 1 (the samples, and every sum over them in the same top -> bottom
 // order, are those of the classic strips: bit-identical results).
-template <int K, int S, int MODE_T, bool PRE = false, bool PAIR = false>
+// STATS (StepArgs::ref_in_kernel): the reference window's (mean1, var1) are formed in the row loop from the packed
+// codes the wave carries (ref_window_stats: exact integers, the bits of the map) instead of one 8-byte load per
+// pixel and row.
+// DHIST (StepArgs::depth_hist): the centre pixel's pre-step depth (propagation: its neighbour's) is the d_raw that
+// lane + K/2 loaded K/2 rows earlier for sampling -- same address, same condition; it travels in a K/2 + 1 deep
+// per-lane history like the hashes instead of being loaded again (centre rows are always own rows of a paired band).
+template <int K, int S, int MODE_T, bool PRE = false, bool PAIR = false, bool STATS = false, bool DHIST = false>
 __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fast_min_waves(K, S)) void pm_step_fast_kernel(const StepArgs a)
 {
     constexpr int WGW = PAIR ? PAIR_WAVES : AMVS_WG_WAVES;      // waves of this workgroup
     static_assert(!(PRE && PAIR), "the paired bands sample for themselves");
+    static_assert(!(PRE && DHIST), "the window half of the split schedule loads no sampling depth to keep");
     constexpr int HALF = K / 2;
     constexpr int OUTW = AMVS_WAVE - 2 * HALF;
     constexpr float C1 = (float)(1.0 / ((double)(K * K) * 255.0));      // 1 / (k^2 * 255)
@@ -214,6 +228,9 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
     float ring_v[FRing<K, S>::NR][K];
     typename Hist<K, S>::T hist_ok = 0;
     uint32_t hist_h0[HALF + 1];
+    float hist_d[DHIST ? HALF + 1 : 1];
+#pragma unroll
+    for (int i = 0; i < (DHIST ? HALF + 1 : 1); ++i) hist_d[i] = 0.0f;
 #pragma unroll
     for (int i = 0; i < RefBytes<K>::NB; ++i) rb[i] = 0u;
 #pragma unroll
@@ -246,6 +263,7 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
         const uint32_t h0 = pixel_hash((uint32_t)pix, key);
         float v[S];
         unsigned okbits = 0u;
+        float d_raw = 0.0f;
         if (PAIR && !own) {
             // a row of the partner band: its samples, taken at its own candidates, from LDS (the partner
             // wrote them walking towards the boundary: the row next to it last)
@@ -266,7 +284,7 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
             }
         } else {
             // ---- candidate depth of this (possibly halo) pixel ----
-            const float d_raw = d_in[AMVS_IDX(inb ? pix + noff : 0, HW)];
+            d_raw = d_in[AMVS_IDX(inb ? pix + noff : 0, HW)];
             const float dc = candidate_depth(a, mode, inb, d_raw, h0);
             okbits = fast_sample_sources_checked<S, true, true>(job, fc, cols, (float)yr, dc, live, v);
             if constexpr (PAIR) {
@@ -287,6 +305,11 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
 #pragma unroll
         for (int i = 0; i < HALF; ++i) hist_h0[i] = hist_h0[i + 1];
         hist_h0[HALF] = h0;
+        if constexpr (DHIST) {
+#pragma unroll
+            for (int i = 0; i < HALF; ++i) hist_d[i] = hist_d[i + 1];
+            hist_d[HALF] = d_raw;
+        }
 
         if ((PAIR ? loc : r) < 2 * HALF) continue;
 
@@ -295,7 +318,12 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
         const int xc = xr + HALF;
         const bool outl = (lane < OUTW) & (xc < W);
         const int pc = AMVS_IDX(outl ? yc * W + xc : 0, HW);
-        const float oldd_tagged = d_in[pc], oldc = cost_io[pc];
+        // DHIST: d_in[pc] (propagation: d_in[pn]) as lane + K/2 loaded it K/2 rows ago.  A lane without an output
+        // pixel gets another lane's depth instead of d_in[0]: nothing of such a lane is stored.
+        float d_kept = 0.0f;
+        if constexpr (DHIST) d_kept = __shfl_down(hist_d[0], HALF);
+        const float oldd_tagged = (DHIST && mode != MODE_PROP) ? d_kept : d_in[pc];
+        const float oldc = cost_io[pc];
         const float oldd = depth_untag(oldd_tagged, a.depth_mask);
         const unsigned buf_c = depth_buffer(oldd_tagged);     // where this pixel's current normal lives
         // propagation: the neighbour the candidate was pulled from (requested with the other state
@@ -304,8 +332,14 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
         // for the negative offsets of odd iterations.
         const bool inb_c = ((unsigned)(yc + oy) < (unsigned)H) & ((unsigned)(xc + ox) < (unsigned)W);
         const int pn = AMVS_IDX((outl & inb_c) ? pc + noff : 0, HW);
-        const float nb_tagged = mode == MODE_PROP ? d_in[pn] : 0.0f;
-        const f32x2_t mv1 = ref_stats[pc];
+        const float nb_tagged = mode == MODE_PROP ? (DHIST ? d_kept : d_in[pn]) : 0.0f;
+        float m1, v1;
+        if constexpr (STATS) {
+            ref_window_stats<K>(rb, m1, v1);
+        } else {
+            const f32x2_t mv1 = ref_stats[pc];
+            m1 = mv1.x; v1 = mv1.y;
+        }
         const unsigned okc = (unsigned)__shfl_down((int)(unsigned)hist_ok, HALF);
         const uint32_t h0c = (uint32_t)__shfl_down((int)hist_h0[0], HALF);
 
@@ -315,7 +349,6 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
         float bvs[S], bvvs[S], brvs[S];
         if (PAIR && up) window_sums_fast<K, S, true>(lring, wslot, rr, ring_v, lane, bvs, bvvs, brvs);
         else window_sums_fast<K, S>(lring, wslot, rr, ring_v, lane, bvs, bvvs, brvs);
-        const float m1 = mv1.x, v1 = mv1.y;
 
         float total = 0.0f, cnt = 0.0f;
 #pragma unroll
@@ -396,6 +429,7 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
     AMVS_TRACE_EXIT(a, wv, lane);
 }
 
+#ifndef AMVS_FAST_STEP_REGS_TU
 // ------------------------------------------------------------------ sample dump ---
 // Test hook (amvs_sample_sources): the sampled value of every pixel in every source at the
 // pixel's own depth, in code units, and the validity bits -- the stage before the box filter.
@@ -510,16 +544,24 @@ void fast_compose(const float K[9], const float Rr[9], const float tr[3], const 
     }
 }
 
+#endif  // !AMVS_FAST_STEP_REGS_TU
+
 // ------------------------------------------------------------------ dispatch -----
-template <int K, int S>
-static hipError_t launch_step_fast_ks(const StepArgs &a, int nblk, hipStream_t st)
+// ST / DH: StepArgs::ref_in_kernel / depth_hist.  The depth history exists where the step samples for itself and
+// selects (the specialised modes): the caller passes DH only for those launches.
+template <int K, int S, bool ST, bool DH>
+static hipError_t launch_step_fast_v(const StepArgs &a, int nblk, hipStream_t st)
 {
     const int nwg = (nblk + AMVS_WG_WAVES - 1) / AMVS_WG_WAVES;
     const dim3 grid(nwg), block(AMVS_WAVE * AMVS_WG_WAVES);
-    if (a.presampled) {
-        if (!a.samples) return hipErrorInvalidValue;
-        dispatch_step_mode(a.mode, [&](auto m) { hipLaunchKernelGGL((pm_step_fast_kernel<K, S, m(), true>), grid, block, 0, st, a); });
-        return hipGetLastError();
+    if constexpr (!DH) {
+        if (a.presampled) {
+            if (!a.samples) return hipErrorInvalidValue;
+            dispatch_step_mode(a.mode, [&](auto m) {
+                hipLaunchKernelGGL((pm_step_fast_kernel<K, S, m(), true, false, ST>), grid, block, 0, st, a);
+            });
+            return hipGetLastError();
+        }
     }
     if constexpr (fast_pair_supported(K, S)) {
         if (a.paired && in_list(StepModes{}, a.mode)) {
@@ -527,15 +569,39 @@ static hipError_t launch_step_fast_ks(const StepArgs &a, int nblk, hipStream_t s
             const unsigned PXL = StepLds<K, S>::extra(a.wg_cap, true);
             const dim3 pblock(AMVS_WAVE * PAIR_WAVES);
             return dispatch(StepModes{}, a.mode, hipErrorInvalidValue, [&](auto m) {
-                hipLaunchKernelGGL((pm_step_fast_kernel<K, S, m(), false, true>), dim3(pwg), pblock, PXL, st, a);
+                hipLaunchKernelGGL((pm_step_fast_kernel<K, S, m(), false, true, ST, DH>), dim3(pwg), pblock, PXL, st, a);
                 return hipGetLastError();
             });
         }
     }
     const unsigned XL = StepLds<K, S>::extra(a.wg_cap);
-    dispatch_step_mode(a.mode, [&](auto m) { hipLaunchKernelGGL((pm_step_fast_kernel<K, S, m()>), grid, block, XL, st, a); });
-    return hipGetLastError();
+    if constexpr (DH) {
+        return dispatch(StepModes{}, a.mode, hipErrorInvalidValue, [&](auto m) {
+            hipLaunchKernelGGL((pm_step_fast_kernel<K, S, m(), false, false, ST, true>), grid, block, XL, st, a);
+            return hipGetLastError();
+        });
+    } else {
+        dispatch_step_mode(a.mode, [&](auto m) { hipLaunchKernelGGL((pm_step_fast_kernel<K, S, m(), false, false, ST>), grid, block, XL, st, a); });
+        return hipGetLastError();
+    }
 }
+
+#ifdef AMVS_FAST_STEP_REGS_TU
+// (amvs_kernels_fast_regs.hip) the launches with StepArgs::ref_in_kernel or depth_hist set
+hipError_t launch_step_fast_regs(int K, int S, const StepArgs &a, hipStream_t st)
+{
+    const int nblk = a.n_jobs * a.tiles_x * a.tiles_y;
+    const bool dh = a.depth_hist && !a.presampled && in_list(StepModes{}, a.mode);
+    return dispatch_ks(K, S, hipErrorInvalidValue, [&](auto k, auto s) {
+        if constexpr (ref_in_kernel_compiled(k())) {
+            if (a.ref_in_kernel)
+                return dh ? launch_step_fast_v<k(), s(), true, true>(a, nblk, st) : launch_step_fast_v<k(), s(), true, false>(a, nblk, st);
+            if (dh) return launch_step_fast_v<k(), s(), false, true>(a, nblk, st);
+        }
+        return hipErrorInvalidValue;            // (launch_step_fast sends nothing else here)
+    });
+}
+#else
 
 template <int K, int S>
 static int step_fast_occupancy_ks(int wg_cap)
@@ -555,11 +621,17 @@ int step_fast_waves_per_cu(int K, int S, int wg_cap)
 
 bool step_fast_pair_supported(int K, int S) { return patch_compiled(K) && in_list(SourceCounts{}, S) && fast_pair_supported(K, S); }
 
+bool step_fast_regs_supported(int K) { return patch_compiled(K) && ref_in_kernel_compiled(K); }
+int step_fast_regs_max_patch() { return AMVS_REF_IN_KERNEL_MAX_PATCH; }
+
 hipError_t launch_step_fast(int K, int S, const StepArgs &a, hipStream_t st)
 {
     if (!a.pairs) return hipErrorInvalidValue;        // fast mode samples the packed 8-bit maps only
+    if ((a.ref_in_kernel || a.depth_hist) && !step_fast_regs_supported(K)) return hipErrorInvalidValue;   // (the host resolves both to 0 there)
+    // the history exists in the launches that sample for themselves and select; the others load the centre depth
+    if (a.ref_in_kernel || (a.depth_hist && !a.presampled && in_list(StepModes{}, a.mode))) return launch_step_fast_regs(K, S, a, st);
     const int nblk = a.n_jobs * a.tiles_x * a.tiles_y;
-    return dispatch_ks(K, S, hipErrorInvalidValue, [&](auto k, auto s) { return launch_step_fast_ks<k(), s()>(a, nblk, st); });
+    return dispatch_ks(K, S, hipErrorInvalidValue, [&](auto k, auto s) { return launch_step_fast_v<k(), s(), false, false>(a, nblk, st); });
 }
 
 // Resident workgroups of the sampling kernel per CU when it runs alone, through unused dynamic LDS;
@@ -583,7 +655,12 @@ hipError_t launch_sample_fast(int S, const StepArgs &a, hipStream_t st)
     if (!a.pairs || !a.samples || a.s_TH < 1) return hipErrorInvalidValue;
     return dispatch(SourceCounts{}, S, hipErrorInvalidValue, [&](auto s) { return launch_sample_fast_s<s()>(a, st); });
 }
+#endif  // AMVS_FAST_STEP_REGS_TU
 
 }  // namespace amvs
 
+#ifdef AMVS_FAST_STEP_REGS_TU
+AMVS_CHECK_TU(kernels_fast_regs)
+#else
 AMVS_CHECK_TU(kernels_fast)
+#endif

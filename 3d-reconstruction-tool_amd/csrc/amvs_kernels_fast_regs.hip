@@ -1,0 +1,8 @@
+// amvs_kernels_fast_regs.hip -- the fast sweep step with the reference statistics formed in the kernel and / or the
+// centre depth kept in registers (StepArgs::ref_in_kernel, depth_hist; launch_step_fast_regs).  The kernel is the
+// one of amvs_kernels_fast.hip, instantiated here with those template flags: a translation unit of its own only so
+// that these instantiations compile beside the others instead of doubling that file's build time.  In the
+// index-checked build a violation is reported with this unit's id and the source line of amvs_kernels_fast.hip.
+#define AMVS_FAST_STEP_REGS_TU
+#define AMVS_TU_ID 22
+#include "amvs_kernels_fast.hip"

@@ -178,6 +178,20 @@ class Engine:
         self._chk(self._lib.amvs_set_launch_order(self._h, -1 if edge_first is None else int(bool(edge_first)),
                                                   -1 if group_overlap is None else int(group_overlap)))
 
+    def set_step_sources(self, ref_stats=None, centre_depth=None):
+        """Inputs of the fast sweep step (include/amvs_step.h amvs_set_step_sources): ref_stats -- False the (mean1, var1)
+        maps, True formed in the kernel; centre_depth -- False loaded again, True kept in registers from the sampling
+        load.  None = the library's choice.  Performance only."""
+        self._chk(self._lib.amvs_set_step_sources(self._h, -1 if ref_stats is None else int(bool(ref_stats)),
+                                                  -1 if centre_depth is None else int(bool(centre_depth))))
+
+    def step_sources(self, patch_size):
+        """(ref_stats, centre_depth) as booleans: what a fast sweep step of this engine takes from registers at this
+        patch size as the switch stands (amvs_get_step_sources)."""
+        r, d = C.c_int(0), C.c_int(0)
+        self._chk(self._lib.amvs_get_step_sources(self._h, int(patch_size), C.byref(r), C.byref(d)))
+        return bool(r.value), bool(d.value)
+
     def step_trace(self):
         """(n_launches, blocks_per_launch, 4) uint64 workgroup timeline of the last PatchMatch call; needs a library
         built with -DAMVS_STEP_TRACE (None from the shipped build)."""
