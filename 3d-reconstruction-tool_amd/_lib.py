@@ -219,6 +219,18 @@ EPIPOLAR_SIGNATURES = {
 # include/amvs_epipolar.h: hypotheses per RANSAC batch, matches per block of a sum, and the limits
 FMAT_BATCH, FMAT_BLOCK, FMAT_MAX_MATCHES, FMAT_MAX_HYP = 1024, 64, 1 << 20, 1 << 20
 
+# name -> (restype, argtypes); every symbol include/amvs_resection.h declares (a table of its own for the same reason)
+PNP_SIGNATURES = {
+    "amvs_pnp_hypotheses": (C.c_int, [C.c_void_p, f32p, f32p, C.c_int, f64p, C.c_uint64, C.c_int, C.c_int, i32p, f64p, f64p]),
+    "amvs_pnp_score": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int, f32p, f32p, C.c_int, f64p, C.c_double, i32p]),
+    "amvs_pnp_inliers": (C.c_int, [C.c_void_p, f64p, f64p, f32p, f32p, C.c_int, f64p, C.c_double, u8p, i64p]),
+    "amvs_pnp_refine": (C.c_int, [C.c_void_p, f32p, f32p, C.c_int, f64p, f64p, f64p, u8p, f64p, f64p, i32p, f64p, i64p]),
+    "amvs_pnp_ransac": (C.c_int, [C.c_void_p, f32p, f32p, C.c_int, f64p, C.c_double, C.c_double, C.c_int, C.c_uint64, f64p, f64p,
+                                  u8p, i64p, i32p]),
+}
+# include/amvs_resection.h: hypotheses per RANSAC batch, correspondences per block of a sum, refit steps, and the limits
+PNP_BATCH, PNP_BLOCK, PNP_REFINE_STEPS, PNP_MAX_POINTS, PNP_MAX_HYP = 1024, 64, 10, 1 << 20, 1 << 20
+
 # name -> (restype, argtypes); every symbol include/amvs_step.h declares (a table of its own for the same reason)
 STEP_SIGNATURES = {
     "amvs_set_step_sources": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -262,7 +274,7 @@ def load():
         _share_torch_hip_runtime()
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(LENS_SIGNATURES.items()) \
-                + list(MATCH_SIGNATURES.items()) + list(EPIPOLAR_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
+                + list(MATCH_SIGNATURES.items()) + list(EPIPOLAR_SIGNATURES.items()) + list(PNP_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
             fn = getattr(lib, name)      # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args

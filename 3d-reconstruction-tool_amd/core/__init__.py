@@ -1,6 +1,7 @@
 """The reconstruction classes.  DenseReconstructor and the method it is built on are resolved lazily, so importing
 the package for the camera types does not import the engine."""
-__all__ = ["DenseReconstructor", "reconstruct_from_features", "FeatureMatcher", "ImageFeatures", "FeatureMatch"]
+__all__ = ["DenseReconstructor", "reconstruct_from_features", "FeatureMatcher", "ImageFeatures", "FeatureMatch",
+           "register_view", "refine_pose"]
 
 
 def __getattr__(name):
@@ -13,4 +14,7 @@ def __getattr__(name):
     if name in ("FeatureMatcher", "ImageFeatures", "FeatureMatch"):
         from . import features
         return getattr(features, name)
+    if name in ("register_view", "refine_pose"):
+        from . import registration
+        return getattr(registration, name)
     raise AttributeError(name)

@@ -692,6 +692,85 @@ class Engine:
         out = {"hypotheses": int(info[0]), "best_hypothesis": int(info[1]), "best_count": int(info[2]), "n_inliers": int(k.value)}
         return (F if k.value >= 8 else None), mask[:m].astype(bool), out
 
+    # -- camera resection (include/amvs_resection.h): the pose of a view from 2D-3D correspondences by RANSAC --
+    @staticmethod
+    def _correspondences(points3d, points2d, K):
+        p3 = np.ascontiguousarray(points3d, dtype=np.float32).reshape(-1, 3)
+        p2 = np.ascontiguousarray(points2d, dtype=np.float32).reshape(-1, 2)
+        if len(p3) != len(p2):
+            raise ValueError("points3d and points2d must have one row per correspondence")
+        return p3, p2, len(p3), np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+
+    @staticmethod
+    def _poses(R, t):
+        Rs = np.ascontiguousarray(R, dtype=np.float64).reshape(-1, 9)
+        ts = np.ascontiguousarray(t, dtype=np.float64).reshape(-1, 3)
+        if len(Rs) != len(ts):
+            raise ValueError("R and t must hold one pose each per row")
+        return Rs, ts
+
+    def pnp_hypotheses(self, points3d, points2d, K, seed=0, first=0, count=_lib.PNP_BATCH):
+        """(idx (count, 6) int32, R (count, 3, 3), t (count, 3) float64): the samples of hypotheses first .. first + count - 1
+        in draw order and their poses, the 6-point DLT and the nearest rotation (amvs_pnp_hypotheses)."""
+        p3, p2, m, Kd = self._correspondences(points3d, points2d, K)
+        n = max(int(count), 1)
+        idx = np.empty((n, 6), np.int32)
+        R, t = np.empty((n, 3, 3), np.float64), np.empty((n, 3), np.float64)
+        self._chk(self._lib.amvs_pnp_hypotheses(self._h, _p(p3), _p(p2), m, _f64(Kd), int(seed) & (2 ** 64 - 1), int(first),
+                                                int(count), idx.ctypes.data_as(i32p), _f64(R), _f64(t)))
+        return idx, R, t
+
+    def pnp_score(self, R, t, points3d, points2d, K, threshold=8.0):
+        """Inlier counts (n,) int32 of n poses R (n, 3, 3), t (n, 3) among the correspondences (amvs_pnp_score)."""
+        p3, p2, m, Kd = self._correspondences(points3d, points2d, K)
+        Rs, ts = self._poses(R, t)
+        counts = np.empty(max(len(Rs), 1), np.int32)
+        self._chk(self._lib.amvs_pnp_score(self._h, _f64(Rs), _f64(ts), len(Rs), _p(p3), _p(p2), m, _f64(Kd), float(threshold),
+                                           counts.ctypes.data_as(i32p)))
+        return counts[:len(Rs)]
+
+    def pnp_inliers(self, R, t, points3d, points2d, K, threshold=8.0):
+        """The inlier mask (m,) bool of one pose: reprojection error <= threshold and a positive depth (amvs_pnp_inliers)."""
+        p3, p2, m, Kd = self._correspondences(points3d, points2d, K)
+        R9 = np.ascontiguousarray(R, dtype=np.float64).reshape(9)
+        t3 = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        mask = np.zeros(max(m, 1), np.uint8)
+        k = C.c_int64(0)
+        self._chk(self._lib.amvs_pnp_inliers(self._h, _f64(R9), _f64(t3), _p(p3), _p(p2), m, _f64(Kd), float(threshold), _u8(mask),
+                                             C.byref(k)))
+        return mask[:m].astype(bool)
+
+    def pnp_refine(self, points3d, points2d, K, R, t, mask=None):
+        """(R (3, 3), t (3,), steps, cost): the pose polished by Gauss-Newton on the reprojection error of the correspondences
+        of `mask` (None: all); cost is the sum of squared residuals in pixels (amvs_pnp_refine)."""
+        p3, p2, m, Kd = self._correspondences(points3d, points2d, K)
+        R9 = np.ascontiguousarray(R, dtype=np.float64).reshape(9)
+        t3 = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        km = None if mask is None else np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+        if km is not None and len(km) != m:
+            raise ValueError("mask must have one entry per correspondence")
+        Ro, to = np.empty((3, 3), np.float64), np.empty(3, np.float64)
+        steps, cost, used = C.c_int32(0), C.c_double(0.0), C.c_int64(0)
+        self._chk(self._lib.amvs_pnp_refine(self._h, _p(p3), _p(p2), m, _f64(Kd), _f64(R9), _f64(t3), None if km is None else _u8(km),
+                                            _f64(Ro), _f64(to), C.byref(steps), C.byref(cost), C.byref(used)))
+        return Ro, to, int(steps.value), float(cost.value)
+
+    def pnp_ransac(self, points3d, points2d, K, threshold=8.0, confidence=0.99, max_hypotheses=5000, seed=0):
+        """(R (3, 3) or None, t (3,) or None, mask (m,) bool, info): the pose of the view by RANSAC, polished on its inliers,
+        and those inliers (amvs_pnp_ransac).  info = {"hypotheses", "best_hypothesis", "best_count", "n_inliers"}; R and t
+        are None when no hypothesis kept 6 correspondences or the refit kept fewer."""
+        p3, p2, m, Kd = self._correspondences(points3d, points2d, K)
+        R, t = np.zeros((3, 3), np.float64), np.zeros(3, np.float64)
+        mask = np.zeros(max(m, 1), np.uint8)
+        k = C.c_int64(0)
+        info = np.zeros(3, np.int32)
+        self._chk(self._lib.amvs_pnp_ransac(self._h, _p(p3), _p(p2), m, _f64(Kd), float(threshold), float(confidence),
+                                            int(max_hypotheses), int(seed) & (2 ** 64 - 1), _f64(R), _f64(t), _u8(mask), C.byref(k),
+                                            info.ctypes.data_as(i32p)))
+        out = {"hypotheses": int(info[0]), "best_hypothesis": int(info[1]), "best_count": int(info[2]), "n_inliers": int(k.value)}
+        found = k.value >= 6
+        return (R if found else None), (t if found else None), mask[:m].astype(bool), out
+
     # -- cross-view depth-map filter (include/amvs_depth.h amvs_depth_filter) --
     def depth_filter(self, K, poses, min_confidence, max_px=1.0, max_rel=0.01, min_consistent=2, refine=True, neighbours=None,
                      depth=None, conf=None, device_ptrs=None, out_ptrs=None, in_place=False):

@@ -16,6 +16,7 @@ for f in $(make -s -C $src print-objs); do
   if [ $f = amvs_kernels_fast ] || [ $f = amvs_sweep_fast ] || { [ $f = amvs_sweep_exact ] && [ -z "$FAST_ONLY" ]; } || { [ $f = amvs_kernels ] && [ -z "$FAST_ONLY" ]; } || [ -n "$ALL" ] || [ ! -f $src/$f.o ]; then
     extra=""; { [ $f = amvs_sweep_fast ] || [ $f = amvs_sweep_exact ]; } && extra="-mllvm -amdgpu-sched-strategy=iterative-maxocc"    # as csrc/Makefile
     [ $f = amvs_match ] && extra="-mllvm -amdgpu-mfma-vgpr-form"
+    [ $f = amvs_pnp ] && extra="-mllvm -pragma-unroll-threshold=1048576"
     /opt/rocm/bin/hipcc $flags $extra "$@" -c $src/$f.hip -o $out/obj_$name/$f.o &
   else
     cp $src/$f.o $out/obj_$name/$f.o
