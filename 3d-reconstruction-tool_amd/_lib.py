@@ -1,5 +1,5 @@
 """ctypes binding of libamvs.so (the C ABI declared in include/amvs.h, include/amvs_depth.h, include/amvs_lens.h,
-include/amvs_match.h and include/amvs_epipolar.h).
+include/amvs_match.h, include/amvs_epipolar.h, include/amvs_resection.h, include/amvs_twoview.h and include/amvs_step.h).
 
 There is no CPU fallback: if the shared library is missing or no HIP device is
 present, loading / context creation raises.
@@ -231,6 +231,19 @@ PNP_SIGNATURES = {
 # include/amvs_resection.h: hypotheses per RANSAC batch, correspondences per block of a sum, refit steps, and the limits
 PNP_BATCH, PNP_BLOCK, PNP_REFINE_STEPS, PNP_MAX_POINTS, PNP_MAX_HYP = 1024, 64, 10, 1 << 20, 1 << 20
 
+# name -> (restype, argtypes); every symbol include/amvs_twoview.h declares (a table of its own for the same reason)
+TWOVIEW_SIGNATURES = {
+    "amvs_twoview_decompose": (C.c_int, [C.c_void_p, f64p, f64p, f64p, f64p, f64p, i32p]),
+    "amvs_twoview_score": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int, f32p, f32p, C.c_int, f64p, C.c_double, i32p]),
+    "amvs_twoview_front": (C.c_int, [C.c_void_p, f64p, f64p, f32p, f32p, C.c_int, f64p, C.c_double, u8p, i64p]),
+    "amvs_twoview_pose": (C.c_int, [C.c_void_p, f64p, f64p, f32p, f32p, C.c_int, C.c_double, f64p, f64p, u8p, i64p, i32p]),
+    "amvs_twoview_triangulate": (C.c_int, [C.c_void_p, f64p, f64p, f64p, f64p, f64p, f32p, f32p, C.c_int, C.c_double, C.c_double,
+                                           C.c_double, C.c_double, f64p, u8p, f64p, i64p]),
+}
+# include/amvs_twoview.h: the limits, the poses a scoring workgroup walks, and the defaults of the Python layer
+TWOVIEW_MAX_MATCHES, TWOVIEW_MAX_POSES, TWOVIEW_POSE_TILE = 1 << 20, 1 << 20, 32
+TWOVIEW_MAX_DEPTH, TWOVIEW_DEPTH_MIN, TWOVIEW_DEPTH_BASELINES, TWOVIEW_MIN_PARALLAX_DEG, TWOVIEW_MAX_REPROJ = 50.0, 0.01, 200.0, 1.0, 4.0
+
 # name -> (restype, argtypes); every symbol include/amvs_step.h declares (a table of its own for the same reason)
 STEP_SIGNATURES = {
     "amvs_set_step_sources": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -274,7 +287,8 @@ def load():
         _share_torch_hip_runtime()
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(LENS_SIGNATURES.items()) \
-                + list(MATCH_SIGNATURES.items()) + list(EPIPOLAR_SIGNATURES.items()) + list(PNP_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
+                + list(MATCH_SIGNATURES.items()) + list(EPIPOLAR_SIGNATURES.items()) + list(PNP_SIGNATURES.items()) + list(TWOVIEW_SIGNATURES.items()) \
+                + list(STEP_SIGNATURES.items()):
             fn = getattr(lib, name)      # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args

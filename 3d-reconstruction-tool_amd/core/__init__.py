@@ -1,7 +1,8 @@
 """The reconstruction classes.  DenseReconstructor and the method it is built on are resolved lazily, so importing
 the package for the camera types does not import the engine."""
 __all__ = ["DenseReconstructor", "reconstruct_from_features", "FeatureMatcher", "ImageFeatures", "FeatureMatch",
-           "register_view", "refine_pose"]
+           "register_view", "refine_pose", "compute_essential_matrix", "decompose_essential", "relative_pose",
+           "triangulate_points", "compute_reprojection_error", "find_best_initial_pair"]
 
 
 def __getattr__(name):
@@ -17,4 +18,8 @@ def __getattr__(name):
     if name in ("register_view", "refine_pose"):
         from . import registration
         return getattr(registration, name)
+    if name in ("compute_essential_matrix", "decompose_essential", "relative_pose", "triangulate_points",
+                "compute_reprojection_error", "find_best_initial_pair"):
+        from . import geometry
+        return getattr(geometry, name)
     raise AttributeError(name)

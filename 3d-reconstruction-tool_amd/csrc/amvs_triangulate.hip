@@ -3,13 +3,14 @@
 // (include/amvs_match.h; the definition is the header's, the judge tests/match_restatement.py, bit for bit).
 //
 // pair_triangulate_kernel: one lane per candidate, float64 throughout, M and V of the Jacobi iteration in registers
-// (the (p, q) pairs are template arguments, so every index is a constant).  The projection matrices and camera centres
+// (amvs_dlt4.h, shared with amvs_twoview.hip).  The projection matrices and camera centres
 // are formed once on the host in the order the header writes.  The accepted candidates are selected in order
 // (hipCUB) and gathered behind the points the cloud holds already.
 //
 // -ffp-contract=off (Makefile): a * b + c below is two roundings, on the device and on the host.
 #define AMVS_TU_ID 20
 #include "amvs_check.h"
+#include "amvs_dlt4.h"
 #include "amvs_kernels.h"
 #include "amvs_match_state.h"
 #include "../../include/amvs_match.h"
@@ -37,36 +38,6 @@ struct PairArgs {
     PairThresholds thr;
 };
 
-// one Jacobi rotation of the header's step 3 on the pair (P, Q)
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rotate(double (&M)[4][4], double (&V)[4][4])
-{
-    const double g = M[P][Q];
-    if (g == 0.0) return;
-    const double theta = (M[Q][Q] - M[P][P]) / (2.0 * g);
-    double t;
-    if (fabs(theta) > 1e150) t = 0.5 / theta;
-    else t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    M[P][P] = M[P][P] - t * g;
-    M[Q][Q] = M[Q][Q] + t * g;
-    M[P][Q] = 0.0;
-    M[Q][P] = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        if (r == P || r == Q) continue;
-        const double x = M[r][P], y = M[r][Q];
-        M[r][P] = M[P][r] = c * x - s * y;
-        M[r][Q] = M[Q][r] = s * x + c * y;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const double x = V[r][P], y = V[r][Q];
-        V[r][P] = c * x - s * y;
-        V[r][Q] = s * x + c * y;
-    }
-}
-
 __device__ __forceinline__ void cam_point(const double R[9], const double t[3], const double X[3], double pc[3])
 {
 #pragma unroll
@@ -89,40 +60,8 @@ __global__ __launch_bounds__(256) void pair_triangulate_kernel(const PairArgs a,
     for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < m; i += (int)(gridDim.x * blockDim.x)) {
         const double x1 = (double)pts1[2 * i], y1 = (double)pts1[2 * i + 1];
         const double x2 = (double)pts2[2 * i], y2 = (double)pts2[2 * i + 1];
-        double A[4][4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            A[0][c] = x1 * a.P1[8 + c] - a.P1[c];
-            A[1][c] = y1 * a.P1[8 + c] - a.P1[4 + c];
-            A[2][c] = x2 * a.P2[8 + c] - a.P2[c];
-            A[3][c] = y2 * a.P2[8 + c] - a.P2[4 + c];
-        }
-        double M[4][4], V[4][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = r; c < 4; ++c) {
-                const double v = ((A[0][r] * A[0][c] + A[1][r] * A[1][c]) + A[2][r] * A[2][c]) + A[3][r] * A[3][c];
-                M[r][c] = v;
-                M[c][r] = v;
-            }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) V[r][c] = r == c ? 1.0 : 0.0;
-#pragma unroll 1
-        for (int sweep = 0; sweep < AMVS_JACOBI_SWEEPS; ++sweep) {
-            jacobi_rotate<0, 1>(M, V); jacobi_rotate<0, 2>(M, V); jacobi_rotate<0, 3>(M, V);
-            jacobi_rotate<1, 2>(M, V); jacobi_rotate<1, 3>(M, V); jacobi_rotate<2, 3>(M, V);
-        }
-        double best = M[0][0], v[4] = {V[0][0], V[1][0], V[2][0], V[3][0]};
-#pragma unroll
-        for (int k = 1; k < 4; ++k)
-            if (M[k][k] < best) {
-                best = M[k][k];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = V[r][k];
-            }
+        double v[4];
+        dlt4_null_vector(a.P1, a.P2, x1, y1, x2, y2, v);
         const double X[3] = {v[0] / v[3], v[1] / v[3], v[2] / v[3]};
         double pc1[3], pc2[3];
         cam_point(a.R1, a.t1, X, pc1);

@@ -1,0 +1,282 @@
+// amvs_twoview.hip -- the cheirality vote over pose candidates and the two-view triangulation that returns every candidate
+// to the host (include/amvs_twoview.h; the definition is the header's, the judge tests/twoview_restatement.py, bit for
+// bit).  The decomposition of F is host arithmetic (amvs_twoview_host.h).
+//
+// twoview_score_kernel: the hot path, poses x matches.  A lane holds one match (four normalised coordinates), a workgroup
+//     of 256 matches walks a tile of AMVS_TWOVIEW_POSE_TILE poses whose twelve doubles are wave-uniform (read through the
+//     scalar cache, as pnp_score_kernel reads its poses), every (pose, match) runs the DLT of amvs_dlt4.h with M and V in
+//     registers, the predicate goes through a ballot and a population count, and lane 0 of a wave adds the count to the
+//     pose's counter (no add for a zero).  Integers only: any grid shape gives the same counts.
+// twoview_front_kernel: the same predicate for one pose, one byte a match.
+// twoview_triangulate_kernel: one candidate per lane in pixels; X, the validity byte and the cosine of the parallax
+//     angle of every candidate go back to the host.
+// No data-dependent index is formed: every index is the lane's own match or the wave's pose.
+//
+// -ffp-contract=off (Makefile): a * b + c below is two roundings, on the device and on the host.
+#define AMVS_TU_ID 24
+#include "amvs_check.h"
+#include "amvs_dlt4.h"
+#include "amvs_twoview_dev.h"
+#include "amvs_twoview_host.h"
+#include "../../include/amvs_twoview.h"
+
+#include <cmath>
+#include <cstring>
+
+namespace amvs {
+
+static_assert(TWOVIEW_JACOBI_SWEEPS == AMVS_JACOBI_SWEEPS, "the host iteration runs the sweeps of amvs_match.h");
+
+namespace {
+
+#define VCHK(call)                                                  \
+    do {                                                            \
+        hipError_t e_ = (call);                                     \
+        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
+    } while (0)
+
+constexpr int POSE_TILE = AMVS_TWOVIEW_POSE_TILE;
+
+struct Intr { double fx, fy, cx, cy; };
+struct Pose { double R[9], t[3]; };
+struct TriArgs {
+    double P1[12], P2[12], C1[3], C2[3], R1[9], t1[3], R2[9], t2[3], K[9];
+    TwoviewThresholds thr;
+};
+
+inline Intr intrinsics_of(const double *K) { return Intr{K[0], K[4], K[2], K[5]}; }
+
+// the header's cheirality test of the match with normalised coordinates (x1, y1), (x2, y2) under (R, t)
+__device__ __forceinline__ bool in_front(const double *R, const double *t, double x1, double y1, double x2, double y2, double max_depth)
+{
+    const double P1[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    const double P2[12] = {R[0], R[1], R[2], t[0], R[3], R[4], R[5], t[1], R[6], R[7], R[8], t[2]};
+    double v[4];
+    dlt4_null_vector(P1, P2, x1, y1, x2, y2, v);
+    const double Q[3] = {v[0] / v[3], v[1] / v[3], v[2] / v[3]};
+    const double z1 = Q[2], z2 = ((P2[8] * Q[0] + P2[9] * Q[1]) + P2[10] * Q[2]) + P2[11];
+    return z1 > 0.0 && z1 < max_depth && z2 > 0.0 && z2 < max_depth;
+}
+
+// counts[h] += matches in front under pose h among this workgroup's 256 matches, for the POSE_TILE poses of blockIdx.y
+__global__ __launch_bounds__(256) void twoview_score_kernel(const double *__restrict__ R, const double *__restrict__ t, int n,
+                                                            const float *__restrict__ pts1, const float *__restrict__ pts2, int m,
+                                                            const Intr k, double max_depth, int *__restrict__ counts)
+{
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    const bool live = i < m;
+    const size_t ii = live ? (size_t)i : 0;
+    const double x1 = ((double)pts1[2 * ii] - k.cx) / k.fx, y1 = ((double)pts1[2 * ii + 1] - k.cy) / k.fy;
+    const double x2 = ((double)pts2[2 * ii] - k.cx) / k.fx, y2 = ((double)pts2[2 * ii + 1] - k.cy) / k.fy;
+    const int h0 = (int)blockIdx.y * POSE_TILE, h1 = h0 + POSE_TILE < n ? h0 + POSE_TILE : n;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    for (int h = h0; h < h1; ++h) {
+        const bool in = live && in_front(R + 9 * (size_t)h, t + 3 * (size_t)h, x1, y1, x2, y2, max_depth);   // wave-uniform pose
+        const int c = __popcll(__ballot(in));
+        if (c != 0 && lane0) atomicAdd(&counts[h], c);
+    }
+}
+
+// mask[i] for one pose
+__global__ __launch_bounds__(256) void twoview_front_kernel(const Pose P, const float *__restrict__ pts1, const float *__restrict__ pts2,
+                                                            int m, const Intr k, double max_depth, unsigned char *__restrict__ mask)
+{
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= m) return;
+    const size_t ii = (size_t)i;
+    const double x1 = ((double)pts1[2 * ii] - k.cx) / k.fx, y1 = ((double)pts1[2 * ii + 1] - k.cy) / k.fy;
+    const double x2 = ((double)pts2[2 * ii] - k.cx) / k.fx, y2 = ((double)pts2[2 * ii + 1] - k.cy) / k.fy;
+    mask[i] = in_front(P.R, P.t, x1, y1, x2, y2, max_depth) ? 1 : 0;
+}
+
+__device__ __forceinline__ void cam_point(const double R[9], const double t[3], const double X[3], double pc[3])
+{
+#pragma unroll
+    for (int r = 0; r < 3; ++r) pc[r] = ((R[3 * r] * X[0] + R[3 * r + 1] * X[1]) + R[3 * r + 2] * X[2]) + t[r];
+}
+
+__device__ __forceinline__ double reproj_error(const double K[9], const double pc[3], double x, double y)
+{
+    double h[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) h[r] = (K[3 * r] * pc[0] + K[3 * r + 1] * pc[1]) + K[3 * r + 2] * pc[2];
+    const double du = h[0] / h[2] - x, dv = h[1] / h[2] - y;
+    return sqrt(du * du + dv * dv);
+}
+
+// one candidate per lane: amvs_match.h steps 1 to 4 and the quantities of steps 5 to 7, the header's seven comparisons
+__global__ __launch_bounds__(256) void twoview_triangulate_kernel(const TriArgs a, const float *__restrict__ pts1,
+                                                                  const float *__restrict__ pts2, int m, double *__restrict__ X_out,
+                                                                  unsigned char *__restrict__ valid, double *__restrict__ cos_out)
+{
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= m) return;
+    const size_t ii = (size_t)i;
+    const double x1 = (double)pts1[2 * ii], y1 = (double)pts1[2 * ii + 1];
+    const double x2 = (double)pts2[2 * ii], y2 = (double)pts2[2 * ii + 1];
+    double v[4];
+    dlt4_null_vector(a.P1, a.P2, x1, y1, x2, y2, v);
+    const double X[3] = {v[0] / v[3], v[1] / v[3], v[2] / v[3]};
+    double pc1[3], pc2[3];
+    cam_point(a.R1, a.t1, X, pc1);
+    cam_point(a.R2, a.t2, X, pc2);
+    const double w1[3] = {X[0] - a.C1[0], X[1] - a.C1[1], X[2] - a.C1[2]};
+    const double w2[3] = {X[0] - a.C2[0], X[1] - a.C2[1], X[2] - a.C2[2]};
+    const double dot = (w1[0] * w2[0] + w1[1] * w2[1]) + w1[2] * w2[2];
+    const double n1 = sqrt((w1[0] * w1[0] + w1[1] * w1[1]) + w1[2] * w1[2]);
+    const double n2 = sqrt((w2[0] * w2[0] + w2[1] * w2[1]) + w2[2] * w2[2]);
+    const double cs = dot / (n1 * n2 + 1e-8);
+    const double e1 = reproj_error(a.K, pc1, x1, y1), e2 = reproj_error(a.K, pc2, x2, y2);
+    const bool ok = pc1[2] > a.thr.depth_min && pc2[2] > a.thr.depth_min && pc1[2] <= a.thr.depth_max && pc2[2] <= a.thr.depth_max &&
+                    cs <= a.thr.cos_max_parallax && e1 <= a.thr.max_reproj && e2 <= a.thr.max_reproj;
+    X_out[3 * ii] = X[0];
+    X_out[3 * ii + 1] = X[1];
+    X_out[3 * ii + 2] = X[2];
+    valid[ii] = ok ? 1 : 0;
+    cos_out[ii] = cs;
+}
+
+inline dim3 blocks_for(long long n, int per) { return dim3((unsigned)((n + per - 1) / per)); }
+
+// the two point arrays of a call, on the device
+struct Points {
+    ScratchCache::Lease buf;
+    const float *p1 = nullptr, *p2 = nullptr;
+    hipError_t upload(const float *h1, const float *h2, int m, ScratchCache &cache, hipStream_t st)
+    {
+        const size_t n = 2 * (size_t)m;
+        hipError_t e = cache.lease(buf, sizeof(float) * 2 * n);
+        if (e != hipSuccess) return e;
+        float *d = buf.get<float>();
+        p1 = d;
+        p2 = d + n;
+        e = hipMemcpyAsync(d, h1, sizeof(float) * n, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
+        return hipMemcpyAsync(d + n, h2, sizeof(float) * n, hipMemcpyHostToDevice, st);
+    }
+};
+
+// counts_h[j] of the n poses (R_h, t_h) over the uploaded matches
+hipError_t score_dev(const double *R_h, const double *t_h, int n, const Points &P, int m, const Intr &k, double max_depth, int *counts_h,
+                     ScratchCache &cache, hipStream_t st)
+{
+    ScratchCache::Lease R, t, counts;
+    VCHK(cache.lease(R, sizeof(double) * 9 * (size_t)n));
+    VCHK(cache.lease(t, sizeof(double) * 3 * (size_t)n));
+    VCHK(cache.lease(counts, sizeof(int) * (size_t)n));
+    VCHK(hipMemcpyAsync(R.get(), R_h, sizeof(double) * 9 * (size_t)n, hipMemcpyHostToDevice, st));
+    VCHK(hipMemcpyAsync(t.get(), t_h, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+    VCHK(hipMemsetAsync(counts.get(), 0, sizeof(int) * (size_t)n, st));
+    hipLaunchKernelGGL(twoview_score_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)((n + POSE_TILE - 1) / POSE_TILE)), dim3(256), 0, st,
+                       (const double *)R.get(), (const double *)t.get(), n, P.p1, P.p2, m, k, max_depth, counts.get<int>());
+    VCHK(hipGetLastError());
+    VCHK(hipMemcpyAsync(counts_h, counts.get(), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    return hipStreamSynchronize(st);
+}
+
+// mask_h[i] of one pose over the uploaded matches, and their number
+hipError_t front_dev(const double R[9], const double t[3], const Points &P, int m, const Intr &k, double max_depth, unsigned char *mask_h,
+                     long long *count, ScratchCache &cache, hipStream_t st)
+{
+    ScratchCache::Lease mask;
+    VCHK(cache.lease(mask, (size_t)m));
+    Pose pose;
+    std::memcpy(pose.R, R, sizeof(pose.R));
+    std::memcpy(pose.t, t, sizeof(pose.t));
+    hipLaunchKernelGGL(twoview_front_kernel, blocks_for(m, 256), dim3(256), 0, st, pose, P.p1, P.p2, m, k, max_depth,
+                       mask.get<unsigned char>());
+    VCHK(hipGetLastError());
+    VCHK(hipMemcpyAsync(mask_h, mask.get(), (size_t)m, hipMemcpyDeviceToHost, st));
+    VCHK(hipStreamSynchronize(st));
+    long long c = 0;
+    for (int i = 0; i < m; ++i) c += mask_h[i] != 0;
+    *count = c;
+    return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t twoview_score(const double *R_h, const double *t_h, int n, const float *pts1_h, const float *pts2_h, int m, const double *K,
+                         double max_depth, int *counts_h, ScratchCache &cache, hipStream_t st)
+{
+    Points P;
+    VCHK(P.upload(pts1_h, pts2_h, m, cache, st));
+    return score_dev(R_h, t_h, n, P, m, intrinsics_of(K), max_depth, counts_h, cache, st);
+}
+
+hipError_t twoview_front(const double R[9], const double t[3], const float *pts1_h, const float *pts2_h, int m, const double *K,
+                         double max_depth, unsigned char *mask_h, long long *count, ScratchCache &cache, hipStream_t st)
+{
+    Points P;
+    VCHK(P.upload(pts1_h, pts2_h, m, cache, st));
+    return front_dev(R, t, P, m, intrinsics_of(K), max_depth, mask_h, count, cache, st);
+}
+
+hipError_t twoview_pose(const double F[9], const double *K, const float *pts1_h, const float *pts2_h, int m, double max_depth,
+                        double R_out[9], double t_out[3], unsigned char *mask_h, long long *n_front, int info[5], bool *model,
+                        ScratchCache &cache, hipStream_t st)
+{
+    for (int e = 0; e < 9; ++e) R_out[e] = 0.0;
+    for (int e = 0; e < 3; ++e) t_out[e] = 0.0;
+    for (int e = 0; e < 5; ++e) info[e] = 0;
+    std::memset(mask_h, 0, (size_t)m);
+    *n_front = 0;
+    *model = false;
+    double R2[18], t[3], w[3], Rc[36], tc[12];
+    if (!twoview_decompose(F, K, R2, t, w)) return hipSuccess;
+    for (int j = 0; j < 4; ++j) twoview_candidate(R2, t, j, Rc + 9 * j, tc + 3 * j);
+    Points P;
+    VCHK(P.upload(pts1_h, pts2_h, m, cache, st));
+    const Intr k = intrinsics_of(K);
+    int counts[4] = {0, 0, 0, 0};
+    VCHK(score_dev(Rc, tc, 4, P, m, k, max_depth, counts, cache, st));
+    int best = 0;
+    for (int j = 1; j < 4; ++j)
+        if (counts[j] > counts[best]) best = j;
+    if (counts[best] == 0) return hipSuccess;
+    VCHK(front_dev(Rc + 9 * best, tc + 3 * best, P, m, k, max_depth, mask_h, n_front, cache, st));
+    std::memcpy(R_out, Rc + 9 * best, sizeof(double) * 9);
+    std::memcpy(t_out, tc + 3 * best, sizeof(double) * 3);
+    info[0] = best;
+    for (int j = 0; j < 4; ++j) info[1 + j] = counts[j];
+    *model = true;
+    return hipSuccess;
+}
+
+hipError_t twoview_triangulate(const double *K, const double R1[9], const double t1[3], const double R2[9], const double t2[3],
+                               const float *pts1_h, const float *pts2_h, int m, const TwoviewThresholds &thr, double *X_h,
+                               unsigned char *valid_h, double *cos_h, long long *n_valid, ScratchCache &cache, hipStream_t st)
+{
+    *n_valid = 0;
+    if (m <= 0) return hipSuccess;
+    TriArgs a;
+    twoview_projection(K, R1, t1, a.P1, a.C1);
+    twoview_projection(K, R2, t2, a.P2, a.C2);
+    std::memcpy(a.R1, R1, sizeof(a.R1));
+    std::memcpy(a.R2, R2, sizeof(a.R2));
+    std::memcpy(a.t1, t1, sizeof(a.t1));
+    std::memcpy(a.t2, t2, sizeof(a.t2));
+    std::memcpy(a.K, K, sizeof(a.K));
+    a.thr = thr;
+    Points P;
+    ScratchCache::Lease X, cs, valid;
+    VCHK(P.upload(pts1_h, pts2_h, m, cache, st));
+    VCHK(cache.lease(X, sizeof(double) * 3 * (size_t)m));
+    VCHK(cache.lease(cs, sizeof(double) * (size_t)m));
+    VCHK(cache.lease(valid, (size_t)m));
+    hipLaunchKernelGGL(twoview_triangulate_kernel, blocks_for(m, 256), dim3(256), 0, st, a, P.p1, P.p2, m, X.get<double>(),
+                       valid.get<unsigned char>(), cs.get<double>());
+    VCHK(hipGetLastError());
+    VCHK(hipMemcpyAsync(X_h, X.get(), sizeof(double) * 3 * (size_t)m, hipMemcpyDeviceToHost, st));
+    VCHK(hipMemcpyAsync(cos_h, cs.get(), sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
+    VCHK(hipMemcpyAsync(valid_h, valid.get(), (size_t)m, hipMemcpyDeviceToHost, st));
+    VCHK(hipStreamSynchronize(st));
+    long long c = 0;
+    for (int i = 0; i < m; ++i) c += valid_h[i] != 0;
+    *n_valid = c;
+    return hipSuccess;
+}
+
+}  // namespace amvs
+
+AMVS_CHECK_TU(twoview)

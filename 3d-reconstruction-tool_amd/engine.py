@@ -771,6 +771,80 @@ class Engine:
         found = k.value >= 6
         return (R if found else None), (t if found else None), mask[:m].astype(bool), out
 
+    # -- the first two views (include/amvs_twoview.h): the relative pose from F, triangulation with everything returned --
+    @staticmethod
+    def _intrinsics(K):
+        return np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+
+    def twoview_decompose(self, F, K):
+        """(R (2, 3, 3), t (3,), w (3,)) float64, or None when F has no model: the two rotations Ra, Rb and the unit
+        translation of the four pose candidates (Ra, t) (Rb, t) (Ra, -t) (Rb, -t) of E = K^T F K, and the squared singular
+        values of E in descending order (amvs_twoview_decompose; host arithmetic)."""
+        F9 = np.ascontiguousarray(F, dtype=np.float64).reshape(9)
+        R, t, w = np.empty((2, 3, 3), np.float64), np.empty(3, np.float64), np.empty(3, np.float64)
+        ok = C.c_int32(0)
+        self._chk(self._lib.amvs_twoview_decompose(self._h, _f64(F9), _f64(self._intrinsics(K)), _f64(R), _f64(t), _f64(w),
+                                                   C.byref(ok)))
+        return (R, t, w) if ok.value else None
+
+    def twoview_score(self, R, t, pts1, pts2, K, max_depth=_lib.TWOVIEW_MAX_DEPTH):
+        """Counts (n,) int32 of the matches that n poses R (n, 3, 3), t (n, 3) put in front of both cameras and nearer than
+        max_depth (amvs_twoview_score)."""
+        p1, p2, m = self._match_points(pts1, pts2)
+        Rs, ts = self._poses(R, t)
+        counts = np.empty(max(len(Rs), 1), np.int32)
+        self._chk(self._lib.amvs_twoview_score(self._h, _f64(Rs), _f64(ts), len(Rs), _p(p1), _p(p2), m, _f64(self._intrinsics(K)),
+                                               float(max_depth), counts.ctypes.data_as(i32p)))
+        return counts[:len(Rs)]
+
+    def twoview_front(self, R, t, pts1, pts2, K, max_depth=_lib.TWOVIEW_MAX_DEPTH):
+        """The mask (m,) bool of the matches in front of both cameras under one pose (amvs_twoview_front)."""
+        p1, p2, m = self._match_points(pts1, pts2)
+        R9 = np.ascontiguousarray(R, dtype=np.float64).reshape(9)
+        t3 = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        mask = np.zeros(max(m, 1), np.uint8)
+        k = C.c_int64(0)
+        self._chk(self._lib.amvs_twoview_front(self._h, _f64(R9), _f64(t3), _p(p1), _p(p2), m, _f64(self._intrinsics(K)),
+                                               float(max_depth), _u8(mask), C.byref(k)))
+        return mask[:m].astype(bool)
+
+    def twoview_pose(self, F, K, pts1, pts2, max_depth=_lib.TWOVIEW_MAX_DEPTH):
+        """(R (3, 3) or None, t (3,) or None, mask (m,) bool, info): the relative pose of the second view from F by the
+        cheirality vote over the four candidates, and the matches in front under it (amvs_twoview_pose; what
+        cv.recoverPose does).  info = {"best", "counts" (4,), "n_front"}; R and t are None when F has no model or no
+        candidate puts a match in front."""
+        p1, p2, m = self._match_points(pts1, pts2)
+        F9 = np.ascontiguousarray(F, dtype=np.float64).reshape(9)
+        R, t = np.zeros((3, 3), np.float64), np.zeros(3, np.float64)
+        mask = np.zeros(max(m, 1), np.uint8)
+        k = C.c_int64(0)
+        info = np.zeros(5, np.int32)
+        self._chk(self._lib.amvs_twoview_pose(self._h, _f64(F9), _f64(self._intrinsics(K)), _p(p1), _p(p2), m, float(max_depth),
+                                              _f64(R), _f64(t), _u8(mask), C.byref(k), info.ctypes.data_as(i32p)))
+        out = {"best": int(info[0]), "counts": info[1:].copy(), "n_front": int(k.value)}
+        found = k.value > 0
+        return (R if found else None), (t if found else None), mask[:m].astype(bool), out
+
+    def twoview_triangulate(self, K, R1, t1, R2, t2, pts1, pts2, depth_min=_lib.TWOVIEW_DEPTH_MIN, depth_max=None,
+                            cos_max_parallax=None, max_reproj=_lib.TWOVIEW_MAX_REPROJ):
+        """(X (m, 3) float64, valid (m,) bool, cos (m,) float64): every candidate's point, whether it passes the depth,
+        parallax and reprojection tests, and the cosine of its parallax angle (amvs_twoview_triangulate).  depth_max
+        defaults to 200 baselines and cos_max_parallax to cos(1 degree), the reference's."""
+        a = [np.ascontiguousarray(x, dtype=np.float64).reshape(n) for x, n in ((K, 9), (R1, 9), (t1, 3), (R2, 9), (t2, 3))]
+        p1, p2, m = self._match_points(pts1, pts2)
+        if depth_max is None:
+            c1, c2 = -(a[1].reshape(3, 3).T @ a[2]), -(a[3].reshape(3, 3).T @ a[4])
+            depth_max = float(np.linalg.norm(c2 - c1)) * _lib.TWOVIEW_DEPTH_BASELINES
+        if cos_max_parallax is None:
+            cos_max_parallax = float(np.cos(np.deg2rad(_lib.TWOVIEW_MIN_PARALLAX_DEG)))
+        X, valid, cs = np.empty((m, 3), np.float64), np.zeros(m, np.uint8), np.empty(m, np.float64)
+        k = C.c_int64(0)
+        self._chk(self._lib.amvs_twoview_triangulate(self._h, *[_f64(x) for x in a], _p(p1) if m else None, _p(p2) if m else None, m,
+                                                     float(depth_min), float(depth_max), float(cos_max_parallax), float(max_reproj),
+                                                     _f64(X) if m else None, _u8(valid) if m else None, _f64(cs) if m else None,
+                                                     C.byref(k)))
+        return X, valid.astype(bool), cs
+
     # -- cross-view depth-map filter (include/amvs_depth.h amvs_depth_filter) --
     def depth_filter(self, K, poses, min_confidence, max_px=1.0, max_rel=0.01, min_consistent=2, refine=True, neighbours=None,
                      depth=None, conf=None, device_ptrs=None, out_ptrs=None, in_place=False):
