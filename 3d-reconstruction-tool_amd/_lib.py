@@ -1,5 +1,5 @@
 """ctypes binding of libamvs.so (the C ABI declared in include/amvs.h, include/amvs_depth.h, include/amvs_lens.h,
-include/amvs_match.h, include/amvs_epipolar.h, include/amvs_resection.h, include/amvs_twoview.h and include/amvs_step.h).
+include/amvs_match.h, include/amvs_epipolar.h, include/amvs_resection.h, include/amvs_twoview.h, include/amvs_bundle.h and include/amvs_step.h).
 
 There is no CPU fallback: if the shared library is missing or no HIP device is
 present, loading / context creation raises.
@@ -244,6 +244,19 @@ TWOVIEW_SIGNATURES = {
 TWOVIEW_MAX_MATCHES, TWOVIEW_MAX_POSES, TWOVIEW_POSE_TILE = 1 << 20, 1 << 20, 32
 TWOVIEW_MAX_DEPTH, TWOVIEW_DEPTH_MIN, TWOVIEW_DEPTH_BASELINES, TWOVIEW_MIN_PARALLAX_DEG, TWOVIEW_MAX_REPROJ = 50.0, 0.01, 200.0, 1.0, 4.0
 
+# name -> (restype, argtypes); every symbol include/amvs_bundle.h declares (a table of its own for the same reason)
+_BA_PROBLEM = [C.c_void_p, f64p, f64p, C.c_int, f64p, C.c_int, i32p, i32p, f32p, C.c_int, f64p]      # ctx, R, t, C, X, P, cam, pt, uv, N, K
+BA_SIGNATURES = {
+    "amvs_ba_cost": (C.c_int, _BA_PROBLEM + [f64p, i64p, f64p]),
+    "amvs_ba_normal": (C.c_int, _BA_PROBLEM + [u8p, f64p, f64p, f64p, f64p, i32p]),
+    "amvs_ba_schur": (C.c_int, _BA_PROBLEM + [u8p, C.c_int, C.c_double, f64p, f64p, i32p, u8p]),
+    "amvs_ba_step": (C.c_int, _BA_PROBLEM + [u8p, C.c_int, C.c_double, i32p, f64p, f64p, f64p, f64p, f64p]),
+    "amvs_ba_solve": (C.c_int, _BA_PROBLEM + [u8p, C.c_int, C.c_double, C.c_double, C.c_int, f64p, f64p, f64p, f64p]),
+}
+# include/amvs_bundle.h: list positions per block of a sum, the limits, and the bounds of the damping
+BA_BLOCK, BA_MAX_CAMERAS, BA_MAX_POINTS, BA_MAX_OBS, BA_MAX_PAIRS = 64, 256, 1 << 22, 1 << 24, 1 << 25
+BA_LAMBDA_MIN, BA_LAMBDA_MAX = 1e-12, 1e12
+
 # name -> (restype, argtypes); every symbol include/amvs_step.h declares (a table of its own for the same reason)
 STEP_SIGNATURES = {
     "amvs_set_step_sources": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -288,7 +301,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(LENS_SIGNATURES.items()) \
                 + list(MATCH_SIGNATURES.items()) + list(EPIPOLAR_SIGNATURES.items()) + list(PNP_SIGNATURES.items()) + list(TWOVIEW_SIGNATURES.items()) \
-                + list(STEP_SIGNATURES.items()):
+                + list(BA_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
             fn = getattr(lib, name)      # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args

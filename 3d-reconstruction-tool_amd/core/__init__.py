@@ -2,7 +2,7 @@
 the package for the camera types does not import the engine."""
 __all__ = ["DenseReconstructor", "reconstruct_from_features", "FeatureMatcher", "ImageFeatures", "FeatureMatch",
            "register_view", "refine_pose", "compute_essential_matrix", "decompose_essential", "relative_pose",
-           "triangulate_points", "compute_reprojection_error", "find_best_initial_pair"]
+           "triangulate_points", "compute_reprojection_error", "find_best_initial_pair", "bundle_adjust", "reprojection_errors"]
 
 
 def __getattr__(name):
@@ -22,4 +22,7 @@ def __getattr__(name):
                 "compute_reprojection_error", "find_best_initial_pair"):
         from . import geometry
         return getattr(geometry, name)
+    if name in ("bundle_adjust", "reprojection_errors"):
+        from . import bundle
+        return getattr(bundle, name)
     raise AttributeError(name)

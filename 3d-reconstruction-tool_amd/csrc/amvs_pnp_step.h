@@ -5,6 +5,13 @@
 #pragma once
 #include <cmath>
 
+// (the rotation update also runs inside the bundle adjustment's kernels, amvs_bundle.hip)
+#ifdef __HIPCC__
+#define AMVS_PNP_HD __host__ __device__
+#else
+#define AMVS_PNP_HD
+#endif
+
 namespace amvs {
 
 constexpr int PNP_SUMS = 29;          // the SUMs of a refit pass: H (21), g (6), cost, front
@@ -18,6 +25,21 @@ inline const char *pnp_intrinsics_error(const double *K)
     if (!std::isfinite(K[2]) || !std::isfinite(K[5])) return "cx and cy must be finite";
     if (K[1] != 0.0) return "K must have no skew";
     return nullptr;
+}
+
+// the pose update of a STEP: (Rn, tn) from (R, t) and the solution x = (om, dt)
+AMVS_PNP_HD inline void pnp_pose_update(const double x[6], const double R[9], const double t[3], double Rn[9], double tn[3])
+{
+    const double hx = 0.5 * x[0], hy = 0.5 * x[1], hz = 0.5 * x[2];
+    const double n = std::sqrt(((1.0 + hx * hx) + hy * hy) + hz * hz);
+    const double qw = 1.0 / n, qx = hx / n, qy = hy / n, qz = hz / n;
+    const double Q[9] = {1.0 - 2.0 * (qy * qy + qz * qz), 2.0 * (qx * qy - qz * qw), 2.0 * (qx * qz + qy * qw),
+                         2.0 * (qx * qy + qz * qw), 1.0 - 2.0 * (qx * qx + qz * qz), 2.0 * (qy * qz - qx * qw),
+                         2.0 * (qx * qz - qy * qw), 2.0 * (qy * qz + qx * qw), 1.0 - 2.0 * (qx * qx + qy * qy)};
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) Rn[3 * r + c] = (Q[3 * r] * R[c] + Q[3 * r + 1] * R[3 + c]) + Q[3 * r + 2] * R[6 + c];
+        tn[r] = ((Q[3 * r] * t[0] + Q[3 * r + 1] * t[1]) + Q[3 * r + 2] * t[2]) + x[3 + r];
+    }
 }
 
 // STEP from the sums of a pass: (Rn, tn) from (R, t); false when a pivot is not positive and finite (no step)
@@ -49,16 +71,7 @@ inline bool pnp_gn_step(const double sums[PNP_SUMS], const double R[9], const do
         for (int k = i + 1; k < 6; ++k) s = s - L[k][i] * x[k];
         x[i] = s / L[i][i];
     }
-    const double hx = 0.5 * x[0], hy = 0.5 * x[1], hz = 0.5 * x[2];
-    const double n = std::sqrt(((1.0 + hx * hx) + hy * hy) + hz * hz);
-    const double qw = 1.0 / n, qx = hx / n, qy = hy / n, qz = hz / n;
-    const double Q[9] = {1.0 - 2.0 * (qy * qy + qz * qz), 2.0 * (qx * qy - qz * qw), 2.0 * (qx * qz + qy * qw),
-                         2.0 * (qx * qy + qz * qw), 1.0 - 2.0 * (qx * qx + qz * qz), 2.0 * (qy * qz - qx * qw),
-                         2.0 * (qx * qz - qy * qw), 2.0 * (qy * qz + qx * qw), 1.0 - 2.0 * (qx * qx + qy * qy)};
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) Rn[3 * r + c] = (Q[3 * r] * R[c] + Q[3 * r + 1] * R[3 + c]) + Q[3 * r + 2] * R[6 + c];
-        tn[r] = ((Q[3 * r] * t[0] + Q[3 * r + 1] * t[1]) + Q[3 * r + 2] * t[2]) + x[3 + r];
-    }
+    pnp_pose_update(x, R, t, Rn, tn);
     return true;
 }
 

@@ -845,6 +845,88 @@ class Engine:
                                                      C.byref(k)))
         return X, valid.astype(bool), cs
 
+    # -- bundle adjustment (include/amvs_bundle.h): poses and points refined together through the Schur complement --
+    @staticmethod
+    def _ba_problem(R, t, X, cam, pt, uv, K, fixed=None):
+        """The arrays of a problem and the leading arguments of every amvs_ba_* call after the context."""
+        Rs = np.ascontiguousarray(R, dtype=np.float64).reshape(-1, 9)
+        ts = np.ascontiguousarray(t, dtype=np.float64).reshape(-1, 3)
+        Xs = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3)
+        cams, pts = np.ascontiguousarray(cam, dtype=np.int32).reshape(-1), np.ascontiguousarray(pt, dtype=np.int32).reshape(-1)
+        uvs = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+        if len(Rs) != len(ts):
+            raise ValueError("R and t must hold one pose each per row")
+        if not (len(cams) == len(pts) == len(uvs)):
+            raise ValueError("cam, pt and uv must have one row per observation")
+        Kd = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+        fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed).reshape(-1) != 0, dtype=np.uint8)
+        if fx is not None and len(fx) != len(Rs):
+            raise ValueError("fixed must have one entry per camera")
+        keep = (Rs, ts, Xs, cams, pts, uvs, Kd, fx)
+        args = (_f64(Rs), _f64(ts), len(Rs), _f64(Xs), len(Xs), cams.ctypes.data_as(i32p), pts.ctypes.data_as(i32p), _p(uvs), len(cams),
+                _f64(Kd))
+        return keep, args, (None if fx is None else _u8(fx))
+
+    def ba_cost(self, R, t, X, cam, pt, uv, K):
+        """(cost, active, err2 (N,)): the sum of squared reprojection errors in pixels over the observations in front of
+        their cameras, their number, and the squared error of each observation, -1.0 behind the camera (amvs_ba_cost)."""
+        keep, args, _ = self._ba_problem(R, t, X, cam, pt, uv, K)
+        cost, act, err2 = C.c_double(0.0), C.c_int64(0), np.empty(max(len(keep[3]), 1), np.float64)
+        self._chk(self._lib.amvs_ba_cost(self._h, *args, C.byref(cost), C.byref(act), _f64(err2)))
+        return float(cost.value), int(act.value), err2[:len(keep[3])]
+
+    def ba_normal(self, R, t, X, cam, pt, uv, K, fixed=None):
+        """(U (C, 21), gc (C, 6), V (P, 6), gp (P, 3), counts (P,) int32): the blocks of the normal equations, upper
+        triangles row by row (amvs_ba_normal)."""
+        keep, args, fx = self._ba_problem(R, t, X, cam, pt, uv, K, fixed)
+        nc, npt = len(keep[0]), len(keep[2])
+        U, gc = np.empty((max(nc, 1), 21), np.float64), np.empty((max(nc, 1), 6), np.float64)
+        V, gp, cnt = np.empty((max(npt, 1), 6), np.float64), np.empty((max(npt, 1), 3), np.float64), np.empty(max(npt, 1), np.int32)
+        self._chk(self._lib.amvs_ba_normal(self._h, *args, fx, _f64(U), _f64(gc), _f64(V), _f64(gp), cnt.ctypes.data_as(i32p)))
+        return U[:nc], gc[:nc], V[:npt], gp[:npt], cnt[:npt]
+
+    @staticmethod
+    def _ba_free(n_cameras, fixed):
+        return n_cameras - 1 if fixed is None else int(np.count_nonzero(np.asarray(fixed).reshape(-1) == 0))
+
+    def ba_schur(self, R, t, X, cam, pt, uv, K, lam, fixed=None, refine_points=True):
+        """(S (n, n), rhs (n,), slot (C,) int32, held (P,) bool): the reduced camera system under the damping lam, n = 6 x
+        the number of free cameras; slot is -1 for a fixed camera (amvs_ba_schur)."""
+        keep, args, fx = self._ba_problem(R, t, X, cam, pt, uv, K, fixed)
+        nc, npt = len(keep[0]), len(keep[2])
+        n = 6 * max(self._ba_free(nc, fixed), 0)
+        S, rhs = np.empty((max(n, 1), max(n, 1)), np.float64), np.empty(max(n, 1), np.float64)
+        slot, held = np.empty(max(nc, 1), np.int32), np.empty(max(npt, 1), np.uint8)
+        self._chk(self._lib.amvs_ba_schur(self._h, *args, fx, int(bool(refine_points)), float(lam), _f64(S), _f64(rhs),
+                                          slot.ctypes.data_as(i32p), _u8(held)))
+        return S[:n, :n], rhs[:n], slot[:nc], held[:npt].astype(bool)
+
+    def ba_step(self, R, t, X, cam, pt, uv, K, lam, fixed=None, refine_points=True):
+        """(ok, dc (C, 6), dp (P, 3), R (C, 3, 3), t (C, 3), X (P, 3)): one Levenberg-Marquardt step under the damping lam
+        and the candidate state; ok is False and everything zero when the reduced system has no Cholesky factor
+        (amvs_ba_step)."""
+        keep, args, fx = self._ba_problem(R, t, X, cam, pt, uv, K, fixed)
+        nc, npt = max(len(keep[0]), 1), max(len(keep[2]), 1)
+        ok = C.c_int32(0)
+        dc, dp = np.empty((nc, 6), np.float64), np.empty((npt, 3), np.float64)
+        Ro, to, Xo = np.empty((nc, 3, 3), np.float64), np.empty((nc, 3), np.float64), np.empty((npt, 3), np.float64)
+        self._chk(self._lib.amvs_ba_step(self._h, *args, fx, int(bool(refine_points)), float(lam), C.byref(ok), _f64(dc), _f64(dp),
+                                         _f64(Ro), _f64(to), _f64(Xo)))
+        return bool(ok.value), dc, dp, Ro, to, Xo
+
+    def ba_solve(self, R, t, X, cam, pt, uv, K, fixed=None, refine_points=True, lambda0=1e-3, ftol=1e-10, max_trials=50):
+        """(R (C, 3, 3), t (C, 3), X (P, 3), info): the state after the Levenberg-Marquardt iteration (amvs_ba_solve).
+        info = {"trials", "kept", "lambda", "first_cost", "cost", "active"}; the costs are sums of squared pixel errors."""
+        keep, args, fx = self._ba_problem(R, t, X, cam, pt, uv, K, fixed)
+        nc, npt = max(len(keep[0]), 1), max(len(keep[2]), 1)
+        Ro, to, Xo = np.empty((nc, 3, 3), np.float64), np.empty((nc, 3), np.float64), np.empty((npt, 3), np.float64)
+        info = np.zeros(6, np.float64)
+        self._chk(self._lib.amvs_ba_solve(self._h, *args, fx, int(bool(refine_points)), float(lambda0), float(ftol), int(max_trials),
+                                          _f64(Ro), _f64(to), _f64(Xo), _f64(info)))
+        out = {"trials": int(info[0]), "kept": int(info[1]), "lambda": float(info[2]), "first_cost": float(info[3]),
+               "cost": float(info[4]), "active": int(info[5])}
+        return Ro, to, Xo, out
+
     # -- cross-view depth-map filter (include/amvs_depth.h amvs_depth_filter) --
     def depth_filter(self, K, poses, min_confidence, max_px=1.0, max_rel=0.01, min_consistent=2, refine=True, neighbours=None,
                      depth=None, conf=None, device_ptrs=None, out_ptrs=None, in_place=False):
