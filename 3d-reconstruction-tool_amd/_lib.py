@@ -257,6 +257,24 @@ BA_SIGNATURES = {
 BA_BLOCK, BA_MAX_CAMERAS, BA_MAX_POINTS, BA_MAX_OBS, BA_MAX_PAIRS = 64, 256, 1 << 22, 1 << 24, 1 << 25
 BA_LAMBDA_MIN, BA_LAMBDA_MAX = 1e-12, 1e12
 
+# name -> (restype, argtypes); every symbol include/amvs_sfm.h declares (a table of its own for the same reason)
+SFM_SIGNATURES = {
+    "amvs_sfm_begin": (C.c_int, [C.c_void_p, C.c_int, i32p, f32p, C.c_int, i32p, i32p, i32p]),
+    "amvs_sfm_register": (C.c_int, [C.c_void_p, C.c_int, f64p, f64p, i32p, i32p, u8p, C.c_int, i64p]),
+    "amvs_sfm_scores": (C.c_int, [C.c_void_p, i32p]),
+    "amvs_sfm_correspondences": (C.c_int, [C.c_void_p, C.c_int, i32p, i32p, f32p, f32p, i64p]),
+    "amvs_sfm_triangulate": (C.c_int, [C.c_void_p, C.c_int, f64p, C.c_double, C.c_double, C.c_double, C.c_double, i64p, i32p]),
+    "amvs_sfm_counts": (C.c_int, [C.c_void_p, i64p, i64p, i64p]),
+    "amvs_sfm_observations": (C.c_int, [C.c_void_p, i32p, i32p, f32p, C.c_int64, i64p]),
+    "amvs_sfm_points_get": (C.c_int, [C.c_void_p, f64p, u8p, C.c_int64]),
+    "amvs_sfm_points_set": (C.c_int, [C.c_void_p, f64p, u8p, C.c_int64]),
+    "amvs_sfm_pose_set": (C.c_int, [C.c_void_p, C.c_int, f64p, f64p]),
+    "amvs_sfm_drop": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int, C.c_int, i64p, i64p]),
+}
+# include/amvs_sfm.h: lanes (rows, keypoints or points) per workgroup, the limits, and the defaults of the Python layer
+SFM_BLOCK, SFM_MAX_VIEWS, SFM_MAX_KEYPOINTS, SFM_MAX_ROWS, SFM_MAX_POINTS = 256, 4096, 1 << 28, 1 << 28, BA_MAX_POINTS
+SFM_MIN_SCORE, SFM_MIN_OBS = 12, 2
+
 # name -> (restype, argtypes); every symbol include/amvs_step.h declares (a table of its own for the same reason)
 STEP_SIGNATURES = {
     "amvs_set_step_sources": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -301,7 +319,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(LENS_SIGNATURES.items()) \
                 + list(MATCH_SIGNATURES.items()) + list(EPIPOLAR_SIGNATURES.items()) + list(PNP_SIGNATURES.items()) + list(TWOVIEW_SIGNATURES.items()) \
-                + list(BA_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
+                + list(BA_SIGNATURES.items()) + list(SFM_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
             fn = getattr(lib, name)      # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args

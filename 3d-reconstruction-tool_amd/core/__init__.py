@@ -1,6 +1,6 @@
 """The reconstruction classes.  DenseReconstructor and the method it is built on are resolved lazily, so importing
 the package for the camera types does not import the engine."""
-__all__ = ["DenseReconstructor", "reconstruct_from_features", "FeatureMatcher", "ImageFeatures", "FeatureMatch",
+__all__ = ["DenseReconstructor", "SfMPipeline", "reconstruct_from_features", "FeatureMatcher", "ImageFeatures", "FeatureMatch",
            "register_view", "refine_pose", "compute_essential_matrix", "decompose_essential", "relative_pose",
            "triangulate_points", "compute_reprojection_error", "find_best_initial_pair", "bundle_adjust", "reprojection_errors"]
 
@@ -9,6 +9,9 @@ def __getattr__(name):
     if name == "DenseReconstructor":
         from .dense import DenseReconstructor
         return DenseReconstructor
+    if name == "SfMPipeline":
+        from .sfm_pipeline import SfMPipeline
+        return SfMPipeline
     if name == "reconstruct_from_features":
         from .dense import DenseReconstructor
         return DenseReconstructor.reconstruct_from_features

@@ -8,8 +8,9 @@
 //     registers, the predicate goes through a ballot and a population count, and lane 0 of a wave adds the count to the
 //     pose's counter (no add for a zero).  Integers only: any grid shape gives the same counts.
 // twoview_front_kernel: the same predicate for one pose, one byte a match.
-// twoview_triangulate_kernel: one candidate per lane in pixels; X, the validity byte and the cosine of the parallax
-//     angle of every candidate go back to the host.
+// twoview_triangulate_kernel: one candidate per lane in pixels (tri_candidate of amvs_twoview_tri.h, the text the track state
+//     of amvs_sfm.hip runs too); X, the validity byte and the cosine of the parallax angle of every candidate go back to
+//     the host.
 // No data-dependent index is formed: every index is the lane's own match or the wave's pose.
 //
 // -ffp-contract=off (Makefile): a * b + c below is two roundings, on the device and on the host.
@@ -18,6 +19,7 @@
 #include "amvs_dlt4.h"
 #include "amvs_twoview_dev.h"
 #include "amvs_twoview_host.h"
+#include "amvs_twoview_tri.h"
 #include "../../include/amvs_twoview.h"
 
 #include <cmath>
@@ -39,11 +41,6 @@ constexpr int POSE_TILE = AMVS_TWOVIEW_POSE_TILE;
 
 struct Intr { double fx, fy, cx, cy; };
 struct Pose { double R[9], t[3]; };
-struct TriArgs {
-    double P1[12], P2[12], C1[3], C2[3], R1[9], t1[3], R2[9], t2[3], K[9];
-    TwoviewThresholds thr;
-};
-
 inline Intr intrinsics_of(const double *K) { return Intr{K[0], K[4], K[2], K[5]}; }
 
 // the header's cheirality test of the match with normalised coordinates (x1, y1), (x2, y2) under (R, t)
@@ -89,22 +86,7 @@ __global__ __launch_bounds__(256) void twoview_front_kernel(const Pose P, const 
     mask[i] = in_front(P.R, P.t, x1, y1, x2, y2, max_depth) ? 1 : 0;
 }
 
-__device__ __forceinline__ void cam_point(const double R[9], const double t[3], const double X[3], double pc[3])
-{
-#pragma unroll
-    for (int r = 0; r < 3; ++r) pc[r] = ((R[3 * r] * X[0] + R[3 * r + 1] * X[1]) + R[3 * r + 2] * X[2]) + t[r];
-}
-
-__device__ __forceinline__ double reproj_error(const double K[9], const double pc[3], double x, double y)
-{
-    double h[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) h[r] = (K[3 * r] * pc[0] + K[3 * r + 1] * pc[1]) + K[3 * r + 2] * pc[2];
-    const double du = h[0] / h[2] - x, dv = h[1] / h[2] - y;
-    return sqrt(du * du + dv * dv);
-}
-
-// one candidate per lane: amvs_match.h steps 1 to 4 and the quantities of steps 5 to 7, the header's seven comparisons
+// one candidate per lane: tri_candidate of amvs_twoview_tri.h
 __global__ __launch_bounds__(256) void twoview_triangulate_kernel(const TriArgs a, const float *__restrict__ pts1,
                                                                   const float *__restrict__ pts2, int m, double *__restrict__ X_out,
                                                                   unsigned char *__restrict__ valid, double *__restrict__ cos_out)
@@ -114,21 +96,8 @@ __global__ __launch_bounds__(256) void twoview_triangulate_kernel(const TriArgs 
     const size_t ii = (size_t)i;
     const double x1 = (double)pts1[2 * ii], y1 = (double)pts1[2 * ii + 1];
     const double x2 = (double)pts2[2 * ii], y2 = (double)pts2[2 * ii + 1];
-    double v[4];
-    dlt4_null_vector(a.P1, a.P2, x1, y1, x2, y2, v);
-    const double X[3] = {v[0] / v[3], v[1] / v[3], v[2] / v[3]};
-    double pc1[3], pc2[3];
-    cam_point(a.R1, a.t1, X, pc1);
-    cam_point(a.R2, a.t2, X, pc2);
-    const double w1[3] = {X[0] - a.C1[0], X[1] - a.C1[1], X[2] - a.C1[2]};
-    const double w2[3] = {X[0] - a.C2[0], X[1] - a.C2[1], X[2] - a.C2[2]};
-    const double dot = (w1[0] * w2[0] + w1[1] * w2[1]) + w1[2] * w2[2];
-    const double n1 = sqrt((w1[0] * w1[0] + w1[1] * w1[1]) + w1[2] * w1[2]);
-    const double n2 = sqrt((w2[0] * w2[0] + w2[1] * w2[1]) + w2[2] * w2[2]);
-    const double cs = dot / (n1 * n2 + 1e-8);
-    const double e1 = reproj_error(a.K, pc1, x1, y1), e2 = reproj_error(a.K, pc2, x2, y2);
-    const bool ok = pc1[2] > a.thr.depth_min && pc2[2] > a.thr.depth_min && pc1[2] <= a.thr.depth_max && pc2[2] <= a.thr.depth_max &&
-                    cs <= a.thr.cos_max_parallax && e1 <= a.thr.max_reproj && e2 <= a.thr.max_reproj;
+    double X[3], cs;
+    const bool ok = tri_candidate(a, x1, y1, x2, y2, X, &cs);
     X_out[3 * ii] = X[0];
     X_out[3 * ii + 1] = X[1];
     X_out[3 * ii + 2] = X[2];
@@ -249,15 +218,7 @@ hipError_t twoview_triangulate(const double *K, const double R1[9], const double
 {
     *n_valid = 0;
     if (m <= 0) return hipSuccess;
-    TriArgs a;
-    twoview_projection(K, R1, t1, a.P1, a.C1);
-    twoview_projection(K, R2, t2, a.P2, a.C2);
-    std::memcpy(a.R1, R1, sizeof(a.R1));
-    std::memcpy(a.R2, R2, sizeof(a.R2));
-    std::memcpy(a.t1, t1, sizeof(a.t1));
-    std::memcpy(a.t2, t2, sizeof(a.t2));
-    std::memcpy(a.K, K, sizeof(a.K));
-    a.thr = thr;
+    const TriArgs a = tri_args(K, R1, t1, R2, t2, thr);
     Points P;
     ScratchCache::Lease X, cs, valid;
     VCHK(P.upload(pts1_h, pts2_h, m, cache, st));

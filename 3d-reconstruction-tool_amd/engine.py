@@ -927,6 +927,118 @@ class Engine:
                "cost": float(info[4]), "active": int(info[5])}
         return Ro, to, Xo, out
 
+    # -- the track state of an incremental reconstruction (include/amvs_sfm.h), resident in the context --
+    _sfm_views, _sfm_n_kp = 0, np.zeros(0, np.int32)       # until sfm_begin
+
+    def sfm_begin(self, keypoints, pairs):
+        """Uploads and resets the track state.  keypoints: one (n_v, 2) array of pixels per view; pairs: a dict or a list of
+        ((i, j), rows) with i < j and rows (m, 2) int32 keypoint indices (k_i, k_j); the pairs are put in (i, j) order."""
+        kps = [np.ascontiguousarray(k, dtype=np.float32).reshape(-1, 2) for k in keypoints]
+        items = sorted(pairs.items() if isinstance(pairs, dict) else pairs, key=lambda it: tuple(it[0]))
+        n_kp = np.array([len(k) for k in kps], np.int32)
+        kp = np.ascontiguousarray(np.concatenate(kps) if kps else np.zeros((0, 2)), dtype=np.float32)
+        rows = [np.ascontiguousarray(r, dtype=np.int32).reshape(-1, 2) for _, r in items]
+        views = np.ascontiguousarray([tuple(p) for p, _ in items], dtype=np.int32).reshape(-1, 2)
+        start = np.zeros(len(items) + 1, np.int32)
+        start[1:] = np.cumsum([len(r) for r in rows])
+        flat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 2)), dtype=np.int32)
+        self._chk(self._lib.amvs_sfm_begin(self._h, len(kps), n_kp.ctypes.data_as(i32p), _p(kp), len(items), views.ctypes.data_as(i32p),
+                                           start.ctypes.data_as(i32p), flat.ctypes.data_as(i32p)))
+        self._sfm_views, self._sfm_n_kp = len(kps), n_kp
+
+    def sfm_register(self, view, R, t, kp=(), pid=(), mask=None):
+        """Marks `view` registered with the pose (R, t) and lets its keypoints kp[i] observe the points pid[i] where mask[i]
+        (None: everywhere); returns the number of owners set (dead points are skipped)."""
+        Rd, td = np.ascontiguousarray(R, dtype=np.float64).reshape(9), np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        (k, kptr), (p, pptr) = _ids(np.asarray(kp).reshape(-1)), _ids(np.asarray(pid).reshape(-1))
+        if len(k) != len(p):
+            raise ValueError("kp and pid must have one entry per row")
+        mk = None if mask is None else np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+        if mk is not None and len(mk) != len(k):
+            raise ValueError("mask must have one entry per row")
+        n = C.c_int64(0)
+        self._chk(self._lib.amvs_sfm_register(self._h, int(view), _f64(Rd), _f64(td), kptr, pptr, None if mk is None else _u8(mk),
+                                              len(k), C.byref(n)))
+        return int(n.value)
+
+    def sfm_scores(self):
+        """(V,) int32: per unregistered view the number of its keypoints matched to an observed point, -1 for a registered
+        view (amvs_sfm_scores)."""
+        out = np.zeros(self._sfm_views, np.int32)
+        self._chk(self._lib.amvs_sfm_scores(self._h, out.ctypes.data_as(i32p)))
+        return out
+
+    def sfm_correspondences(self, view):
+        """(kp (m,) int32, pid (m,) int32, X (m, 3) float32, x (m, 2) float32) of an unregistered view, keypoints ascending
+        (amvs_sfm_correspondences)."""
+        n = max(int(self._sfm_n_kp[int(view)]), 1) if 0 <= int(view) < self._sfm_views else 1
+        kp, pid = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        X, x = np.zeros((n, 3), np.float32), np.zeros((n, 2), np.float32)
+        m = C.c_int64(0)
+        self._chk(self._lib.amvs_sfm_correspondences(self._h, int(view), kp.ctypes.data_as(i32p), pid.ctypes.data_as(i32p), _p(X), _p(x),
+                                                     C.byref(m)))
+        m = int(m.value)
+        return kp[:m].copy(), pid[:m].copy(), X[:m].copy(), x[:m].copy()
+
+    def sfm_triangulate(self, view, K, depth_min=_lib.TWOVIEW_DEPTH_MIN, depth_baselines=_lib.TWOVIEW_DEPTH_BASELINES,
+                        cos_max_parallax=None, max_reproj=_lib.TWOVIEW_MAX_REPROJ):
+        """New points from the matches of a registered view with every other registered view; returns (n_new, new_per_view
+        (V,) int32) (amvs_sfm_triangulate).  cos_max_parallax defaults to cos(1 degree), the reference's."""
+        Kd = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+        if cos_max_parallax is None:
+            cos_max_parallax = float(np.cos(np.deg2rad(_lib.TWOVIEW_MIN_PARALLAX_DEG)))
+        per = np.zeros(self._sfm_views, np.int32)
+        n = C.c_int64(0)
+        self._chk(self._lib.amvs_sfm_triangulate(self._h, int(view), _f64(Kd), float(depth_min), float(depth_baselines),
+                                                 float(cos_max_parallax), float(max_reproj), C.byref(n), per.ctypes.data_as(i32p)))
+        return int(n.value), per
+
+    def sfm_counts(self):
+        """(points made, points alive, observations) (amvs_sfm_counts)."""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.amvs_sfm_counts(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def sfm_observations(self):
+        """(cam (n,) int32, pt (n,) int32, uv (n, 2) float32): every observation of a live point, ascending in (pt, cam), the
+        order bundle_adjust takes (amvs_sfm_observations)."""
+        cap = max(self.sfm_counts()[2], 1)
+        cam, pt, uv = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros((cap, 2), np.float32)
+        n = C.c_int64(0)
+        self._chk(self._lib.amvs_sfm_observations(self._h, cam.ctypes.data_as(i32p), pt.ctypes.data_as(i32p), _p(uv), cap, C.byref(n)))
+        n = int(n.value)
+        return cam[:n].copy(), pt[:n].copy(), uv[:n].copy()
+
+    def sfm_points(self):
+        """(X (n_points, 3) float64, alive (n_points,) bool), dead points included (amvs_sfm_points_get)."""
+        n = self.sfm_counts()[0]
+        X, alive = np.zeros((max(n, 1), 3), np.float64), np.zeros(max(n, 1), np.uint8)
+        self._chk(self._lib.amvs_sfm_points_get(self._h, _f64(X), _u8(alive), max(n, 1)))
+        return X[:n].copy(), alive[:n].astype(bool)
+
+    def sfm_set_points(self, X, alive):
+        """Replaces the points and their alive flags; a point may die, and its observations go with it (amvs_sfm_points_set)."""
+        Xd = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3)
+        al = np.ascontiguousarray(np.asarray(alive).reshape(-1) != 0, dtype=np.uint8)
+        if len(al) != len(Xd):
+            raise ValueError("X and alive must have one row per point")
+        self._chk(self._lib.amvs_sfm_points_set(self._h, _f64(Xd), _u8(al), len(Xd)))
+
+    def sfm_set_pose(self, view, R, t):
+        """Replaces the pose of a registered view (amvs_sfm_pose_set)."""
+        Rd, td = np.ascontiguousarray(R, dtype=np.float64).reshape(9), np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        self._chk(self._lib.amvs_sfm_pose_set(self._h, int(view), _f64(Rd), _f64(td)))
+
+    def sfm_drop(self, cam, pt, min_obs=_lib.SFM_MIN_OBS):
+        """Takes the observations (cam[i], pt[i]) away, then lets every live point with fewer than min_obs observations die;
+        returns (observations dropped, points dropped) (amvs_sfm_drop)."""
+        (c, cptr), (p, pptr) = _ids(np.asarray(cam).reshape(-1)), _ids(np.asarray(pt).reshape(-1))
+        if len(c) != len(p):
+            raise ValueError("cam and pt must have one entry per observation")
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.amvs_sfm_drop(self._h, cptr, pptr, len(c), int(min_obs), C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     # -- cross-view depth-map filter (include/amvs_depth.h amvs_depth_filter) --
     def depth_filter(self, K, poses, min_confidence, max_px=1.0, max_rel=0.01, min_consistent=2, refine=True, neighbours=None,
                      depth=None, conf=None, device_ptrs=None, out_ptrs=None, in_place=False):
