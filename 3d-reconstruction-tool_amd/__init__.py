@@ -10,7 +10,7 @@ repository root.
 from .core.camera import Camera, CameraPose, load_calibration  # noqa: F401
 
 __all__ = ["Camera", "CameraPose", "load_calibration", "PatchMatchMVS", "DepthNormalMap",
-           "DenseStereoReconstructor", "DenseReconstructor", "SfMPipeline", "Engine", "AmvsError", "save_ply", "save_mesh_ply"]
+           "DenseStereoReconstructor", "DenseReconstructor", "SfMPipeline", "FeatureExtractor", "Engine", "AmvsError", "save_ply", "save_mesh_ply"]
 
 
 def __getattr__(name):
@@ -28,6 +28,9 @@ def __getattr__(name):
     if name == "SfMPipeline":
         from .core import sfm_pipeline
         return sfm_pipeline.SfMPipeline
+    if name == "FeatureExtractor":
+        from .core import features
+        return features.FeatureExtractor
     if name == "Engine":
         from .engine import Engine
         return Engine

@@ -1,5 +1,5 @@
 """ctypes binding of libamvs.so (the C ABI declared in include/amvs.h, include/amvs_depth.h, include/amvs_lens.h,
-include/amvs_match.h, include/amvs_epipolar.h, include/amvs_resection.h, include/amvs_twoview.h, include/amvs_bundle.h and include/amvs_step.h).
+include/amvs_match.h, include/amvs_epipolar.h, include/amvs_resection.h, include/amvs_twoview.h, include/amvs_bundle.h, include/amvs_sfm.h, include/amvs_features.h and include/amvs_step.h).
 
 There is no CPU fallback: if the shared library is missing or no HIP device is
 present, loading / context creation raises.
@@ -282,6 +282,20 @@ STEP_SIGNATURES = {
     "amvs_step_sources_max_patch": (C.c_int, []),
 }
 
+# name -> (restype, argtypes); every symbol include/amvs_features.h declares (a table of its own for the same reason)
+FEATURE_SIGNATURES = {
+    "amvs_clahe_u8": (C.c_int, [C.c_void_p, u8p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, u8p]),
+    "amvs_sift_scale_space": (C.c_int, [C.c_void_p, u8p, C.c_int, C.c_int, C.c_double, i32p]),
+    "amvs_sift_extract": (C.c_int, [C.c_void_p, u8p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_double, i32p]),
+    "amvs_sift_fetch": (C.c_int, [C.c_void_p, f32p, u8p, C.c_int]),
+    "amvs_sift_to_slot": (C.c_int, [C.c_void_p, C.c_int]),
+    "amvs_sift_fetch_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, i32p, i32p]),
+}
+# include/amvs_features.h: the limits of the image side, the CLAHE grid and sigma, and the shape of an octave
+FEATURES_MAX_SIDE, CLAHE_MAX_GRID, SIFT_MIN_SIDE, SIFT_MAX_SIGMA, SIFT_MAX_RADIUS = 8192, 64, 3, 4.0, 32
+SIFT_LAYERS, SIFT_GAUSS, SIFT_DOG = 3, 6, 5
+SIFT_MIN_SIGMA, SIFT_MAX_FEATURES = 0.1, 1048576
+
 _lib = None
 
 
@@ -319,7 +333,8 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(LENS_SIGNATURES.items()) \
                 + list(MATCH_SIGNATURES.items()) + list(EPIPOLAR_SIGNATURES.items()) + list(PNP_SIGNATURES.items()) + list(TWOVIEW_SIGNATURES.items()) \
-                + list(BA_SIGNATURES.items()) + list(SFM_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
+                + list(BA_SIGNATURES.items()) + list(SFM_SIGNATURES.items()) + list(STEP_SIGNATURES.items()) \
+                + list(FEATURE_SIGNATURES.items()):
             fn = getattr(lib, name)      # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args

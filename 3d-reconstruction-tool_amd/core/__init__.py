@@ -1,6 +1,7 @@
 """The reconstruction classes.  DenseReconstructor and the method it is built on are resolved lazily, so importing
 the package for the camera types does not import the engine."""
 __all__ = ["DenseReconstructor", "SfMPipeline", "reconstruct_from_features", "FeatureMatcher", "ImageFeatures", "FeatureMatch",
+           "FeatureExtractor", "SiftFeatures",
            "register_view", "refine_pose", "compute_essential_matrix", "decompose_essential", "relative_pose",
            "triangulate_points", "compute_reprojection_error", "find_best_initial_pair", "bundle_adjust", "reprojection_errors"]
 
@@ -15,7 +16,7 @@ def __getattr__(name):
     if name == "reconstruct_from_features":
         from .dense import DenseReconstructor
         return DenseReconstructor.reconstruct_from_features
-    if name in ("FeatureMatcher", "ImageFeatures", "FeatureMatch"):
+    if name in ("FeatureMatcher", "ImageFeatures", "FeatureMatch", "FeatureExtractor", "SiftFeatures"):
         from . import features
         return getattr(features, name)
     if name in ("register_view", "refine_pose"):

@@ -65,8 +65,38 @@ class DenseReconstructor:
         self.min_parallax = MIN_PARALLAX_DEG
         self.max_reproj_error = MAX_REPROJ_ERROR
 
-    # -- the reference's entry point: extractor on the CPU (OpenCV), the rest on the GPU ---------------------------------
-    def reconstruct(self, images: List[dict], poses: Dict[int, CameraPose], window: int = 20) -> Tuple[np.ndarray, np.ndarray]:
+    # -- the extractor on the device (include/amvs_features.h) --------------------------------------------------------------
+    def device_extractor(self, engine=None):
+        """A FeatureExtractor with the dense mode's values (the reference's: CLAHE 3.0 on 8 x 8, SIFT with 100000 features,
+        contrast 0.01, edge 20, sigma 1.4), on `engine`, or on a context of its own that its close() ends."""
+        from .features import FeatureExtractor
+        return FeatureExtractor(n_features=100000, contrast_threshold=0.01, edge_threshold=20, sigma=1.4, clahe_clip=3.0,
+                                clahe_grid=(8, 8), device=self.device_id, engine=engine)
+
+    def extract_features(self, images: List[dict], poses: Dict[int, CameraPose], extractor="device") -> Dict[int, dict]:
+        """The feature records reconstruct_from_features takes, of the posed views' "gray" images.  With "device" the
+        extraction has one context, closed before this returns."""
+        if isinstance(extractor, str) and extractor == "device":
+            with Engine(8, 8, 1, np.eye(3, dtype=np.float32), device=self.device_id) as eng:
+                return self.extract_features(images, poses, self.device_extractor(eng))
+        features = {}
+        for idx in sorted(poses.keys()):
+            if idx < len(images):
+                f = extractor.extract(images[idx]["gray"])
+                if len(f) > 0:
+                    features[idx] = {"points": f.points, "descriptors": f.descriptors}
+        return features
+
+    # -- the reference's entry point: extractor on the CPU (OpenCV) by default, the rest on the GPU -----------------------
+    def reconstruct(self, images: List[dict], poses: Dict[int, CameraPose], window: int = 20,
+                    extractor=None) -> Tuple[np.ndarray, np.ndarray]:
+        """extractor=None: the reference's path, the extractor OpenCV's.  extractor="device" or a FeatureExtractor: CLAHE
+        and SIFT on the device (include/amvs_features.h), nothing of OpenCV."""
+        if extractor is not None:
+            self._banner()
+            features = self.extract_features(images, poses, extractor)
+            print(f"  {sum(len(f['points']) for f in features.values()):,} keypoints found")
+            return self._match_and_triangulate(features, images, poses, window, 0.85, False)
         try:
             import cv2 as cv
         except ImportError as e:

@@ -78,8 +78,8 @@ def bridge_pairs(comps: List[List[int]]) -> List[Tuple[int, int]]:
 
 
 class SfMPipeline:
-    """Sparse reconstruction of a set of views with one camera.  fast_mode is accepted for the reference's signature (it
-    selects its feature extractor's settings, which stay the caller's here)."""
+    """Sparse reconstruction of a set of views with one camera.  fast_mode selects, as in the reference, the feature
+    extractor's n_features (4000, else 8000) where this class extracts itself (reconstruct_images)."""
 
     def __init__(self, camera, fast_mode: bool = False, device: int = 0, engine=None):
         self.camera, self.fast_mode, self.device_id = camera, bool(fast_mode), int(device)
@@ -235,9 +235,56 @@ class SfMPipeline:
         self.colors, self.failed = colors, failed
         return self.points, self.colors, self.poses
 
-    def reconstruct(self, image_dir: str, max_images: Optional[int] = None):
+    def _extractor(self, extractor):
+        if extractor is None or (isinstance(extractor, str) and extractor == "device"):
+            from .features import FeatureExtractor
+            return FeatureExtractor(n_features=4000 if self.fast_mode else 8000, device=self.device_id, engine=self._eng())
+        return extractor
+
+    def reconstruct_images(self, images, max_images: Optional[int] = None, extractor=None):
+        """reconstruct_from_features on the features a FeatureExtractor (default: the reference's values, on this
+        pipeline's engine) extracts from `images`, BGR or gray uint8 arrays, already undistorted.  The points' colours are
+        sampled from the same arrays (a gray value gives all three channels)."""
+        images = list(images)[:max_images] if max_images else list(images)
+        if len(images) < 2:
+            raise ValueError("Need at least 2 images")
+        ex = self._extractor(extractor)
+        return self.reconstruct_from_features([ex.extract(im) for im in images], images=images)
+
+    def _load_images(self, image_dir, max_images):
+        """The folder's images as BGR uint8 arrays, through cv2 or PIL, whichever imports."""
+        import os
+        names = sorted(f for f in os.listdir(image_dir) if f.lower().endswith((".jpg", ".jpeg", ".png", ".tif", ".tiff", ".bmp")))
+        names = names[:max_images] if max_images else names
+        try:
+            import cv2 as cv
+            images = [cv.imread(os.path.join(image_dir, f)) for f in names]
+        except ImportError:
+            try:
+                from PIL import Image
+            except ImportError:
+                raise RuntimeError("loading images needs OpenCV (cv2) or PIL, and neither is installed; load them yourself "
+                                   "and call reconstruct_images") from None
+            images = []
+            for f in names:
+                try:
+                    images.append(np.ascontiguousarray(np.asarray(Image.open(os.path.join(image_dir, f)).convert("RGB"))[:, :, ::-1]))
+                except OSError:
+                    images.append(None)
+        return [im for im in images if im is not None]
+
+    def reconstruct(self, image_dir: str, max_images: Optional[int] = None, extractor=None):
         """The reference's reconstruct: the images of a folder, undistorted, SIFT features, then reconstruct_from_features.
-        Loading, undistortion and extraction are OpenCV's; without it use reconstruct_from_features."""
+        With extractor=None loading, undistortion and extraction are OpenCV's.  With extractor="device" or a
+        FeatureExtractor the images are loaded through cv2 or PIL, undistorted and extracted on the device."""
+        if extractor is not None:
+            images = self._load_images(image_dir, max_images)
+            if len(images) < 2:
+                raise ValueError("Need at least 2 images")
+            dist = getattr(self.camera, "dist", None)
+            if dist is not None and np.any(np.asarray(dist) != 0):
+                images = [self._eng().undistort_bgr8(im, np.asarray(self.camera.K, np.float64), dist)[0] for im in images]
+            return self.reconstruct_images(images, extractor=extractor)
         try:
             import cv2 as cv
         except ImportError:

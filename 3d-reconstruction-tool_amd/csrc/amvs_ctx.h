@@ -7,6 +7,7 @@
 #include "amvs_handles.h"
 #include "amvs_match_state.h"
 #include "amvs_sfm_state.h"
+#include "amvs_features_state.h"
 
 #include <array>
 #include <map>
@@ -108,6 +109,8 @@ struct amvs_ctx {
     std::map<int, amvs::DescSlot> desc;   // resident descriptors by slot (include/amvs_match.h amvs_desc_set)
     amvs::PairCloud pair_cloud;          // what amvs_pair_triangulate appends to, until amvs_pair_cloud_finish
     amvs::SfmState sfm;                  // the track state of an incremental reconstruction (include/amvs_sfm.h)
+    amvs::ClaheState clahe;              // the result of the last amvs_clahe_u8 (include/amvs_features.h)
+    amvs::SiftState sift;                // the scale space of the last amvs_sift_scale_space
     amvs::DeviceBuffer<float> d_depth_normals;   // [depth_normal_maps][H*W][3] of the last amvs_depth_normals / amvs_cloud_normals
     int depth_normal_maps = 0;           // (grown only; 0 = none to fetch)
     // volume, scans and mesh of amvs_tsdf_* (amvs_mesh.hip), lazily created

@@ -253,24 +253,32 @@ int desc_knn2_splits(int n_q, int n_t, int *chunks_per_split)
     return (chunks + cps - 1) / cps;
 }
 
-hipError_t desc_set(const unsigned char *desc_h, int n, ScratchCache &cache, DescSlot &slot, hipStream_t st)
+hipError_t desc_set_device(const unsigned char *desc_d, int n, ScratchCache &cache, DescSlot &slot, hipStream_t st)
 {
     slot.n = -1;
     const int n_pad = padded(n);
     if (n_pad > 0) {
-        ScratchCache::Lease src;
         MCHK(slot.frag.reserve((size_t)n_pad * 8, cache));
         MCHK(slot.norm.reserve((size_t)n_pad, cache));
         MCHK(slot.normk.reserve((size_t)n_pad, cache));
-        MCHK(cache.lease(src, (size_t)n * AMVS_DESC_DIM));
-        MCHK(hipMemcpyAsync(src.get(), desc_h, (size_t)n * AMVS_DESC_DIM, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(desc_pack_kernel, grid_for(n_pad), dim3(256), 0, st, (const uint4 *)src.get(), n, n_pad, slot.frag.get(),
+        hipLaunchKernelGGL(desc_pack_kernel, grid_for(n_pad), dim3(256), 0, st, (const uint4 *)desc_d, n, n_pad, slot.frag.get(),
                            slot.norm.get(), slot.normk.get());
         MCHK(hipGetLastError());
-        MCHK(hipStreamSynchronize(st));                 // (the staging lease goes back with nothing in flight)
+        MCHK(hipStreamSynchronize(st));
     }
     slot.n = n;
     return hipSuccess;
+}
+
+hipError_t desc_set(const unsigned char *desc_h, int n, ScratchCache &cache, DescSlot &slot, hipStream_t st)
+{
+    slot.n = -1;
+    ScratchCache::Lease src;
+    if (n > 0) {
+        MCHK(cache.lease(src, (size_t)n * AMVS_DESC_DIM));
+        MCHK(hipMemcpyAsync(src.get(), desc_h, (size_t)n * AMVS_DESC_DIM, hipMemcpyHostToDevice, st));
+    }
+    return desc_set_device(src.get<unsigned char>(), n, cache, slot, st);   // (synchronises: the staging lease goes back idle)
 }
 
 // idx, dist2: [n_q][2] int32 on the device.  Does not synchronise unless it fails.

@@ -26,6 +26,8 @@ struct PairCloud {
 // amvs_match.hip.  desc_set and desc_knn2_host / desc_match synchronise `st`; the caller has validated the parameters.
 int desc_knn2_splits(int n_q, int n_t, int *chunks_per_split);
 hipError_t desc_set(const unsigned char *desc_h, int n, ScratchCache &cache, DescSlot &slot, hipStream_t st);
+// the same from [n][128] bytes already on the device, 16-byte aligned (amvs_sift_to_slot)
+hipError_t desc_set_device(const unsigned char *desc_d, int n, ScratchCache &cache, DescSlot &slot, hipStream_t st);
 hipError_t desc_knn2_host(const DescSlot &q, const DescSlot &t, ScratchCache &cache, int *idx_h, int *dist2_h, hipStream_t st);
 hipError_t desc_match(const DescSlot &q, const DescSlot &t, float ratio, bool cross_check, ScratchCache &cache, int *q_idx_h,
                       int *t_idx_h, int *dist2_h, long long *n_matches, hipStream_t st);

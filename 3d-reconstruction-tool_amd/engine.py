@@ -126,6 +126,8 @@ class Engine:
         self._h = h
         self._render_views = 0           # views of the last mesh_render: the image count mesh_color_views expects
         self._desc_rows = {}             # rows of every descriptor slot that was set: the sizes of knn2's outputs
+        self._clahe_shape = None         # (h, w) of the context's resident CLAHE result
+        self._sift_rows = None           # keypoints of the last sift_extract
         if mode != "exact":
             self.set_mode(mode)
 
@@ -308,6 +310,86 @@ class Engine:
         self._chk(self._lib.amvs_set_view_bgr8_undistorted(
             self._h, int(view), _u8(img), img.shape[0], img.shape[1], _f64(K9), _f64(d), d.size, _p(R), _p(t),
             _u8(out) if want_color else None))
+        return out
+
+    # -- CLAHE and SIFT (include/amvs_features.h) --
+    @staticmethod
+    def _gray8(gray):
+        g = np.ascontiguousarray(gray)
+        if g.dtype != np.uint8 or g.ndim != 2:
+            raise ValueError("expected an (h, w) uint8 gray image")
+        if max(g.shape) > _lib.FEATURES_MAX_SIDE:
+            raise ValueError(f"image side above {_lib.FEATURES_MAX_SIDE} (AMVS_FEATURES_MAX_SIDE)")
+        return g
+
+    def clahe(self, gray, clip_limit=2.0, grid=(8, 8)):
+        """The (h, w) uint8 gray image after CLAHE with `grid` = (tiles across, tiles down) (amvs_clahe_u8).  The result
+        also stays resident for sift_scale_space(None).  Touches no view."""
+        g = self._gray8(gray)
+        out = np.empty_like(g)
+        self._clahe_shape = None         # (a call that fails leaves none resident)
+        self._chk(self._lib.amvs_clahe_u8(self._h, _u8(g), g.shape[0], g.shape[1], float(np.float32(clip_limit)),
+                                          int(grid[0]), int(grid[1]), _u8(out)))
+        self._clahe_shape = g.shape
+        return out
+
+    def sift_scale_space(self, gray, sigma=1.6):
+        """Builds the Gaussian / difference-of-Gaussian scale space of a (h, w) uint8 gray image, or with gray=None of the
+        resident result of the last clahe(), and keeps it resident (amvs_sift_scale_space).  Returns the list of the
+        octaves' (rows, columns); octave 0 has twice the image's size."""
+        if gray is None:
+            if self._clahe_shape is None:
+                raise ValueError("sift_scale_space(None) needs a clahe() before it")
+            g, (h, w) = None, self._clahe_shape
+        else:
+            g = self._gray8(gray)
+            h, w = g.shape
+        n = C.c_int32(0)
+        self._sift_rows = None           # (the library drops the resident keypoints with their scale space)
+        self._chk(self._lib.amvs_sift_scale_space(self._h, None if g is None else _u8(g), h, w, float(sigma), C.byref(n)))
+        shapes = [(2 * h, 2 * w)]
+        for _ in range(1, n.value):
+            shapes.append((shapes[-1][0] // 2, shapes[-1][1] // 2))
+        return shapes
+
+    def sift_extract(self, gray, n_features=0, contrast_threshold=0.04, edge_threshold=10.0, sigma=1.6, clahe=None):
+        """SIFT keypoints and descriptors of a (h, w) uint8 gray image (amvs_sift_extract, amvs_sift_fetch): (keypoints
+        (n, 6) float32 with the columns x, y, size, angle in degrees, response, packed octave + 256 * layer; descriptors
+        (n, 128) uint8), in the canonical order, the n_features strongest (0: all).  clahe=(clip_limit, (tiles across,
+        tiles down)) applies CLAHE first, on the device.  The descriptors stay resident for sift_to_slot."""
+        g = self._gray8(gray)
+        self._sift_rows = None
+        if clahe is not None:
+            self._clahe_shape = None
+            self._chk(self._lib.amvs_clahe_u8(self._h, _u8(g), g.shape[0], g.shape[1], float(np.float32(clahe[0])),
+                                              int(clahe[1][0]), int(clahe[1][1]), None))
+            self._clahe_shape = g.shape
+        n = C.c_int32(0)
+        self._chk(self._lib.amvs_sift_extract(self._h, None if clahe is not None else _u8(g), g.shape[0], g.shape[1], int(n_features),
+                                              float(np.float32(contrast_threshold)), float(np.float32(edge_threshold)),
+                                              float(sigma), C.byref(n)))
+        kps = np.empty((n.value, 6), np.float32)
+        desc = np.empty((n.value, 128), np.uint8)
+        self._chk(self._lib.amvs_sift_fetch(self._h, _p(kps), _u8(desc), n.value))
+        self._sift_rows = n.value
+        return kps, desc
+
+    def sift_to_slot(self, slot):
+        """The descriptors of the last sift_extract into descriptor slot `slot`, as set_descriptors of them would, without
+        a visit to the host (amvs_sift_to_slot)."""
+        if self._sift_rows is None:
+            raise ValueError("sift_to_slot needs a sift_extract before it")
+        self._chk(self._lib.amvs_sift_to_slot(self._h, int(slot)))
+        self._desc_rows[int(slot)] = self._sift_rows
+
+    def sift_level(self, octave, index, dog=False):
+        """Gaussian image `index` (0 .. 5) or, with dog, difference image `index` (0 .. 4) of an octave of the resident
+        scale space, float32 (amvs_sift_fetch_level)."""
+        h, w = C.c_int32(0), C.c_int32(0)
+        args = (self._h, int(octave), int(index), int(bool(dog)))
+        self._chk(self._lib.amvs_sift_fetch_level(*args, None, C.byref(h), C.byref(w)))
+        out = np.empty((h.value, w.value), np.float32)
+        self._chk(self._lib.amvs_sift_fetch_level(*args, _p(out), None, None))
         return out
 
     def set_view_colors(self, view, image_bgr_u8):
