@@ -3,7 +3,8 @@ device, the restatement of tests/features_restatement.py against plain loops and
 the input family of tests/features_inputs.py against the edges the GPU comparison relies on, the float32 functions of
 the keypoint stages against NumPy, the restated extractor on a rotated and magnified texture ("it is SIFT"), and the
 Python classes' argument handling.
-tests/test_hip_features.py compares the device with the same restatement."""
+tests/test_hip_features.py compares the device with the same restatement, tests/test_hip_features_scale.py on the second
+input family (larger and crowded images, the ends of the sigma range), whose conditions are asserted here."""
 import ctypes as C
 import math
 import os
@@ -332,6 +333,134 @@ def test_descriptors_are_what_the_matcher_takes():
     assert len(kps) > 10 and descriptors_u8(desc) is not None and desc.max() <= 255 and desc.max() > 100
     assert (kps[:, 0] >= 0).all() and (kps[:, 0] < CASES[0].gray.shape[1]).all() and (kps[:, 3] >= 0).all() and (kps[:, 3] < 360).all()
     assert (kps[:, 4] * 3 >= np.float32(0.04)).all() and stages["n_candidates"] >= stages["n_refined"] > 0
+
+
+# ------------------------------------------------------------------------------------------ the second family ---
+# The conditions tests/test_hip_features_scale.py relies on, with the restatement alone.  The counts in the docstrings were
+# measured with it; the assertions are the conditions, not the counts.
+def _oriented(name):
+    case, params = fi.scale_cases()[name]
+    kps, desc, stages = fi.restated_extract(case, params)
+    return case, params, kps, desc, stages
+
+
+def _orientations_per_keypoint(stages):
+    per = {}
+    for k in stages["oriented"]:
+        per[k["key"][:4]] = per.get(k["key"][:4], 0) + 1
+    return per
+
+
+@pytest.mark.parametrize("name,layers", [("wrap", (3,)), ("wrap, mid-layer", (2, 3))])
+def test_wrap_inputs_have_keypoints_beyond_the_first_pass(name, layers):
+    """One pass of the extrema search takes 8192 * 256 interior pixels, in (layer, row, column) order.
+    520 x 520: octave 0 has 3 * 1030 * 1030 of them; 4446 candidates, 2462 keypoints, 406 of octave 0 from a candidate
+    beyond the first pass, all of layer 3: the pass ends at row 1006 of the 1030 of layer 2, and no keypoint starts
+    in those last rows (the texture's periods are 14 pixels and more there, layers 1 and 2 are nearly empty).
+    520 x 700, with a blob planted on the last pixel of the first pass: the pass ends at row 478 of layer 2; 5968
+    candidates, 3304 keypoints, 548 beyond the first pass, 1 of layer 2 and 547 of layer 3, and a keypoint that starts
+    at index 8192 * 256 - 1."""
+    case, _, kps, _, stages = _oriented(name)
+    h, w = 2 * case.gray.shape[0], 2 * case.gray.shape[1]
+    assert 3 * (h - 10) * (w - 10) > fi.EXTREMA_PASS > (h - 10) * (w - 10)
+    late = [k["cand"][0] for k in stages["oriented"] if k["o"] == 0 and fi.extrema_index(k["cand"], h, w) >= fi.EXTREMA_PASS]
+    print(f"{case.name}: {stages['n_candidates']} candidates, {len(kps)} keypoints, {len(late)} beyond the first pass, by layer "
+          f"{[late.count(i) for i in (1, 2, 3)]}")
+    assert len(late) >= 50 and all(i in late for i in layers)
+    if name == "wrap, mid-layer":
+        # a stride of gridDim.x * 256 - 1 visits every pixel, and pixel k (stride) a second time: only a keypoint that starts
+        # exactly there shows it (as a keypoint too many).  The planted blob's does.
+        seam = fi.seam_pixel(*case.gray.shape)
+        assert fi.extrema_index(seam, h, w) == fi.EXTREMA_PASS - 1 and seam[0] == 2
+        assert any(k["o"] == 0 and k["cand"] == seam for k in stages["oriented"])
+
+
+def test_candidates_input_overflows_the_first_array():
+    """220 x 220 blobs in noise: 24 611 candidates against the 16 384 the first array holds, 9 refined, 27 keypoints.
+    By octave the candidates are 13 596, 8 399, 2 140, 420, 53, 3 and 0, and every keypoint lies in octaves 2 to 4.  The
+    octaves are searched one after the other on one stream, so the hits of octaves 0 and 1 fill an array of 16 384 before
+    any other arrives: a search that dropped what does not fit would lose every keypoint, whatever the atomics' order."""
+    case, params, kps, _, stages = _oriented("candidates")
+    print(f"{stages['n_candidates']} candidates, {stages['n_refined']} refined, {len(kps)} keypoints")
+    assert fr.pre_threshold(params[1]) == 0
+    assert stages["n_candidates"] > 16384 and stages["n_candidates"] >= 20000 and len(kps) > 0
+    per_octave = [len(fr.candidates(d, fr.pre_threshold(params[1]))) for d in fi.restated_space(case, params[3])[1]]
+    first = min(k["o"] for k in stages["oriented"])
+    assert sum(per_octave) == stages["n_candidates"] and sum(per_octave[:first]) > 16384
+
+
+def test_crowd_input_ties_and_its_cuts():
+    """150 x 150 noise: 11 130 candidates, 7 724 refined, 10 594 keypoints with 7 707 distinct responses, up to 6
+    orientations on one keypoint.  The cut at 3000 falls between two responses; the tie cut is 6008.  Both equal
+    the rule by hand: the strictly stronger keypoints, then the first of the tie in canonical order."""
+    case, params, kps, desc, stages = _oriented("crowd")
+    resp = np.sort(kps[:, 4])[::-1]
+    n_tie = fi.tie_cut_near(kps, 6000)
+    print(f"{stages['n_candidates']} candidates, {stages['n_refined']} refined, {len(kps)} keypoints, {len(np.unique(resp))} distinct responses, "
+          f"tie cut at {n_tie}")
+    assert len(kps) > 8192 and len(np.unique(resp)) < len(kps) * 0.8
+    assert fi.CUT < n_tie < len(kps) and resp[n_tie - 1] == resp[n_tie]
+    keys = [k["key"] for k in stages["oriented"]]
+    assert keys == sorted(set(keys))
+    for n in (fi.CUT, n_tie):
+        cut, cut_desc, _ = fi.restated_extract(case, (n,) + params[1:])
+        want, want_desc = fi.cut_by_hand(kps, desc, n)
+        assert len(cut) == n and np.array_equal(cut, want) and np.array_equal(cut_desc, want_desc)
+
+
+def test_sigma_ends_reach_their_windows():
+    """70 x 150 texture at sigma 4: 73 candidates, 78 keypoints, orientation radius 20 .. 37, descriptor radius 48 .. 88,
+    up to 3 orientations.  60 x 60 noise at sigma 0.3: 77 candidates, 66 keypoints, orientation radius 2 .. 3, up to 4
+    orientations (25 to 49 samples a histogram).  150 x 150 noise at sigma 0.5: orientation radius 3 .. 5, up to 6
+    orientations.  The 70 x 150 texture at sigma 0.5, an ordinary image under the crowded images' parameters: 38 keypoints,
+    orientation radius 3 .. 5, up to 3 orientations.  Radius 2 needs sigma below 0.5: a refined scale is at least
+    sigma 2^(0.5 / 3), and rint(4.5 * 0.5 * 1.1225) is 3; so radius 2 is asked of the sigma 0.3 input alone, radius 3 of
+    the two at 0.5.  At sigma 0.1 the outer taps are 1e-37 to 1.5e-6, the differences vanish: no candidate."""
+    def radii(stages):
+        return [int(np.rint(np.float32(4.5) * k["scl"])) for k in stages["oriented"]], [fi.descriptor_radius(k["scl"]) for k in stages["oriented"]]
+
+    _, _, kps, _, stages = _oriented("wide")
+    ori, desc = radii(stages)
+    print(f"sigma 4: {len(kps)} keypoints, orientation radius {min(ori)} .. {max(ori)}, descriptor radius {min(desc)} .. {max(desc)}")
+    assert max(ori) >= 30 and max(desc) >= 64 and (2 * max(ori) + 1) ** 2 > 3600
+    for name, reach in (("fine", 2), ("crowd", 3), ("busy", 3)):
+        _, _, kps, _, stages = _oriented(name)
+        ori, _ = radii(stages)
+        most = max(_orientations_per_keypoint(stages).values())
+        print(f"{name}: {len(kps)} keypoints, orientation radius {min(ori)} .. {max(ori)}, up to {most} orientations")
+        assert len(kps) > 10 and min(ori) <= reach and most >= 3
+    kps, desc, stages = fi.restated_extract(fi.SPACE_CASE, (0, 0.04, 10.0, 0.1))
+    assert stages["n_candidates"] == 0 and kps.shape == (0, 6) and kps.dtype == np.float32 and desc.shape == (0, 128) and desc.dtype == np.uint8
+
+
+def test_space_input_spans_tiles_at_both_ends_of_sigma():
+    """70 x 300: octave 0 is 140 x 600, three 256-column tiles of the row pass, ten by three 64 x 64 tiles of the column
+    pass.  Radii at sigma 4: 16, 13, 16, 20, 25, 31; at sigma 0.5: 1, 2, 2, 3, 3, 4; at sigma 0.1: 1 six times."""
+    radii = {s: [(len(fr.taps(v)) - 1) // 2 for v in fr.sigmas(s)] for s in fi.SPACE_SIGMAS}
+    print(radii)
+    assert radii[4.0][-1] == 31 and max(radii[0.5]) <= 4 and radii[0.1] == [1] * 6
+    gauss, dog = fi.restated_space(fi.SPACE_CASE, 4.0)
+    h, w = gauss[0][0].shape
+    assert w > 512 and h > 128 and len(gauss) == fr.octaves(*fi.SPACE_CASE.gray.shape)
+    for s in fi.SPACE_SIGMAS:                              # the levels are images, not a constant: the blur has something to get wrong
+        gauss, dog = fi.restated_space(fi.SPACE_CASE, s)
+        assert all(a.max() - a.min() > 10 for a in gauss[0])
+        top = max(np.abs(a).max() for a in dog[0])
+        assert top < 1e-3 if s == 0.1 else top > 0.01        # outer taps of 1e-37 to 1.5e-6: the levels differ in the last place at most
+
+
+def test_clip_search_and_its_frozen_case():
+    """The bounded search of features_inputs.clip_recipes() (360 off-centre blobs of sigma 4 to 8 on 12 side pairs up to
+    40 x 40, then 200 textures) finds its first input at recipe 19, in 0.3 s: a dark blob of sigma 7 on 14 x 30, whose
+    one keypoint lies in octave 1 (14 x 30, rows + columns 44) with scale 4.84 and descriptor radius 51."""
+    found = fi.clip_search(limit=40)
+    assert found is not None and found[0] == fi.CLIP_RECIPE and fi.clip_recipes().index(fi.CLIP_RECIPE) < 40
+    case, params, kps, _, stages = _oriented("clip")
+    assert max(case.gray.shape) <= 40 and 3.0 <= params[3] <= 4.0 and params[1:3] == (0.005, 50.0)
+    hits = [k for k in stages["oriented"]
+            if int(np.rint(np.float32(3) * k["scl"] * np.float32(1.4142135) * np.float32(2.5))) > sum(dim >> k["o"] for dim in (2 * case.gray.shape[0], 2 * case.gray.shape[1]))]
+    print(f"{len(kps)} keypoints, {len(hits)} clipped: {[(k['o'], k['i'], float(k['scl'])) for k in hits]}")
+    assert len(hits) >= 1
 
 
 # ---------------------------------------------------------------------------------------------- the classes ---
