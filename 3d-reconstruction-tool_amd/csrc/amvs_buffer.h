@@ -8,6 +8,14 @@
 #include <map>
 #include <vector>
 
+// In a function that runs on the stream `st` and returns hipError_t: return the error of `call`, after `st` has
+// drained -- the scratch leases of the function go back to the cache with nothing in flight (Ordering, below).
+#define STCHK(call)                                                 \
+    do {                                                            \
+        hipError_t e_ = (call);                                     \
+        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
+    } while (0)
+
 namespace amvs {
 
 // A context's cache of device blocks for the post-steps' SHORT-LIVED buffers (the neighbour statistic of the stereo

@@ -30,6 +30,7 @@
 #include "amvs_bundle_dev.h"
 #include "amvs_bundle_host.h"
 #include "amvs_handles.h"
+#include "amvs_pose.h"
 
 #include <cmath>
 #include <cstdio>
@@ -40,15 +41,7 @@ namespace amvs {
 
 namespace {
 
-#define BCHK(call)                                                  \
-    do {                                                            \
-        hipError_t e_ = (call);                                     \
-        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
-    } while (0)
-
 constexpr int NB = 32;                // columns of a Cholesky panel, and the side of an update tile
-
-struct Intr { double fx, fy, cx, cy; };
 
 // the device arrays of a problem and of one state
 struct Prob {
@@ -588,12 +581,12 @@ hipError_t upload(const BaProblem &h, const BaLists &L, bool with_system, bool w
                                        &L.pair_k, &L.pair_k2, &L.seg_ab, &L.seg_blk0, &L.seg_blk};
     size_t off[14] = {0};
     for (int i = 0; i < 13; ++i) off[i + 1] = off[i] + ((parts[i]->size() + 63) & ~size_t(63));     // (each list on a 256-byte boundary)
-    BCHK(cache.lease(d.ints, sizeof(int) * off[13]));
+    STCHK(cache.lease(d.ints, sizeof(int) * off[13]));
     int *base = d.ints.get<int>();
     for (int i = 0; i < 13; ++i)
         if (!parts[i]->empty())
-            BCHK(hipMemcpyAsync(base + off[i], parts[i]->data(), sizeof(int) * parts[i]->size(), hipMemcpyHostToDevice, st));
-    BCHK(hipStreamSynchronize(st));                 // (cam_v, pt_v and cam_of_slot are locals)
+            STCHK(hipMemcpyAsync(base + off[i], parts[i]->data(), sizeof(int) * parts[i]->size(), hipMemcpyHostToDevice, st));
+    STCHK(hipStreamSynchronize(st));                 // (cam_v, pt_v and cam_of_slot are locals)
     d.pt_start = base + off[2]; d.cam_list = base + off[3]; d.cam_blk0 = base + off[4]; d.cam_blk = base + off[5];
     d.slot = base + off[6]; d.cam_of_slot = base + off[7]; d.pair_k = base + off[8]; d.pair_k2 = base + off[9];
     d.seg_ab = base + off[10]; d.seg_blk0 = base + off[11]; d.seg_blk = base + off[12];
@@ -603,37 +596,37 @@ hipError_t upload(const BaProblem &h, const BaLists &L, bool with_system, bool w
     d.n_pairs = (long long)L.pair_k.size();
     d.F = L.F;
     d.n = with_system ? L.n : 0;
-    BCHK(cache.lease(d.uvb, sizeof(float) * 2 * (size_t)N));
-    BCHK(hipMemcpyAsync(d.uvb.get(), h.uv, sizeof(float) * 2 * (size_t)N, hipMemcpyHostToDevice, st));
-    d.q = Prob{base + off[0], base + off[1], d.uvb.get<float>(), C, P, N, Intr{h.K[0], h.K[4], h.K[2], h.K[5]}};
+    STCHK(cache.lease(d.uvb, sizeof(float) * 2 * (size_t)N));
+    STCHK(hipMemcpyAsync(d.uvb.get(), h.uv, sizeof(float) * 2 * (size_t)N, hipMemcpyHostToDevice, st));
+    d.q = Prob{base + off[0], base + off[1], d.uvb.get<float>(), C, P, N, intrinsics_of(h.K)};
     const size_t n_state = 12 * (size_t)C + 3 * (size_t)P;
     for (int i = 0; i < (with_step ? 2 : 1); ++i) {
-        BCHK(cache.lease(d.state[i], sizeof(double) * n_state));
+        STCHK(cache.lease(d.state[i], sizeof(double) * n_state));
         double *b = d.state[i].get<double>();
         d.s[i] = State{b, b + 9 * (size_t)C, b + 12 * (size_t)C};
-        BCHK(cache.lease(d.camsum[i], sizeof(double) * BA_CAM_SUMS * (size_t)C));
+        STCHK(cache.lease(d.camsum[i], sizeof(double) * BA_CAM_SUMS * (size_t)C));
     }
-    BCHK(hipMemcpyAsync(d.s[0].R, h.R, sizeof(double) * 9 * (size_t)C, hipMemcpyHostToDevice, st));
-    BCHK(hipMemcpyAsync(d.s[0].t, h.t, sizeof(double) * 3 * (size_t)C, hipMemcpyHostToDevice, st));
-    BCHK(hipMemcpyAsync(d.s[0].X, h.X, sizeof(double) * 3 * (size_t)P, hipMemcpyHostToDevice, st));
-    BCHK(cache.lease(d.cpart, sizeof(double) * BA_CAM_SUMS * (size_t)(d.n_cblk > 0 ? d.n_cblk : 1)));
-    BCHK(cache.lease(d.costact, sizeof(double) * 4));
-    BCHK(cache.lease(d.V, sizeof(double) * 6 * (size_t)P));
-    BCHK(cache.lease(d.gp, sizeof(double) * 3 * (size_t)P));
-    BCHK(cache.lease(d.cnt, sizeof(int) * (size_t)P));
-    BCHK(cache.lease(d.Lp, sizeof(double) * 6 * (size_t)P));
-    BCHK(cache.lease(d.held, (size_t)P));
-    BCHK(cache.lease(d.bad, sizeof(int) * 2));
-    BCHK(hipMemsetAsync(d.bad.get(), 0, sizeof(int) * 2, st));
+    STCHK(hipMemcpyAsync(d.s[0].R, h.R, sizeof(double) * 9 * (size_t)C, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(d.s[0].t, h.t, sizeof(double) * 3 * (size_t)C, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(d.s[0].X, h.X, sizeof(double) * 3 * (size_t)P, hipMemcpyHostToDevice, st));
+    STCHK(cache.lease(d.cpart, sizeof(double) * BA_CAM_SUMS * (size_t)(d.n_cblk > 0 ? d.n_cblk : 1)));
+    STCHK(cache.lease(d.costact, sizeof(double) * 4));
+    STCHK(cache.lease(d.V, sizeof(double) * 6 * (size_t)P));
+    STCHK(cache.lease(d.gp, sizeof(double) * 3 * (size_t)P));
+    STCHK(cache.lease(d.cnt, sizeof(int) * (size_t)P));
+    STCHK(cache.lease(d.Lp, sizeof(double) * 6 * (size_t)P));
+    STCHK(cache.lease(d.held, (size_t)P));
+    STCHK(cache.lease(d.bad, sizeof(int) * 2));
+    STCHK(hipMemsetAsync(d.bad.get(), 0, sizeof(int) * 2, st));
     if (d.n > 0) {
-        BCHK(cache.lease(d.spart, sizeof(double) * BA_SEG_SUMS * (size_t)(d.n_sblk > 0 ? d.n_sblk : 1)));
-        BCHK(cache.lease(d.S, sizeof(double) * (size_t)d.n * (size_t)d.n));
-        BCHK(cache.lease(d.rhs, sizeof(double) * (size_t)d.n));
-        BCHK(cache.lease(d.x, sizeof(double) * (size_t)d.n));
+        STCHK(cache.lease(d.spart, sizeof(double) * BA_SEG_SUMS * (size_t)(d.n_sblk > 0 ? d.n_sblk : 1)));
+        STCHK(cache.lease(d.S, sizeof(double) * (size_t)d.n * (size_t)d.n));
+        STCHK(cache.lease(d.rhs, sizeof(double) * (size_t)d.n));
+        STCHK(cache.lease(d.x, sizeof(double) * (size_t)d.n));
     }
     if (with_step) {
-        BCHK(cache.lease(d.dc, sizeof(double) * 6 * (size_t)C));
-        BCHK(cache.lease(d.dp, sizeof(double) * 3 * (size_t)P));
+        STCHK(cache.lease(d.dc, sizeof(double) * 6 * (size_t)C));
+        STCHK(cache.lease(d.dp, sizeof(double) * 3 * (size_t)P));
     }
     return hipSuccess;
 }
@@ -644,11 +637,11 @@ hipError_t cam_pass(Device &d, int i, hipStream_t st)
     if (d.n_cblk > 0) {
         hipLaunchKernelGGL(ba_cam_partials_kernel, blocks_for((long long)d.n_cblk * BA_CAM_SUMS, 256), dim3(256), 0, st, d.q, d.s[i],
                            d.cam_list, d.cam_blk, d.n_cblk, d.cpart.get<double>());
-        BCHK(hipGetLastError());
+        STCHK(hipGetLastError());
     }
     hipLaunchKernelGGL(ba_total_kernel, blocks_for((long long)d.q.C * BA_CAM_SUMS, 256), dim3(256), 0, st, (const double *)d.cpart.get(),
                        d.cam_blk0, d.q.C, BA_CAM_SUMS, d.camsum[i].get<double>());
-    BCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     hipLaunchKernelGGL(ba_cost_total_kernel, dim3(1), dim3(64), 0, st, (const double *)d.camsum[i].get(), d.q.C, (const int *)d.bad.get(),
                        d.costact.get<double>());
     return hipGetLastError();
@@ -665,16 +658,16 @@ hipError_t point_pass(Device &d, int i, double lambda, int refine_points, bool f
 // S and rhs of state i under lambda; camsum[i] holds the state's sums
 hipError_t schur(Device &d, int i, double lambda, int refine_points, hipStream_t st)
 {
-    BCHK(point_pass(d, i, lambda, refine_points, true, st));
+    STCHK(point_pass(d, i, lambda, refine_points, true, st));
     d.timer.mark("points", st);
     if (d.n_sblk > 0) {
         hipLaunchKernelGGL(ba_schur_partials_kernel, blocks_for((long long)d.n_sblk * 6, 256), dim3(256), 0, st, d.q, d.s[i],
                            d.pair_k, d.pair_k2, d.n_pairs, d.seg_blk, d.n_sblk, (const double *)d.Lp.get(),
                            (const unsigned char *)d.held.get(), (const double *)d.gp.get(), d.spart.get<double>());
-        BCHK(hipGetLastError());
+        STCHK(hipGetLastError());
     }
     d.timer.mark("schur_partials", st);
-    BCHK(hipMemsetAsync(d.S.get(), 0, sizeof(double) * (size_t)d.n * (size_t)d.n, st));
+    STCHK(hipMemsetAsync(d.S.get(), 0, sizeof(double) * (size_t)d.n * (size_t)d.n, st));
     hipLaunchKernelGGL(ba_schur_assemble_kernel, blocks_for((long long)d.n_seg * BA_SEG_SUMS, 256), dim3(256), 0, st,
                        (const double *)d.spart.get(), d.seg_ab, d.seg_blk0, d.n_seg, d.cam_of_slot, (const double *)d.camsum[i].get(), lambda,
                        d.n, d.S.get<double>(), d.rhs.get<double>());
@@ -685,29 +678,29 @@ hipError_t schur(Device &d, int i, double lambda, int refine_points, hipStream_t
 // the candidate of state i under lambda into state 1 - i, with dc, dp and the no-step flag
 hipError_t step(Device &d, int i, double lambda, int refine_points, hipStream_t st)
 {
-    BCHK(schur(d, i, lambda, refine_points, st));
-    BCHK(hipMemsetAsync(d.bad.get(), 0, sizeof(int), st));
+    STCHK(schur(d, i, lambda, refine_points, st));
+    STCHK(hipMemsetAsync(d.bad.get(), 0, sizeof(int), st));
     const int n = d.n;
     double *A = d.S.get<double>();
     for (int j0 = 0; j0 < n; j0 += NB) {
         const int below = n - j0 - NB;
         hipLaunchKernelGGL(ba_chol_diag_kernel, dim3(1), dim3(256), 0, st, A, n, j0, d.bad.get<int>());
-        BCHK(hipGetLastError());
+        STCHK(hipGetLastError());
         if (below > 0) {
             hipLaunchKernelGGL(ba_chol_rows_kernel, blocks_for(below, 256), dim3(256), 0, st, A, n, j0);
-            BCHK(hipGetLastError());
+            STCHK(hipGetLastError());
             const unsigned nt = (unsigned)((below + NB - 1) / NB);
             hipLaunchKernelGGL(ba_chol_update_kernel, dim3(nt, nt), dim3(256), 0, st, A, n, j0);
-            BCHK(hipGetLastError());
+            STCHK(hipGetLastError());
         }
     }
     d.timer.mark("cholesky", st);
     hipLaunchKernelGGL(ba_solve_kernel, dim3(1), dim3(1024), 0, st, (const double *)A, n, (const double *)d.rhs.get(), d.x.get<double>());
-    BCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     d.timer.mark("solve", st);
     hipLaunchKernelGGL(ba_pose_step_kernel, blocks_for(d.q.C, 64), dim3(64), 0, st, d.s[i], d.q.C, d.slot, (const double *)d.x.get(),
                        (const int *)d.bad.get(), d.dc.get<double>(), d.s[1 - i]);
-    BCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     hipLaunchKernelGGL(ba_point_step_kernel, blocks_for(d.q.P, 256), dim3(256), 0, st, d.q, d.s[i], d.pt_start, d.slot,
                        (const double *)d.dc.get(), (const double *)d.Lp.get(), (const unsigned char *)d.held.get(),
                        (const double *)d.gp.get(), (const int *)d.bad.get(), d.dp.get<double>(), d.s[1 - i].X);
@@ -717,8 +710,8 @@ hipError_t step(Device &d, int i, double lambda, int refine_points, hipStream_t 
 
 hipError_t fetch_state(const Device &d, int i, double *R, double *t, double *X, hipStream_t st)
 {
-    BCHK(hipMemcpyAsync(R, d.s[i].R, sizeof(double) * 9 * (size_t)d.q.C, hipMemcpyDeviceToHost, st));
-    BCHK(hipMemcpyAsync(t, d.s[i].t, sizeof(double) * 3 * (size_t)d.q.C, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(R, d.s[i].R, sizeof(double) * 9 * (size_t)d.q.C, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(t, d.s[i].t, sizeof(double) * 3 * (size_t)d.q.C, hipMemcpyDeviceToHost, st));
     return hipMemcpyAsync(X, d.s[i].X, sizeof(double) * 3 * (size_t)d.q.P, hipMemcpyDeviceToHost, st);
 }
 
@@ -729,15 +722,15 @@ hipError_t ba_cost(const BaProblem &h, double *cost, long long *active, double *
     BaLists L;
     ba_build_lists(h, false, L);
     Device d;
-    BCHK(upload(h, L, false, false, d, cache, st));
-    BCHK(cache.lease(d.err2, sizeof(double) * (size_t)h.N));
+    STCHK(upload(h, L, false, false, d, cache, st));
+    STCHK(cache.lease(d.err2, sizeof(double) * (size_t)h.N));
     hipLaunchKernelGGL(ba_err_kernel, blocks_for(h.N, 256), dim3(256), 0, st, d.q, d.s[0], d.err2.get<double>());
-    BCHK(hipGetLastError());
-    BCHK(cam_pass(d, 0, st));
+    STCHK(hipGetLastError());
+    STCHK(cam_pass(d, 0, st));
     double ca[3];
-    BCHK(hipMemcpyAsync(ca, d.costact.get(), sizeof(ca), hipMemcpyDeviceToHost, st));
-    BCHK(hipMemcpyAsync(err2, d.err2.get(), sizeof(double) * (size_t)h.N, hipMemcpyDeviceToHost, st));
-    BCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(ca, d.costact.get(), sizeof(ca), hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(err2, d.err2.get(), sizeof(double) * (size_t)h.N, hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     *cost = ca[0];
     *active = (long long)ca[1];
     return hipSuccess;
@@ -748,15 +741,15 @@ hipError_t ba_normal(const BaProblem &h, double *U, double *gc, double *V, doubl
     BaLists L;
     ba_build_lists(h, false, L);
     Device d;
-    BCHK(upload(h, L, false, false, d, cache, st));
-    BCHK(point_pass(d, 0, 0.0, 1, false, st));
-    BCHK(cam_pass(d, 0, st));
+    STCHK(upload(h, L, false, false, d, cache, st));
+    STCHK(point_pass(d, 0, 0.0, 1, false, st));
+    STCHK(cam_pass(d, 0, st));
     std::vector<double> sums((size_t)h.C * BA_CAM_SUMS);
-    BCHK(hipMemcpyAsync(sums.data(), d.camsum[0].get(), sizeof(double) * sums.size(), hipMemcpyDeviceToHost, st));
-    BCHK(hipMemcpyAsync(V, d.V.get(), sizeof(double) * 6 * (size_t)h.P, hipMemcpyDeviceToHost, st));
-    BCHK(hipMemcpyAsync(gp, d.gp.get(), sizeof(double) * 3 * (size_t)h.P, hipMemcpyDeviceToHost, st));
-    BCHK(hipMemcpyAsync(counts, d.cnt.get(), sizeof(int) * (size_t)h.P, hipMemcpyDeviceToHost, st));
-    BCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(sums.data(), d.camsum[0].get(), sizeof(double) * sums.size(), hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(V, d.V.get(), sizeof(double) * 6 * (size_t)h.P, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(gp, d.gp.get(), sizeof(double) * 3 * (size_t)h.P, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(counts, d.cnt.get(), sizeof(int) * (size_t)h.P, hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     for (int c = 0; c < h.C; ++c) {
         std::memcpy(U + 21 * (size_t)c, sums.data() + (size_t)c * BA_CAM_SUMS, sizeof(double) * 21);
         std::memcpy(gc + 6 * (size_t)c, sums.data() + (size_t)c * BA_CAM_SUMS + 21, sizeof(double) * 6);
@@ -770,13 +763,13 @@ hipError_t ba_schur(const BaProblem &h, int refine_points, double lambda, double
     BaLists L;
     ba_build_lists(h, true, L);
     Device d;
-    BCHK(upload(h, L, true, false, d, cache, st));
-    BCHK(cam_pass(d, 0, st));
-    BCHK(schur(d, 0, lambda, refine_points, st));
-    BCHK(hipMemcpyAsync(S, d.S.get(), sizeof(double) * (size_t)d.n * (size_t)d.n, hipMemcpyDeviceToHost, st));
-    BCHK(hipMemcpyAsync(rhs, d.rhs.get(), sizeof(double) * (size_t)d.n, hipMemcpyDeviceToHost, st));
-    BCHK(hipMemcpyAsync(held, d.held.get(), (size_t)h.P, hipMemcpyDeviceToHost, st));
-    BCHK(hipStreamSynchronize(st));
+    STCHK(upload(h, L, true, false, d, cache, st));
+    STCHK(cam_pass(d, 0, st));
+    STCHK(schur(d, 0, lambda, refine_points, st));
+    STCHK(hipMemcpyAsync(S, d.S.get(), sizeof(double) * (size_t)d.n * (size_t)d.n, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(rhs, d.rhs.get(), sizeof(double) * (size_t)d.n, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(held, d.held.get(), (size_t)h.P, hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     std::memcpy(slot, L.slot.data(), sizeof(int) * (size_t)h.C);
     return hipSuccess;
 }
@@ -787,15 +780,15 @@ hipError_t ba_step(const BaProblem &h, int refine_points, double lambda, int *ok
     BaLists L;
     ba_build_lists(h, true, L);
     Device d;
-    BCHK(upload(h, L, true, true, d, cache, st));
-    BCHK(cam_pass(d, 0, st));
-    BCHK(step(d, 0, lambda, refine_points, st));
+    STCHK(upload(h, L, true, true, d, cache, st));
+    STCHK(cam_pass(d, 0, st));
+    STCHK(step(d, 0, lambda, refine_points, st));
     int bad = 0;
-    BCHK(hipMemcpyAsync(&bad, d.bad.get(), sizeof(int), hipMemcpyDeviceToHost, st));
-    BCHK(hipMemcpyAsync(dc, d.dc.get(), sizeof(double) * 6 * (size_t)h.C, hipMemcpyDeviceToHost, st));
-    BCHK(hipMemcpyAsync(dp, d.dp.get(), sizeof(double) * 3 * (size_t)h.P, hipMemcpyDeviceToHost, st));
-    BCHK(fetch_state(d, 1, R_out, t_out, X_out, st));
-    BCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(&bad, d.bad.get(), sizeof(int), hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(dc, d.dc.get(), sizeof(double) * 6 * (size_t)h.C, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(dp, d.dp.get(), sizeof(double) * 3 * (size_t)h.P, hipMemcpyDeviceToHost, st));
+    STCHK(fetch_state(d, 1, R_out, t_out, X_out, st));
+    STCHK(hipStreamSynchronize(st));
     *ok = bad ? 0 : 1;
     return hipSuccess;
 }
@@ -806,23 +799,23 @@ hipError_t ba_solve(const BaProblem &h, int refine_points, double lambda0, doubl
     BaLists L;
     ba_build_lists(h, true, L);
     Device d;
-    BCHK(upload(h, L, true, true, d, cache, st));
+    STCHK(upload(h, L, true, true, d, cache, st));
     d.timer.enable();
     int cur = 0, trials = 0, kept = 0;
     double ca[3], lambda = lambda0;
-    BCHK(cam_pass(d, cur, st));
-    BCHK(hipMemcpyAsync(ca, d.costact.get(), sizeof(ca), hipMemcpyDeviceToHost, st));
-    BCHK(hipStreamSynchronize(st));
+    STCHK(cam_pass(d, cur, st));
+    STCHK(hipMemcpyAsync(ca, d.costact.get(), sizeof(ca), hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     double cost = ca[0], act = ca[1];
     const double first = cost;
     while (trials < max_trials) {
         trials += 1;
         d.timer.begin(st);
-        BCHK(step(d, cur, lambda, refine_points, st));
-        BCHK(cam_pass(d, 1 - cur, st));             // (without a step the candidate is all zero: nothing active, and not looked at)
+        STCHK(step(d, cur, lambda, refine_points, st));
+        STCHK(cam_pass(d, 1 - cur, st));             // (without a step the candidate is all zero: nothing active, and not looked at)
         d.timer.mark("pass", st);
-        BCHK(hipMemcpyAsync(ca, d.costact.get(), sizeof(ca), hipMemcpyDeviceToHost, st));
-        BCHK(hipStreamSynchronize(st));
+        STCHK(hipMemcpyAsync(ca, d.costact.get(), sizeof(ca), hipMemcpyDeviceToHost, st));
+        STCHK(hipStreamSynchronize(st));
         d.timer.flush(d.n, h.N, h.P, d.n_pairs);
         const bool have = ca[2] == 0.0;
         if (have && ca[0] <= cost && ca[1] >= act) {
@@ -838,8 +831,8 @@ hipError_t ba_solve(const BaProblem &h, int refine_points, double lambda0, doubl
             if (lambda > AMVS_BA_LAMBDA_MAX) break;
         }
     }
-    BCHK(fetch_state(d, cur, R_out, t_out, X_out, st));
-    BCHK(hipStreamSynchronize(st));
+    STCHK(fetch_state(d, cur, R_out, t_out, X_out, st));
+    STCHK(hipStreamSynchronize(st));
     info[0] = (double)trials; info[1] = (double)kept; info[2] = lambda; info[3] = first; info[4] = cost; info[5] = act;
     return hipSuccess;
 }

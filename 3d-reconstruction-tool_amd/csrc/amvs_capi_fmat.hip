@@ -4,8 +4,6 @@
 #include "amvs_fmat_host.h"
 #include "../../include/amvs_epipolar.h"
 
-#include <cmath>
-
 using namespace amvs::host;
 
 namespace {
@@ -17,8 +15,6 @@ const char *points_error(const float *pts1, const float *pts2, int m)
     if (!pts1 || !pts2) return "NULL points";
     return nullptr;
 }
-
-bool bad_threshold(double t) { return !(t > 0.0) || !std::isfinite(t); }
 
 }  // namespace
 
@@ -74,11 +70,7 @@ int amvs_fmat_fit(amvs_ctx *c, const float *pts1, const float *pts2, const uint8
     if (!c) return AMVS_EINVAL;
     if (const char *why = points_error(pts1, pts2, m)) return fail(c, AMVS_EINVAL, why);
     if (!F_out || !n_used) return fail(c, AMVS_EINVAL, "NULL output");
-    long long n_set = m;
-    if (mask) {
-        n_set = 0;
-        for (int i = 0; i < m; ++i) n_set += mask[i] != 0;
-    }
+    const long long n_set = mask ? count_set(mask, m) : m;
     if (n_set < 8) return fail(c, AMVS_EINVAL, "fewer than 8 matches in the set");
     int rc = bind_device(c);
     if (rc) return rc;

@@ -5,8 +5,6 @@
 #include "amvs_pnp_step.h"
 #include "../../include/amvs_resection.h"
 
-#include <cmath>
-
 using namespace amvs::host;
 
 namespace {
@@ -18,8 +16,6 @@ const char *points_error(const float *pts3d, const float *pts2d, int m, const do
     if (!pts3d || !pts2d) return "NULL points";
     return amvs::pnp_intrinsics_error(K);
 }
-
-bool bad_threshold(double t) { return !(t > 0.0) || !std::isfinite(t); }
 
 }  // namespace
 
@@ -78,11 +74,7 @@ int amvs_pnp_refine(amvs_ctx *c, const float *pts3d, const float *pts2d, int m, 
     if (const char *why = points_error(pts3d, pts2d, m, K)) return fail(c, AMVS_EINVAL, why);
     if (!R_in || !t_in) return fail(c, AMVS_EINVAL, "NULL pose");
     if (!R_out || !t_out || !steps || !cost || !n_used) return fail(c, AMVS_EINVAL, "NULL output");
-    long long n_set = m;
-    if (mask) {
-        n_set = 0;
-        for (int i = 0; i < m; ++i) n_set += mask[i] != 0;
-    }
+    const long long n_set = mask ? count_set(mask, m) : m;
     if (n_set < 6) return fail(c, AMVS_EINVAL, "fewer than 6 correspondences in the set");
     int rc = bind_device(c);
     if (rc) return rc;

@@ -29,13 +29,6 @@ namespace amvs {
 
 namespace {
 
-// (a failure synchronises `st` first: the scratch leases go back to the cache with nothing in flight, amvs_buffer.h)
-#define NCHK(call)                                                  \
-    do {                                                            \
-        hipError_t e_ = (call);                                     \
-        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
-    } while (0)
-
 __device__ __forceinline__ bool pixel_valid(float d, float c, float min_conf)
 {
     return d > 0.0f && d <= FLT_MAX && c >= min_conf;      // (NaN fails each)
@@ -183,11 +176,11 @@ hipError_t stage_constants(ScratchCache &cache, ScratchCache::Lease &consts, int
                            hipStream_t st)
 {
     const size_t nd = 9 + 12 * (size_t)n_maps;
-    NCHK(cache.lease(consts, sizeof(double) * nd + 16));
+    STCHK(cache.lease(consts, sizeof(double) * nd + 16));
     double *d = consts.get<double>();
-    NCHK(hipMemcpyAsync(d, K_h, sizeof(double) * 9, hipMemcpyHostToDevice, st));
-    NCHK(hipMemcpyAsync(d + 9, poses_h, sizeof(double) * 12 * (size_t)n_maps, hipMemcpyHostToDevice, st));
-    NCHK(hipMemsetAsync(d + nd, 0, 16, st));
+    STCHK(hipMemcpyAsync(d, K_h, sizeof(double) * 9, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(d + 9, poses_h, sizeof(double) * 12 * (size_t)n_maps, hipMemcpyHostToDevice, st));
+    STCHK(hipMemsetAsync(d + nd, 0, 16, st));
     return hipSuccess;
 }
 
@@ -214,15 +207,15 @@ hipError_t depth_normals(const float *depth, const float *conf, int n_maps, int 
     const long long n = (long long)n_maps * H * W;
     if (n <= 0 || n > 0x7FFFFFFFll) return hipErrorInvalidValue;
     ScratchCache::Lease consts;
-    NCHK(stage_constants(cache, consts, n_maps, K_h, poses_h, st));
-    NCHK(normals.reserve(3 * (size_t)n, cache));
+    STCHK(stage_constants(cache, consts, n_maps, K_h, poses_h, st));
+    STCHK(normals.reserve(3 * (size_t)n, cache));
     unsigned long long *counters = (unsigned long long *)(consts.get<double>() + 9 + 12 * (size_t)n_maps);
     launch_fit(depth, conf, n_maps, H, W, consts.get<double>(), min_confidence, radius, jump, min_points, world, normals.get(),
                counters, st);
-    NCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     unsigned long long h = 0;
-    NCHK(hipMemcpyAsync(&h, counters, 8, hipMemcpyDeviceToHost, st));
-    NCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(&h, counters, 8, hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     *n_normals = (long long)h;
     return hipSuccess;
 }
@@ -236,21 +229,21 @@ hipError_t cloud_normals(const double *pts, long long n_pts, const float *depth,
     const long long n = (long long)n_maps * H * W;
     if (n <= 0 || n > 0x7FFFFFFFll || n_pts <= 0 || n_pts > 0x7FFFFFFFll) return hipErrorInvalidValue;
     ScratchCache::Lease consts;
-    NCHK(stage_constants(cache, consts, n_maps, K_h, poses_h, st));
-    NCHK(map_normals.reserve(3 * (size_t)n, cache));
-    NCHK(nrm_out.reserve(3 * (size_t)n_pts, cache));
-    NCHK(seen_out.reserve((size_t)n_pts, cache));
+    STCHK(stage_constants(cache, consts, n_maps, K_h, poses_h, st));
+    STCHK(map_normals.reserve(3 * (size_t)n, cache));
+    STCHK(nrm_out.reserve(3 * (size_t)n_pts, cache));
+    STCHK(seen_out.reserve((size_t)n_pts, cache));
     const double *d_consts = consts.get<double>();
     unsigned long long *counters = (unsigned long long *)(consts.get<double>() + 9 + 12 * (size_t)n_maps);
     launch_fit(depth, conf, n_maps, H, W, d_consts, min_confidence, radius, jump, min_points, true, map_normals.get(), counters, st);
-    NCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     hipLaunchKernelGGL(cloud_normal_kernel, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, st, pts, n_pts, depth,
                        (const float *)map_normals.get(), n_maps, H, W, d_consts, d_consts + 9, depth_tolerance, min_views,
                        nrm_out.get(), seen_out.get(), counters + 1);
-    NCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     unsigned long long h[2] = {0, 0};
-    NCHK(hipMemcpyAsync(h, counters, 16, hipMemcpyDeviceToHost, st));
-    NCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(h, counters, 16, hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     counts[0] = (long long)h[0]; counts[1] = (long long)h[1];
     return hipSuccess;
 }

@@ -10,6 +10,7 @@
 #include "amvs_features_state.h"
 
 #include <array>
+#include <cmath>
 #include <map>
 #include <memory>
 #include <string>
@@ -194,6 +195,17 @@ void resolve_timing(amvs_ctx *c);
 int check_colour_views(amvs_ctx *c, int n, const int *view_ids);
 int gather_colours(amvs_ctx *c, int n, const int *view_ids, amvs::DeviceBuffer<unsigned char> &out);
 int stage_maps(amvs_ctx *c, size_t n, const float *&depth, const float *&conf, amvs::DeviceBuffer<float> (&copy)[2]);
+
+// a threshold the entry points refuse: not positive, or not finite
+inline bool bad_threshold(double t) { return !(t > 0.0) || !std::isfinite(t); }
+
+// the non-zero bytes of mask[0 .. m)
+inline long long count_set(const uint8_t *mask, int m)
+{
+    long long n = 0;
+    for (int i = 0; i < m; ++i) n += mask[i] != 0;
+    return n;
+}
 
 // n elements of host memory into `out` (a post-step's inputs)
 template <class T>

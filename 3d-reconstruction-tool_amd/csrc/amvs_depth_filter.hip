@@ -29,13 +29,6 @@ namespace amvs {
 
 namespace {
 
-// (a failure synchronises `st` first: the scratch leases go back to the cache with nothing in flight, amvs_buffer.h)
-#define FCHK(call)                                                  \
-    do {                                                            \
-        hipError_t e_ = (call);                                     \
-        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
-    } while (0)
-
 // pixels of one map a launch covers in one trip of the grid-stride loop: FILTER_MAX_BLOCKS_X workgroups of 256 lanes
 constexpr int FILTER_MAX_BLOCKS_X = 256;
 
@@ -156,13 +149,13 @@ hipError_t depth_filter(const float *depth, const float *conf, int n_maps, int H
     // the poses, two zeroed totals and the neighbour rows on the device: [12 n_maps doubles][2 x uint64][n_maps n_nbr int32]
     const size_t nd = 12 * (size_t)n_maps, ni = (size_t)n_maps * (size_t)n_nbr;
     ScratchCache::Lease consts;
-    FCHK(cache.lease(consts, sizeof(double) * nd + 16 + sizeof(int) * ni));
+    STCHK(cache.lease(consts, sizeof(double) * nd + 16 + sizeof(int) * ni));
     double *d_poses = consts.get<double>();
     unsigned long long *totals = (unsigned long long *)(d_poses + nd);
     int *d_nbr = (int *)(totals + 2);
-    FCHK(hipMemcpyAsync(d_poses, poses_h, sizeof(double) * nd, hipMemcpyHostToDevice, st));
-    FCHK(hipMemsetAsync(totals, 0, 16, st));
-    if (ni) FCHK(hipMemcpyAsync(d_nbr, nbr_h, sizeof(int) * ni, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(d_poses, poses_h, sizeof(double) * nd, hipMemcpyHostToDevice, st));
+    STCHK(hipMemsetAsync(totals, 0, 16, st));
+    if (ni) STCHK(hipMemcpyAsync(d_nbr, nbr_h, sizeof(int) * ni, hipMemcpyHostToDevice, st));
     FilterCamera cam;
     for (int k = 0; k < 9; ++k) { cam.K[k] = K_h[k]; cam.Ki[k] = Ki_h[k]; }
     // at most FILTER_MAX_BLOCKS_X workgroups along a map (an image above 65 536 pixels walks the grid-stride loop) and
@@ -173,10 +166,10 @@ hipError_t depth_filter(const float *depth, const float *conf, int n_maps, int H
     hipLaunchKernelGGL(depth_filter_kernel, dim3((unsigned)bx, (unsigned)by), dim3(256), 0, st, depth, conf, n_maps, H, W, cam,
                        (const double *)d_poses, (const int *)d_nbr, n_nbr, min_confidence, (double)max_px * (double)max_px,
                        (double)max_rel, min_consistent, refine ? 1 : 0, depth_out, count_out, totals);
-    FCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     unsigned long long h[2] = {0, 0};
-    FCHK(hipMemcpyAsync(h, totals, 16, hipMemcpyDeviceToHost, st));
-    FCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(h, totals, 16, hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     counts[0] = (long long)h[0]; counts[1] = (long long)h[1];
     return hipSuccess;
 }

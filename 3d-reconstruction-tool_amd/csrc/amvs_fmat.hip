@@ -10,16 +10,18 @@
 //     hypotheses whose nine doubles are wave-uniform (read through the scalar cache), the inlier predicate goes through
 //     a ballot and a population count, and lane 0 adds the count to the hypothesis' counter (no add for a zero).
 //     Integers only: any grid shape gives the same counts.
-// fmat_partials_kernel / fmat_total_kernel: the sums of the refit, one lane per (block of 64 matches, entry), then one
+// fmat_partials_kernel / ransac_total_kernel: the sums of the refit, one lane per (block of 64 matches, entry), then one
 //     lane per entry adding the partials in ascending order.  The 9 x 9 Jacobi of the refit runs once, on the host,
 //     through the same jacobi<N>() the hypothesis kernel compiles.
-// jacobi<N>(), mix64(), fmat_total_kernel and fmat_argmax_kernel are in amvs_ransac_common.h, shared with amvs_pnp.hip.
+// Shared with amvs_pnp.hip: jacobi<N>(), the sampler, the wave's tally, the scoring tile and Points
+// (amvs_ransac_common.h); ransac_total_kernel, ransac_argmax_kernel, Work, the halves of a pass and the RANSAC itself,
+// ransac_run, to which FmatModel below gives what is the fundamental matrix's own (amvs_ransac_run.h).
 //
 // -ffp-contract=off (Makefile): a * b + c below is two roundings, on the device and on the host.
 #define AMVS_TU_ID 21
 #include "amvs_check.h"
 #include "amvs_fmat_host.h"
-#include "amvs_ransac_common.h"
+#include "amvs_ransac_run.h"
 #include "../../include/amvs_epipolar.h"
 
 #include <cmath>
@@ -30,13 +32,8 @@ namespace amvs {
 
 namespace {
 
-#define FCHK(call)                                                  \
-    do {                                                            \
-        hipError_t e_ = (call);                                     \
-        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
-    } while (0)
-
-constexpr int HYP_TILE = 32;          // hypotheses a scoring workgroup walks
+using Tile = ScoreTile<32>;           // hypotheses a scoring workgroup walks
+using Points2 = Points<2, 2>;         // a: the matches' points in the first view, b: in the second
 constexpr int N_TRI = 45;             // entries of the upper triangle of the 9 x 9 M
 constexpr double ROOT2 = 1.4142135623730951;
 
@@ -91,20 +88,13 @@ __global__ __launch_bounds__(64) void fmat_hypotheses_kernel(const float *__rest
     if (j >= count) return;                     // (no barrier below: a lane touches its own LDS column only)
     const unsigned long long h = (unsigned long long)first + (unsigned long long)j;
 
-    int idx[8], sorted[8];
+    int idx[8];
+    sample<8>(seed, h, m, idx);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        int r = (int)(mix64(seed ^ mix64(8ull * h + (unsigned long long)k)) % (unsigned long long)(m - k));
-#pragma unroll
-        for (int i = 0; i < k; ++i)
-            if (r >= sorted[i]) r += 1;
-        idx[k] = AMVS_IDX(r, m);
-        int v = r;                              // insert into the ascending list
-#pragma unroll
-        for (int i = 0; i < k; ++i)
-            if (v < sorted[i]) { const int tmp = sorted[i]; sorted[i] = v; v = tmp; }
-        sorted[k] = v;
+        const int r = idx[k];
         idx_out[8 * (size_t)j + k] = r;
+        idx[k] = AMVS_IDX(r, m);
     }
 
     double x1[8], y1[8], x2[8], y2[8];
@@ -160,13 +150,10 @@ __global__ __launch_bounds__(256) void fmat_score_kernel(const double *__restric
     const int ii = live ? i : 0;
     const double x1 = (double)pts1[2 * ii], y1 = (double)pts1[2 * ii + 1];
     const double x2 = (double)pts2[2 * ii], y2 = (double)pts2[2 * ii + 1];
-    const int h0 = (int)blockIdx.y * HYP_TILE, h1 = h0 + HYP_TILE < n ? h0 + HYP_TILE : n;
-    const bool lane0 = (threadIdx.x & 63) == 0;
-    for (int h = h0; h < h1; ++h) {
+    const int h1 = Tile::end(n);
+    for (int h = Tile::begin(); h < h1; ++h) {
         const double *Fh = F + 9 * (size_t)h;                       // wave-uniform: scalar loads
-        const bool in = live && fmat_is_inlier(Fh, x1, y1, x2, y2, t2);
-        const int c = __popcll(__ballot(in));
-        if (c != 0 && lane0) atomicAdd(&counts[h], c);
+        tally_wave(live && fmat_is_inlier(Fh, x1, y1, x2, y2, t2), counts, h);
     }
 }
 
@@ -180,8 +167,7 @@ __global__ __launch_bounds__(256) void fmat_inliers_kernel(const FMat F, const f
         in = fmat_is_inlier(F.f, (double)pts1[2 * i], (double)pts1[2 * i + 1], (double)pts2[2 * i], (double)pts2[2 * i + 1], t2);
         mask[i] = in ? 1 : 0;
     }
-    const int c = __popcll(__ballot(in));
-    if (c != 0 && (threadIdx.x & 63) == 0) atomicAdd(count, c);
+    tally_wave(in, count);
 }
 
 // The block partials of the refit's sums.  pass 0: x1, y1, x2, y2 (4 entries); pass 1: the two distances to the
@@ -221,66 +207,32 @@ __global__ __launch_bounds__(256) void fmat_partials_kernel(int pass, int entrie
     part[t] = acc;
 }
 
-inline dim3 blocks_for(long long n, int per) { return dim3((unsigned)((n + per - 1) / per)); }
-
-// the two point arrays of a call, on the device
-struct Points {
-    ScratchCache::Lease buf;
-    const float *p1 = nullptr, *p2 = nullptr;
-    hipError_t upload(const float *h1, const float *h2, int m, ScratchCache &cache, hipStream_t st)
-    {
-        const size_t bytes = sizeof(float) * 2 * (size_t)m;
-        hipError_t e = cache.lease(buf, 2 * bytes);
-        if (e != hipSuccess) return e;
-        float *d = buf.get<float>();
-        p1 = d;
-        p2 = d + 2 * (size_t)m;
-        e = hipMemcpyAsync(d, h1, bytes, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-        return hipMemcpyAsync(d + 2 * (size_t)m, h2, bytes, hipMemcpyHostToDevice, st);
-    }
-};
-
-// scratch of the fits and inlier passes of one call
-struct Work {
-    ScratchCache::Lease part, total, count;
-    hipError_t reserve(int m, ScratchCache &cache)
-    {
-        const size_t n_blocks = ((size_t)m + AMVS_FMAT_BLOCK - 1) / AMVS_FMAT_BLOCK;
-        hipError_t e = cache.lease(part, sizeof(double) * N_TRI * n_blocks);
-        if (e == hipSuccess) e = cache.lease(total, sizeof(double) * 64);
-        if (e == hipSuccess) e = cache.lease(count, sizeof(int) * 2);
-        return e;
-    }
-};
+inline int n_blocks_of(int m) { return (m + AMVS_FMAT_BLOCK - 1) / AMVS_FMAT_BLOCK; }
 
 // SUM of one pass over the set into out[entries]
-hipError_t sum_pass(int pass, int entries, const Norm &nrm, const Points &P, const unsigned char *mask_d, int m, Work &w, double *out,
+hipError_t sum_pass(int pass, int entries, const Norm &nrm, const Points2 &P, const unsigned char *mask_d, int m, Work &w, double *out,
                     hipStream_t st)
 {
-    const int n_blocks = (m + AMVS_FMAT_BLOCK - 1) / AMVS_FMAT_BLOCK;
-    hipLaunchKernelGGL(fmat_partials_kernel, blocks_for((long long)n_blocks * entries, 256), dim3(256), 0, st, pass, entries, nrm, P.p1, P.p2,
+    const int n_blocks = n_blocks_of(m);
+    hipLaunchKernelGGL(fmat_partials_kernel, blocks_for((long long)n_blocks * entries, 256), dim3(256), 0, st, pass, entries, nrm, P.a, P.b,
                        mask_d, m, n_blocks, w.part.get<double>());
-    FCHK(hipGetLastError());
-    hipLaunchKernelGGL(fmat_total_kernel, dim3(1), dim3(64), 0, st, (const double *)w.part.get(), n_blocks, entries, w.total.get<double>());
-    FCHK(hipGetLastError());
-    FCHK(hipMemcpyAsync(out, w.total.get(), sizeof(double) * entries, hipMemcpyDeviceToHost, st));
-    return hipStreamSynchronize(st);
+    STCHK(hipGetLastError());
+    return pass_totals(w, n_blocks, entries, out, st);
 }
 
 // the refit (steps 1-7 of the header) to the set mask_d (NULL: all) of n_set members
-hipError_t refit(const Points &P, const unsigned char *mask_d, int m, long long n_set, Work &w, double F[9], hipStream_t st)
+hipError_t refit_dev(const Points2 &P, const unsigned char *mask_d, int m, long long n_set, Work &w, double F[9], hipStream_t st)
 {
     const double N = (double)n_set;
     Norm nrm{};
     double s[N_TRI];
-    FCHK(sum_pass(0, 4, nrm, P, mask_d, m, w, s, st));
+    STCHK(sum_pass(0, 4, nrm, P, mask_d, m, w, s, st));
     nrm.cx1 = s[0] / N; nrm.cy1 = s[1] / N; nrm.cx2 = s[2] / N; nrm.cy2 = s[3] / N;
-    FCHK(sum_pass(1, 2, nrm, P, mask_d, m, w, s, st));
+    STCHK(sum_pass(1, 2, nrm, P, mask_d, m, w, s, st));
     nrm.s1 = ROOT2 / (s[0] / N);
     nrm.s2 = ROOT2 / (s[1] / N);
     double tri[N_TRI], V[81], f[9];
-    FCHK(sum_pass(2, N_TRI, nrm, P, mask_d, m, w, tri, st));
+    STCHK(sum_pass(2, N_TRI, nrm, P, mask_d, m, w, tri, st));
     jacobi<9, 1>(JacobiState<9, 1>{tri, V}, f);
     // rank 2
     double A[6], VA[9], v[3];
@@ -306,164 +258,125 @@ hipError_t refit(const Points &P, const unsigned char *mask_d, int m, long long 
 }
 
 // mask_d[i] and the count of the inliers of F
-hipError_t inliers_dev(const double F[9], const Points &P, int m, double t2, unsigned char *mask_d, Work &w, long long *count,
+hipError_t inliers_dev(const double F[9], const Points2 &P, int m, double t2, unsigned char *mask_d, Work &w, long long *count,
                        hipStream_t st)
 {
     FMat a;
     std::memcpy(a.f, F, sizeof(a.f));
-    FCHK(hipMemsetAsync(w.count.get(), 0, sizeof(int), st));
-    hipLaunchKernelGGL(fmat_inliers_kernel, blocks_for(m, 256), dim3(256), 0, st, a, P.p1, P.p2, m, t2, mask_d, w.count.get<int>());
-    FCHK(hipGetLastError());
-    int c = 0;
-    FCHK(hipMemcpyAsync(&c, w.count.get(), sizeof(int), hipMemcpyDeviceToHost, st));
-    FCHK(hipStreamSynchronize(st));
-    *count = c;
-    return hipSuccess;
+    return count_inliers(w, count, st, [&](int *count_d) {
+        hipLaunchKernelGGL(fmat_inliers_kernel, blocks_for(m, 256), dim3(256), 0, st, a, P.a, P.b, m, t2, mask_d, count_d);
+    });
 }
 
-void launch_hypotheses(const Points &P, int m, uint64_t seed, int first, int count, int *idx_d, double *F_d, hipStream_t st)
+void launch_hypotheses(const Points2 &P, int m, uint64_t seed, int first, int count, int *idx_d, double *F_d, hipStream_t st)
 {
-    hipLaunchKernelGGL(fmat_hypotheses_kernel, blocks_for(count, 64), dim3(64), 0, st, P.p1, P.p2, m, (unsigned long long)seed, first, count,
+    hipLaunchKernelGGL(fmat_hypotheses_kernel, blocks_for(count, 64), dim3(64), 0, st, P.a, P.b, m, (unsigned long long)seed, first, count,
                        idx_d, F_d);
 }
 
-void launch_score(const double *F_d, int n, const Points &P, int m, double t2, int *counts_d, hipStream_t st)
+void launch_score(const double *F_d, int n, const Points2 &P, int m, double t2, int *counts_d, hipStream_t st)
 {
-    hipLaunchKernelGGL(fmat_score_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)((n + HYP_TILE - 1) / HYP_TILE)), dim3(256), 0, st, F_d,
-                       n, P.p1, P.p2, m, t2, counts_d);
+    hipLaunchKernelGGL(fmat_score_kernel, Tile::grid(m, n), dim3(256), 0, st, F_d, n, P.a, P.b, m, t2, counts_d);
 }
+
+// what ransac_run asks of a model (amvs_ransac_run.h): the fundamental matrix, from samples of eight matches
+struct FmatModel {
+    static constexpr int SAMPLE = 8, BATCH = AMVS_FMAT_BATCH;
+    using Estimate = FMat;
+    const float *pts1_h, *pts2_h;
+    int m;
+    double t2;
+    uint64_t seed;
+    Points2 P;
+    Work w;
+    ScratchCache::Lease idx, F;
+
+    hipError_t prepare(ScratchCache &cache, hipStream_t st)
+    {
+        STCHK(P.upload(pts1_h, pts2_h, m, cache, st));
+        STCHK(w.reserve(N_TRI, n_blocks_of(m), cache));
+        STCHK(cache.lease(idx, sizeof(int) * 8 * BATCH));
+        return cache.lease(F, sizeof(double) * 9 * BATCH);
+    }
+    void hypotheses(int first, int count, hipStream_t st) { launch_hypotheses(P, m, seed, first, count, idx.get<int>(), F.get<double>(), st); }
+    void score(int n, int *counts_d, hipStream_t st) { launch_score(F.get<double>(), n, P, m, t2, counts_d, st); }
+    hipError_t fetch(FMat &e, hipStream_t st) { return hipMemcpyAsync(e.f, F.get(), sizeof(e.f), hipMemcpyDeviceToHost, st); }
+    hipError_t inliers(const FMat &e, unsigned char *mask, long long *n, hipStream_t st) { return inliers_dev(e.f, P, m, t2, mask, w, n, st); }
+    hipError_t refit(FMat &e, const unsigned char *mask, long long n_set, hipStream_t st) { return refit_dev(P, mask, m, n_set, w, e.f, st); }
+    static double all_inliers(double wr) { const double w2 = wr * wr, w4 = w2 * w2; return w4 * w4; }     // the header's ((w w)^2)^2
+};
 
 }  // namespace
 
 hipError_t fmat_hypotheses(const float *pts1_h, const float *pts2_h, int m, uint64_t seed, int first, int count, int *idx_h,
                            double *F_h, ScratchCache &cache, hipStream_t st)
 {
-    Points P;
+    Points2 P;
     ScratchCache::Lease idx, F;
-    FCHK(P.upload(pts1_h, pts2_h, m, cache, st));
-    FCHK(cache.lease(idx, sizeof(int) * 8 * (size_t)count));
-    FCHK(cache.lease(F, sizeof(double) * 9 * (size_t)count));
+    STCHK(P.upload(pts1_h, pts2_h, m, cache, st));
+    STCHK(cache.lease(idx, sizeof(int) * 8 * (size_t)count));
+    STCHK(cache.lease(F, sizeof(double) * 9 * (size_t)count));
     launch_hypotheses(P, m, seed, first, count, idx.get<int>(), F.get<double>(), st);
-    FCHK(hipGetLastError());
-    FCHK(hipMemcpyAsync(idx_h, idx.get(), sizeof(int) * 8 * (size_t)count, hipMemcpyDeviceToHost, st));
-    FCHK(hipMemcpyAsync(F_h, F.get(), sizeof(double) * 9 * (size_t)count, hipMemcpyDeviceToHost, st));
+    STCHK(hipGetLastError());
+    STCHK(hipMemcpyAsync(idx_h, idx.get(), sizeof(int) * 8 * (size_t)count, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(F_h, F.get(), sizeof(double) * 9 * (size_t)count, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
 hipError_t fmat_score(const double *F_h, int n, const float *pts1_h, const float *pts2_h, int m, double threshold, int *counts_h,
                       ScratchCache &cache, hipStream_t st)
 {
-    Points P;
+    Points2 P;
     ScratchCache::Lease F, counts;
-    FCHK(P.upload(pts1_h, pts2_h, m, cache, st));
-    FCHK(cache.lease(F, sizeof(double) * 9 * (size_t)n));
-    FCHK(cache.lease(counts, sizeof(int) * (size_t)n));
-    FCHK(hipMemcpyAsync(F.get(), F_h, sizeof(double) * 9 * (size_t)n, hipMemcpyHostToDevice, st));
-    FCHK(hipMemsetAsync(counts.get(), 0, sizeof(int) * (size_t)n, st));
+    STCHK(P.upload(pts1_h, pts2_h, m, cache, st));
+    STCHK(cache.lease(F, sizeof(double) * 9 * (size_t)n));
+    STCHK(cache.lease(counts, sizeof(int) * (size_t)n));
+    STCHK(hipMemcpyAsync(F.get(), F_h, sizeof(double) * 9 * (size_t)n, hipMemcpyHostToDevice, st));
+    STCHK(hipMemsetAsync(counts.get(), 0, sizeof(int) * (size_t)n, st));
     launch_score(F.get<double>(), n, P, m, threshold * threshold, counts.get<int>(), st);
-    FCHK(hipGetLastError());
-    FCHK(hipMemcpyAsync(counts_h, counts.get(), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    STCHK(hipGetLastError());
+    STCHK(hipMemcpyAsync(counts_h, counts.get(), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
 hipError_t fmat_inliers(const double F[9], const float *pts1_h, const float *pts2_h, int m, double threshold,
                         unsigned char *mask_h, long long *count, ScratchCache &cache, hipStream_t st)
 {
-    Points P;
+    Points2 P;
     Work w;
     ScratchCache::Lease mask;
-    FCHK(P.upload(pts1_h, pts2_h, m, cache, st));
-    FCHK(w.reserve(m, cache));
-    FCHK(cache.lease(mask, (size_t)m));
-    FCHK(inliers_dev(F, P, m, threshold * threshold, mask.get<unsigned char>(), w, count, st));
-    FCHK(hipMemcpyAsync(mask_h, mask.get(), (size_t)m, hipMemcpyDeviceToHost, st));
+    STCHK(P.upload(pts1_h, pts2_h, m, cache, st));
+    STCHK(w.reserve(N_TRI, n_blocks_of(m), cache));
+    STCHK(cache.lease(mask, (size_t)m));
+    STCHK(inliers_dev(F, P, m, threshold * threshold, mask.get<unsigned char>(), w, count, st));
+    STCHK(hipMemcpyAsync(mask_h, mask.get(), (size_t)m, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
 hipError_t fmat_fit(const float *pts1_h, const float *pts2_h, const unsigned char *mask_h, int m, long long n_set, double F_out[9],
                     ScratchCache &cache, hipStream_t st)
 {
-    Points P;
+    Points2 P;
     Work w;
     ScratchCache::Lease mask;
-    FCHK(P.upload(pts1_h, pts2_h, m, cache, st));
-    FCHK(w.reserve(m, cache));
+    STCHK(P.upload(pts1_h, pts2_h, m, cache, st));
+    STCHK(w.reserve(N_TRI, n_blocks_of(m), cache));
     if (mask_h) {
-        FCHK(cache.lease(mask, (size_t)m));
-        FCHK(hipMemcpyAsync(mask.get(), mask_h, (size_t)m, hipMemcpyHostToDevice, st));
+        STCHK(cache.lease(mask, (size_t)m));
+        STCHK(hipMemcpyAsync(mask.get(), mask_h, (size_t)m, hipMemcpyHostToDevice, st));
     }
-    return refit(P, mask_h ? mask.get<unsigned char>() : nullptr, m, n_set, w, F_out, st);
+    return refit_dev(P, mask_h ? mask.get<unsigned char>() : nullptr, m, n_set, w, F_out, st);
 }
 
 hipError_t fmat_ransac(const float *pts1_h, const float *pts2_h, int m, double threshold, double confidence, int max_hypotheses,
                        uint64_t seed, double F_out[9], unsigned char *mask_h, long long *n_inliers, int info[3],
                        ScratchCache &cache, hipStream_t st)
 {
-    const double t2 = threshold * threshold;
-    Points P;
-    Work w;
-    ScratchCache::Lease idx, F, counts, best2, mask_a, mask_b;
-    FCHK(P.upload(pts1_h, pts2_h, m, cache, st));
-    FCHK(w.reserve(m, cache));
-    FCHK(cache.lease(idx, sizeof(int) * 8 * AMVS_FMAT_BATCH));
-    FCHK(cache.lease(F, sizeof(double) * 9 * AMVS_FMAT_BATCH));
-    FCHK(cache.lease(counts, sizeof(int) * AMVS_FMAT_BATCH));
-    FCHK(cache.lease(best2, sizeof(int) * 2));
-    FCHK(cache.lease(mask_a, (size_t)m));
-    FCHK(cache.lease(mask_b, (size_t)m));
-
-    int done = 0, best = -1, best_h = 0;
-    for (;;) {
-        const int nb = max_hypotheses - done < AMVS_FMAT_BATCH ? max_hypotheses - done : AMVS_FMAT_BATCH;
-        launch_hypotheses(P, m, seed, done, nb, idx.get<int>(), F.get<double>(), st);
-        FCHK(hipGetLastError());
-        FCHK(hipMemsetAsync(counts.get(), 0, sizeof(int) * (size_t)nb, st));
-        launch_score(F.get<double>(), nb, P, m, t2, counts.get<int>(), st);
-        FCHK(hipGetLastError());
-        hipLaunchKernelGGL(fmat_argmax_kernel, dim3(1), dim3(1024), 0, st, (const int *)counts.get(), nb, done, best2.get<int>());
-        FCHK(hipGetLastError());
-        int got[2] = {0, 0};
-        FCHK(hipMemcpyAsync(got, best2.get(), sizeof(got), hipMemcpyDeviceToHost, st));
-        FCHK(hipStreamSynchronize(st));
-        if (got[0] > best) { best = got[0]; best_h = got[1]; }     // (a later batch wins only with a larger count)
-        done += nb;
-        const double wr = (double)best / (double)m;
-        double p = wr * wr;
-        p = p * p;
-        p = p * p;
-        double N;
-        if (p >= 1.0) N = 0.0;
-        else if (1.0 - p == 1.0) N = (double)max_hypotheses;
-        else N = std::ceil(std::log(1.0 - confidence) / std::log(1.0 - p));
-        if ((double)done >= N || done == max_hypotheses) break;
-    }
-    info[0] = done; info[1] = best_h; info[2] = best;
-
-    for (int e = 0; e < 9; ++e) F_out[e] = 0.0;
-    std::memset(mask_h, 0, (size_t)m);
-    *n_inliers = 0;
-    if (best < 8) return hipSuccess;
-
-    // the best hypothesis' F again (the sampler is a function of h), its inliers, and the two refits
-    double Fh[9], F1[9], F2[9];
-    launch_hypotheses(P, m, seed, best_h, 1, idx.get<int>(), F.get<double>(), st);
-    FCHK(hipGetLastError());
-    FCHK(hipMemcpyAsync(Fh, F.get(), sizeof(Fh), hipMemcpyDeviceToHost, st));
-    FCHK(hipStreamSynchronize(st));
-    long long n0 = 0, n1 = 0, n2 = 0;
-    unsigned char *ma = mask_a.get<unsigned char>(), *mb = mask_b.get<unsigned char>();
-    FCHK(inliers_dev(Fh, P, m, t2, ma, w, &n0, st));
-    if (n0 < 8) return hipSuccess;                      // (n0 == best >= 8: unreachable, kept for the refit's division)
-    FCHK(refit(P, ma, m, n0, w, F1, st));
-    FCHK(inliers_dev(F1, P, m, t2, mb, w, &n1, st));
-    if (n1 < 8) return hipSuccess;
-    FCHK(refit(P, mb, m, n1, w, F2, st));
-    FCHK(inliers_dev(F2, P, m, t2, ma, w, &n2, st));
-    const bool second = n2 >= n1;
-    std::memcpy(F_out, second ? F2 : F1, sizeof(double) * 9);
-    *n_inliers = second ? n2 : n1;
-    FCHK(hipMemcpyAsync(mask_h, second ? ma : mb, (size_t)m, hipMemcpyDeviceToHost, st));
-    return hipStreamSynchronize(st);
+    FmatModel model{pts1_h, pts2_h, m, threshold * threshold, seed};
+    FMat best{};
+    const hipError_t e = ransac_run(model, m, confidence, max_hypotheses, &best, mask_h, n_inliers, info, cache, st);
+    std::memcpy(F_out, best.f, sizeof(best.f));
+    return e;
 }
 
 }  // namespace amvs

@@ -20,13 +20,6 @@ namespace amvs {
 
 namespace {
 
-// (a failure synchronises `st` first: the scratch leases go back to the cache with nothing in flight, amvs_buffer.h)
-#define FCHK(call)                                                  \
-    do {                                                            \
-        hipError_t e_ = (call);                                     \
-        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
-    } while (0)
-
 // per-pixel flag: confidence >= min_views (mvs_patchmatch.py:545)
 __global__ __launch_bounds__(256) void fuse_flag_kernel(const float *__restrict__ conf, long long n,
                                                         float min_views, unsigned char *__restrict__ flag)
@@ -201,18 +194,18 @@ hipError_t select_indices(const unsigned char *flag, long long n, long long *out
 {
     hipcub::CountingInputIterator<long long> iota(0);
     size_t bytes = 0;
-    FCHK(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flag, out, d_count, (int)n, st));
-    FCHK(cache.lease(tmp, bytes));
-    FCHK(hipcub::DeviceSelect::Flagged(tmp.get(), bytes, iota, flag, out, d_count, (int)n, st));
-    FCHK(hipMemcpyAsync(h_count, d_count, sizeof(long long), hipMemcpyDeviceToHost, st));
+    STCHK(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flag, out, d_count, (int)n, st));
+    STCHK(cache.lease(tmp, bytes));
+    STCHK(hipcub::DeviceSelect::Flagged(tmp.get(), bytes, iota, flag, out, d_count, (int)n, st));
+    STCHK(hipMemcpyAsync(h_count, d_count, sizeof(long long), hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
 hipError_t sort_keys(double *in, double *out, long long n, ScratchCache &cache, Lease &tmp, hipStream_t st)
 {
     size_t bytes = 0;
-    FCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, in, out, (int)n, 0, 64, st));
-    FCHK(cache.lease(tmp, bytes));
+    STCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, in, out, (int)n, 0, 64, st));
+    STCHK(cache.lease(tmp, bytes));
     return hipcub::DeviceRadixSort::SortKeys(tmp.get(), bytes, in, out, (int)n, 0, 64, st);
 }
 
@@ -225,9 +218,9 @@ hipError_t voxel_first_of_key(const double *pts, const unsigned char *rgb, long 
 {
     *m3_out = 0;
     Lease keysA, keysB, idxA, idxB, pick;
-    FCHK(cache.lease(keysA, 8 * m2)); FCHK(cache.lease(keysB, 8 * m2)); FCHK(cache.lease(idxA, 8 * m2));
-    FCHK(cache.lease(idxB, 8 * m2)); FCHK(cache.lease(pick, 8 * m2));
-    FCHK(cache.lease(flag, m2));
+    STCHK(cache.lease(keysA, 8 * m2)); STCHK(cache.lease(keysB, 8 * m2)); STCHK(cache.lease(idxA, 8 * m2));
+    STCHK(cache.lease(idxB, 8 * m2)); STCHK(cache.lease(pick, 8 * m2));
+    STCHK(cache.lease(flag, m2));
     if (grid)
         hipLaunchKernelGGL(grid_key_kernel, grid_for(m2), dim3(256), 0, st, pts, sel, m2, m_src, voxel, *grid, keysA.get<long long>());
     else
@@ -235,29 +228,29 @@ hipError_t voxel_first_of_key(const double *pts, const unsigned char *rgb, long 
     hipLaunchKernelGGL(iota_kernel, grid_for(m2), dim3(256), 0, st, idxA.get<long long>(), m2);
     {
         size_t bytes = 0;
-        FCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, keysA.get<long long>(), keysB.get<long long>(),
+        STCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, keysA.get<long long>(), keysB.get<long long>(),
                                                 idxA.get<long long>(), idxB.get<long long>(), (int)m2, 0, 64, st));
-        FCHK(cache.lease(tmp, bytes));
-        FCHK(hipcub::DeviceRadixSort::SortPairs(tmp.get(), bytes, keysA.get<long long>(), keysB.get<long long>(),
+        STCHK(cache.lease(tmp, bytes));
+        STCHK(hipcub::DeviceRadixSort::SortPairs(tmp.get(), bytes, keysA.get<long long>(), keysB.get<long long>(),
                                                 idxA.get<long long>(), idxB.get<long long>(), (int)m2, 0, 64, st));
     }
     hipLaunchKernelGGL(run_head_kernel, grid_for(m2), dim3(256), 0, st, (const long long *)keysB.get(), m2, flag.get<unsigned char>());
     long long m3 = 0;
     {   // positions (in sorted order) of the run heads -> original indices idxB[pos]
         size_t bytes = 0;
-        FCHK(hipcub::DeviceSelect::Flagged(nullptr, bytes, idxB.get<long long>(), flag.get<unsigned char>(),
+        STCHK(hipcub::DeviceSelect::Flagged(nullptr, bytes, idxB.get<long long>(), flag.get<unsigned char>(),
                                            pick.get<long long>(), cnt.get<long long>(), (int)m2, st));
-        FCHK(cache.lease(tmp, bytes));
-        FCHK(hipcub::DeviceSelect::Flagged(tmp.get(), bytes, idxB.get<long long>(), flag.get<unsigned char>(),
+        STCHK(cache.lease(tmp, bytes));
+        STCHK(hipcub::DeviceSelect::Flagged(tmp.get(), bytes, idxB.get<long long>(), flag.get<unsigned char>(),
                                            pick.get<long long>(), cnt.get<long long>(), (int)m2, st));
-        FCHK(hipMemcpyAsync(&m3, cnt.get(), 8, hipMemcpyDeviceToHost, st));
-        FCHK(hipStreamSynchronize(st));
+        STCHK(hipMemcpyAsync(&m3, cnt.get(), 8, hipMemcpyDeviceToHost, st));
+        STCHK(hipStreamSynchronize(st));
     }
-    FCHK(pts_out.reserve(3 * (size_t)(m3 > 0 ? m3 : 1), cache));
-    FCHK(rgb_out.reserve(3 * (size_t)(m3 > 0 ? m3 : 1), cache));
+    STCHK(pts_out.reserve(3 * (size_t)(m3 > 0 ? m3 : 1), cache));
+    STCHK(rgb_out.reserve(3 * (size_t)(m3 > 0 ? m3 : 1), cache));
     hipLaunchKernelGGL(gather_kernel, grid_for(m3), dim3(256), 0, st, pts, rgb, sel, (const long long *)pick.get(), m3, m2, m_src,
                        pts_out.get(), rgb_out.get());
-    FCHK(hipStreamSynchronize(st));
+    STCHK(hipStreamSynchronize(st));
     *m3_out = m3;
     return hipSuccess;
 }
@@ -278,49 +271,49 @@ hipError_t fuse_filter(const float *depth, const float *conf, const unsigned cha
     const long long n = (long long)n_maps * H * W;
     if (n <= 0 || n > 0x7FFFFFFFll) return hipErrorInvalidValue;
     Lease tmp, flag, sel, consts, cnt;
-    FCHK(cache.lease(flag, n));
-    FCHK(cache.lease(sel, sizeof(long long) * n));
-    FCHK(cache.lease(consts, sizeof(double) * (9 + 12 * n_maps)));
-    FCHK(cache.lease(cnt, sizeof(long long)));
+    STCHK(cache.lease(flag, n));
+    STCHK(cache.lease(sel, sizeof(long long) * n));
+    STCHK(cache.lease(consts, sizeof(double) * (9 + 12 * n_maps)));
+    STCHK(cache.lease(cnt, sizeof(long long)));
     double *d_Kinv = consts.get<double>(), *d_poses = d_Kinv + 9;
-    FCHK(hipMemcpyAsync(d_Kinv, Kinv_h, sizeof(double) * 9, hipMemcpyHostToDevice, st));
-    FCHK(hipMemcpyAsync(d_poses, poses_h, sizeof(double) * 12 * n_maps, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(d_Kinv, Kinv_h, sizeof(double) * 9, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(d_poses, poses_h, sizeof(double) * 12 * n_maps, hipMemcpyHostToDevice, st));
 
     // ---- fusion: np.where(confidence >= min_views), view by view, row-major ----
     hipLaunchKernelGGL(fuse_flag_kernel, grid_for(n), dim3(256), 0, st, conf, n, min_views, flag.get<unsigned char>());
     long long m = 0;
-    FCHK(select_indices(flag.get<unsigned char>(), n, sel.get<long long>(), cnt.get<long long>(), &m, cache, tmp, st));
+    STCHK(select_indices(flag.get<unsigned char>(), n, sel.get<long long>(), cnt.get<long long>(), &m, cache, tmp, st));
     counts[0] = counts[1] = m;
     if (m == 0) return hipSuccess;
     DeviceBuffer<double> pts;
     DeviceBuffer<unsigned char> rgb;
-    FCHK(pts.reserve(3 * (size_t)m, cache));
-    FCHK(rgb.reserve(3 * (size_t)m, cache));
+    STCHK(pts.reserve(3 * (size_t)m, cache));
+    STCHK(rgb.reserve(3 * (size_t)m, cache));
     hipLaunchKernelGGL(fuse_project_kernel, grid_for(m), dim3(256), 0, st, (const long long *)sel.get(), m, depth, bgr, H,
                        W, d_Kinv, d_poses, n_maps, pts.get(), rgb.get());
     if (!do_filter) {
-        FCHK(hipStreamSynchronize(st));
+        STCHK(hipStreamSynchronize(st));
         pts_out = std::move(pts); rgb_out = std::move(rgb);
         return hipSuccess;
     }
 
     // ---- filter: 95th-percentile radius around the per-axis median ----
     Lease colA, colB;
-    FCHK(cache.lease(colA, sizeof(double) * m));
-    FCHK(cache.lease(colB, sizeof(double) * m));
+    STCHK(cache.lease(colA, sizeof(double) * m));
+    STCHK(cache.lease(colB, sizeof(double) * m));
     double centroid[3];
     const long long lo = (m - 1) / 2;                         // middle element(s) of a sorted column
     for (int c = 0; c < 3; ++c) {
         hipLaunchKernelGGL(column_kernel, grid_for(m), dim3(256), 0, st, pts.get(), m, c, colA.get<double>());
-        FCHK(sort_keys(colA.get<double>(), colB.get<double>(), m, cache, tmp, st));
+        STCHK(sort_keys(colA.get<double>(), colB.get<double>(), m, cache, tmp, st));
         std::vector<double> mid(2, 0.0);
-        FCHK(hipMemcpyAsync(mid.data(), colB.get<double>() + lo, sizeof(double) * (m % 2 ? 1 : 2), hipMemcpyDeviceToHost, st));
-        FCHK(hipStreamSynchronize(st));
+        STCHK(hipMemcpyAsync(mid.data(), colB.get<double>() + lo, sizeof(double) * (m % 2 ? 1 : 2), hipMemcpyDeviceToHost, st));
+        STCHK(hipStreamSynchronize(st));
         centroid[c] = median_sorted(mid, m);
     }
     hipLaunchKernelGGL(dist_kernel, grid_for(m), dim3(256), 0, st, pts.get(), m, centroid[0], centroid[1], centroid[2],
                        colA.get<double>());
-    FCHK(sort_keys(colA.get<double>(), colB.get<double>(), m, cache, tmp, st));
+    STCHK(sort_keys(colA.get<double>(), colB.get<double>(), m, cache, tmp, st));
     // np.percentile(d, 95), method 'linear': virtual index 0.95*(m-1), numpy's _lerp
     double thr;
     {
@@ -330,20 +323,20 @@ hipError_t fuse_filter(const float *depth, const float *conf, const unsigned cha
         const long long next = prev + 1 < m ? prev + 1 : m - 1;
         const double t = vi - (double)prev;
         double ab[2];
-        FCHK(hipMemcpyAsync(&ab[0], colB.get<double>() + prev, sizeof(double), hipMemcpyDeviceToHost, st));
-        FCHK(hipMemcpyAsync(&ab[1], colB.get<double>() + next, sizeof(double), hipMemcpyDeviceToHost, st));
-        FCHK(hipStreamSynchronize(st));
+        STCHK(hipMemcpyAsync(&ab[0], colB.get<double>() + prev, sizeof(double), hipMemcpyDeviceToHost, st));
+        STCHK(hipMemcpyAsync(&ab[1], colB.get<double>() + next, sizeof(double), hipMemcpyDeviceToHost, st));
+        STCHK(hipStreamSynchronize(st));
         const double diff = ab[1] - ab[0];
         thr = t >= 0.5 ? ab[1] - diff * (1.0 - t) : ab[0] + diff * t;
     }
     hipLaunchKernelGGL(below_kernel, grid_for(m), dim3(256), 0, st, (const double *)colA.get(), m, thr, flag.get<unsigned char>());
     long long m2 = 0;
-    FCHK(select_indices(flag.get<unsigned char>(), m, sel.get<long long>(), cnt.get<long long>(), &m2, cache, tmp, st));
+    STCHK(select_indices(flag.get<unsigned char>(), m, sel.get<long long>(), cnt.get<long long>(), &m2, cache, tmp, st));
     if (m2 == 0) { counts[1] = 0; return hipSuccess; }
 
     // ---- voxel de-duplication: first point of every key, in key order ----
     long long m3 = 0;
-    FCHK(voxel_first_of_key(pts.get(), rgb.get(), m, (const long long *)sel.get(), m2, 0.01, cache, tmp, flag, cnt, pts_out,
+    STCHK(voxel_first_of_key(pts.get(), rgb.get(), m, (const long long *)sel.get(), m2, 0.01, cache, tmp, flag, cnt, pts_out,
                             rgb_out, &m3, st));
     counts[1] = m3;
     return hipSuccess;
@@ -362,30 +355,30 @@ hipError_t stereo_backproject(const float *depth, const float *conf, const unsig
     const long long HW = (long long)H * W, n = (long long)n_maps * HW;
     if (n <= 0 || n > 0x7FFFFFFFll) return hipErrorInvalidValue;
     Lease tmp, flag, sel, consts, cnt, bounds;
-    FCHK(cache.lease(flag, n));
-    FCHK(cache.lease(sel, sizeof(long long) * n));
-    FCHK(cache.lease(consts, sizeof(double) * (9 + 12 * n_maps)));
-    FCHK(cache.lease(cnt, sizeof(long long)));
-    FCHK(cache.lease(bounds, sizeof(long long) * (n_maps + 1)));
+    STCHK(cache.lease(flag, n));
+    STCHK(cache.lease(sel, sizeof(long long) * n));
+    STCHK(cache.lease(consts, sizeof(double) * (9 + 12 * n_maps)));
+    STCHK(cache.lease(cnt, sizeof(long long)));
+    STCHK(cache.lease(bounds, sizeof(long long) * (n_maps + 1)));
     double *d_Kinv = consts.get<double>(), *d_poses = d_Kinv + 9;
-    FCHK(hipMemcpyAsync(d_Kinv, Kinv_h, sizeof(double) * 9, hipMemcpyHostToDevice, st));
-    FCHK(hipMemcpyAsync(d_poses, poses_h, sizeof(double) * 12 * n_maps, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(d_Kinv, Kinv_h, sizeof(double) * 9, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(d_poses, poses_h, sizeof(double) * 12 * n_maps, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(stereo_flag_kernel, grid_for(n), dim3(256), 0, st, conf, depth, n, min_confidence,
                        flag.get<unsigned char>());
     long long m = 0;
-    FCHK(select_indices(flag.get<unsigned char>(), n, sel.get<long long>(), cnt.get<long long>(), &m, cache, tmp, st));
+    STCHK(select_indices(flag.get<unsigned char>(), n, sel.get<long long>(), cnt.get<long long>(), &m, cache, tmp, st));
     *total = m;
     if (per_map_h) {
         std::vector<long long> first(n_maps + 1, 0);
         hipLaunchKernelGGL(map_bounds_kernel, dim3((n_maps + 1 + 63) / 64), dim3(64), 0, st, (const long long *)sel.get(), m, HW,
                            n_maps, bounds.get<long long>());
-        FCHK(hipMemcpyAsync(first.data(), bounds.get(), sizeof(long long) * (n_maps + 1), hipMemcpyDeviceToHost, st));
-        FCHK(hipStreamSynchronize(st));
+        STCHK(hipMemcpyAsync(first.data(), bounds.get(), sizeof(long long) * (n_maps + 1), hipMemcpyDeviceToHost, st));
+        STCHK(hipStreamSynchronize(st));
         for (int j = 0; j < n_maps; ++j) per_map_h[j] = first[j + 1] - first[j];
     }
     if (m == 0) return hipSuccess;
-    FCHK(pts_out.reserve(3 * (size_t)m, cache));
-    FCHK(rgb_out.reserve(3 * (size_t)m, cache));
+    STCHK(pts_out.reserve(3 * (size_t)m, cache));
+    STCHK(rgb_out.reserve(3 * (size_t)m, cache));
     hipLaunchKernelGGL(fuse_project_kernel, grid_for(m), dim3(256), 0, st, (const long long *)sel.get(), m, depth, bgr, H,
                        W, d_Kinv, d_poses, n_maps, pts_out.get(), rgb_out.get());
     return hipStreamSynchronize(st);
@@ -400,10 +393,10 @@ hipError_t cloud_take(const double *pts, const unsigned char *rgb, long long n, 
     for (long long i = 0; i < m; ++i)
         if (idx_h[i] < 0 || idx_h[i] >= n) return hipErrorInvalidValue;
     Lease idx;
-    FCHK(cache.lease(idx, sizeof(long long) * m));
-    FCHK(hipMemcpyAsync(idx.get(), idx_h, sizeof(long long) * m, hipMemcpyHostToDevice, st));
-    FCHK(pts_out.reserve(3 * (size_t)m, cache));
-    FCHK(rgb_out.reserve(3 * (size_t)m, cache));
+    STCHK(cache.lease(idx, sizeof(long long) * m));
+    STCHK(hipMemcpyAsync(idx.get(), idx_h, sizeof(long long) * m, hipMemcpyHostToDevice, st));
+    STCHK(pts_out.reserve(3 * (size_t)m, cache));
+    STCHK(rgb_out.reserve(3 * (size_t)m, cache));
     hipLaunchKernelGGL(take_kernel, grid_for(m), dim3(256), 0, st, pts, rgb, (const long long *)idx.get(), m, n, pts_out.get(),
                        rgb_out.get());
     return hipStreamSynchronize(st);
@@ -421,13 +414,13 @@ hipError_t voxel_downsample(const double *pts, const unsigned char *rgb, long lo
     if (m <= 0) return hipSuccess;
     if (m > 0x7FFFFFFFll) return hipErrorInvalidValue;
     Lease tmp, flag, sel, cnt;
-    FCHK(cache.lease(flag, m));
-    FCHK(cache.lease(sel, sizeof(long long) * m));
-    FCHK(cache.lease(cnt, sizeof(long long)));
+    STCHK(cache.lease(flag, m));
+    STCHK(cache.lease(sel, sizeof(long long) * m));
+    STCHK(cache.lease(cnt, sizeof(long long)));
     long long m2 = m;
     if (keep_h) {
-        FCHK(hipMemcpyAsync(flag.get(), keep_h, m, hipMemcpyHostToDevice, st));
-        FCHK(select_indices(flag.get<unsigned char>(), m, sel.get<long long>(), cnt.get<long long>(), &m2, cache, tmp, st));
+        STCHK(hipMemcpyAsync(flag.get(), keep_h, m, hipMemcpyHostToDevice, st));
+        STCHK(select_indices(flag.get<unsigned char>(), m, sel.get<long long>(), cnt.get<long long>(), &m2, cache, tmp, st));
     } else {
         hipLaunchKernelGGL(iota_kernel, grid_for(m), dim3(256), 0, st, sel.get<long long>(), m);
     }
@@ -451,13 +444,13 @@ hipError_t voxel_downsample_grid(const double *pts, const unsigned char *rgb, lo
     GridKey g;
     for (int a = 0; a < 3; ++a) { g.origin[a] = origin[a]; g.lo[a] = lo[a]; g.ext[a] = ext[a]; }
     Lease tmp, flag, sel, cnt;
-    FCHK(cache.lease(flag, m));
-    FCHK(cache.lease(sel, sizeof(long long) * m));
-    FCHK(cache.lease(cnt, sizeof(long long)));
+    STCHK(cache.lease(flag, m));
+    STCHK(cache.lease(sel, sizeof(long long) * m));
+    STCHK(cache.lease(cnt, sizeof(long long)));
     long long m2 = m;
     if (keep_h) {
-        FCHK(hipMemcpyAsync(flag.get(), keep_h, m, hipMemcpyHostToDevice, st));
-        FCHK(select_indices(flag.get<unsigned char>(), m, sel.get<long long>(), cnt.get<long long>(), &m2, cache, tmp, st));
+        STCHK(hipMemcpyAsync(flag.get(), keep_h, m, hipMemcpyHostToDevice, st));
+        STCHK(select_indices(flag.get<unsigned char>(), m, sel.get<long long>(), cnt.get<long long>(), &m2, cache, tmp, st));
     } else {
         hipLaunchKernelGGL(iota_kernel, grid_for(m), dim3(256), 0, st, sel.get<long long>(), m);
     }

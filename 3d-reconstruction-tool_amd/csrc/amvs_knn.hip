@@ -37,13 +37,6 @@ namespace amvs {
 
 namespace {
 
-// (a failure synchronises `st` first: the scratch leases go back to the cache with nothing in flight, amvs_buffer.h)
-#define KCHK(call)                                                  \
-    do {                                                            \
-        hipError_t e_ = (call);                                     \
-        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
-    } while (0)
-
 constexpr int KNN_KMAX = 32;
 constexpr int KNN_GMAX = 256;       // cells per axis (dense table of at most 2^24 cells)
 constexpr int KNN_SHELLS = 2;       // Chebyshev shells a query walks on one grid level
@@ -391,12 +384,12 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
             // gathered on the device, then ONE contiguous copy (a strided hipMemcpy2D of 65 536 rows of 24 bytes took
             // 2 ms; dereferencing device memory from the host works through the PCIe BAR but takes ~4 us per read)
             ScratchCache::Lease d_sample;
-            KCHK(cache.lease(d_sample, sizeof(double) * 3 * (size_t)cnt));
+            STCHK(cache.lease(d_sample, sizeof(double) * 3 * (size_t)cnt));
             hipLaunchKernelGGL(knn_sample_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, points, stride, cnt,
                                d_sample.get<double>());
-            KCHK(hipGetLastError());
-            KCHK(hipMemcpyAsync(sample.data(), d_sample.get(), sizeof(double) * 3 * (size_t)cnt, hipMemcpyDeviceToHost, st));
-            KCHK(hipStreamSynchronize(st));
+            STCHK(hipGetLastError());
+            STCHK(hipMemcpyAsync(sample.data(), d_sample.get(), sizeof(double) * 3 * (size_t)cnt, hipMemcpyDeviceToHost, st));
+            STCHK(hipStreamSynchronize(st));
         } else {
             for (long long j = 0; j < cnt; ++j)
                 for (int a = 0; a < 3; ++a) sample[(size_t)(3 * j + a)] = points[3 * j * stride + a];
@@ -429,19 +422,19 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
     // the cell tables and the scan / select temporary grow with the grid levels
     ScratchCache::Lease l_pts, l_sorted, l_mean, l_cell, l_origin, l_pending, l_occ, l_iota, l_queries, l_nsel, l_count,
         l_start, l_tmp;
-    KCHK(cache.lease(l_pts, sizeof(double) * 3 * n));
-    KCHK(cache.lease(l_sorted, sizeof(double) * 3 * n));
-    KCHK(cache.lease(l_mean, sizeof(double) * n));
-    KCHK(cache.lease(l_cell, sizeof(int) * n));
-    KCHK(cache.lease(l_origin, sizeof(int) * n));
-    KCHK(cache.lease(l_pending, (size_t)n));
-    KCHK(cache.lease(l_occ, sizeof(int)));
+    STCHK(cache.lease(l_pts, sizeof(double) * 3 * n));
+    STCHK(cache.lease(l_sorted, sizeof(double) * 3 * n));
+    STCHK(cache.lease(l_mean, sizeof(double) * n));
+    STCHK(cache.lease(l_cell, sizeof(int) * n));
+    STCHK(cache.lease(l_origin, sizeof(int) * n));
+    STCHK(cache.lease(l_pending, (size_t)n));
+    STCHK(cache.lease(l_occ, sizeof(int)));
     double *const d_pts = l_pts.get<double>(), *const d_sorted = l_sorted.get<double>(), *const d_mean = l_mean.get<double>();
     int *const d_cell = l_cell.get<int>(), *const d_origin = l_origin.get<int>(), *const d_occ = l_occ.get<int>();
     unsigned char *const d_pending = l_pending.get<unsigned char>();
-    KCHK(hipMemcpyAsync(d_pts, points, sizeof(double) * 3 * n,
+    STCHK(hipMemcpyAsync(d_pts, points, sizeof(double) * 3 * n,
                         points_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    KCHK(hipMemsetAsync(d_pending, 1, (size_t)n, st));
+    STCHK(hipMemsetAsync(d_pending, 1, (size_t)n, st));
 
     const int bx = (int)std::min<long long>((n + 255) / 256, 4096);
     Grid gr{};
@@ -452,34 +445,34 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
         gr.h = edge; gr.inv_h = 1.0 / edge;
         for (int a = 0; a < 3; ++a) gr.g[a] = std::max(1, std::min(KNN_GMAX, (int)std::floor(ext[a] / edge) + 1));
         cells = (long long)gr.g[0] * gr.g[1] * gr.g[2];
-        KCHK(cache.lease(l_count, sizeof(int) * (cells + 1)));
-        KCHK(cache.lease(l_start, sizeof(int) * (cells + 1)));
+        STCHK(cache.lease(l_count, sizeof(int) * (cells + 1)));
+        STCHK(cache.lease(l_start, sizeof(int) * (cells + 1)));
         int *const d_count = l_count.get<int>(), *const d_start = l_start.get<int>();
-        KCHK(hipMemsetAsync(d_count, 0, sizeof(int) * (cells + 1), st));
+        STCHK(hipMemsetAsync(d_count, 0, sizeof(int) * (cells + 1), st));
         hipLaunchKernelGGL(knn_count_kernel, dim3(bx), dim3(256), 0, st, d_pts, n, gr, d_cell, d_count);
-        KCHK(hipGetLastError());
+        STCHK(hipGetLastError());
         size_t need = 0;
-        KCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_count, d_start, (int)(cells + 1), st));
-        KCHK(cache.lease(l_tmp, need));
-        KCHK(hipcub::DeviceScan::ExclusiveSum(l_tmp.get(), need, d_count, d_start, (int)(cells + 1), st));
+        STCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_count, d_start, (int)(cells + 1), st));
+        STCHK(cache.lease(l_tmp, need));
+        STCHK(hipcub::DeviceScan::ExclusiveSum(l_tmp.get(), need, d_count, d_start, (int)(cells + 1), st));
         if (per_cell >= 0.0) {
-            KCHK(hipMemsetAsync(d_occ, 0, sizeof(int), st));
+            STCHK(hipMemsetAsync(d_occ, 0, sizeof(int), st));
             const int cb = (int)std::min<long long>((cells + 255) / 256, 2048);
             hipLaunchKernelGGL(knn_occupied_kernel, dim3(cb), dim3(256), 0, st, d_count, cells, d_occ);
-            KCHK(hipGetLastError());
+            STCHK(hipGetLastError());
             int occupied = 0;
-            KCHK(hipMemcpyAsync(&occupied, d_occ, sizeof(int), hipMemcpyDeviceToHost, st));
-            KCHK(hipStreamSynchronize(st));
+            STCHK(hipMemcpyAsync(&occupied, d_occ, sizeof(int), hipMemcpyDeviceToHost, st));
+            STCHK(hipStreamSynchronize(st));
             per_cell = (double)n / (double)std::max(occupied, 1);
         }
         return hipSuccess;
     };
     auto query = [&](int max_shells) -> hipError_t {
         int *const d_count = l_count.get<int>(), *const d_start = l_start.get<int>();
-        KCHK(hipMemsetAsync(d_count, 0, sizeof(int) * (cells + 1), st));     // reused as the placement cursor
+        STCHK(hipMemsetAsync(d_count, 0, sizeof(int) * (cells + 1), st));     // reused as the placement cursor
         hipLaunchKernelGGL(knn_place_kernel, dim3(bx), dim3(256), 0, st, d_pts, n, d_cell, d_start, d_count,
                            d_sorted, d_origin, cells);
-        KCHK(hipGetLastError());
+        STCHK(hipGetLastError());
         return dispatch(KnnSizes{}, k, hipErrorInvalidValue, [&](auto kc) {
             return launch_query<kc()>(d_sorted, n, gr, d_start, d_origin, d_pending, max_shells, d_mean, st);
         });
@@ -490,7 +483,7 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
     int walk_again = 0;
     for (int attempt = 0; attempt < 6; ++attempt) {
         double per_cell = 0.0;
-        KCHK(bin(h, per_cell));
+        STCHK(bin(h, per_cell));
         fitted_per_cell = per_cell;
         const bool at_limit = gr.g[0] == KNN_GMAX || gr.g[1] == KNN_GMAX || gr.g[2] == KNN_GMAX;
         if (per_cell > 24.0 && !at_limit && h > h_min) { h = std::max(h * 0.5, h_min); continue; }
@@ -500,20 +493,20 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
     // coarser levels (edge x2 each) pick up the queries whose neighbourhood is sparser than two
     // shells of the level before; the last level may scan
     const double t_binned = debug ? ((void)hipStreamSynchronize(st), now_ms()) : 0.0;
-    KCHK(cache.lease(l_iota, sizeof(int) * n));
-    KCHK(cache.lease(l_queries, sizeof(int) * n));
-    KCHK(cache.lease(l_nsel, sizeof(int)));
+    STCHK(cache.lease(l_iota, sizeof(int) * n));
+    STCHK(cache.lease(l_queries, sizeof(int) * n));
+    STCHK(cache.lease(l_nsel, sizeof(int)));
     int *const d_iota = l_iota.get<int>(), *const d_queries = l_queries.get<int>(), *const d_nsel = l_nsel.get<int>();
     const int *const d_start = l_start.get<int>();           // (the tables of the last level are final)
     hipLaunchKernelGGL(knn_iota_kernel, dim3(bx), dim3(256), 0, st, d_iota, n);
-    KCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     // the still-pending queries, compacted (and counted) after every level
     auto pending_list = [&](int &count) -> hipError_t {
         size_t need = 0;
-        KCHK(hipcub::DeviceSelect::Flagged(nullptr, need, d_iota, d_pending, d_queries, d_nsel, (int)n, st));
-        KCHK(cache.lease(l_tmp, need));
-        KCHK(hipcub::DeviceSelect::Flagged(l_tmp.get(), need, d_iota, d_pending, d_queries, d_nsel, (int)n, st));
-        KCHK(hipMemcpyAsync(&count, d_nsel, sizeof(int), hipMemcpyDeviceToHost, st));
+        STCHK(hipcub::DeviceSelect::Flagged(nullptr, need, d_iota, d_pending, d_queries, d_nsel, (int)n, st));
+        STCHK(cache.lease(l_tmp, need));
+        STCHK(hipcub::DeviceSelect::Flagged(l_tmp.get(), need, d_iota, d_pending, d_queries, d_nsel, (int)n, st));
+        STCHK(hipMemcpyAsync(&count, d_nsel, sizeof(int), hipMemcpyDeviceToHost, st));
         return hipStreamSynchronize(st);
     };
     // the cell walk on the fine grid, then one cooperative box scan per query it left pending
@@ -528,15 +521,15 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
         };
         // a thread per query walks shells 0..1; a wave per query left scans the box R = 2 (the cells of shells
         // 0..2); a block per query still left scans the boxes R = 4, 8, ... until its rule holds
-        KCHK(query(1));
-        KCHK(pending_list(left));
+        STCHK(query(1));
+        STCHK(pending_list(left));
         walk_again = left;
         if (left > 0) {
-            KCHK(box(KNN_SHELLS, KNN_SHELLS, left));
-            KCHK(pending_list(left));
+            STCHK(box(KNN_SHELLS, KNN_SHELLS, left));
+            STCHK(pending_list(left));
         }
         if (debug) (void)hipEventRecord(e1.get(), st);
-        if (left > 0) KCHK(box(2 * KNN_SHELLS, 1 << 30, left));     // (R = 4 as a wave's pass of its own: no gain, measured)
+        if (left > 0) STCHK(box(2 * KNN_SHELLS, 1 << 30, left));     // (R = 4 as a wave's pass of its own: no gain, measured)
         if (debug) {
             (void)hipEventRecord(e2.get(), st);
             (void)hipStreamSynchronize(st);
@@ -549,8 +542,8 @@ hipError_t knn_mean_distance(const double *points, long long n, int k, double *m
         }
     }
     const double t_searched = debug ? ((void)hipStreamSynchronize(st), now_ms()) : 0.0;
-    KCHK(hipMemcpyAsync(mean_out, d_mean, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    KCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(mean_out, d_mean, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     if (debug)
         std::fprintf(stderr, "knn: box sample %.2f ms, allocate + bin %.2f, search %.2f, result to the host %.2f\n",
                      t_sampled - t_begin, t_binned - t_sampled, t_searched - t_binned, now_ms() - t_searched);

@@ -37,12 +37,6 @@ namespace amvs {
 
 namespace {
 
-#define MCHK(call)                                                  \
-    do {                                                            \
-        hipError_t e_ = (call);                                     \
-        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
-    } while (0)
-
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
@@ -258,13 +252,13 @@ hipError_t desc_set_device(const unsigned char *desc_d, int n, ScratchCache &cac
     slot.n = -1;
     const int n_pad = padded(n);
     if (n_pad > 0) {
-        MCHK(slot.frag.reserve((size_t)n_pad * 8, cache));
-        MCHK(slot.norm.reserve((size_t)n_pad, cache));
-        MCHK(slot.normk.reserve((size_t)n_pad, cache));
+        STCHK(slot.frag.reserve((size_t)n_pad * 8, cache));
+        STCHK(slot.norm.reserve((size_t)n_pad, cache));
+        STCHK(slot.normk.reserve((size_t)n_pad, cache));
         hipLaunchKernelGGL(desc_pack_kernel, grid_for(n_pad), dim3(256), 0, st, (const uint4 *)desc_d, n, n_pad, slot.frag.get(),
                            slot.norm.get(), slot.normk.get());
-        MCHK(hipGetLastError());
-        MCHK(hipStreamSynchronize(st));
+        STCHK(hipGetLastError());
+        STCHK(hipStreamSynchronize(st));
     }
     slot.n = n;
     return hipSuccess;
@@ -275,8 +269,8 @@ hipError_t desc_set(const unsigned char *desc_h, int n, ScratchCache &cache, Des
     slot.n = -1;
     ScratchCache::Lease src;
     if (n > 0) {
-        MCHK(cache.lease(src, (size_t)n * AMVS_DESC_DIM));
-        MCHK(hipMemcpyAsync(src.get(), desc_h, (size_t)n * AMVS_DESC_DIM, hipMemcpyHostToDevice, st));
+        STCHK(cache.lease(src, (size_t)n * AMVS_DESC_DIM));
+        STCHK(hipMemcpyAsync(src.get(), desc_h, (size_t)n * AMVS_DESC_DIM, hipMemcpyHostToDevice, st));
     }
     return desc_set_device(src.get<unsigned char>(), n, cache, slot, st);   // (synchronises: the staging lease goes back idle)
 }
@@ -289,14 +283,14 @@ hipError_t desc_knn2(const DescSlot &q, const DescSlot &t, ScratchCache &cache, 
     int cps = 1;
     const int splits = desc_knn2_splits(q.n, t.n, &cps);
     const int n_t_tiles = padded(t.n) / TILE, n_chunks = (t.n + CHUNK - 1) / CHUNK;
-    MCHK(cache.lease(partial, sizeof(unsigned long long) * 2 * (size_t)splits * q.n));
+    STCHK(cache.lease(partial, sizeof(unsigned long long) * 2 * (size_t)splits * q.n));
     hipLaunchKernelGGL(desc_knn2_kernel, dim3((unsigned)((q.n + QBLOCK - 1) / QBLOCK), (unsigned)splits), dim3(256), 0, st,
                        (const v4i *)q.frag.get(), (const int *)q.norm.get(), q.n, (const v4i *)t.frag.get(),
                        (const uint4 *)t.normk.get(), n_t_tiles, n_chunks, cps, partial.get<unsigned long long>());
-    MCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     hipLaunchKernelGGL(desc_knn2_merge_kernel, grid_for(q.n), dim3(256), 0, st, (const unsigned long long *)partial.get(), splits, q.n,
                        idx, dist2);
-    MCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     return hipSuccess;
 }
 
@@ -306,11 +300,11 @@ hipError_t desc_knn2_host(const DescSlot &q, const DescSlot &t, ScratchCache &ca
     if (q.n <= 0) return hipSuccess;
     ScratchCache::Lease partial, out;
     const size_t n2 = 2 * (size_t)q.n;
-    MCHK(cache.lease(out, sizeof(int) * 2 * n2));
+    STCHK(cache.lease(out, sizeof(int) * 2 * n2));
     int *idx = out.get<int>(), *dist2 = idx + n2;
-    MCHK(desc_knn2(q, t, cache, partial, idx, dist2, st));
-    MCHK(hipMemcpyAsync(idx_h, idx, sizeof(int) * n2, hipMemcpyDeviceToHost, st));
-    MCHK(hipMemcpyAsync(dist2_h, dist2, sizeof(int) * n2, hipMemcpyDeviceToHost, st));
+    STCHK(desc_knn2(q, t, cache, partial, idx, dist2, st));
+    STCHK(hipMemcpyAsync(idx_h, idx, sizeof(int) * n2, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(dist2_h, dist2, sizeof(int) * n2, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
@@ -322,38 +316,38 @@ hipError_t desc_match(const DescSlot &q, const DescSlot &t, float ratio, bool cr
     const double ratio2 = (double)ratio * (double)ratio;
     ScratchCache::Lease partial, partial_rev, fwd, rev, flag, sel, cnt, tmp, out;
     const size_t n2 = 2 * (size_t)q.n, r2 = 2 * (size_t)t.n;
-    MCHK(cache.lease(fwd, sizeof(int) * 2 * n2));
+    STCHK(cache.lease(fwd, sizeof(int) * 2 * n2));
     int *idx = fwd.get<int>(), *dist2 = idx + n2, *ridx = nullptr, *rdist2 = nullptr;
-    MCHK(desc_knn2(q, t, cache, partial, idx, dist2, st));
+    STCHK(desc_knn2(q, t, cache, partial, idx, dist2, st));
     if (cross_check) {
-        MCHK(cache.lease(rev, sizeof(int) * 2 * r2));
+        STCHK(cache.lease(rev, sizeof(int) * 2 * r2));
         ridx = rev.get<int>();
         rdist2 = ridx + r2;
-        MCHK(desc_knn2(t, q, cache, partial_rev, ridx, rdist2, st));
+        STCHK(desc_knn2(t, q, cache, partial_rev, ridx, rdist2, st));
     }
-    MCHK(cache.lease(flag, (size_t)q.n));
-    MCHK(cache.lease(sel, sizeof(int) * (size_t)q.n));
-    MCHK(cache.lease(cnt, sizeof(int)));
-    MCHK(cache.lease(out, sizeof(int) * 3 * (size_t)q.n));
+    STCHK(cache.lease(flag, (size_t)q.n));
+    STCHK(cache.lease(sel, sizeof(int) * (size_t)q.n));
+    STCHK(cache.lease(cnt, sizeof(int)));
+    STCHK(cache.lease(out, sizeof(int) * 3 * (size_t)q.n));
     hipLaunchKernelGGL(desc_ratio_kernel, grid_for(q.n), dim3(256), 0, st, (const int *)idx, (const int *)dist2, q.n, ratio2,
                        (const int *)ridx, (const int *)rdist2, t.n, flag.get<unsigned char>());
-    MCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     hipcub::CountingInputIterator<int> iota(0);
     size_t bytes = 0;
-    MCHK(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flag.get<unsigned char>(), sel.get<int>(), cnt.get<int>(), q.n, st));
-    MCHK(cache.lease(tmp, bytes));
-    MCHK(hipcub::DeviceSelect::Flagged(tmp.get(), bytes, iota, flag.get<unsigned char>(), sel.get<int>(), cnt.get<int>(), q.n, st));
+    STCHK(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flag.get<unsigned char>(), sel.get<int>(), cnt.get<int>(), q.n, st));
+    STCHK(cache.lease(tmp, bytes));
+    STCHK(hipcub::DeviceSelect::Flagged(tmp.get(), bytes, iota, flag.get<unsigned char>(), sel.get<int>(), cnt.get<int>(), q.n, st));
     int m = 0;
-    MCHK(hipMemcpyAsync(&m, cnt.get(), sizeof(int), hipMemcpyDeviceToHost, st));
-    MCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(&m, cnt.get(), sizeof(int), hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     if (m > 0) {
         hipLaunchKernelGGL(desc_gather_kernel, grid_for(m), dim3(256), 0, st, (const int *)sel.get(), m, q.n, (const int *)idx,
                            (const int *)dist2, out.get<int>());
-        MCHK(hipGetLastError());
-        MCHK(hipMemcpyAsync(q_idx_h, out.get<int>(), sizeof(int) * m, hipMemcpyDeviceToHost, st));
-        MCHK(hipMemcpyAsync(t_idx_h, out.get<int>() + q.n, sizeof(int) * m, hipMemcpyDeviceToHost, st));
-        MCHK(hipMemcpyAsync(dist2_h, out.get<int>() + 2 * (size_t)q.n, sizeof(int) * m, hipMemcpyDeviceToHost, st));
-        MCHK(hipStreamSynchronize(st));
+        STCHK(hipGetLastError());
+        STCHK(hipMemcpyAsync(q_idx_h, out.get<int>(), sizeof(int) * m, hipMemcpyDeviceToHost, st));
+        STCHK(hipMemcpyAsync(t_idx_h, out.get<int>() + q.n, sizeof(int) * m, hipMemcpyDeviceToHost, st));
+        STCHK(hipMemcpyAsync(dist2_h, out.get<int>() + 2 * (size_t)q.n, sizeof(int) * m, hipMemcpyDeviceToHost, st));
+        STCHK(hipStreamSynchronize(st));
     }
     *n_matches = m;
     return hipSuccess;

@@ -9,16 +9,20 @@
 //     a tile of poses whose twelve doubles are wave-uniform (read through the scalar cache), the inlier predicate goes
 //     through a ballot and a population count, and lane 0 adds the count to the pose's counter (no add for a zero).
 //     Integers only: any grid shape gives the same counts.
-// pnp_partials_kernel / fmat_total_kernel: the 29 sums of a refit pass, one lane per (block of 64 correspondences,
+// pnp_partials_kernel / ransac_total_kernel: the 29 sums of a refit pass, one lane per (block of 64 correspondences,
 //     entry), then one lane per entry adding the partials in ascending order.  The 6 x 6 solve and the rotation update of
 //     a step run on the host (amvs_pnp_step.h).
+// Shared with amvs_fmat.hip: jacobi<N>(), the sampler, the wave's tally, the scoring tile and Points
+// (amvs_ransac_common.h); ransac_total_kernel, ransac_argmax_kernel, Work, the halves of a pass and the RANSAC itself,
+// ransac_run, to which PnpModel below gives what is the resection's own (amvs_ransac_run.h).
 //
 // -ffp-contract=off (Makefile): a * b + c below is two roundings, on the device and on the host.
 #define AMVS_TU_ID 23
 #include "amvs_check.h"
 #include "amvs_pnp_host.h"
 #include "amvs_pnp_step.h"
-#include "amvs_ransac_common.h"
+#include "amvs_pose.h"
+#include "amvs_ransac_run.h"
 #include "../../include/amvs_resection.h"
 
 #include <cmath>
@@ -28,20 +32,10 @@ namespace amvs {
 
 namespace {
 
-#define PCHK(call)                                                  \
-    do {                                                            \
-        hipError_t e_ = (call);                                     \
-        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
-    } while (0)
-
-constexpr int HYP_TILE = 32;          // poses a scoring workgroup walks
+using Tile = ScoreTile<32>;           // poses a scoring workgroup walks
+using Points32 = Points<3, 2>;        // a: the points in space, b: their observations in the image
 constexpr int N_TRI = 78;             // entries of the upper triangle of the 12 x 12 M
 constexpr double ROOT3 = 1.7320508075688772;
-
-struct Intr { double fx, fy, cx, cy; };
-struct Pose { double R[9], t[3]; };
-
-inline Intr intrinsics_of(const double *K) { return Intr{K[0], K[4], K[2], K[5]}; }
 
 // Xc = R X + t in the header's order
 __device__ __forceinline__ void camera_point(const double *R, const double *t, double X, double Y, double Z, double Xc[3])
@@ -73,20 +67,13 @@ __global__ __launch_bounds__(64) void pnp_hypotheses_kernel(const float *__restr
     if (j >= count) return;                     // (no barrier below: a lane touches its own LDS column only)
     const unsigned long long h = (unsigned long long)first + (unsigned long long)j;
 
-    int idx[6], sorted[6];
+    int idx[6];
+    sample<6>(seed, h, m, idx);
 #pragma unroll
     for (int s = 0; s < 6; ++s) {
-        int r = (int)(mix64(seed ^ mix64(6ull * h + (unsigned long long)s)) % (unsigned long long)(m - s));
-#pragma unroll
-        for (int i = 0; i < s; ++i)
-            if (r >= sorted[i]) r += 1;
-        idx[s] = AMVS_IDX(r, m);
-        int v = r;                              // insert into the ascending list
-#pragma unroll
-        for (int i = 0; i < s; ++i)
-            if (v < sorted[i]) { const int tmp = sorted[i]; sorted[i] = v; v = tmp; }
-        sorted[s] = v;
+        const int r = idx[s];
         idx_out[6 * (size_t)j + s] = r;
+        idx[s] = AMVS_IDX(r, m);
     }
 
     double Px[6], Py[6], Pz[6], xn[6], yn[6];
@@ -210,13 +197,9 @@ __global__ __launch_bounds__(256) void pnp_score_kernel(const double *__restrict
     const size_t ii = live ? (size_t)i : 0;
     const double X = (double)pts3d[3 * ii], Y = (double)pts3d[3 * ii + 1], Z = (double)pts3d[3 * ii + 2];
     const double cu = k.cx - (double)pts2d[2 * ii], cv = k.cy - (double)pts2d[2 * ii + 1];
-    const int h0 = (int)blockIdx.y * HYP_TILE, h1 = h0 + HYP_TILE < n ? h0 + HYP_TILE : n;
-    const bool lane0 = (threadIdx.x & 63) == 0;
-    for (int h = h0; h < h1; ++h) {
-        const bool in = live && pnp_is_inlier(R + 9 * (size_t)h, t + 3 * (size_t)h, k.fx, k.fy, X, Y, Z, cu, cv, t2);   // wave-uniform pose
-        const int c = __popcll(__ballot(in));
-        if (c != 0 && lane0) atomicAdd(&counts[h], c);
-    }
+    const int h1 = Tile::end(n);
+    for (int h = Tile::begin(); h < h1; ++h)                        // (wave-uniform pose)
+        tally_wave(live && pnp_is_inlier(R + 9 * (size_t)h, t + 3 * (size_t)h, k.fx, k.fy, X, Y, Z, cu, cv, t2), counts, h);
 }
 
 // mask[i] and *count for one pose
@@ -232,8 +215,7 @@ __global__ __launch_bounds__(256) void pnp_inliers_kernel(const Pose P, const fl
                            k.cx - (double)pts2d[2 * ii], k.cy - (double)pts2d[2 * ii + 1], t2);
         mask[i] = in ? 1 : 0;
     }
-    const int c = __popcll(__ballot(in));
-    if (c != 0 && (threadIdx.x & 63) == 0) atomicAdd(count, c);
+    tally_wave(in, count);
 }
 
 // The block partials of a refit pass under P: entries 0 .. 20 the upper triangle of H row by row, 21 .. 26 g, 27 the cost,
@@ -283,71 +265,29 @@ __global__ __launch_bounds__(256) void pnp_partials_kernel(const Pose P, const I
     part[t] = acc;
 }
 
-inline dim3 blocks_for(long long n, int per) { return dim3((unsigned)((n + per - 1) / per)); }
-
-// the two point arrays of a call, on the device
-struct Points {
-    ScratchCache::Lease buf;
-    const float *p3 = nullptr, *p2 = nullptr;
-    hipError_t upload(const float *h3, const float *h2, int m, ScratchCache &cache, hipStream_t st)
-    {
-        const size_t n3 = 3 * (size_t)m, n2 = 2 * (size_t)m;
-        hipError_t e = cache.lease(buf, sizeof(float) * (n3 + n2));
-        if (e != hipSuccess) return e;
-        float *d = buf.get<float>();
-        p3 = d;
-        p2 = d + n3;
-        e = hipMemcpyAsync(d, h3, sizeof(float) * n3, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-        return hipMemcpyAsync(d + n3, h2, sizeof(float) * n2, hipMemcpyHostToDevice, st);
-    }
-};
-
-// scratch of the refit passes and inlier passes of one call
-struct Work {
-    ScratchCache::Lease part, total, count;
-    hipError_t reserve(int m, ScratchCache &cache)
-    {
-        const size_t n_blocks = ((size_t)m + AMVS_PNP_BLOCK - 1) / AMVS_PNP_BLOCK;
-        hipError_t e = cache.lease(part, sizeof(double) * PNP_SUMS * n_blocks);
-        if (e == hipSuccess) e = cache.lease(total, sizeof(double) * 64);
-        if (e == hipSuccess) e = cache.lease(count, sizeof(int) * 2);
-        return e;
-    }
-};
-
-Pose pose_of(const double R[9], const double t[3])
-{
-    Pose P;
-    std::memcpy(P.R, R, sizeof(P.R));
-    std::memcpy(P.t, t, sizeof(P.t));
-    return P;
-}
+inline int n_blocks_of(int m) { return (m + AMVS_PNP_BLOCK - 1) / AMVS_PNP_BLOCK; }
 
 // the 29 SUMs of a pass under (R, t) over the set mask_d (NULL: all)
-hipError_t refit_pass(const double R[9], const double t[3], const Intr &k, const Points &P, const unsigned char *mask_d, int m, Work &w,
+hipError_t refit_pass(const double R[9], const double t[3], const Intr &k, const Points32 &P, const unsigned char *mask_d, int m, Work &w,
                       double out[PNP_SUMS], hipStream_t st)
 {
-    const int n_blocks = (m + AMVS_PNP_BLOCK - 1) / AMVS_PNP_BLOCK;
-    hipLaunchKernelGGL(pnp_partials_kernel, blocks_for((long long)n_blocks * PNP_SUMS, 256), dim3(256), 0, st, pose_of(R, t), k, P.p3, P.p2,
+    const int n_blocks = n_blocks_of(m);
+    hipLaunchKernelGGL(pnp_partials_kernel, blocks_for((long long)n_blocks * PNP_SUMS, 256), dim3(256), 0, st, pose_of(R, t), k, P.a, P.b,
                        mask_d, m, n_blocks, w.part.get<double>());
-    PCHK(hipGetLastError());
-    hipLaunchKernelGGL(fmat_total_kernel, dim3(1), dim3(64), 0, st, (const double *)w.part.get(), n_blocks, PNP_SUMS, w.total.get<double>());
-    PCHK(hipGetLastError());
-    PCHK(hipMemcpyAsync(out, w.total.get(), sizeof(double) * PNP_SUMS, hipMemcpyDeviceToHost, st));
-    return hipStreamSynchronize(st);
+    STCHK(hipGetLastError());
+    return pass_totals(w, n_blocks, PNP_SUMS, out, st);
 }
 
 // the header's refit of (R, t), in place
-hipError_t refit(double R[9], double t[3], const Intr &k, const Points &P, const unsigned char *mask_d, int m, Work &w, int *steps,
+hipError_t refit_dev(double R[9], double t[3], const Intr &k, const Points32 &P, const unsigned char *mask_d, int m, Work &w, int *steps,
                  double *cost, hipStream_t st)
 {
     double sums[PNP_SUMS], next[PNP_SUMS], Rn[9], tn[3];
-    PCHK(refit_pass(R, t, k, P, mask_d, m, w, sums, st));
+    STCHK(refit_pass(R, t, k, P, mask_d, m, w, sums, st));
     int taken = 0;
     for (int it = 0; it < AMVS_PNP_REFINE_STEPS; ++it) {
         if (!pnp_gn_step(sums, R, t, Rn, tn)) break;
-        PCHK(refit_pass(Rn, tn, k, P, mask_d, m, w, next, st));
+        STCHK(refit_pass(Rn, tn, k, P, mask_d, m, w, next, st));
         if (!(next[PNP_COST] <= sums[PNP_COST] && next[PNP_FRONT] >= sums[PNP_FRONT])) break;
         std::memcpy(R, Rn, sizeof(Rn));
         std::memcpy(t, tn, sizeof(tn));
@@ -360,82 +300,119 @@ hipError_t refit(double R[9], double t[3], const Intr &k, const Points &P, const
 }
 
 // mask_d[i] and the count of the inliers of (R, t)
-hipError_t inliers_dev(const double R[9], const double t[3], const Intr &k, const Points &P, int m, double t2, unsigned char *mask_d,
+hipError_t inliers_dev(const double R[9], const double t[3], const Intr &k, const Points32 &P, int m, double t2, unsigned char *mask_d,
                        Work &w, long long *count, hipStream_t st)
 {
-    PCHK(hipMemsetAsync(w.count.get(), 0, sizeof(int), st));
-    hipLaunchKernelGGL(pnp_inliers_kernel, blocks_for(m, 256), dim3(256), 0, st, pose_of(R, t), P.p3, P.p2, m, k, t2, mask_d,
-                       w.count.get<int>());
-    PCHK(hipGetLastError());
-    int c = 0;
-    PCHK(hipMemcpyAsync(&c, w.count.get(), sizeof(int), hipMemcpyDeviceToHost, st));
-    PCHK(hipStreamSynchronize(st));
-    *count = c;
-    return hipSuccess;
+    return count_inliers(w, count, st, [&](int *count_d) {
+        hipLaunchKernelGGL(pnp_inliers_kernel, blocks_for(m, 256), dim3(256), 0, st, pose_of(R, t), P.a, P.b, m, k, t2, mask_d, count_d);
+    });
 }
 
-void launch_hypotheses(const Points &P, int m, const Intr &k, uint64_t seed, int first, int count, int *idx_d, double *R_d, double *t_d,
+void launch_hypotheses(const Points32 &P, int m, const Intr &k, uint64_t seed, int first, int count, int *idx_d, double *R_d, double *t_d,
                        hipStream_t st)
 {
-    hipLaunchKernelGGL(pnp_hypotheses_kernel, blocks_for(count, 64), dim3(64), 0, st, P.p3, P.p2, m, k, (unsigned long long)seed, first,
+    hipLaunchKernelGGL(pnp_hypotheses_kernel, blocks_for(count, 64), dim3(64), 0, st, P.a, P.b, m, k, (unsigned long long)seed, first,
                        count, idx_d, R_d, t_d);
 }
 
-void launch_score(const double *R_d, const double *t_d, int n, const Points &P, int m, const Intr &k, double t2, int *counts_d,
+void launch_score(const double *R_d, const double *t_d, int n, const Points32 &P, int m, const Intr &k, double t2, int *counts_d,
                   hipStream_t st)
 {
-    hipLaunchKernelGGL(pnp_score_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)((n + HYP_TILE - 1) / HYP_TILE)), dim3(256), 0, st,
-                       R_d, t_d, n, P.p3, P.p2, m, k, t2, counts_d);
+    hipLaunchKernelGGL(pnp_score_kernel, Tile::grid(m, n), dim3(256), 0, st, R_d, t_d, n, P.a, P.b, m, k, t2, counts_d);
 }
+
+// what ransac_run asks of a model (amvs_ransac_run.h): the pose, from samples of six correspondences
+struct PnpModel {
+    static constexpr int SAMPLE = 6, BATCH = AMVS_PNP_BATCH;
+    using Estimate = Pose;
+    const float *pts3d_h, *pts2d_h;
+    int m;
+    Intr k;
+    double t2;
+    uint64_t seed;
+    Points32 P;
+    Work w;
+    ScratchCache::Lease idx, R, t;
+
+    hipError_t prepare(ScratchCache &cache, hipStream_t st)
+    {
+        STCHK(P.upload(pts3d_h, pts2d_h, m, cache, st));
+        STCHK(w.reserve(PNP_SUMS, n_blocks_of(m), cache));
+        STCHK(cache.lease(idx, sizeof(int) * 6 * BATCH));
+        STCHK(cache.lease(R, sizeof(double) * 9 * BATCH));
+        return cache.lease(t, sizeof(double) * 3 * BATCH);
+    }
+    void hypotheses(int first, int count, hipStream_t st)
+    {
+        launch_hypotheses(P, m, k, seed, first, count, idx.get<int>(), R.get<double>(), t.get<double>(), st);
+    }
+    void score(int n, int *counts_d, hipStream_t st) { launch_score(R.get<double>(), t.get<double>(), n, P, m, k, t2, counts_d, st); }
+    hipError_t fetch(Pose &e, hipStream_t st)
+    {
+        STCHK(hipMemcpyAsync(e.R, R.get(), sizeof(e.R), hipMemcpyDeviceToHost, st));
+        return hipMemcpyAsync(e.t, t.get(), sizeof(e.t), hipMemcpyDeviceToHost, st);
+    }
+    hipError_t inliers(const Pose &e, unsigned char *mask_d, long long *count, hipStream_t st)
+    {
+        return inliers_dev(e.R, e.t, k, P, m, t2, mask_d, w, count, st);
+    }
+    hipError_t refit(Pose &e, const unsigned char *mask_d, long long, hipStream_t st)
+    {
+        int steps = 0;
+        double cost = 0.0;
+        return refit_dev(e.R, e.t, k, P, mask_d, m, w, &steps, &cost, st);
+    }
+    static double all_inliers(double wr) { const double w2 = wr * wr; return (w2 * w2) * w2; }              // the header's (w^2 w^2) w^2
+};
 
 }  // namespace
 
 hipError_t pnp_hypotheses(const float *pts3d_h, const float *pts2d_h, int m, const double *K, uint64_t seed, int first, int count,
                           int *idx_h, double *R_h, double *t_h, ScratchCache &cache, hipStream_t st)
 {
-    Points P;
+    Points32 P;
     ScratchCache::Lease idx, R, t;
-    PCHK(P.upload(pts3d_h, pts2d_h, m, cache, st));
-    PCHK(cache.lease(idx, sizeof(int) * 6 * (size_t)count));
-    PCHK(cache.lease(R, sizeof(double) * 9 * (size_t)count));
-    PCHK(cache.lease(t, sizeof(double) * 3 * (size_t)count));
+    STCHK(P.upload(pts3d_h, pts2d_h, m, cache, st));
+    STCHK(cache.lease(idx, sizeof(int) * 6 * (size_t)count));
+    STCHK(cache.lease(R, sizeof(double) * 9 * (size_t)count));
+    STCHK(cache.lease(t, sizeof(double) * 3 * (size_t)count));
     launch_hypotheses(P, m, intrinsics_of(K), seed, first, count, idx.get<int>(), R.get<double>(), t.get<double>(), st);
-    PCHK(hipGetLastError());
-    PCHK(hipMemcpyAsync(idx_h, idx.get(), sizeof(int) * 6 * (size_t)count, hipMemcpyDeviceToHost, st));
-    PCHK(hipMemcpyAsync(R_h, R.get(), sizeof(double) * 9 * (size_t)count, hipMemcpyDeviceToHost, st));
-    PCHK(hipMemcpyAsync(t_h, t.get(), sizeof(double) * 3 * (size_t)count, hipMemcpyDeviceToHost, st));
+    STCHK(hipGetLastError());
+    STCHK(hipMemcpyAsync(idx_h, idx.get(), sizeof(int) * 6 * (size_t)count, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(R_h, R.get(), sizeof(double) * 9 * (size_t)count, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(t_h, t.get(), sizeof(double) * 3 * (size_t)count, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
 hipError_t pnp_score(const double *R_h, const double *t_h, int n, const float *pts3d_h, const float *pts2d_h, int m, const double *K,
                      double threshold, int *counts_h, ScratchCache &cache, hipStream_t st)
 {
-    Points P;
+    Points32 P;
     ScratchCache::Lease R, t, counts;
-    PCHK(P.upload(pts3d_h, pts2d_h, m, cache, st));
-    PCHK(cache.lease(R, sizeof(double) * 9 * (size_t)n));
-    PCHK(cache.lease(t, sizeof(double) * 3 * (size_t)n));
-    PCHK(cache.lease(counts, sizeof(int) * (size_t)n));
-    PCHK(hipMemcpyAsync(R.get(), R_h, sizeof(double) * 9 * (size_t)n, hipMemcpyHostToDevice, st));
-    PCHK(hipMemcpyAsync(t.get(), t_h, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
-    PCHK(hipMemsetAsync(counts.get(), 0, sizeof(int) * (size_t)n, st));
+    STCHK(P.upload(pts3d_h, pts2d_h, m, cache, st));
+    STCHK(cache.lease(R, sizeof(double) * 9 * (size_t)n));
+    STCHK(cache.lease(t, sizeof(double) * 3 * (size_t)n));
+    STCHK(cache.lease(counts, sizeof(int) * (size_t)n));
+    STCHK(hipMemcpyAsync(R.get(), R_h, sizeof(double) * 9 * (size_t)n, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(t.get(), t_h, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+    STCHK(hipMemsetAsync(counts.get(), 0, sizeof(int) * (size_t)n, st));
     launch_score(R.get<double>(), t.get<double>(), n, P, m, intrinsics_of(K), threshold * threshold, counts.get<int>(), st);
-    PCHK(hipGetLastError());
-    PCHK(hipMemcpyAsync(counts_h, counts.get(), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    STCHK(hipGetLastError());
+    STCHK(hipMemcpyAsync(counts_h, counts.get(), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
 hipError_t pnp_inliers(const double R[9], const double t[3], const float *pts3d_h, const float *pts2d_h, int m, const double *K,
                        double threshold, unsigned char *mask_h, long long *count, ScratchCache &cache, hipStream_t st)
 {
-    Points P;
+    Points32 P;
     Work w;
     ScratchCache::Lease mask;
-    PCHK(P.upload(pts3d_h, pts2d_h, m, cache, st));
-    PCHK(w.reserve(m, cache));
-    PCHK(cache.lease(mask, (size_t)m));
-    PCHK(inliers_dev(R, t, intrinsics_of(K), P, m, threshold * threshold, mask.get<unsigned char>(), w, count, st));
-    PCHK(hipMemcpyAsync(mask_h, mask.get(), (size_t)m, hipMemcpyDeviceToHost, st));
+    STCHK(P.upload(pts3d_h, pts2d_h, m, cache, st));
+    STCHK(w.reserve(PNP_SUMS, n_blocks_of(m), cache));
+    STCHK(cache.lease(mask, (size_t)m));
+    STCHK(inliers_dev(R, t, intrinsics_of(K), P, m, threshold * threshold, mask.get<unsigned char>(), w, count, st));
+    STCHK(hipMemcpyAsync(mask_h, mask.get(), (size_t)m, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
@@ -443,19 +420,19 @@ hipError_t pnp_refine(const float *pts3d_h, const float *pts2d_h, int m, const d
                       const unsigned char *mask_h, double R_out[9], double t_out[3], int *steps, double *cost, ScratchCache &cache,
                       hipStream_t st)
 {
-    Points P;
+    Points32 P;
     Work w;
     ScratchCache::Lease mask;
-    PCHK(P.upload(pts3d_h, pts2d_h, m, cache, st));
-    PCHK(w.reserve(m, cache));
+    STCHK(P.upload(pts3d_h, pts2d_h, m, cache, st));
+    STCHK(w.reserve(PNP_SUMS, n_blocks_of(m), cache));
     if (mask_h) {
-        PCHK(cache.lease(mask, (size_t)m));
-        PCHK(hipMemcpyAsync(mask.get(), mask_h, (size_t)m, hipMemcpyHostToDevice, st));
+        STCHK(cache.lease(mask, (size_t)m));
+        STCHK(hipMemcpyAsync(mask.get(), mask_h, (size_t)m, hipMemcpyHostToDevice, st));
     }
     double R[9], t[3];
     std::memcpy(R, R_in, sizeof(R));
     std::memcpy(t, t_in, sizeof(t));
-    PCHK(refit(R, t, intrinsics_of(K), P, mask_h ? mask.get<unsigned char>() : nullptr, m, w, steps, cost, st));
+    STCHK(refit_dev(R, t, intrinsics_of(K), P, mask_h ? mask.get<unsigned char>() : nullptr, m, w, steps, cost, st));
     std::memcpy(R_out, R, sizeof(R));
     std::memcpy(t_out, t, sizeof(t));
     return hipSuccess;
@@ -465,76 +442,12 @@ hipError_t pnp_ransac(const float *pts3d_h, const float *pts2d_h, int m, const d
                       int max_hypotheses, uint64_t seed, double R_out[9], double t_out[3], unsigned char *mask_h, long long *n_inliers,
                       int info[3], ScratchCache &cache, hipStream_t st)
 {
-    const double t2 = threshold * threshold;
-    const Intr k = intrinsics_of(K);
-    Points P;
-    Work w;
-    ScratchCache::Lease idx, R, t, counts, best2, mask_a, mask_b;
-    PCHK(P.upload(pts3d_h, pts2d_h, m, cache, st));
-    PCHK(w.reserve(m, cache));
-    PCHK(cache.lease(idx, sizeof(int) * 6 * AMVS_PNP_BATCH));
-    PCHK(cache.lease(R, sizeof(double) * 9 * AMVS_PNP_BATCH));
-    PCHK(cache.lease(t, sizeof(double) * 3 * AMVS_PNP_BATCH));
-    PCHK(cache.lease(counts, sizeof(int) * AMVS_PNP_BATCH));
-    PCHK(cache.lease(best2, sizeof(int) * 2));
-    PCHK(cache.lease(mask_a, (size_t)m));
-    PCHK(cache.lease(mask_b, (size_t)m));
-
-    int done = 0, best = -1, best_h = 0;
-    for (;;) {
-        const int nb = max_hypotheses - done < AMVS_PNP_BATCH ? max_hypotheses - done : AMVS_PNP_BATCH;
-        launch_hypotheses(P, m, k, seed, done, nb, idx.get<int>(), R.get<double>(), t.get<double>(), st);
-        PCHK(hipGetLastError());
-        PCHK(hipMemsetAsync(counts.get(), 0, sizeof(int) * (size_t)nb, st));
-        launch_score(R.get<double>(), t.get<double>(), nb, P, m, k, t2, counts.get<int>(), st);
-        PCHK(hipGetLastError());
-        hipLaunchKernelGGL(fmat_argmax_kernel, dim3(1), dim3(1024), 0, st, (const int *)counts.get(), nb, done, best2.get<int>());
-        PCHK(hipGetLastError());
-        int got[2] = {0, 0};
-        PCHK(hipMemcpyAsync(got, best2.get(), sizeof(got), hipMemcpyDeviceToHost, st));
-        PCHK(hipStreamSynchronize(st));
-        if (got[0] > best) { best = got[0]; best_h = got[1]; }     // (a later batch wins only with a larger count)
-        done += nb;
-        const double wr = (double)best / (double)m, w2 = wr * wr, p = (w2 * w2) * w2;
-        double N;
-        if (p >= 1.0) N = 0.0;
-        else if (1.0 - p == 1.0) N = (double)max_hypotheses;
-        else N = std::ceil(std::log(1.0 - confidence) / std::log(1.0 - p));
-        if ((double)done >= N || done == max_hypotheses) break;
-    }
-    info[0] = done; info[1] = best_h; info[2] = best;
-
-    for (int e = 0; e < 9; ++e) R_out[e] = 0.0;
-    for (int e = 0; e < 3; ++e) t_out[e] = 0.0;
-    std::memset(mask_h, 0, (size_t)m);
-    *n_inliers = 0;
-    if (best < 6) return hipSuccess;
-
-    // the best hypothesis' pose again (the sampler is a function of h), its inliers, and the two refits
-    double R1[9], t1[3], R2[9], t2v[3], cost = 0.0;
-    int steps = 0;
-    launch_hypotheses(P, m, k, seed, best_h, 1, idx.get<int>(), R.get<double>(), t.get<double>(), st);
-    PCHK(hipGetLastError());
-    PCHK(hipMemcpyAsync(R1, R.get(), sizeof(R1), hipMemcpyDeviceToHost, st));
-    PCHK(hipMemcpyAsync(t1, t.get(), sizeof(t1), hipMemcpyDeviceToHost, st));
-    PCHK(hipStreamSynchronize(st));
-    long long n0 = 0, n1 = 0, n2 = 0;
-    unsigned char *ma = mask_a.get<unsigned char>(), *mb = mask_b.get<unsigned char>();
-    PCHK(inliers_dev(R1, t1, k, P, m, t2, ma, w, &n0, st));
-    if (n0 < 6) return hipSuccess;                      // (n0 == best >= 6: unreachable, kept as the refit's precondition)
-    PCHK(refit(R1, t1, k, P, ma, m, w, &steps, &cost, st));
-    PCHK(inliers_dev(R1, t1, k, P, m, t2, mb, w, &n1, st));
-    if (n1 < 6) return hipSuccess;
-    std::memcpy(R2, R1, sizeof(R2));
-    std::memcpy(t2v, t1, sizeof(t2v));
-    PCHK(refit(R2, t2v, k, P, mb, m, w, &steps, &cost, st));
-    PCHK(inliers_dev(R2, t2v, k, P, m, t2, ma, w, &n2, st));
-    const bool second = n2 >= n1;
-    std::memcpy(R_out, second ? R2 : R1, sizeof(double) * 9);
-    std::memcpy(t_out, second ? t2v : t1, sizeof(double) * 3);
-    *n_inliers = second ? n2 : n1;
-    PCHK(hipMemcpyAsync(mask_h, second ? ma : mb, (size_t)m, hipMemcpyDeviceToHost, st));
-    return hipStreamSynchronize(st);
+    PnpModel model{pts3d_h, pts2d_h, m, intrinsics_of(K), threshold * threshold, seed};
+    Pose best{};
+    const hipError_t e = ransac_run(model, m, confidence, max_hypotheses, &best, mask_h, n_inliers, info, cache, st);
+    std::memcpy(R_out, best.R, sizeof(best.R));
+    std::memcpy(t_out, best.t, sizeof(best.t));
+    return e;
 }
 
 }  // namespace amvs

@@ -1,15 +1,17 @@
-// amvs_ransac_common.h -- what the RANSAC units share (amvs_fmat.hip, amvs_pnp.hip): the fixed-sweep cyclic Jacobi of
-// include/amvs_match.h step 3 on an N x N symmetric matrix, for the device (state in LDS, one column a lane) and the
-// host (state in plain arrays); the mix() of the counter-based sampler of include/amvs_epipolar.h; the kernel that adds
-// block partials in ascending order and the one that finds the best count of a batch.  Private to the library.  The
-// kernels are static: each unit that launches them compiles its own.  No data-dependent global-memory index is formed
-// here, so nothing goes through amvs_check.h.
+// amvs_ransac_common.h -- what the units with hypothesis and scoring kernels share (amvs_fmat.hip, amvs_pnp.hip; the
+// scoring pieces, Points and blocks_for also amvs_twoview.hip): the fixed-sweep cyclic Jacobi of include/amvs_match.h
+// step 3 on an N x N symmetric matrix, for the device (state in LDS, one column a lane) and the host (state in plain
+// arrays); the counter-based sampler of include/amvs_epipolar.h; the tile of a scoring launch and the wave's tally of a
+// predicate; the two point arrays of a call on the device.  Private to the library.  No kernel is defined here (the two
+// the RANSAC units share are in amvs_ransac_run.h), and no global-memory access with a data-dependent index is made:
+// the sampler returns its draw and the kernel that gathers with it checks it (amvs_check.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "../../include/amvs_match.h"
+#include "amvs_buffer.h"
 
 namespace amvs {
 
@@ -83,35 +85,65 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long z)
     return z ^ (z >> 31);
 }
 
-// out[0] = count, out[1] = hypothesis of the best of counts[0 .. n): count descending, index ascending.  One workgroup.
-static __global__ __launch_bounds__(1024) void fmat_argmax_kernel(const int *__restrict__ counts, int n, int first, int *__restrict__ out)
+// The sampler: draw[0 .. K) = the K distinct indices of [0, m) of hypothesis h in the order drawn -- member k a draw from
+// the m - k indices left, shifted past the kept ones.  The kernel that gathers with them checks them (amvs_check.h).
+template <int K>
+__device__ __forceinline__ void sample(unsigned long long seed, unsigned long long h, int m, int *draw)
 {
-    __shared__ unsigned long long sh[1024];
-    unsigned long long best = 0ull;
-    for (int j = (int)threadIdx.x; j < n; j += 1024) {
-        const unsigned long long key = ((unsigned long long)(unsigned)counts[j] << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)j);
-        if (key > best) best = key;
-    }
-    sh[threadIdx.x] = best;
-    __syncthreads();
-    for (int step = 512; step > 0; step >>= 1) {
-        if ((int)threadIdx.x < step && sh[threadIdx.x + step] > sh[threadIdx.x]) sh[threadIdx.x] = sh[threadIdx.x + step];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        out[0] = (int)(sh[0] >> 32);
-        out[1] = first + (int)(0xFFFFFFFFu - (unsigned)(sh[0] & 0xFFFFFFFFull));
+    int sorted[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        int r = (int)(mix64(seed ^ mix64((unsigned long long)K * h + (unsigned long long)k)) % (unsigned long long)(m - k));
+#pragma unroll
+        for (int i = 0; i < k; ++i)
+            if (r >= sorted[i]) r += 1;
+        draw[k] = r;
+        int v = r;                              // insert into the ascending list
+#pragma unroll
+        for (int i = 0; i < k; ++i)
+            if (v < sorted[i]) { const int tmp = sorted[i]; sorted[i] = v; v = tmp; }
+        sorted[k] = v;
     }
 }
 
-// total[e] = the partials of entry e added in ascending block order, from +0.0
-static __global__ __launch_bounds__(64) void fmat_total_kernel(const double *__restrict__ part, int n_blocks, int entries, double *__restrict__ total)
+// counters[at] += the lanes of this wave with `in` set (every lane of the wave calls; no add for a zero).  The index
+// comes separately so that the address is formed where it is used, after the count: formed by the caller, it moves an
+// instruction of twoview_score_kernel.
+__device__ __forceinline__ void tally_wave(bool in, int *counters, size_t at = 0)
 {
-    const int e = (int)threadIdx.x;
-    if (e >= entries) return;
-    double acc = 0.0;
-    for (int b = 0; b < n_blocks; ++b) acc = acc + part[(size_t)b * entries + e];
-    total[e] = acc;
+    const int c = __popcll(__ballot(in));
+    if (c != 0 && (threadIdx.x & 63) == 0) atomicAdd(&counters[at], c);
 }
+
+// A scoring launch: workgroups of 256 correspondences in x, TILE hypotheses a workgroup in y.  The kernel walks
+// [begin(), end(n)) and its launch takes grid(m, n), so the two cannot disagree on TILE.
+template <int TILE>
+struct ScoreTile {
+    __device__ static __forceinline__ int begin() { return (int)blockIdx.y * TILE; }
+    __device__ static __forceinline__ int end(int n) { const int h0 = begin(); return h0 + TILE < n ? h0 + TILE : n; }
+    static dim3 grid(int m, int n) { return dim3((unsigned)((m + 255) / 256), (unsigned)((n + TILE - 1) / TILE)); }
+};
+
+// workgroups of `per` for n items
+inline dim3 blocks_for(long long n, int per) { return dim3((unsigned)((n + per - 1) / per)); }
+
+// the two point arrays of a call, m x D1 and m x D2 floats, on the device in one lease
+template <int D1, int D2>
+struct Points {
+    ScratchCache::Lease buf;
+    const float *a = nullptr, *b = nullptr;
+    hipError_t upload(const float *ha, const float *hb, int m, ScratchCache &cache, hipStream_t st)
+    {
+        const size_t na = D1 * (size_t)m, nb = D2 * (size_t)m;
+        hipError_t e = cache.lease(buf, sizeof(float) * (na + nb));
+        if (e != hipSuccess) return e;
+        float *d = buf.get<float>();
+        a = d;
+        b = d + na;
+        e = hipMemcpyAsync(d, ha, sizeof(float) * na, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
+        return hipMemcpyAsync(d + na, hb, sizeof(float) * nb, hipMemcpyHostToDevice, st);
+    }
+};
 
 }  // namespace amvs

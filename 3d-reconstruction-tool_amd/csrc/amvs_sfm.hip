@@ -39,12 +39,6 @@ namespace amvs {
 
 namespace {
 
-#define SCHK(call)                                                  \
-    do {                                                            \
-        hipError_t e_ = (call);                                     \
-        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
-    } while (0)
-
 constexpr int B = AMVS_SFM_BLOCK;
 using Lease = ScratchCache::Lease;
 
@@ -336,14 +330,14 @@ hipError_t select_flagged(const unsigned char *flag, long long n, int *sel, int 
 {
     hipcub::CountingInputIterator<int> iota(0);
     size_t bytes = 0;
-    SCHK(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flag, sel, d_count, (int)n, st));
-    SCHK(cache.lease(tmp, bytes));
+    STCHK(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flag, sel, d_count, (int)n, st));
+    STCHK(cache.lease(tmp, bytes));
     return hipcub::DeviceSelect::Flagged(tmp.get(), bytes, iota, flag, sel, d_count, (int)n, st);
 }
 
 hipError_t upload_segs(const std::vector<SfmSeg> &segs, Lease &l, ScratchCache &cache, hipStream_t st)
 {
-    SCHK(cache.lease(l, sizeof(SfmSeg) * segs.size()));
+    STCHK(cache.lease(l, sizeof(SfmSeg) * segs.size()));
     return hipMemcpyAsync(l.get(), segs.data(), sizeof(SfmSeg) * segs.size(), hipMemcpyHostToDevice, st);
 }
 
@@ -356,13 +350,13 @@ hipError_t grow_points(SfmState &s, long long need, ScratchCache &cache, hipStre
     cap = std::min<long long>(std::max<long long>(cap, 1024), std::max<long long>(need, AMVS_SFM_MAX_POINTS));
     DeviceBuffer<double> X;
     DeviceBuffer<unsigned char> alive;
-    SCHK(X.reserve(3 * (size_t)cap, cache));
-    SCHK(alive.reserve((size_t)cap, cache));
+    STCHK(X.reserve(3 * (size_t)cap, cache));
+    STCHK(alive.reserve((size_t)cap, cache));
     if (s.n_points > 0) {
-        SCHK(hipMemcpyAsync(X.get(), s.X.get(), sizeof(double) * 3 * (size_t)s.n_points, hipMemcpyDeviceToDevice, st));
-        SCHK(hipMemcpyAsync(alive.get(), s.alive.get(), (size_t)s.n_points, hipMemcpyDeviceToDevice, st));
+        STCHK(hipMemcpyAsync(X.get(), s.X.get(), sizeof(double) * 3 * (size_t)s.n_points, hipMemcpyDeviceToDevice, st));
+        STCHK(hipMemcpyAsync(alive.get(), s.alive.get(), (size_t)s.n_points, hipMemcpyDeviceToDevice, st));
     }
-    SCHK(hipStreamSynchronize(st));
+    STCHK(hipStreamSynchronize(st));
     s.X = std::move(X);
     s.alive = std::move(alive);
     return hipSuccess;
@@ -382,16 +376,16 @@ hipError_t sfm_upload(SfmState &s, const float *kp_h, const int *rows_h, Scratch
         for (int m = s.pair_start[p]; m < s.pair_start[p + 1]; ++m)
             rows[(size_t)m] = make_int2(oi + rows_h[2 * (size_t)m], oj + rows_h[2 * (size_t)m + 1]);
     }
-    SCHK(s.kp.reserve(std::max<size_t>((size_t)s.G, 1), cache));
-    SCHK(s.kview.reserve(std::max<size_t>((size_t)s.G, 1), cache));
-    SCHK(s.owner.reserve(std::max<size_t>((size_t)s.G, 1), cache));
-    SCHK(s.rows.reserve(std::max<size_t>((size_t)s.M, 1), cache));
+    STCHK(s.kp.reserve(std::max<size_t>((size_t)s.G, 1), cache));
+    STCHK(s.kview.reserve(std::max<size_t>((size_t)s.G, 1), cache));
+    STCHK(s.owner.reserve(std::max<size_t>((size_t)s.G, 1), cache));
+    STCHK(s.rows.reserve(std::max<size_t>((size_t)s.M, 1), cache));
     if (s.G > 0) {
-        SCHK(hipMemcpyAsync(s.kp.get(), kp_h, sizeof(float2) * (size_t)s.G, hipMemcpyHostToDevice, st));
-        SCHK(hipMemcpyAsync(s.kview.get(), kview.data(), sizeof(int) * (size_t)s.G, hipMemcpyHostToDevice, st));
-        SCHK(hipMemsetAsync(s.owner.get(), 0xFF, sizeof(int) * (size_t)s.G, st));
+        STCHK(hipMemcpyAsync(s.kp.get(), kp_h, sizeof(float2) * (size_t)s.G, hipMemcpyHostToDevice, st));
+        STCHK(hipMemcpyAsync(s.kview.get(), kview.data(), sizeof(int) * (size_t)s.G, hipMemcpyHostToDevice, st));
+        STCHK(hipMemsetAsync(s.owner.get(), 0xFF, sizeof(int) * (size_t)s.G, st));
     }
-    if (s.M > 0) SCHK(hipMemcpyAsync(s.rows.get(), rows.data(), sizeof(int2) * (size_t)s.M, hipMemcpyHostToDevice, st));
+    if (s.M > 0) STCHK(hipMemcpyAsync(s.rows.get(), rows.data(), sizeof(int2) * (size_t)s.M, hipMemcpyHostToDevice, st));
     s.n_points = 0;
     return hipStreamSynchronize(st);
 }
@@ -402,19 +396,19 @@ hipError_t sfm_register(SfmState &s, int view, const int *kp_h, const int *pid_h
     *n_set = 0;
     if (n <= 0) return hipSuccess;
     Lease in, cnt;
-    SCHK(cache.lease(in, sizeof(int) * 2 * (size_t)n));
-    SCHK(cache.lease(cnt, sizeof(unsigned long long)));
+    STCHK(cache.lease(in, sizeof(int) * 2 * (size_t)n));
+    STCHK(cache.lease(cnt, sizeof(unsigned long long)));
     int *d = in.get<int>();
-    SCHK(hipMemcpyAsync(d, kp_h, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
-    SCHK(hipMemcpyAsync(d + n, pid_h, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
-    SCHK(hipMemsetAsync(cnt.get(), 0, sizeof(unsigned long long), st));
+    STCHK(hipMemcpyAsync(d, kp_h, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(d + n, pid_h, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
+    STCHK(hipMemsetAsync(cnt.get(), 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(sfm_register_kernel, grid_for(n), dim3(B), 0, st, (const int *)d, (const int *)(d + n), n, s.off[view],
                        s.off[view + 1] - s.off[view], (const unsigned char *)s.alive.get(), s.n_points, s.owner.get(),
                        cnt.get<unsigned long long>());
-    SCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     unsigned long long k = 0;
-    SCHK(hipMemcpyAsync(&k, cnt.get(), sizeof(k), hipMemcpyDeviceToHost, st));
-    SCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(&k, cnt.get(), sizeof(k), hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     *n_set = (long long)k;
     return hipSuccess;
 }
@@ -424,18 +418,18 @@ hipError_t sfm_scores(SfmState &s, const std::vector<SfmSeg> &segs, int total, i
     for (int v = 0; v < s.V; ++v) counts_h[v] = 0;
     if (total <= 0 || s.G <= 0) return hipSuccess;
     Lease seg, flag, counts;
-    SCHK(upload_segs(segs, seg, cache, st));
-    SCHK(cache.lease(flag, (size_t)s.G));
-    SCHK(cache.lease(counts, sizeof(int) * (size_t)s.V));
-    SCHK(hipMemsetAsync(flag.get(), 0, (size_t)s.G, st));
-    SCHK(hipMemsetAsync(counts.get(), 0, sizeof(int) * (size_t)s.V, st));
+    STCHK(upload_segs(segs, seg, cache, st));
+    STCHK(cache.lease(flag, (size_t)s.G));
+    STCHK(cache.lease(counts, sizeof(int) * (size_t)s.V));
+    STCHK(hipMemsetAsync(flag.get(), 0, (size_t)s.G, st));
+    STCHK(hipMemsetAsync(counts.get(), 0, sizeof(int) * (size_t)s.V, st));
     hipLaunchKernelGGL(sfm_score_rows_kernel, grid_for(total), dim3(B), 0, st, (const SfmSeg *)seg.get(), (int)segs.size(), total,
                        (const int2 *)s.rows.get(), s.M, (const int *)s.owner.get(), s.G, flag.get<unsigned char>());
-    SCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     hipLaunchKernelGGL(sfm_score_count_kernel, grid_for(s.G), dim3(B), 0, st, (const unsigned char *)flag.get(), (const int *)s.kview.get(),
                        s.G, s.V, counts.get<int>());
-    SCHK(hipGetLastError());
-    SCHK(hipMemcpyAsync(counts_h, counts.get(), sizeof(int) * (size_t)s.V, hipMemcpyDeviceToHost, st));
+    STCHK(hipGetLastError());
+    STCHK(hipMemcpyAsync(counts_h, counts.get(), sizeof(int) * (size_t)s.V, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
@@ -446,17 +440,17 @@ hipError_t sfm_correspondences(SfmState &s, int view, const std::vector<SfmSeg> 
     const int off = s.off[view], n_view = s.off[view + 1] - off;
     if (total <= 0 || n_view <= 0 || s.n_points <= 0) return hipSuccess;
     Lease seg, best, pbest, keep, point, sel, cnt, tmp, out;
-    SCHK(upload_segs(segs, seg, cache, st));
-    SCHK(cache.lease(best, sizeof(int) * (size_t)n_view));
-    SCHK(cache.lease(pbest, sizeof(int) * (size_t)s.n_points));
-    SCHK(cache.lease(keep, (size_t)n_view));
-    SCHK(cache.lease(point, sizeof(int) * (size_t)n_view));
-    SCHK(cache.lease(sel, sizeof(int) * (size_t)n_view));
-    SCHK(cache.lease(cnt, sizeof(int)));
-    SCHK(cache.lease(out, (sizeof(int) + 5 * sizeof(float)) * (size_t)n_view));
+    STCHK(upload_segs(segs, seg, cache, st));
+    STCHK(cache.lease(best, sizeof(int) * (size_t)n_view));
+    STCHK(cache.lease(pbest, sizeof(int) * (size_t)s.n_points));
+    STCHK(cache.lease(keep, (size_t)n_view));
+    STCHK(cache.lease(point, sizeof(int) * (size_t)n_view));
+    STCHK(cache.lease(sel, sizeof(int) * (size_t)n_view));
+    STCHK(cache.lease(cnt, sizeof(int)));
+    STCHK(cache.lease(out, (sizeof(int) + 5 * sizeof(float)) * (size_t)n_view));
     hipLaunchKernelGGL(sfm_fill_kernel, grid_for(n_view), dim3(B), 0, st, best.get<int>(), (long long)n_view, INT_MAX);
     hipLaunchKernelGGL(sfm_fill_kernel, grid_for(s.n_points), dim3(B), 0, st, pbest.get<int>(), s.n_points, INT_MAX);
-    SCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     const int2 *rows = s.rows.get();
     const int *owner = s.owner.get();
     hipLaunchKernelGGL(sfm_corr_a_kernel, grid_for(total), dim3(B), 0, st, (const SfmSeg *)seg.get(), (int)segs.size(), total, rows, s.M,
@@ -465,23 +459,23 @@ hipError_t sfm_correspondences(SfmState &s, int view, const std::vector<SfmSeg> 
                        pbest.get<int>(), s.n_points);
     hipLaunchKernelGGL(sfm_corr_c_kernel, grid_for(n_view), dim3(B), 0, st, (const int *)best.get(), off, n_view, rows, s.M, owner, s.G,
                        (const int *)pbest.get(), s.n_points, keep.get<unsigned char>(), point.get<int>());
-    SCHK(hipGetLastError());
-    SCHK(select_flagged(keep.get<unsigned char>(), n_view, sel.get<int>(), cnt.get<int>(), cache, tmp, st));
+    STCHK(hipGetLastError());
+    STCHK(select_flagged(keep.get<unsigned char>(), n_view, sel.get<int>(), cnt.get<int>(), cache, tmp, st));
     int *d_pid = out.get<int>();
     float *d_X = reinterpret_cast<float *>(d_pid + n_view);
     float2 *d_x = reinterpret_cast<float2 *>(d_X + 3 * (size_t)n_view);
     hipLaunchKernelGGL(sfm_corr_gather_kernel, grid_for(n_view), dim3(B), 0, st, (const int *)sel.get(), (const int *)cnt.get(), off, n_view,
                        (const int *)point.get(), (const double *)s.X.get(), s.n_points, (const float2 *)s.kp.get(), d_pid, d_X, d_x);
-    SCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     int k = 0;
-    SCHK(hipMemcpyAsync(&k, cnt.get(), sizeof(int), hipMemcpyDeviceToHost, st));
-    SCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(&k, cnt.get(), sizeof(int), hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     if (k > 0) {
-        SCHK(hipMemcpyAsync(kp_h, sel.get(), sizeof(int) * (size_t)k, hipMemcpyDeviceToHost, st));
-        SCHK(hipMemcpyAsync(pid_h, d_pid, sizeof(int) * (size_t)k, hipMemcpyDeviceToHost, st));
-        SCHK(hipMemcpyAsync(X_h, d_X, sizeof(float) * 3 * (size_t)k, hipMemcpyDeviceToHost, st));
-        SCHK(hipMemcpyAsync(x_h, d_x, sizeof(float2) * (size_t)k, hipMemcpyDeviceToHost, st));
-        SCHK(hipStreamSynchronize(st));
+        STCHK(hipMemcpyAsync(kp_h, sel.get(), sizeof(int) * (size_t)k, hipMemcpyDeviceToHost, st));
+        STCHK(hipMemcpyAsync(pid_h, d_pid, sizeof(int) * (size_t)k, hipMemcpyDeviceToHost, st));
+        STCHK(hipMemcpyAsync(X_h, d_X, sizeof(float) * 3 * (size_t)k, hipMemcpyDeviceToHost, st));
+        STCHK(hipMemcpyAsync(x_h, d_x, sizeof(float2) * (size_t)k, hipMemcpyDeviceToHost, st));
+        STCHK(hipStreamSynchronize(st));
     }
     *m = k;
     return hipSuccess;
@@ -497,18 +491,18 @@ hipError_t sfm_triangulate(SfmState &s, const double *K, const std::vector<SfmTr
     for (const SfmTriPair &p : pairs)
         if (p.count > 0) { ++steps; longest = std::max(longest, p.count); room += p.count; }
     if (steps == 0) return hipSuccess;
-    SCHK(grow_points(s, s.n_points + std::min(room, max_new), cache, st));     // the caller has checked n_points + max_new against the limit
+    STCHK(grow_points(s, s.n_points + std::min(room, max_new), cache, st));     // the caller has checked n_points + max_new against the limit
     const long long capacity = (long long)s.alive.capacity();
     Lease flag, scan, cand, made, base, tmp;
-    SCHK(cache.lease(flag, sizeof(int) * (size_t)longest));
-    SCHK(cache.lease(scan, sizeof(int) * (size_t)longest));
-    SCHK(cache.lease(cand, sizeof(double) * 3 * (size_t)longest));
-    SCHK(cache.lease(made, sizeof(int) * (size_t)steps));
-    SCHK(cache.lease(base, sizeof(long long) * (size_t)(steps + 1)));
+    STCHK(cache.lease(flag, sizeof(int) * (size_t)longest));
+    STCHK(cache.lease(scan, sizeof(int) * (size_t)longest));
+    STCHK(cache.lease(cand, sizeof(double) * 3 * (size_t)longest));
+    STCHK(cache.lease(made, sizeof(int) * (size_t)steps));
+    STCHK(cache.lease(base, sizeof(long long) * (size_t)(steps + 1)));
     size_t bytes = 0;
-    SCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, flag.get<int>(), scan.get<int>(), longest, st));
-    SCHK(cache.lease(tmp, bytes));
-    SCHK(hipMemcpyAsync(base.get(), &s.n_points, sizeof(long long), hipMemcpyHostToDevice, st));
+    STCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, flag.get<int>(), scan.get<int>(), longest, st));
+    STCHK(cache.lease(tmp, bytes));
+    STCHK(hipMemcpyAsync(base.get(), &s.n_points, sizeof(long long), hipMemcpyHostToDevice, st));
     int step = 0;
     for (const SfmTriPair &p : pairs) {
         if (p.count <= 0) continue;
@@ -516,19 +510,19 @@ hipError_t sfm_triangulate(SfmState &s, const double *K, const std::vector<SfmTr
         const TriArgs a = tri_args(K, p.R1, p.t1, p.R2, p.t2, thr);
         hipLaunchKernelGGL(sfm_tri_kernel, grid_for(p.count), dim3(B), 0, st, a, (const int2 *)s.rows.get(), s.M, p.row0, p.count,
                            (const int *)s.owner.get(), s.G, (const float2 *)s.kp.get(), flag.get<int>(), cand.get<double>());
-        SCHK(hipGetLastError());
-        SCHK(hipcub::DeviceScan::ExclusiveSum(tmp.get(), bytes, flag.get<int>(), scan.get<int>(), p.count, st));   // sized for the longest
+        STCHK(hipGetLastError());
+        STCHK(hipcub::DeviceScan::ExclusiveSum(tmp.get(), bytes, flag.get<int>(), scan.get<int>(), p.count, st));   // sized for the longest
         hipLaunchKernelGGL(sfm_tri_base_kernel, dim3(1), dim3(1), 0, st, (const int *)flag.get(), (const int *)scan.get(), p.count, step,
                            made.get<int>(), base.get<long long>());
         hipLaunchKernelGGL(sfm_tri_assign_kernel, grid_for(p.count), dim3(B), 0, st, (const int2 *)s.rows.get(), s.M, p.row0, p.count,
                            (const int *)flag.get(), (const int *)scan.get(), (const double *)cand.get(), (const long long *)base.get(), step,
                            s.owner.get(), s.G, s.X.get(), s.alive.get(), capacity);
-        SCHK(hipGetLastError());
+        STCHK(hipGetLastError());
         ++step;
     }
     std::vector<int> made_h((size_t)steps);
-    SCHK(hipMemcpyAsync(made_h.data(), made.get(), sizeof(int) * (size_t)steps, hipMemcpyDeviceToHost, st));
-    SCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(made_h.data(), made.get(), sizeof(int) * (size_t)steps, hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     step = 0;
     for (const SfmTriPair &p : pairs) {
         if (p.count <= 0) continue;
@@ -543,15 +537,15 @@ hipError_t sfm_counts(SfmState &s, long long *n_alive, long long *n_obs, Scratch
 {
     *n_alive = *n_obs = 0;
     Lease cnt;
-    SCHK(cache.lease(cnt, 2 * sizeof(unsigned long long)));
+    STCHK(cache.lease(cnt, 2 * sizeof(unsigned long long)));
     unsigned long long *d = cnt.get<unsigned long long>();
-    SCHK(hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), st));
+    STCHK(hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), st));
     if (s.n_points > 0) hipLaunchKernelGGL(sfm_count_alive_kernel, grid_for(s.n_points), dim3(B), 0, st, (const unsigned char *)s.alive.get(), s.n_points, d);
     if (s.G > 0) hipLaunchKernelGGL(sfm_count_owned_kernel, grid_for(s.G), dim3(B), 0, st, (const int *)s.owner.get(), s.G, d + 1);
-    SCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     unsigned long long h[2] = {0, 0};
-    SCHK(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, st));
-    SCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     *n_alive = (long long)h[0];
     *n_obs = (long long)h[1];
     return hipSuccess;
@@ -561,33 +555,33 @@ hipError_t sfm_observations(SfmState &s, int *cam_h, int *pt_h, float *uv_h, lon
 {
     if (n_obs <= 0) return hipSuccess;
     Lease flag, sel, cnt, tmp, keyA, keyB, out;
-    SCHK(cache.lease(flag, (size_t)s.G));
-    SCHK(cache.lease(sel, sizeof(int) * (size_t)s.G));
-    SCHK(cache.lease(cnt, sizeof(int)));
-    SCHK(cache.lease(keyA, sizeof(unsigned long long) * (size_t)n_obs));
-    SCHK(cache.lease(keyB, sizeof(unsigned long long) * (size_t)n_obs));
-    SCHK(cache.lease(out, (2 * sizeof(int) + sizeof(float2)) * (size_t)n_obs));
+    STCHK(cache.lease(flag, (size_t)s.G));
+    STCHK(cache.lease(sel, sizeof(int) * (size_t)s.G));
+    STCHK(cache.lease(cnt, sizeof(int)));
+    STCHK(cache.lease(keyA, sizeof(unsigned long long) * (size_t)n_obs));
+    STCHK(cache.lease(keyB, sizeof(unsigned long long) * (size_t)n_obs));
+    STCHK(cache.lease(out, (2 * sizeof(int) + sizeof(float2)) * (size_t)n_obs));
     hipLaunchKernelGGL(sfm_owned_flag_kernel, grid_for(s.G), dim3(B), 0, st, (const int *)s.owner.get(), s.G, flag.get<unsigned char>());
-    SCHK(hipGetLastError());
-    SCHK(select_flagged(flag.get<unsigned char>(), s.G, sel.get<int>(), cnt.get<int>(), cache, tmp, st));   // n_obs of them: nothing changed the owners since the count
+    STCHK(hipGetLastError());
+    STCHK(select_flagged(flag.get<unsigned char>(), s.G, sel.get<int>(), cnt.get<int>(), cache, tmp, st));   // n_obs of them: nothing changed the owners since the count
     hipLaunchKernelGGL(sfm_obs_key_kernel, grid_for(n_obs), dim3(B), 0, st, (const int *)sel.get(), n_obs, (const int *)s.owner.get(), s.G,
                        keyA.get<unsigned long long>());
-    SCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     {
         Lease tmp2;
         size_t bytes = 0;
-        SCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, keyA.get<unsigned long long>(), keyB.get<unsigned long long>(), (int)n_obs, 0, 64, st));
-        SCHK(cache.lease(tmp2, bytes));
-        SCHK(hipcub::DeviceRadixSort::SortKeys(tmp2.get(), bytes, keyA.get<unsigned long long>(), keyB.get<unsigned long long>(), (int)n_obs, 0, 64, st));
+        STCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, keyA.get<unsigned long long>(), keyB.get<unsigned long long>(), (int)n_obs, 0, 64, st));
+        STCHK(cache.lease(tmp2, bytes));
+        STCHK(hipcub::DeviceRadixSort::SortKeys(tmp2.get(), bytes, keyA.get<unsigned long long>(), keyB.get<unsigned long long>(), (int)n_obs, 0, 64, st));
         int *d_cam = out.get<int>(), *d_pt = d_cam + n_obs;
         float2 *d_uv = reinterpret_cast<float2 *>(d_pt + n_obs);
         hipLaunchKernelGGL(sfm_obs_decode_kernel, grid_for(n_obs), dim3(B), 0, st, (const unsigned long long *)keyB.get(), n_obs,
                            (const int *)s.kview.get(), (const float2 *)s.kp.get(), s.G, d_cam, d_pt, d_uv);
-        SCHK(hipGetLastError());
-        SCHK(hipMemcpyAsync(cam_h, d_cam, sizeof(int) * (size_t)n_obs, hipMemcpyDeviceToHost, st));
-        SCHK(hipMemcpyAsync(pt_h, d_pt, sizeof(int) * (size_t)n_obs, hipMemcpyDeviceToHost, st));
-        SCHK(hipMemcpyAsync(uv_h, d_uv, sizeof(float2) * (size_t)n_obs, hipMemcpyDeviceToHost, st));
-        SCHK(hipStreamSynchronize(st));              // before tmp2 goes back to the cache
+        STCHK(hipGetLastError());
+        STCHK(hipMemcpyAsync(cam_h, d_cam, sizeof(int) * (size_t)n_obs, hipMemcpyDeviceToHost, st));
+        STCHK(hipMemcpyAsync(pt_h, d_pt, sizeof(int) * (size_t)n_obs, hipMemcpyDeviceToHost, st));
+        STCHK(hipMemcpyAsync(uv_h, d_uv, sizeof(float2) * (size_t)n_obs, hipMemcpyDeviceToHost, st));
+        STCHK(hipStreamSynchronize(st));              // before tmp2 goes back to the cache
     }
     return hipSuccess;
 }
@@ -595,8 +589,8 @@ hipError_t sfm_observations(SfmState &s, int *cam_h, int *pt_h, float *uv_h, lon
 hipError_t sfm_points_get(SfmState &s, double *X_h, unsigned char *alive_h, hipStream_t st)
 {
     if (s.n_points <= 0) return hipSuccess;
-    if (X_h) SCHK(hipMemcpyAsync(X_h, s.X.get(), sizeof(double) * 3 * (size_t)s.n_points, hipMemcpyDeviceToHost, st));
-    SCHK(hipMemcpyAsync(alive_h, s.alive.get(), (size_t)s.n_points, hipMemcpyDeviceToHost, st));
+    if (X_h) STCHK(hipMemcpyAsync(X_h, s.X.get(), sizeof(double) * 3 * (size_t)s.n_points, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(alive_h, s.alive.get(), (size_t)s.n_points, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
@@ -604,12 +598,12 @@ hipError_t sfm_points_set(SfmState &s, const double *X_h, const unsigned char *a
 {
     (void)cache;
     if (s.n_points <= 0) return hipSuccess;
-    SCHK(hipMemcpyAsync(s.X.get(), X_h, sizeof(double) * 3 * (size_t)s.n_points, hipMemcpyHostToDevice, st));
-    SCHK(hipMemcpyAsync(s.alive.get(), alive_h, (size_t)s.n_points, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(s.X.get(), X_h, sizeof(double) * 3 * (size_t)s.n_points, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(s.alive.get(), alive_h, (size_t)s.n_points, hipMemcpyHostToDevice, st));
     if (s.G > 0) {
         hipLaunchKernelGGL(sfm_unown_dead_kernel, grid_for(s.G), dim3(B), 0, st, s.owner.get(), s.G, (const unsigned char *)s.alive.get(),
                            s.n_points);
-        SCHK(hipGetLastError());
+        STCHK(hipGetLastError());
     }
     return hipStreamSynchronize(st);
 }
@@ -620,14 +614,14 @@ hipError_t sfm_drop(SfmState &s, const long long *keys_h, int n, int min_obs, lo
     *obs_dropped = *points_dropped = 0;
     if (s.G <= 0 || s.n_points <= 0) return hipSuccess;
     Lease keys, cnt, per;
-    SCHK(cache.lease(keys, sizeof(long long) * (size_t)std::max(n, 1)));
-    SCHK(cache.lease(cnt, 2 * sizeof(unsigned long long)));
-    SCHK(cache.lease(per, sizeof(int) * (size_t)s.n_points));
+    STCHK(cache.lease(keys, sizeof(long long) * (size_t)std::max(n, 1)));
+    STCHK(cache.lease(cnt, 2 * sizeof(unsigned long long)));
+    STCHK(cache.lease(per, sizeof(int) * (size_t)s.n_points));
     unsigned long long *d = cnt.get<unsigned long long>();
-    SCHK(hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), st));
-    SCHK(hipMemsetAsync(per.get(), 0, sizeof(int) * (size_t)s.n_points, st));
+    STCHK(hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), st));
+    STCHK(hipMemsetAsync(per.get(), 0, sizeof(int) * (size_t)s.n_points, st));
     if (n > 0) {
-        SCHK(hipMemcpyAsync(keys.get(), keys_h, sizeof(long long) * (size_t)n, hipMemcpyHostToDevice, st));
+        STCHK(hipMemcpyAsync(keys.get(), keys_h, sizeof(long long) * (size_t)n, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(sfm_drop_obs_kernel, grid_for(s.G), dim3(B), 0, st, (const long long *)keys.get(), n, (const int *)s.kview.get(),
                            s.owner.get(), s.G, d);
     }
@@ -636,10 +630,10 @@ hipError_t sfm_drop(SfmState &s, const long long *keys_h, int n, int min_obs, lo
                        s.alive.get(), d + 1);
     hipLaunchKernelGGL(sfm_unown_dead_kernel, grid_for(s.G), dim3(B), 0, st, s.owner.get(), s.G, (const unsigned char *)s.alive.get(),
                        s.n_points);
-    SCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     unsigned long long h[2] = {0, 0};
-    SCHK(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, st));
-    SCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     *obs_dropped = (long long)h[0];
     *points_dropped = (long long)h[1];
     return hipSuccess;

@@ -25,12 +25,6 @@ namespace amvs {
 
 namespace {
 
-#define TCHK(call)                                                  \
-    do {                                                            \
-        hipError_t e_ = (call);                                     \
-        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
-    } while (0)
-
 inline dim3 grid_for(long long n) { long long b = (n + 255) / 256; return dim3((unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b))); }
 
 struct PairArgs {
@@ -172,47 +166,47 @@ hipError_t pair_triangulate(const double K[9], const double R1[9], const double 
 
     ScratchCache::Lease in, X, flag, sel, cnt, tmp;
     const size_t pt_bytes = sizeof(float) * 2 * (size_t)m;
-    TCHK(cache.lease(in, 2 * pt_bytes + 3 * (size_t)m));
+    STCHK(cache.lease(in, 2 * pt_bytes + 3 * (size_t)m));
     float *d1 = in.get<float>(), *d2 = d1 + 2 * (size_t)m;
     unsigned char *drgb = (unsigned char *)(d2 + 2 * (size_t)m);
-    TCHK(cache.lease(X, sizeof(double) * 3 * (size_t)m));
-    TCHK(cache.lease(flag, (size_t)m));
-    TCHK(cache.lease(sel, sizeof(int) * (size_t)m));
-    TCHK(cache.lease(cnt, sizeof(int)));
-    TCHK(hipMemcpyAsync(d1, pts1_h, pt_bytes, hipMemcpyHostToDevice, st));
-    TCHK(hipMemcpyAsync(d2, pts2_h, pt_bytes, hipMemcpyHostToDevice, st));
-    TCHK(hipMemcpyAsync(drgb, rgb_h, 3 * (size_t)m, hipMemcpyHostToDevice, st));
+    STCHK(cache.lease(X, sizeof(double) * 3 * (size_t)m));
+    STCHK(cache.lease(flag, (size_t)m));
+    STCHK(cache.lease(sel, sizeof(int) * (size_t)m));
+    STCHK(cache.lease(cnt, sizeof(int)));
+    STCHK(hipMemcpyAsync(d1, pts1_h, pt_bytes, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(d2, pts2_h, pt_bytes, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(drgb, rgb_h, 3 * (size_t)m, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(pair_triangulate_kernel, grid_for(m), dim3(256), 0, st, a, (const float *)d1, (const float *)d2, m,
                        X.get<double>(), flag.get<unsigned char>());
-    TCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     hipcub::CountingInputIterator<int> iota(0);
     size_t bytes = 0;
-    TCHK(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flag.get<unsigned char>(), sel.get<int>(), cnt.get<int>(), m, st));
-    TCHK(cache.lease(tmp, bytes));
-    TCHK(hipcub::DeviceSelect::Flagged(tmp.get(), bytes, iota, flag.get<unsigned char>(), sel.get<int>(), cnt.get<int>(), m, st));
+    STCHK(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flag.get<unsigned char>(), sel.get<int>(), cnt.get<int>(), m, st));
+    STCHK(cache.lease(tmp, bytes));
+    STCHK(hipcub::DeviceSelect::Flagged(tmp.get(), bytes, iota, flag.get<unsigned char>(), sel.get<int>(), cnt.get<int>(), m, st));
     int k_n = 0;
-    TCHK(hipMemcpyAsync(&k_n, cnt.get(), sizeof(int), hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(&k_n, cnt.get(), sizeof(int), hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     if (k_n > 0) {
         const size_t need = (size_t)acc.n + (size_t)k_n;
         if (3 * need > acc.pts.capacity()) {
             const size_t cap = std::max<size_t>(std::max<size_t>(need, 2 * (acc.pts.capacity() / 3)), 4096);
             DeviceBuffer<double> np;
             DeviceBuffer<unsigned char> nc;
-            TCHK(np.reserve(3 * cap, cache));
-            TCHK(nc.reserve(3 * cap, cache));
+            STCHK(np.reserve(3 * cap, cache));
+            STCHK(nc.reserve(3 * cap, cache));
             if (acc.n > 0) {
-                TCHK(hipMemcpyAsync(np.get(), acc.pts.get(), sizeof(double) * 3 * (size_t)acc.n, hipMemcpyDeviceToDevice, st));
-                TCHK(hipMemcpyAsync(nc.get(), acc.rgb.get(), 3 * (size_t)acc.n, hipMemcpyDeviceToDevice, st));
-                TCHK(hipStreamSynchronize(st));
+                STCHK(hipMemcpyAsync(np.get(), acc.pts.get(), sizeof(double) * 3 * (size_t)acc.n, hipMemcpyDeviceToDevice, st));
+                STCHK(hipMemcpyAsync(nc.get(), acc.rgb.get(), 3 * (size_t)acc.n, hipMemcpyDeviceToDevice, st));
+                STCHK(hipStreamSynchronize(st));
             }
             acc.pts = std::move(np);
             acc.rgb = std::move(nc);
         }
         hipLaunchKernelGGL(pair_append_kernel, grid_for(k_n), dim3(256), 0, st, (const int *)sel.get(), k_n, m, (const double *)X.get(),
                            (const unsigned char *)drgb, acc.pts.get() + 3 * (size_t)acc.n, acc.rgb.get() + 3 * (size_t)acc.n);
-        TCHK(hipGetLastError());
-        TCHK(hipStreamSynchronize(st));
+        STCHK(hipGetLastError());
+        STCHK(hipStreamSynchronize(st));
         acc.n += k_n;
     }
     *n_accepted = k_n;
@@ -225,17 +219,17 @@ hipError_t cloud_bounds(const double *pts, long long n, const unsigned char *kee
     if (n <= 0) return hipErrorInvalidValue;
     const dim3 grid = grid_for(n);
     ScratchCache::Lease keep, part;
-    TCHK(cache.lease(part, sizeof(double) * 8 * grid.x));
+    STCHK(cache.lease(part, sizeof(double) * 8 * grid.x));
     if (keep_h) {
-        TCHK(cache.lease(keep, (size_t)n));
-        TCHK(hipMemcpyAsync(keep.get(), keep_h, (size_t)n, hipMemcpyHostToDevice, st));
+        STCHK(cache.lease(keep, (size_t)n));
+        STCHK(hipMemcpyAsync(keep.get(), keep_h, (size_t)n, hipMemcpyHostToDevice, st));
     }
     hipLaunchKernelGGL(cloud_bounds_kernel, grid, dim3(256), 0, st, pts, n, keep_h ? (const unsigned char *)keep.get() : nullptr,
                        part.get<double>());
-    TCHK(hipGetLastError());
+    STCHK(hipGetLastError());
     std::vector<double> h(8 * (size_t)grid.x);
-    TCHK(hipMemcpyAsync(h.data(), part.get(), sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    STCHK(hipMemcpyAsync(h.data(), part.get(), sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     double kept = 0.0, bad = 0.0;
     for (int a = 0; a < 3; ++a) { mn[a] = INFINITY; mx[a] = -INFINITY; }
     for (unsigned b = 0; b < grid.x; ++b) {
@@ -255,12 +249,12 @@ hipError_t selftest_sqrt(const double *in_h, int n, double *out_h, ScratchCache 
 {
     if (n <= 0) return hipSuccess;
     ScratchCache::Lease buf;
-    TCHK(cache.lease(buf, sizeof(double) * 2 * (size_t)n));
+    STCHK(cache.lease(buf, sizeof(double) * 2 * (size_t)n));
     double *in = buf.get<double>(), *out = in + n;
-    TCHK(hipMemcpyAsync(in, in_h, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(in, in_h, sizeof(double) * n, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(sqrt_kernel, grid_for(n), dim3(256), 0, st, (const double *)in, n, out);
-    TCHK(hipGetLastError());
-    TCHK(hipMemcpyAsync(out_h, out, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    STCHK(hipGetLastError());
+    STCHK(hipMemcpyAsync(out_h, out, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 

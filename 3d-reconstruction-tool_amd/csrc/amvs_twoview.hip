@@ -6,17 +6,21 @@
 //     of 256 matches walks a tile of AMVS_TWOVIEW_POSE_TILE poses whose twelve doubles are wave-uniform (read through the
 //     scalar cache, as pnp_score_kernel reads its poses), every (pose, match) runs the DLT of amvs_dlt4.h with M and V in
 //     registers, the predicate goes through a ballot and a population count, and lane 0 of a wave adds the count to the
-//     pose's counter (no add for a zero).  Integers only: any grid shape gives the same counts.
+//     pose's counter (no add for a zero; tally_wave and the tile of amvs_ransac_common.h).  Integers only: any grid shape
+//     gives the same counts.
 // twoview_front_kernel: the same predicate for one pose, one byte a match.
 // twoview_triangulate_kernel: one candidate per lane in pixels (tri_candidate of amvs_twoview_tri.h, the text the track state
 //     of amvs_sfm.hip runs too); X, the validity byte and the cosine of the parallax angle of every candidate go back to
 //     the host.
 // No data-dependent index is formed: every index is the lane's own match or the wave's pose.
+// Intr and Pose are those of amvs_pose.h, the two point arrays of a call those of amvs_ransac_common.h.
 //
 // -ffp-contract=off (Makefile): a * b + c below is two roundings, on the device and on the host.
 #define AMVS_TU_ID 24
 #include "amvs_check.h"
 #include "amvs_dlt4.h"
+#include "amvs_pose.h"
+#include "amvs_ransac_common.h"
 #include "amvs_twoview_dev.h"
 #include "amvs_twoview_host.h"
 #include "amvs_twoview_tri.h"
@@ -31,17 +35,8 @@ static_assert(TWOVIEW_JACOBI_SWEEPS == AMVS_JACOBI_SWEEPS, "the host iteration r
 
 namespace {
 
-#define VCHK(call)                                                  \
-    do {                                                            \
-        hipError_t e_ = (call);                                     \
-        if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); return e_; } \
-    } while (0)
-
-constexpr int POSE_TILE = AMVS_TWOVIEW_POSE_TILE;
-
-struct Intr { double fx, fy, cx, cy; };
-struct Pose { double R[9], t[3]; };
-inline Intr intrinsics_of(const double *K) { return Intr{K[0], K[4], K[2], K[5]}; }
+using Tile = ScoreTile<AMVS_TWOVIEW_POSE_TILE>;
+using Points2 = Points<2, 2>;         // a: the matches' points in the first view, b: in the second
 
 // the header's cheirality test of the match with normalised coordinates (x1, y1), (x2, y2) under (R, t)
 __device__ __forceinline__ bool in_front(const double *R, const double *t, double x1, double y1, double x2, double y2, double max_depth)
@@ -55,7 +50,7 @@ __device__ __forceinline__ bool in_front(const double *R, const double *t, doubl
     return z1 > 0.0 && z1 < max_depth && z2 > 0.0 && z2 < max_depth;
 }
 
-// counts[h] += matches in front under pose h among this workgroup's 256 matches, for the POSE_TILE poses of blockIdx.y
+// counts[h] += matches in front under pose h among this workgroup's 256 matches, for the tile of poses of blockIdx.y
 __global__ __launch_bounds__(256) void twoview_score_kernel(const double *__restrict__ R, const double *__restrict__ t, int n,
                                                             const float *__restrict__ pts1, const float *__restrict__ pts2, int m,
                                                             const Intr k, double max_depth, int *__restrict__ counts)
@@ -65,13 +60,9 @@ __global__ __launch_bounds__(256) void twoview_score_kernel(const double *__rest
     const size_t ii = live ? (size_t)i : 0;
     const double x1 = ((double)pts1[2 * ii] - k.cx) / k.fx, y1 = ((double)pts1[2 * ii + 1] - k.cy) / k.fy;
     const double x2 = ((double)pts2[2 * ii] - k.cx) / k.fx, y2 = ((double)pts2[2 * ii + 1] - k.cy) / k.fy;
-    const int h0 = (int)blockIdx.y * POSE_TILE, h1 = h0 + POSE_TILE < n ? h0 + POSE_TILE : n;
-    const bool lane0 = (threadIdx.x & 63) == 0;
-    for (int h = h0; h < h1; ++h) {
-        const bool in = live && in_front(R + 9 * (size_t)h, t + 3 * (size_t)h, x1, y1, x2, y2, max_depth);   // wave-uniform pose
-        const int c = __popcll(__ballot(in));
-        if (c != 0 && lane0) atomicAdd(&counts[h], c);
-    }
+    const int h1 = Tile::end(n);
+    for (int h = Tile::begin(); h < h1; ++h)                        // (wave-uniform pose)
+        tally_wave(live && in_front(R + 9 * (size_t)h, t + 3 * (size_t)h, x1, y1, x2, y2, max_depth), counts, h);
 }
 
 // mask[i] for one pose
@@ -105,58 +96,35 @@ __global__ __launch_bounds__(256) void twoview_triangulate_kernel(const TriArgs 
     cos_out[ii] = cs;
 }
 
-inline dim3 blocks_for(long long n, int per) { return dim3((unsigned)((n + per - 1) / per)); }
-
-// the two point arrays of a call, on the device
-struct Points {
-    ScratchCache::Lease buf;
-    const float *p1 = nullptr, *p2 = nullptr;
-    hipError_t upload(const float *h1, const float *h2, int m, ScratchCache &cache, hipStream_t st)
-    {
-        const size_t n = 2 * (size_t)m;
-        hipError_t e = cache.lease(buf, sizeof(float) * 2 * n);
-        if (e != hipSuccess) return e;
-        float *d = buf.get<float>();
-        p1 = d;
-        p2 = d + n;
-        e = hipMemcpyAsync(d, h1, sizeof(float) * n, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-        return hipMemcpyAsync(d + n, h2, sizeof(float) * n, hipMemcpyHostToDevice, st);
-    }
-};
-
 // counts_h[j] of the n poses (R_h, t_h) over the uploaded matches
-hipError_t score_dev(const double *R_h, const double *t_h, int n, const Points &P, int m, const Intr &k, double max_depth, int *counts_h,
+hipError_t score_dev(const double *R_h, const double *t_h, int n, const Points2 &P, int m, const Intr &k, double max_depth, int *counts_h,
                      ScratchCache &cache, hipStream_t st)
 {
     ScratchCache::Lease R, t, counts;
-    VCHK(cache.lease(R, sizeof(double) * 9 * (size_t)n));
-    VCHK(cache.lease(t, sizeof(double) * 3 * (size_t)n));
-    VCHK(cache.lease(counts, sizeof(int) * (size_t)n));
-    VCHK(hipMemcpyAsync(R.get(), R_h, sizeof(double) * 9 * (size_t)n, hipMemcpyHostToDevice, st));
-    VCHK(hipMemcpyAsync(t.get(), t_h, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
-    VCHK(hipMemsetAsync(counts.get(), 0, sizeof(int) * (size_t)n, st));
-    hipLaunchKernelGGL(twoview_score_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)((n + POSE_TILE - 1) / POSE_TILE)), dim3(256), 0, st,
-                       (const double *)R.get(), (const double *)t.get(), n, P.p1, P.p2, m, k, max_depth, counts.get<int>());
-    VCHK(hipGetLastError());
-    VCHK(hipMemcpyAsync(counts_h, counts.get(), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    STCHK(cache.lease(R, sizeof(double) * 9 * (size_t)n));
+    STCHK(cache.lease(t, sizeof(double) * 3 * (size_t)n));
+    STCHK(cache.lease(counts, sizeof(int) * (size_t)n));
+    STCHK(hipMemcpyAsync(R.get(), R_h, sizeof(double) * 9 * (size_t)n, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(t.get(), t_h, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+    STCHK(hipMemsetAsync(counts.get(), 0, sizeof(int) * (size_t)n, st));
+    hipLaunchKernelGGL(twoview_score_kernel, Tile::grid(m, n), dim3(256), 0, st, (const double *)R.get(), (const double *)t.get(), n, P.a, P.b,
+                       m, k, max_depth, counts.get<int>());
+    STCHK(hipGetLastError());
+    STCHK(hipMemcpyAsync(counts_h, counts.get(), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
 // mask_h[i] of one pose over the uploaded matches, and their number
-hipError_t front_dev(const double R[9], const double t[3], const Points &P, int m, const Intr &k, double max_depth, unsigned char *mask_h,
+hipError_t front_dev(const double R[9], const double t[3], const Points2 &P, int m, const Intr &k, double max_depth, unsigned char *mask_h,
                      long long *count, ScratchCache &cache, hipStream_t st)
 {
     ScratchCache::Lease mask;
-    VCHK(cache.lease(mask, (size_t)m));
-    Pose pose;
-    std::memcpy(pose.R, R, sizeof(pose.R));
-    std::memcpy(pose.t, t, sizeof(pose.t));
-    hipLaunchKernelGGL(twoview_front_kernel, blocks_for(m, 256), dim3(256), 0, st, pose, P.p1, P.p2, m, k, max_depth,
+    STCHK(cache.lease(mask, (size_t)m));
+    hipLaunchKernelGGL(twoview_front_kernel, blocks_for(m, 256), dim3(256), 0, st, pose_of(R, t), P.a, P.b, m, k, max_depth,
                        mask.get<unsigned char>());
-    VCHK(hipGetLastError());
-    VCHK(hipMemcpyAsync(mask_h, mask.get(), (size_t)m, hipMemcpyDeviceToHost, st));
-    VCHK(hipStreamSynchronize(st));
+    STCHK(hipGetLastError());
+    STCHK(hipMemcpyAsync(mask_h, mask.get(), (size_t)m, hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     long long c = 0;
     for (int i = 0; i < m; ++i) c += mask_h[i] != 0;
     *count = c;
@@ -168,16 +136,16 @@ hipError_t front_dev(const double R[9], const double t[3], const Points &P, int 
 hipError_t twoview_score(const double *R_h, const double *t_h, int n, const float *pts1_h, const float *pts2_h, int m, const double *K,
                          double max_depth, int *counts_h, ScratchCache &cache, hipStream_t st)
 {
-    Points P;
-    VCHK(P.upload(pts1_h, pts2_h, m, cache, st));
+    Points2 P;
+    STCHK(P.upload(pts1_h, pts2_h, m, cache, st));
     return score_dev(R_h, t_h, n, P, m, intrinsics_of(K), max_depth, counts_h, cache, st);
 }
 
 hipError_t twoview_front(const double R[9], const double t[3], const float *pts1_h, const float *pts2_h, int m, const double *K,
                          double max_depth, unsigned char *mask_h, long long *count, ScratchCache &cache, hipStream_t st)
 {
-    Points P;
-    VCHK(P.upload(pts1_h, pts2_h, m, cache, st));
+    Points2 P;
+    STCHK(P.upload(pts1_h, pts2_h, m, cache, st));
     return front_dev(R, t, P, m, intrinsics_of(K), max_depth, mask_h, count, cache, st);
 }
 
@@ -194,16 +162,16 @@ hipError_t twoview_pose(const double F[9], const double *K, const float *pts1_h,
     double R2[18], t[3], w[3], Rc[36], tc[12];
     if (!twoview_decompose(F, K, R2, t, w)) return hipSuccess;
     for (int j = 0; j < 4; ++j) twoview_candidate(R2, t, j, Rc + 9 * j, tc + 3 * j);
-    Points P;
-    VCHK(P.upload(pts1_h, pts2_h, m, cache, st));
+    Points2 P;
+    STCHK(P.upload(pts1_h, pts2_h, m, cache, st));
     const Intr k = intrinsics_of(K);
     int counts[4] = {0, 0, 0, 0};
-    VCHK(score_dev(Rc, tc, 4, P, m, k, max_depth, counts, cache, st));
+    STCHK(score_dev(Rc, tc, 4, P, m, k, max_depth, counts, cache, st));
     int best = 0;
     for (int j = 1; j < 4; ++j)
         if (counts[j] > counts[best]) best = j;
     if (counts[best] == 0) return hipSuccess;
-    VCHK(front_dev(Rc + 9 * best, tc + 3 * best, P, m, k, max_depth, mask_h, n_front, cache, st));
+    STCHK(front_dev(Rc + 9 * best, tc + 3 * best, P, m, k, max_depth, mask_h, n_front, cache, st));
     std::memcpy(R_out, Rc + 9 * best, sizeof(double) * 9);
     std::memcpy(t_out, tc + 3 * best, sizeof(double) * 3);
     info[0] = best;
@@ -219,19 +187,19 @@ hipError_t twoview_triangulate(const double *K, const double R1[9], const double
     *n_valid = 0;
     if (m <= 0) return hipSuccess;
     const TriArgs a = tri_args(K, R1, t1, R2, t2, thr);
-    Points P;
+    Points2 P;
     ScratchCache::Lease X, cs, valid;
-    VCHK(P.upload(pts1_h, pts2_h, m, cache, st));
-    VCHK(cache.lease(X, sizeof(double) * 3 * (size_t)m));
-    VCHK(cache.lease(cs, sizeof(double) * (size_t)m));
-    VCHK(cache.lease(valid, (size_t)m));
-    hipLaunchKernelGGL(twoview_triangulate_kernel, blocks_for(m, 256), dim3(256), 0, st, a, P.p1, P.p2, m, X.get<double>(),
+    STCHK(P.upload(pts1_h, pts2_h, m, cache, st));
+    STCHK(cache.lease(X, sizeof(double) * 3 * (size_t)m));
+    STCHK(cache.lease(cs, sizeof(double) * (size_t)m));
+    STCHK(cache.lease(valid, (size_t)m));
+    hipLaunchKernelGGL(twoview_triangulate_kernel, blocks_for(m, 256), dim3(256), 0, st, a, P.a, P.b, m, X.get<double>(),
                        valid.get<unsigned char>(), cs.get<double>());
-    VCHK(hipGetLastError());
-    VCHK(hipMemcpyAsync(X_h, X.get(), sizeof(double) * 3 * (size_t)m, hipMemcpyDeviceToHost, st));
-    VCHK(hipMemcpyAsync(cos_h, cs.get(), sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
-    VCHK(hipMemcpyAsync(valid_h, valid.get(), (size_t)m, hipMemcpyDeviceToHost, st));
-    VCHK(hipStreamSynchronize(st));
+    STCHK(hipGetLastError());
+    STCHK(hipMemcpyAsync(X_h, X.get(), sizeof(double) * 3 * (size_t)m, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(cos_h, cs.get(), sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(valid_h, valid.get(), (size_t)m, hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
     long long c = 0;
     for (int i = 0; i < m; ++i) c += valid_h[i] != 0;
     *n_valid = c;
