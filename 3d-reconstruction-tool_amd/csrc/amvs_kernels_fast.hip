@@ -28,6 +28,11 @@
 #endif
 #include "amvs_fast_common.h"
 
+// the sweep step requests a row's candidate depth one own row ahead (0: at the top of its own row, for A/B builds)
+#ifndef AMVS_FAST_STEP_DEPTH_AHEAD
+#define AMVS_FAST_STEP_DEPTH_AHEAD 1
+#endif
+
 namespace amvs {
 
 template <int K, int S> struct StepLds {
@@ -244,6 +249,26 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
     const int oy = mode == MODE_PROP ? a.oy : 0, ox = mode == MODE_PROP ? a.ox : 0;
     const int noff = oy * W + ox;
 
+    // The candidate depth of a row is the first thing the row needs: loaded at the top of the row it exposes one
+    // memory round trip per row.  It is requested one own row ahead instead (the first one here), at the top of the
+    // row before, AHEAD of that row's gathers: the waits for the gathers then cover it.  (Requested behind the gathers
+    // it is the youngest load in flight when the row's reference code is waited for -- the counter is in order, and at
+    // that join of the own and the partner rows the wait is vmcnt(0) -- and the round trip is exposed there instead:
+    // measured slower than no request ahead at all)  Same address and same in-image rule as the
+    // load it replaces (index 0 for a pixel without a neighbour in the image: never 0 + noff); no request for a
+    // step the wave does not sample (a row of the partner band, a step outside its n_loc, the PRE variant).
+    // Compiled where the mode is a template argument (the launches of a sweep; the run-time-mode instantiations serve
+    // single evaluation and confidence launches) and up to four sources: beyond, the wave-uniform values of the request
+    // push SGPRs into VGPR lanes, and <11, 6, PROP> from 127 to 130 VGPRs (tools/gather_issue.py --table); so they do
+    // in the paired 3 x 3 propagation with four sources, which only a forced schedule reaches.
+    constexpr bool AHEAD = !PRE && MODE_T >= 0 && S <= 4 && !(PAIR && K == 3) && AMVS_FAST_STEP_DEPTH_AHEAD != 0;
+    const auto request_depth = [&](int y) {                  // y: the image row of an own step of this wave
+        const bool in = col_in & ((unsigned)y < (unsigned)H) & ((unsigned)(y + oy) < (unsigned)H) & ((unsigned)(xr + ox) < (unsigned)W);
+        return d_in[AMVS_IDX(in ? y * W + xr + noff : 0, HW)];
+    };
+    float d_next = 0.0f;
+    if constexpr (AHEAD) d_next = request_depth(PAIR ? y_start : y0 - HALF);    // (step 0 is an own step of every wave with a strip)
+
     for (int r = 0; r < rows; ++r) {
 #if AMVS_WG_WAVES > 1 && AMVS_WG_SYNC_ROWS > 0
         if (r % AMVS_WG_SYNC_ROWS == 0) __builtin_amdgcn_s_barrier();
@@ -284,7 +309,13 @@ __global__ __launch_bounds__(AMVS_WAVE * (PAIR ? PAIR_WAVES : AMVS_WG_WAVES), fa
             }
         } else {
             // ---- candidate depth of this (possibly halo) pixel ----
-            d_raw = d_in[AMVS_IDX(inb ? pix + noff : 0, HW)];
+            if constexpr (AHEAD) {
+                d_raw = d_next;
+                const int next = (PAIR ? loc : r) + 1;          // (wave-uniform)
+                if (next < n_own) d_next = request_depth(PAIR ? yr + dy : yr + 1);
+            } else {
+                d_raw = d_in[AMVS_IDX(inb ? pix + noff : 0, HW)];
+            }
             const float dc = candidate_depth(a, mode, inb, d_raw, h0);
             okbits = fast_sample_sources_checked<S, true, true>(job, fc, cols, (float)yr, dc, live, v);
             if constexpr (PAIR) {

@@ -54,7 +54,7 @@ if tr:
     if tot_n:
         out.append(f"{KF}*: {tot_n} dispatches in the traced step(s), launch-weighted mean {tot_t/tot_n:.4f} ms, sum {tot_t:.2f} ms")
 vals = {}
-for name in ("pmc_sq", "pmc_sq2", "pmc_fetch", "pmc_write"):
+for name in ("pmc_sq", "pmc_sq2", "pmc_vmem", "pmc_fetch", "pmc_write"):
     f = latest(f"{PROF}/{name}/*/*_counter_collection.csv")
     if not f:
         continue
