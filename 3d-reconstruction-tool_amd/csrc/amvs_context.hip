@@ -37,6 +37,7 @@ void check_fetch_twoview(unsigned long long out[4], bool reset);
 void check_fetch_kernels_fast_regs(unsigned long long out[4], bool reset);
 void check_fetch_bundle(unsigned long long out[4], bool reset);
 void check_fetch_sfm(unsigned long long out[4], bool reset);
+void check_fetch_kernels_fast_regs_packed(unsigned long long out[4], bool reset);
 }  // namespace amvs
 #endif
 
@@ -52,7 +53,8 @@ std::string g_create_error;
 // 4 amvs_sweep_exact, 5 amvs_generic, 6 amvs_extended, 7 amvs_fusion, 8 amvs_knn, 9 amvs_mesh, 10 amvs_mesh_clean,
 // 11 amvs_mesh_decimate, 12 amvs_mesh_render, 13 amvs_mesh_color, 14 amvs_mesh_texture, 15 amvs_mesh_fill,
 // 16 amvs_cloud_normals, 17 amvs_depth_filter, 18 amvs_undistort, 19 amvs_match, 20 amvs_triangulate, 21 amvs_fmat,
-// 22 amvs_kernels_fast_regs (lines of amvs_kernels_fast.hip), 23 amvs_pnp, 24 amvs_twoview, 25 amvs_bundle, 26 amvs_sfm;
+// 22 amvs_kernels_fast_regs (lines of amvs_kernels_fast.hip), 23 amvs_pnp, 24 amvs_twoview, 25 amvs_bundle, 26 amvs_sfm,
+// 27 amvs_kernels_fast_regs_packed (lines of amvs_kernels_fast.hip);
 // out[2] = the index, out[3] = the extent it was compared with).  Zeros in the shipped build.
 void index_report(uint64_t out[4], bool reset)
 {
@@ -67,7 +69,7 @@ void index_report(uint64_t out[4], bool reset)
         amvs::check_fetch_mesh_fill, amvs::check_fetch_cloud_normals, amvs::check_fetch_depth_filter,
         amvs::check_fetch_undistort, amvs::check_fetch_match, amvs::check_fetch_triangulate,
         amvs::check_fetch_fmat, amvs::check_fetch_kernels_fast_regs, amvs::check_fetch_pnp, amvs::check_fetch_twoview,
-        amvs::check_fetch_bundle, amvs::check_fetch_sfm};
+        amvs::check_fetch_bundle, amvs::check_fetch_sfm, amvs::check_fetch_kernels_fast_regs_packed};
     for (auto f : fetch) {
         unsigned long long r[4] = {0, 0, 0, 0};
         f(r, reset);

@@ -8,8 +8,16 @@ namespace amvs {
 
 template <int... Vs> using IntList = std::integer_sequence<int, Vs...>;
 
+template <class A, class B> struct Concat;
+template <int... As, int... Bs> struct Concat<IntList<As...>, IntList<Bs...>> { using type = IntList<As..., Bs...>; };
+
 using CompiledPatches = IntList<3, 5, 7, 9, 11, 13, 15, 17, 19, 21, 23, 25, 27, 29>;   // patch sizes K with kernels of their own
-using SourceCounts = IntList<2, 3, 4, 5, 6>;                                             // source views S per reference view
+// source views S per reference view, in the two parts the fast sweep step's register-source variants are compiled in:
+// amvs_kernels_fast_regs.hip holds the first, built without the packing of f32 pairs (csrc/Makefile), and
+// amvs_kernels_fast_regs_packed.hip the second, built as every other unit
+using UnpackedRegsSourceCounts = IntList<2, 3, 4, 5>;
+using PackedRegsSourceCounts = IntList<6>;
+using SourceCounts = Concat<UnpackedRegsSourceCounts, PackedRegsSourceCounts>::type;
 using ExtendedTaps = IntList<3, 4, 5, 6, 7>;                                             // extended mode: cost taps per axis
 using KnnSizes = IntList<8, 10, 16, 20, 32>;                                             // neighbours k of the kNN statistic
 
@@ -34,13 +42,20 @@ R dispatch(IntList<Vs...>, int v, R miss, F &&f)
     return r;
 }
 
-// f(K, S) over the compiled patch sizes and the source counts; `miss` when either is not in its list
+// f(K, S) over the compiled patch sizes and the given source counts; `miss` when either is not in its list
+template <class Sources, class R, class F>
+R dispatch_ks_of(Sources, int K, int S, R miss, F &&f)
+{
+    return dispatch(CompiledPatches{}, K, miss, [&](auto k) {
+        return dispatch(Sources{}, S, miss, [&](auto s) { return f(k, s); });
+    });
+}
+
+// ... over all source counts
 template <class R, class F>
 R dispatch_ks(int K, int S, R miss, F &&f)
 {
-    return dispatch(CompiledPatches{}, K, miss, [&](auto k) {
-        return dispatch(SourceCounts{}, S, miss, [&](auto s) { return f(k, s); });
-    });
+    return dispatch_ks_of(SourceCounts{}, K, S, miss, std::forward<F>(f));
 }
 
 }  // namespace amvs

@@ -20,9 +20,11 @@
 //     forms the same two values from those bytes instead of loading them (STATS below; amvs_set_step_sources);
 //   * NCC epilogue: cov * RN(1/den) (no quotient refinement).
 // The sweep step's variants that take the reference statistics or the centre depth from registers (StepArgs::
-// ref_in_kernel / depth_hist) are compiled from this file by a translation unit of their own, so that they build
+// ref_in_kernel / depth_hist) are compiled from this file by translation units of their own, so that they build
 // beside the others: amvs_kernels_fast_regs.hip defines AMVS_FAST_STEP_REGS_TU and includes this file, which then
-// compiles the step kernel, launch_step_fast_v and launch_step_fast_regs only.
+// compiles the step kernel, launch_step_fast_v and launch_step_fast_regs only; amvs_kernels_fast_regs_packed.hip
+// defines AMVS_FAST_STEP_REGS_PACKED as well and gets launch_step_fast_regs_packed, the same for the other part of
+// SourceCounts (amvs_dispatch.h).
 #ifndef AMVS_FAST_STEP_REGS_TU
 #define AMVS_TU_ID 2
 #endif
@@ -618,12 +620,20 @@ static hipError_t launch_step_fast_v(const StepArgs &a, int nblk, hipStream_t st
 }
 
 #ifdef AMVS_FAST_STEP_REGS_TU
-// (amvs_kernels_fast_regs.hip) the launches with StepArgs::ref_in_kernel or depth_hist set
+// (amvs_kernels_fast_regs.hip, amvs_kernels_fast_regs_packed.hip) the launches with StepArgs::ref_in_kernel or
+// depth_hist set, for the source counts of the including unit's part of SourceCounts
+#ifdef AMVS_FAST_STEP_REGS_PACKED
+hipError_t launch_step_fast_regs_packed(int K, int S, const StepArgs &a, hipStream_t st)
+{
+    using Sources = PackedRegsSourceCounts;
+#else
 hipError_t launch_step_fast_regs(int K, int S, const StepArgs &a, hipStream_t st)
 {
+    using Sources = UnpackedRegsSourceCounts;
+#endif
     const int nblk = a.n_jobs * a.tiles_x * a.tiles_y;
     const bool dh = a.depth_hist && !a.presampled && in_list(StepModes{}, a.mode);
-    return dispatch_ks(K, S, hipErrorInvalidValue, [&](auto k, auto s) {
+    return dispatch_ks_of(Sources{}, K, S, hipErrorInvalidValue, [&](auto k, auto s) {
         if constexpr (ref_in_kernel_compiled(k())) {
             if (a.ref_in_kernel)
                 return dh ? launch_step_fast_v<k(), s(), true, true>(a, nblk, st) : launch_step_fast_v<k(), s(), true, false>(a, nblk, st);
@@ -655,12 +665,16 @@ bool step_fast_pair_supported(int K, int S) { return patch_compiled(K) && in_lis
 bool step_fast_regs_supported(int K) { return patch_compiled(K) && ref_in_kernel_compiled(K); }
 int step_fast_regs_max_patch() { return AMVS_REF_IN_KERNEL_MAX_PATCH; }
 
+// (amvs_kernels_fast_regs_packed.hip: launch_step_fast_regs of amvs_kernels.h for S of PackedRegsSourceCounts)
+hipError_t launch_step_fast_regs_packed(int K, int S, const StepArgs &a, hipStream_t st);
+
 hipError_t launch_step_fast(int K, int S, const StepArgs &a, hipStream_t st)
 {
     if (!a.pairs) return hipErrorInvalidValue;        // fast mode samples the packed 8-bit maps only
     if ((a.ref_in_kernel || a.depth_hist) && !step_fast_regs_supported(K)) return hipErrorInvalidValue;   // (the host resolves both to 0 there)
     // the history exists in the launches that sample for themselves and select; the others load the centre depth
-    if (a.ref_in_kernel || (a.depth_hist && !a.presampled && in_list(StepModes{}, a.mode))) return launch_step_fast_regs(K, S, a, st);
+    if (a.ref_in_kernel || (a.depth_hist && !a.presampled && in_list(StepModes{}, a.mode)))
+        return in_list(PackedRegsSourceCounts{}, S) ? launch_step_fast_regs_packed(K, S, a, st) : launch_step_fast_regs(K, S, a, st);
     const int nblk = a.n_jobs * a.tiles_x * a.tiles_y;
     return dispatch_ks(K, S, hipErrorInvalidValue, [&](auto k, auto s) { return launch_step_fast_v<k(), s(), false, false>(a, nblk, st); });
 }
@@ -690,7 +704,9 @@ hipError_t launch_sample_fast(int S, const StepArgs &a, hipStream_t st)
 
 }  // namespace amvs
 
-#ifdef AMVS_FAST_STEP_REGS_TU
+#if defined(AMVS_FAST_STEP_REGS_PACKED)
+AMVS_CHECK_TU(kernels_fast_regs_packed)
+#elif defined(AMVS_FAST_STEP_REGS_TU)
 AMVS_CHECK_TU(kernels_fast_regs)
 #else
 AMVS_CHECK_TU(kernels_fast)

@@ -14,9 +14,7 @@ flags="--offload-arch=${ARCH:-gfx950} -O3 -ffp-contract=off -fPIC -std=c++17 -fv
 for f in $(make -s -C $src print-objs); do
   f=${f%.o}
   if [ $f = amvs_kernels_fast ] || [ $f = amvs_sweep_fast ] || { [ $f = amvs_sweep_exact ] && [ -z "$FAST_ONLY" ]; } || { [ $f = amvs_kernels ] && [ -z "$FAST_ONLY" ]; } || [ -n "$ALL" ] || [ ! -f $src/$f.o ]; then
-    extra=""; { [ $f = amvs_sweep_fast ] || [ $f = amvs_sweep_exact ]; } && extra="-mllvm -amdgpu-sched-strategy=iterative-maxocc"    # as csrc/Makefile
-    [ $f = amvs_match ] && extra="-mllvm -amdgpu-mfma-vgpr-form"
-    [ $f = amvs_pnp ] && extra="-mllvm -pragma-unroll-threshold=1048576"
+    extra=$(make -s -C $src print-sched-flags-$f)    # the unit's own flags: the one statement in csrc/Makefile
     /opt/rocm/bin/hipcc $flags $extra "$@" -c $src/$f.hip -o $out/obj_$name/$f.o &
   else
     cp $src/$f.o $out/obj_$name/$f.o

@@ -5,14 +5,16 @@ pm_step_fast_kernel.
 
     tools/gather_issue.py [--root DIR] [--asm FILE ...] [--table] [K,S,MODE,PRE,PAIR,STATS,DHIST ...]
 
-Compiles the device assembly of the two step translation units (csrc/amvs_kernels_fast.hip and
-csrc/amvs_kernels_fast_regs.hip of the tree at DIR, default this one; a few minutes, both at once) with the flags of
-csrc/Makefile, or reads assembly files given with --asm.  An instantiation is named by its template arguments as
+Compiles the device assembly of the step translation units (csrc/amvs_kernels_fast.hip, csrc/amvs_kernels_fast_regs.hip
+and, where the tree at DIR has it, csrc/amvs_kernels_fast_regs_packed.hip; DIR defaults to this tree; a few minutes, all at
+once) with the flags of csrc/Makefile, each unit's own included (`make print-sched-flags-<unit>`), or reads assembly files
+given with --asm.  An instantiation is named by its template arguments as
 numbers: 7,4,2,0,1,1,1 is <7, 4, MODE_REFINE, PRE false, PAIR, STATS, DHIST> (MODE: 1 propagation, 2 refinement,
 -1 the run-time mode); without any, every instantiation found is listed.  For each it prints
   * the `global_load_*` and `s_waitcnt vmcnt` instructions of the FIRST priority window, in order,
   * the number of vmcnt waits inside that window (a wait between two gathers is a round trip the row stands still for),
-  * VGPRs, SGPRs, scratch bytes and the number of v_writelane / v_readlane instructions (SGPR spills into lanes).
+  * VGPRs, SGPRs, scratch bytes and the number of v_writelane / v_readlane instructions (SGPR spills into lanes),
+  * in the whole kernel: packed f32 operations (v_pk_fma_f32, v_pk_add_f32, v_pk_mul_f32), v_mov_b32_e32 and s_nop.
 --table prints one line per instantiation instead.  It reads wait counts and loads only; it judges nothing.
 """
 import os
@@ -22,7 +24,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UNITS = ("amvs_kernels_fast.hip", "amvs_kernels_fast_regs.hip")
+UNITS = ("amvs_kernels_fast.hip", "amvs_kernels_fast_regs.hip", "amvs_kernels_fast_regs_packed.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--cuda-device-only", "-S"]
 BEGIN = re.compile(r"; -- Begin function (\S+)")
 STEP = re.compile(r"pm_step_fast_kernelIL(i\d+|in\d+)EL(i\d+|in\d+)EL(i\d+|in\d+)ELb([01])ELb([01])ELb([01])ELb([01])EE")
@@ -35,8 +37,13 @@ def compile_units(root, extra):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     jobs = []
     for u in UNITS:
+        if not os.path.exists(os.path.join(csrc, u)):
+            continue
+        # (a tree from before the Makefile stated them per unit has none for these units: the empty answer of a failed make)
+        own = subprocess.run(["make", "-s", "-C", csrc, "print-sched-flags-" + u[:-4]], capture_output=True, text=True)
+        own = own.stdout.split() if own.returncode == 0 else []
         out = os.path.join(tmp, u.replace(".hip", ".s"))
-        jobs.append((out, subprocess.Popen([hipcc] + FLAGS + extra + [os.path.join(csrc, u), "-o", out])))
+        jobs.append((out, subprocess.Popen([hipcc] + FLAGS + own + extra + [os.path.join(csrc, u), "-o", out])))
     for out, p in jobs:
         if p.wait() != 0:
             raise SystemExit(f"compiling {out} failed")
@@ -85,7 +92,11 @@ def describe(body):
                 return int(m.group(1))
         return -1
     lanes = sum(1 for line in body if re.match(r"\s*v_(writelane|readlane)_b32", line))
-    return {"window": window, "waits": sum(1 for w in window if w.startswith("s_waitcnt")),
+
+    def count(pattern):
+        return sum(1 for line in body if re.match(r"\s*" + pattern + r"\b", line))
+    return {"pk": count(r"v_pk_(fma|add|mul)_f32"), "mov": count(r"v_mov_b32_e32"), "nop": count(r"s_nop"),
+            "window": window, "waits": sum(1 for w in window if w.startswith("s_waitcnt")),
             "loads": sum(1 for w in window if w.startswith("global_load")),
             "vgpr": field("NumVgprs"), "sgpr": field("TotalNumSgprs"), "scratch": field("ScratchSize"), "lanes": lanes}
 
@@ -126,15 +137,16 @@ def main():
           f"{sum(1 for d in every if d['lanes'])} with v_writelane/v_readlane ({sum(d['lanes'] for d in every)} in all), "
           f"largest SGPR count {max(d['sgpr'] for d in every)}")
     if table:
-        print("# K S mode PRE PAIR STATS DHIST : loads and vmcnt waits in the first priority window, VGPRs, SGPRs, scratch bytes, lane moves")
+        print("# K S mode PRE PAIR STATS DHIST : loads and vmcnt waits in the first priority window, VGPRs, SGPRs, scratch bytes, lane moves; in the kernel: packed f32 operations, v_mov_b32_e32, s_nop")
     for key in wanted or sorted(kernels):
         d = describe(kernels[key])
         if table:
             print(f"{key[0]:2d} {key[1]} {MODES.get(key[2], key[2]):7s} {key[3]} {key[4]} {key[5]} {key[6]} : loads {d['loads']} waits {d['waits']} "
-                  f"vgpr {d['vgpr']} sgpr {d['sgpr']} scratch {d['scratch']} lanes {d['lanes']}")
+                  f"vgpr {d['vgpr']} sgpr {d['sgpr']} scratch {d['scratch']} lanes {d['lanes']} pk {d['pk']} mov {d['mov']} nop {d['nop']}")
             continue
         print(f"{label(key)}: {d['waits']} vmcnt waits among {d['loads']} loads in the first priority window; "
-              f"VGPRs {d['vgpr']}, SGPRs {d['sgpr']}, scratch {d['scratch']} B, v_writelane/v_readlane {d['lanes']}")
+              f"VGPRs {d['vgpr']}, SGPRs {d['sgpr']}, scratch {d['scratch']} B, v_writelane/v_readlane {d['lanes']}; "
+              f"packed f32 operations {d['pk']}, v_mov_b32_e32 {d['mov']}, s_nop {d['nop']}")
         for w in d["window"]:
             print("    " + w)
 
