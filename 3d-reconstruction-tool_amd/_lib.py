@@ -1,5 +1,5 @@
 """ctypes binding of libamvs.so (the C ABI declared in include/amvs.h, include/amvs_depth.h, include/amvs_lens.h,
-include/amvs_match.h, include/amvs_epipolar.h, include/amvs_resection.h, include/amvs_twoview.h, include/amvs_bundle.h, include/amvs_sfm.h, include/amvs_features.h and include/amvs_step.h).
+include/amvs_match.h, include/amvs_epipolar.h, include/amvs_resection.h, include/amvs_twoview.h, include/amvs_bundle.h, include/amvs_sfm.h, include/amvs_features.h, include/amvs_step.h and include/amvs_plan.h).
 
 There is no CPU fallback: if the shared library is missing or no HIP device is
 present, loading / context creation raises.
@@ -37,6 +37,46 @@ class XpmParams(C.Structure):
                 ("view_propagation", C.c_int32), ("depth_min", C.c_float), ("depth_max", C.c_float),
                 ("log_depth_scale", C.c_float), ("log_depth_min", C.c_float),
                 ("consistency_px", C.c_float), ("consistency_rel", C.c_float)]
+
+
+def _i32_struct(name, fields):
+    return type(name, (C.Structure,), {"_fields_": [(f, C.c_int32) for f in fields.split()]})
+
+
+# include/amvs_plan.h: the launch planner's inputs and outputs (plan_patchmatch, plan_plane_sweep)
+PlanDevice = _i32_struct("PlanDevice", "H W n_cu packed_maps")
+PlanSweep = _i32_struct("PlanSweep", "tile_rows tiles_x tiles_y chunk n_chunks key8")
+
+
+class PlanCall(C.Structure):
+    _fields_ = [("n_ref", C.c_int32), ("n_src", C.c_int32), ("fast", C.c_int32), ("p", PmParams)]
+
+
+class PlanTuning(C.Structure):
+    _fields_ = [("default_band_major", C.c_int32), ("n_tune", C.c_int32),
+                ("tune_rows", C.POINTER(C.c_int32)), ("tune_cap", C.POINTER(C.c_int32))] + \
+               [(f, C.c_int32) for f in "split_groups split_sample_rows split_sample_lds edge_first group_overlap "
+                                         "sweep_tile_rows sweep_chunk sweep_key8 ref_stats_source depth_source".split()]
+
+
+class PlanFacts(C.Structure):
+    _fields_ = [("out_width", C.c_int32), ("waves_per_cu", C.c_int32 * 9)] + \
+               [(f, C.c_int32) for f in "patch_compiled pair_supported fast_pair_supported fast_regs_supported "
+                                         "sweep_max_th sweep_max_th8 sweep_max_chunk sweep_max_chunk8".split()]
+
+
+class PlanStep(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("oy", C.c_int32), ("ox", C.c_int32), ("depth_range", C.c_float),
+                ("normal_range", C.c_float), ("draw", C.c_uint32), ("flip_d", C.c_int32), ("iter", C.c_int32),
+                ("rows", C.c_int32), ("wg_cap", C.c_int32), ("tiles_y", C.c_int32)]
+
+
+class PmPlan(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in "band_major paired views_per_launch n_groups tile_rows tiles_x tiles_y overlap "
+                                         "edge_first n_steps final_parity last_tile_rows".split()] + \
+               [("launches", C.c_int64)] + \
+               [(f, C.c_int32) for f in "split_groups split_vpl split_tile_rows s_tile_rows s_lds s_tiles_x s_tiles_y "
+                                         "ref_in_kernel depth_hist single_step_rows".split()]
 
 
 class Timing(C.Structure):
@@ -282,6 +322,14 @@ STEP_SIGNATURES = {
     "amvs_step_sources_max_patch": (C.c_int, []),
 }
 
+# name -> (restype, argtypes); every symbol include/amvs_plan.h declares (a table of its own for the same reason)
+PLAN_SIGNATURES = {
+    "amvs_plan_patchmatch": (C.c_int, [C.POINTER(PlanDevice), C.POINTER(PlanCall), C.POINTER(PlanTuning), C.POINTER(PlanFacts),
+                                       C.POINTER(PmPlan), C.POINTER(PlanStep), C.c_int32]),
+    "amvs_plan_plane_sweep": (C.c_int, [C.POINTER(PlanDevice), C.POINTER(PlanTuning), C.POINTER(PlanFacts), C.c_int, C.c_int,
+                                        C.POINTER(PlanSweep)]),
+}
+
 # name -> (restype, argtypes); every symbol include/amvs_features.h declares (a table of its own for the same reason)
 FEATURE_SIGNATURES = {
     "amvs_clahe_u8": (C.c_int, [C.c_void_p, u8p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, u8p]),
@@ -334,7 +382,7 @@ def load():
         for name, (res, args) in list(SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(LENS_SIGNATURES.items()) \
                 + list(MATCH_SIGNATURES.items()) + list(EPIPOLAR_SIGNATURES.items()) + list(PNP_SIGNATURES.items()) + list(TWOVIEW_SIGNATURES.items()) \
                 + list(BA_SIGNATURES.items()) + list(SFM_SIGNATURES.items()) + list(STEP_SIGNATURES.items()) \
-                + list(FEATURE_SIGNATURES.items()):
+                + list(FEATURE_SIGNATURES.items()) + list(PLAN_SIGNATURES.items()):
             fn = getattr(lib, name)      # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args
@@ -362,6 +410,44 @@ def sweep_order(n_jobs, tiles_x, tiles_y, band_major=False, paired=False, edge_f
     out = np.full((n.value, 4, 5), -2, np.int32)
     lib.amvs_sweep_order(*args, out.size, out.ctypes.data_as(i32p), C.byref(n))
     return out
+
+
+def _struct_dict(s):
+    return {f: (list(v) if hasattr(v, "__len__") else v) for f, _ in s._fields_ for v in [getattr(s, f)]}
+
+
+def _plan_inputs(device, tuning, facts):
+    """(PlanDevice, PlanTuning, PlanFacts, keep) from dicts keyed by the fields of include/amvs_plan.h; tuning's
+    tune_rows / tune_cap are flat lists of one length (two values per iteration) or absent, facts' waves_per_cu a list of 9."""
+    t = dict(tuning)
+    rows, cap = [(C.c_int32 * len(v))(*v) if v else None for v in (t.pop("tune_rows", None), t.pop("tune_cap", None))]
+    if rows and cap and len(rows) != len(cap):
+        raise ValueError("tune_rows and tune_cap are tables of one size")
+    tun = PlanTuning(n_tune=len(rows or cap or ()), tune_rows=rows, tune_cap=cap, **t)
+    f = dict(facts)
+    return PlanDevice(**device), tun, PlanFacts(waves_per_cu=(C.c_int32 * 9)(*f.pop("waves_per_cu")), **f), (rows, cap)
+
+
+def plan_patchmatch(device, call, tuning, facts):
+    """(plan, steps) -- dicts keyed by the fields of amvs_pm_plan / amvs_plan_step -- of a PatchMatch call as the entry
+    points plan it (include/amvs_plan.h amvs_plan_patchmatch; no GPU involved).  call: n_ref, n_src, fast, p (PmParams)."""
+    lib = load()
+    dev, tun, fac, _keep = _plan_inputs(device, tuning, facts)
+    cal, plan = PlanCall(**call), PmPlan()
+    if lib.amvs_plan_patchmatch(dev, cal, tun, fac, plan, None, 0) != 0:
+        raise AmvsError("amvs_plan_patchmatch: bad argument")
+    steps = (PlanStep * max(plan.n_steps, 1))()
+    lib.amvs_plan_patchmatch(dev, cal, tun, fac, plan, steps, plan.n_steps)
+    return _struct_dict(plan), [_struct_dict(s) for s in steps[:plan.n_steps]]
+
+
+def plan_plane_sweep(device, tuning, facts, n_ref, n_planes):
+    """The amvs_sweep_plan of a plane sweep as a dict (include/amvs_plan.h amvs_plan_plane_sweep; no GPU involved)."""
+    dev, tun, fac, _keep = _plan_inputs(device, tuning, facts)
+    plan = PlanSweep()
+    if load().amvs_plan_plane_sweep(dev, tun, fac, int(n_ref), int(n_planes), plan) != 0:
+        raise AmvsError("amvs_plan_plane_sweep: bad argument")
+    return _struct_dict(plan)
 
 
 def index_checks_enabled():

@@ -1,5 +1,6 @@
-// amvs_capi.hip -- the C ABI of include/amvs.h: view upload and the PatchMatch step scheduling.
-// (The context: amvs_context.hip; the other entry points: amvs_capi_*.hip, amvs_comm.hip.)
+// amvs_capi.hip -- the C ABI of include/amvs.h: view upload and the issuing of the PatchMatch sweep steps.
+// (The context: amvs_context.hip; the other entry points: amvs_capi_*.hip, amvs_comm.hip.  What a call launches -- views
+// per launch, strip rows, schedule -- is decided in amvs_launch_plan.h; the schedules here issue that plan.)
 //
 // Host-side orchestration of PatchMatchMVS._patchmatch_cuda (mvs_patchmatch.py:225-321)
 // and DenseStereoReconstructor._plane_sweep_torch (dense_stereo.py:222-316): all views of
@@ -17,98 +18,17 @@ using namespace amvs::host;
 
 namespace {
 
-// Views swept together by one launch (the views of a batch are independent, mvs_patchmatch.py:104-123, so
-// a batch can be swept in groups, each through the whole schedule).  Groups of FOUR views against the
-// whole 16-view batch, measured on MI355X in round 3 (S=4, G px-hyp/s, automatic strip heights, one run
-// per pair):
-//     fast, 1080p:  k=3  52.0 / 49.3    k=5  46.2 / 45.0    k=7  42.1 / 41.6    k=9  36.4 / 38.3    k=11  33.8 / 35.4
-//     fast, k=7:    2560x1440  36.4 / 38.8      3840x2160 (8 views: 4 / 8 per launch)  35.4 / 36.1
-//     exact, 1080p, k=7:  37.0 / 38.2           fast, 1080p, k=7, 8-view rank shard:  42.2 / 40.0
-// Four 1080p views are two generations of resident waves at 18-row strips and an XCD's L2 then serves the
-// sources of 4 views instead of 16 (hit rate 0.81 against 0.69); a launch of two generations also has a
-// relatively longer tail than one of six, which is what the wider images, the larger patches and the
-// slower exact kernel lose more to than the L2 returns.  Hence groups of four exactly where they were
-// measured to win, else the whole batch (capped so that the per-launch state stays in the low GB).
-// Paired bands (round 3, later; bench.py, G px-hyp/s, groups of four / whole batch): 16 views 43.3 / 43.2,
-// 8 views 44.2 / 42.3, k=5 47.2 / 45.9 -- the same rule holds.
-int default_views_per_launch(const amvs_ctx *c, int n_ref, int patch, bool fast)
-{
-    if (fast && patch <= 7 && c->W <= 2048 && n_ref >= 8 && n_ref % 4 == 0) return 4;
-    return n_ref < 32 ? n_ref : 32;
-}
+using amvs::plan::PmPlan;
 
-// Rows per wave strip.  A strip re-samples 2*(patch/2) halo rows, so tall strips waste less; two
-// things pull the other way.  (1) The set of source rows the resident waves touch at once: measured
-// on MI355X (S=4, 16 views 1080p; best strip height per patch size) k=3: 10-12 rows, k=5: 14-18, k=7:
-// 20-26 (32: -3 %, 40+: -15 %), k=9: 24-32, k=11: 32-40, i.e. about 4k-4, and lower for wider images
-// (8 views 4K, k=7: 12-16 rows best, 24: -6 %) -- that is the cap `tall`.  (2) Wave quantisation: the
-// launch runs in generations of `slots` resident waves, and a last generation that is nearly empty
-// costs as much as a full one.  Measured, k=7, 1080p, G px-hyp/s by (views per launch: strip rows):
-// 16: 24 -> 40.2; 8: 24 / 20 / 16 / 12 -> 39.2 / 39.2 / 39.1 / 38.5; 4: 24 / 16 / 12 / 8 -> 36.7 / 38.4 /
-// 39.9 / 37.5; 2: 24 / 16 / 12 / 8 -> 39.4 / 34.5 / 38.6 / 35.9; 1: 24 / 16 / 12 / 8 -> 26.5 / 29.0 / 35.3 / 29.1
-// -- the winners are the heights whose wave count is just below a whole number of generations
-// (or at least 3/4 of one).  Hence: among the heights up to `tall`, the best product of the last
-// generation's fill and the strip's useful fraction rows / (rows + patch - 1).
-// Paired bands (`paired`): a pair of bands samples 2 th + patch - 1 rows for 2 th output rows (an odd last
-// band keeps the classic th + patch - 1), and the locality cap is lower -- measured, 16 views 1080p, k=7, ms
-// per launch by band rows 12 / 14 / 16 / 18 / 20 / 22 / 24 / 27 / 30 / 36: 0.761 / 0.755 / 0.750 / 0.749 /
-// 0.751 / 0.755 / 0.762 / 0.761 / 0.765 / 0.780 -> 3 * patch - 3; k=5 in groups of 4 views: 12 rows 47.2, 16 rows
-// 44.0 G px-hyp/s; 2560x1440: 12 / 16 / 18 rows 40.5 / 41.1 / 41.3; 8 views 3840x2160: 38.5 / 38.4 / 38.2 (the
-// reduction for wide images applies beyond 3072 columns only).
-int pick_tile_rows(const amvs_ctx *c, int patch, int n_src, int n_jobs, int requested, int cap, bool fast = false,
-                   int wg_cap = 0, bool paired = false)
-{
-    if (requested > 0) return requested < cap ? requested : cap;
-    const int tiles_x = (c->W + amvs::strip_out_width(patch) - 1) / amvs::strip_out_width(patch);
-    const long long slots = (long long)c->n_cu * (fast ? amvs::step_fast_waves_per_cu(patch, n_src, wg_cap)
-                                                       : amvs::step_waves_per_cu(patch, n_src, usable_pairs(c) != nullptr, wg_cap));
-    int tall = 4 * patch - 4 > 12 ? 4 * patch - 4 : 12;
-    if (paired) tall = 3 * patch - 3 > 8 ? 3 * patch - 3 : 8;
-    if (c->W > (paired ? 3072 : 2048)) tall = tall * 2 / 3 > 8 ? tall * 2 / 3 : 8;
-    if (tall > cap) tall = cap;
-    int best = tall < 8 ? tall : 8;
-    double best_score = -1.0;
-    for (int th = tall; th >= (tall < 8 ? tall : 8); th -= 2) {
-        const double waves = (double)n_jobs * tiles_x * ((c->H + th - 1) / th);
-        const double g = waves / (double)slots;
-        const double fill = g > 1.0 ? g / std::ceil(g) : (g >= 0.75 ? 1.0 : g / 0.75);
-        double useful = (double)th / (double)(th + patch - 1);
-        if (paired) {
-            const int bands = (c->H + th - 1) / th;
-            const double sampled = (double)(bands / 2) * (2 * th + patch - 1) + (double)(bands % 2) * (th + patch - 1);
-            useful = (double)c->H / sampled;
-        }
-        const double score = fill * useful;
-        if (score > best_score + 1e-9) { best_score = score; best = th; }
-    }
-    return best;
-}
-
-// Band-major schedule (StepArgs::band_major): strip height such that ONE band of all views of the
-// launch about fills an XCD's wave slots, i.e. every XCD walks its own band(s) of all views top to
-// bottom in one generation of waves.  Few views: several adjacent bands per XCD.
-int pick_band_rows(const amvs_ctx *c, int patch, int n_src, int n_jobs, bool fast)
-{
-    const int tiles_x = (c->W + amvs::strip_out_width(patch) - 1) / amvs::strip_out_width(patch);
-    const long long slots_xcd = (long long)(c->n_cu / 8 > 0 ? c->n_cu / 8 : 1) *
-                                (fast ? amvs::step_fast_waves_per_cu(patch, n_src)
-                                      : amvs::step_waves_per_cu(patch, n_src, usable_pairs(c) != nullptr));
-    const long long per_band = (long long)n_jobs * tiles_x;
-    long long g = slots_xcd / per_band;             // bands resident together per XCD
-    if (g < 1) g = 1;
-    const long long bands = 8 * g;
-    long long th = (c->H + bands - 1) / bands;
-    const int min_th = 2 * patch > 8 ? 2 * patch : 8;
-    if (th < min_th) th = min_th;
-    return (int)th;
-}
+static_assert(amvs::plan::STEP_PROP == amvs::MODE_PROP && amvs::plan::STEP_REFINE == amvs::MODE_REFINE, "step modes out of sync");
+static_assert(amvs::plan::SPLIT_MAX_GROUPS == 8, "amvs_ctx::split_events holds 1 + 2 * 8 events");
 
 amvs::StepArgs base_args(const amvs_ctx *c, int patch, int n_jobs, int TH)
 {
     amvs::StepArgs a{};
     a.H = c->H; a.W = c->W; a.TH = TH;
-    a.tiles_x = (c->W + amvs::strip_out_width(patch) - 1) / amvs::strip_out_width(patch);
-    a.tiles_y = (c->H + TH - 1) / TH;
+    a.tiles_x = amvs::plan::strip_cols(c->W, amvs::strip_out_width(patch));
+    a.tiles_y = amvs::plan::ceil_div(c->H, TH);
     a.n_jobs = n_jobs;
     a.img_stride = c->stride;
     a.images = c->d_images.get();
@@ -135,74 +55,19 @@ void set_io(amvs::StepArgs &a, const amvs_ctx *c, int cur_d, bool tagged = true)
     a.depth_mask = tagged ? 0x7FFFFFFFu : 0xFFFFFFFFu;
 }
 
-// Launch shape of one sweep step.  The gathers of an early iteration are scattered over the whole
-// depth range (every pixel perturbs its depth by up to depth_range / 2^it), those of a late one are
-// coherent, so the best strip height / residency differ by iteration; measured table: DESIGN.md
-// section 5 (round 3).  An explicit amvs_pm_params.tile_rows, then amvs_set_step_tuning, override it.
-struct StepShape { int rows, wg_cap; };
-
-StepShape step_shape(const amvs_ctx *c, const amvs_pm_params *p, int n_src, int n_jobs, int iter, bool refine, bool fast,
-                     int default_rows)
-{
-    StepShape s{default_rows, 0};
-    const size_t idx = (size_t)2 * (size_t)iter + (refine ? 1 : 0);
-    const size_t last = c->tune_rows.size() >= 2 ? c->tune_rows.size() - 2 + (refine ? 1 : 0) : 0;
-    int rows = 0, cap = 0;
-    if (!c->tune_rows.empty()) rows = c->tune_rows[idx < c->tune_rows.size() ? idx : last];
-    if (!c->tune_cap.empty()) cap = c->tune_cap[idx < c->tune_cap.size() ? idx : last];
-    if (cap > 0) s.wg_cap = cap;
-    if (p->tile_rows > 0) return s;                       // the caller fixed the strip height
-    if (rows > 0) s.rows = rows;
-    else if (cap > 0) s.rows = pick_tile_rows(c, p->patch_size, n_src, n_jobs, 0, 1 << 20, fast, cap);
-    return s;
-}
-
-// The sweep schedule of one PatchMatch call as a list of launches (the same for every view).
-struct SchedStep {
-    int mode, oy, ox;
-    float depth_range, normal_range;
-    unsigned draw;
-    int flip_d;                          // depth buffers ping-ponged by the step (set_io)
-    int iter;
-};
-
-std::vector<SchedStep> build_schedule(const amvs_pm_params *p)
-{
-    std::vector<SchedStep> v;
-    for (int it = p->first_iteration; it < p->first_iteration + p->num_iterations; ++it) {
-        // _spatial_propagation (mvs_patchmatch.py:415-457): even iterations pull from
-        // (y+1,x) then (y,x+1), odd iterations from (y-1,x) then (y,x-1)
-        const int sgn = (it % 2 == 0) ? 1 : -1;
-        for (int k = 0; k < 2; ++k)
-            v.push_back(SchedStep{amvs::MODE_PROP, k == 0 ? sgn : 0, k == 0 ? 0 : sgn, 0.f, 0.f, 0u, 1, it});
-        // _random_refinement (mvs_patchmatch.py:459-491): ranges formed in double, cast once
-        const float dr = (float)(((double)p->depth_max - (double)p->depth_min) * std::pow(0.5, it));
-        const float nr = (float)(0.5 * std::pow(0.5, it));
-        for (int s = 0; s < p->num_samples; ++s)
-            v.push_back(SchedStep{amvs::MODE_REFINE, 0, 0, dr, nr, (unsigned)(1 + it * p->num_samples + s), 1, it});
-    }
-    return v;
-}
-
-void apply_step(amvs::StepArgs &a, const SchedStep &st)
+// one launch of the plan: what it does and its shape
+void apply_step(amvs::StepArgs &a, const amvs::plan::Step &st)
 {
     a.mode = st.mode; a.oy = st.oy; a.ox = st.ox;
     if (st.mode == amvs::MODE_REFINE) { a.depth_range = st.depth_range; a.normal_range = st.normal_range; a.draw = st.draw; }
+    a.TH = st.rows; a.tiles_y = st.tiles_y; a.wg_cap = st.wg_cap;
 }
 
-// The two streams of amvs_ctx::group_overlap = 1 (equal priorities) or 2 (high / low: distinct priorities land on
-// distinct hardware queues, see run_split_schedule), created once per context.
+// The two streams of SweepTuning::group_overlap = 1 (equal priorities) or 2 (high / low), created once per context.
 int group_streams(amvs_ctx *c, int overlap, hipStream_t out[2])
 {
-    amvs::Stream *st = c->group_streams[overlap - 1];
-    if (!st[0].get()) {
-        int lo = 0, hi = 0;
-        HIPCHK(c, hipDeviceGetStreamPriorityRange(&lo, &hi));      // (numerically: hi <= lo)
-        amvs::Stream made[2];                                      // (both or neither: a failure leaves the pair empty)
-        for (int i = 0; i < 2; ++i)
-            HIPCHK(c, made[i].create(overlap == 2 ? (i == 0 ? hi : lo) : lo));
-        for (int i = 0; i < 2; ++i) st[i] = std::move(made[i]);
-    }
+    amvs::Stream (&st)[2] = c->group_streams[overlap - 1];
+    if (!st[0].get()) HIPCHK(c, amvs::create_stream_pair(st, overlap == 2, false));
     if (!c->group_fork.get()) {
         amvs::Event fork, join;
         HIPCHK(c, fork.create(false));
@@ -213,86 +78,48 @@ int group_streams(amvs_ctx *c, int overlap, hipStream_t out[2])
     return AMVS_OK;
 }
 
-// The batch in groups of `vpl` views, each group through the whole schedule with the fused kernel (sampling +
-// window sums + selection in one launch).  One stream, or (amvs_ctx::group_overlap) the groups dealt to two streams
+// The batch in the plan's groups of views, each group through the whole schedule with the fused kernel (sampling +
+// window sums + selection in one launch).  One stream, or (PmPlan::overlap) the groups dealt to two streams
 // that fork from the context's stream and join it again: the groups are independent (mvs_patchmatch.py:104-123) --
 // their StepArgs, state slots, job entries and confidence slots are disjoint, the images and the job table are
 // read-only, and the fused launches use no other scratch -- so the workgroups of one group fill the wave slots the
 // tail of the other leaves empty.  Every group still runs its whole schedule in order on its stream.
-int run_fused_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *p, uint64_t seed, int fast,
-                       const std::vector<SchedStep> &sched, void *conf_dev, int cur0, bool do_init, bool do_conf)
+int run_fused_schedule(amvs_ctx *c, int n_src, const amvs_pm_params *p, uint64_t seed, int fast, const PmPlan &plan, void *conf_dev,
+                       int cur0, bool do_init, bool do_conf)
 {
     const size_t hw = (size_t)c->H * c->W;
-    // Views per launch: the views of a batch are independent, so the batch can be swept in groups of
-    // `vpl` views, each group through the whole schedule (see default_views_per_launch).
-    const int band_major = p->schedule == 0 ? c->default_band_major : (p->schedule == 2);
-    // paired bands: asked for, or the automatic choice where they were measured faster (round 3, fast
-    // arithmetic, one run per pair, G px-hyp/s paired / classic: k=7 1080p 43.3 / 41.9, k=5 47.3 / 46.2,
-    // k=3 51.2 / 52.0 -- a one-row halo leaves nothing to save --, 2560x1440 41.6 / 39.3, 8 views of
-    // 3840x2160 38.7 / 36.4, 32 views 43.0 / 41.7)
-    // 9x9 / 11x11 (round 4: compiled, their exchange fits four workgroups per CU, bit-identical -- and measured NOT
-    // faster: fast 11x11 36.2 paired at its best height (34 rows) against 36.4 classic, 9x9 38.2 against 39.2, exact
-    // 35.4 / 35.7 and 30.7 / 32.3: at these sizes the k - 1 cross-lane adds of the window sums, not the sampled rows,
-    // carry the launch): the automatic schedule keeps them classic
-    const bool paired = (p->schedule == AMVS_SCHEDULE_PAIRED ||
-                         (p->schedule == AMVS_SCHEDULE_AUTO && !band_major && p->patch_size >= 5 && p->patch_size <= 7)) &&
-                        (fast ? amvs::step_fast_pair_supported(p->patch_size, n_src)
-                              : (usable_pairs(c) != nullptr && amvs::step_pair_supported(p->patch_size, n_src)));
-    int vpl = p->views_per_launch > 0 ? p->views_per_launch : default_views_per_launch(c, n_ref, p->patch_size, fast != 0);
-    if (vpl > n_ref) vpl = n_ref;
-    const int TH = p->tile_rows > 0 || !band_major
-                       ? pick_tile_rows(c, p->patch_size, n_src, vpl, p->tile_rows, 1 << 20, fast != 0, 0, paired)
-                       : pick_band_rows(c, p->patch_size, n_src, vpl, fast != 0);
-    c->last_tile_rows = TH;
-    // launch shape of every step: strip rows and resident workgroups per CU (step_shape)
-    std::vector<StepShape> shapes(sched.size());
-    for (size_t i = 0; i < sched.size(); ++i) {
-        shapes[i] = band_major ? StepShape{TH, 0}
-                               : step_shape(c, p, n_src, vpl, sched[i].iter, sched[i].mode == amvs::MODE_REFINE, fast != 0, TH);
-        c->last_tile_rows = shapes[i].rows;
-    }
-    const int n_steps_timed = c->step_timing ? (int)sched.size() * ((n_ref + vpl - 1) / vpl) : 0;
-    HIPCHK(c, c->ev_steps.reserve(n_steps_timed + (n_ref + vpl - 1) / vpl));
+    const size_t n_groups = plan.groups.size();
+    HIPCHK(c, c->ev_steps.reserve((c->step_timing ? (size_t)plan.launches : 0) + n_groups));
     c->n_step_events = 0;
-    const int n_groups = (n_ref + vpl - 1) / vpl;
     // events: [0] start, then per group: after init, after steps, after confidence
     HIPCHK(c, c->ev_groups.reserve(3 * n_groups));
-    c->timing_groups = n_groups;
+    c->timing_groups = (int)n_groups;
 #ifdef AMVS_STEP_TRACE
     // (cleared on the context's stream BEFORE the group streams fork from it)
-    {
-        long long blocks = 0;
-        for (const StepShape &sh : shapes) {
-            const long long b = (long long)vpl * base_args(c, p->patch_size, vpl, TH).tiles_x * ((c->H + sh.rows - 1) / sh.rows);
-            blocks = b > blocks ? b : blocks;                  // (one strip per block at most: the run-time-k kernels)
-        }
-        c->trace_stride = blocks;
-        c->trace_launches = (long long)n_groups * (long long)sched.size();
-        HIPCHK(c, c->d_trace.reserve((size_t)(4 * blocks * c->trace_launches) + 1, c->cache));
-        HIPCHK(c, hipMemsetAsync(c->d_trace.get(), 0, sizeof(unsigned long long) * (size_t)(4 * blocks * c->trace_launches), c->stream));
-    }
+    c->trace_stride = plan.trace_blocks;
+    c->trace_launches = plan.launches;
+    HIPCHK(c, c->d_trace.reserve((size_t)(4 * c->trace_stride * c->trace_launches) + 1, c->cache));
+    HIPCHK(c, hipMemsetAsync(c->d_trace.get(), 0, sizeof(unsigned long long) * (size_t)(4 * c->trace_stride * c->trace_launches), c->stream));
 #endif
-    const int overlap = n_groups > 1 ? c->group_overlap : 0;
-    c->timing_overlapped = overlap != 0;
+    c->timing_overlapped = plan.overlap != 0;
     hipStream_t lanes[2] = {c->stream, c->stream};
-    if (overlap) {
-        int rc = group_streams(c, overlap, lanes);
+    if (plan.overlap) {
+        int rc = group_streams(c, plan.overlap, lanes);
         if (rc) return rc;
         HIPCHK(c, hipEventRecord(c->group_fork.get(), c->stream));
         for (hipStream_t st : lanes) HIPCHK(c, hipStreamWaitEvent(st, c->group_fork.get(), 0));
     }
-    int64_t launches = 0;
-    for (int g = 0; g < n_groups; ++g) {
-        const int j0 = g * vpl, nj = (n_ref - j0) < vpl ? (n_ref - j0) : vpl;
+    for (size_t g = 0; g < n_groups; ++g) {
+        const int nj = plan.groups[g].count;
         hipStream_t stream = lanes[g % 2];
-        amvs::StepArgs a = base_args(c, p->patch_size, nj, TH);
+        amvs::StepArgs a = base_args(c, p->patch_size, nj, plan.TH);
         a.fast = fast;
-        a.band_major = band_major;
-        a.paired = paired ? 1 : 0;
-        a.jobs = c->d_jobs.get() + j0;                   // slots stay global: job.slot = index in the batch
+        a.band_major = plan.band_major;
+        a.paired = plan.paired ? 1 : 0;
+        a.jobs = c->d_jobs.get() + plan.groups[g].first;     // slots stay global: job.slot = index in the batch
         a.depth_min = p->depth_min; a.depth_max = p->depth_max;
         a.seed = seed;
-        a.edge_first = c->edge_first < 0 ? (overlap != 0) : c->edge_first;
+        a.edge_first = plan.edge_first;
         int cur = cur0;
         // initialisation (mvs_patchmatch.py:268-284); a continuation call resumes the context's state
         if (do_init)
@@ -300,22 +127,19 @@ int run_fused_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
                                         c->d_depth[cur].get(), c->d_normal[0].get(), c->d_cost.get(), stream));
         HIPCHK(c, hipEventRecord(c->ev_groups[3 * g], stream));
         if (c->step_timing) HIPCHK(c, hipEventRecord(c->ev_steps[c->n_step_events++], stream));
-        for (size_t i = 0; i < sched.size(); ++i) {
-            const SchedStep &st = sched[i];
+        for (size_t i = 0; i < plan.steps.size(); ++i) {
+            const amvs::plan::Step &st = plan.steps[i];
             apply_step(a, st);
-            a.TH = shapes[i].rows;
-            a.tiles_y = (c->H + a.TH - 1) / a.TH;
-            a.wg_cap = shapes[i].wg_cap;
             set_io(a, c, cur);
 #ifdef AMVS_STEP_TRACE
-            a.trace = c->d_trace.get() + 4 * c->trace_stride * ((long long)g * (long long)sched.size() + (long long)i);
+            a.trace = c->d_trace.get() + 4 * c->trace_stride * (long long)(g * plan.steps.size() + i);
 #endif
             HIPCHK(c, amvs::launch_step(p->patch_size, n_src, a, stream));
             if (c->step_timing) HIPCHK(c, hipEventRecord(c->ev_steps[c->n_step_events++], stream));
-            cur ^= st.flip_d; ++launches;
+            cur ^= st.flip_d;
         }
-        a.TH = TH;
-        a.tiles_y = (c->H + TH - 1) / TH;
+        a.TH = plan.TH;
+        a.tiles_y = plan.tiles_y;
         a.wg_cap = 0;
         a.trace = nullptr;
         HIPCHK(c, hipEventRecord(c->ev_groups[3 * g + 1], stream));
@@ -328,72 +152,48 @@ int run_fused_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
         }
         HIPCHK(c, hipEventRecord(c->ev_groups[3 * g + 2], stream));
     }
-    if (overlap)
+    if (plan.overlap)
         for (hipStream_t st : lanes) {
             HIPCHK(c, hipEventRecord(c->group_join.get(), st));
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->group_join.get(), 0));
         }
-    c->timing.sweep_launches = launches;
-    c->last_views_per_launch = vpl;
     return AMVS_OK;
 }
 
 // Split schedule (fast mode).  A sweep step is two kernels: the SAMPLING kernel visits every pixel
 // once -- no strip halo -- and is bound by the CU's L1 line rate for scattered gathers; the WINDOW
 // kernel streams the sample maps (coalesced) through the box sums, NCC and selection.  They stress
-// different parts of the CU, so the batch is cut into G view groups and the two kernel kinds run on
+// different parts of the CU, so the batch is cut into view groups (SplitPlan) and the two kernel kinds run on
 // two streams (distinct priorities, so that they land on distinct hardware queues):
 //     sampling stream:  sample(g0,n) sample(g1,n) sample(g0,n+1) ...   (never two of them at once)
 //     window stream:    window(g,n) after sample(g,n); sample(g,n+1) after window(g,n)   (events)
 // so window(g,n) runs under the sampling of the next group.  Views are independent
 // (mvs_patchmatch.py:104-123), nothing else orders the groups.  Results are those of the fused kernel
 // bit for bit (same arithmetic, same order of every sum).
-int run_split_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *p, uint64_t seed,
-                       const std::vector<SchedStep> &sched, void *conf_dev)
+int run_split_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *p, uint64_t seed, const PmPlan &plan, void *conf_dev)
 {
     const size_t hw = (size_t)c->H * c->W;
-    constexpr int MAXG = 8;
-    int G = p->views_per_launch > 0 ? (n_ref + p->views_per_launch - 1) / p->views_per_launch
-                                    : (c->split_groups > 0 ? c->split_groups : 2);
-    if (G > n_ref) G = n_ref;
-    if (G > MAXG) G = MAXG;
-    const int vpl = (n_ref + G - 1) / G;
-    G = (n_ref + vpl - 1) / vpl;
+    const amvs::plan::SplitPlan &sp = plan.split;
     HIPCHK(c, c->d_samples.reserve((size_t)n_ref * n_src * hw, c->cache));
-    if (!c->split_streams[0].get()) {
-        int lo = 0, hi = 0;
-        HIPCHK(c, hipDeviceGetStreamPriorityRange(&lo, &hi));        // lo = least urgent
-        amvs::Stream made[2];                                        // (both or neither, as group_streams)
-        for (int i = 0; i < 2; ++i)
-            HIPCHK(c, made[i].create(i == 0 ? lo : hi));
-        for (int i = 0; i < 2; ++i) c->split_streams[i] = std::move(made[i]);
-    }
-    HIPCHK(c, c->split_events.reserve(1 + 2 * MAXG));
+    if (!c->split_streams[0].get()) HIPCHK(c, amvs::create_stream_pair(c->split_streams, false, true));
+    HIPCHK(c, c->split_events.reserve(1 + 2 * amvs::plan::SPLIT_MAX_GROUPS));
     HIPCHK(c, c->ev_groups.reserve(3));
     c->timing_groups = 1;
     c->n_step_events = 0;                       // (no per-launch events in this schedule: amvs_get_step_times returns none)
-    // The window kernel gathers nothing, so its strips can be tall (vertical halo 1.09 at 64 rows);
-    // the sampling kernel has no halo at all and wants SHORT strips (the resident waves then touch
-    // fewer source rows at once).  Measured on MI355X, 16 views 1080p, k=7, S=4, 2 groups, ms per step:
-    // window rows 32 / 48 / 64 / 96: 67.4 / 67.3 / 66.5 / 68.3; sampling rows 16 / 8 / 4 / 2: 70.8 / 68.4 /
-    // 65.2-66.8 / 66.5.
-    const int TH = p->tile_rows > 0 ? p->tile_rows : (c->H < 64 ? c->H : 64);
-    c->last_tile_rows = TH;
-    const int s_TH = c->split_sample_rows > 0 ? c->split_sample_rows : 4;
     hipStream_t s_smp = c->split_streams[0].get(), s_win = c->split_streams[1].get();
     hipEvent_t ev_fork = c->split_events[0];
-    const hipEvent_t *ev_sampled = &c->split_events[1], *ev_windowed = &c->split_events[1 + MAXG];
+    const hipEvent_t *ev_sampled = &c->split_events[1], *ev_windowed = &c->split_events[1 + amvs::plan::SPLIT_MAX_GROUPS];
 
-    amvs::StepArgs all = base_args(c, p->patch_size, n_ref, TH);
+    amvs::StepArgs all = base_args(c, p->patch_size, n_ref, sp.TH);
     all.fast = 1;
     all.depth_min = p->depth_min; all.depth_max = p->depth_max;
     all.seed = seed;
     all.samples = c->d_samples.get();
     all.half = p->patch_size / 2;
-    all.s_TH = s_TH;
-    all.s_lds = c->split_sample_lds;
-    all.s_tiles_x = (c->W + 63) / 64;
-    all.s_tiles_y = (c->H + s_TH - 1) / s_TH;
+    all.s_TH = sp.s_TH;
+    all.s_lds = sp.s_lds;
+    all.s_tiles_x = sp.s_tiles_x;
+    all.s_tiles_y = sp.s_tiles_y;
     int cur = 0;
     HIPCHK(c, amvs::launch_init(all.jobs, n_ref, (long long)hw, seed, p->log_depth_scale, p->log_depth_min,
                                 c->d_depth[cur].get(), c->d_normal[0].get(), c->d_cost.get(), c->stream));
@@ -402,12 +202,11 @@ int run_split_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
     HIPCHK(c, hipStreamWaitEvent(s_smp, ev_fork, 0));
     HIPCHK(c, hipStreamWaitEvent(s_win, ev_fork, 0));
     bool first = true;
-    for (const SchedStep &st : sched) {
-        for (int g = 0; g < G; ++g) {
-            const int j0 = g * vpl, nj = (n_ref - j0) < vpl ? (n_ref - j0) : vpl;
+    for (const amvs::plan::Step &st : plan.steps) {
+        for (size_t g = 0; g < sp.groups.size(); ++g) {
             amvs::StepArgs a = all;
-            a.n_jobs = nj;
-            a.jobs = c->d_jobs.get() + j0;
+            a.n_jobs = sp.groups[g].count;
+            a.jobs = c->d_jobs.get() + sp.groups[g].first;
             apply_step(a, st);
             set_io(a, c, cur);
             if (!first) HIPCHK(c, hipStreamWaitEvent(s_smp, ev_windowed[g], 0));
@@ -422,7 +221,7 @@ int run_split_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
         cur ^= st.flip_d;
     }
     // the window stream is in order, so its last event covers every group
-    if (!sched.empty()) HIPCHK(c, hipStreamWaitEvent(c->stream, ev_windowed[G - 1], 0));
+    if (!plan.steps.empty()) HIPCHK(c, hipStreamWaitEvent(c->stream, ev_windowed[sp.groups.size() - 1], 0));
     HIPCHK(c, hipEventRecord(c->ev_groups[1], c->stream));
     // _compute_confidence (mvs_patchmatch.py:493-534): one fused launch over the whole batch
     if ((p->flags & AMVS_PM_NO_CONFIDENCE) == 0) {
@@ -432,8 +231,6 @@ int run_split_schedule(amvs_ctx *c, int n_ref, int n_src, const amvs_pm_params *
         HIPCHK(c, amvs::launch_step(p->patch_size, n_src, all, c->stream));
     }
     HIPCHK(c, hipEventRecord(c->ev_groups[2], c->stream));
-    c->timing.sweep_launches = (int64_t)sched.size();     // one hypothesis of the whole batch each
-    c->last_views_per_launch = n_ref;
     return AMVS_OK;
 }
 
@@ -457,7 +254,8 @@ int one_step_begin(amvs_ctx *c, int ref, const int *src_ids, int n_src, int patc
     if ((rc = upload_jobs(c, 1, &ref, src_ids, n_src, fast ? patch : 0, false, !step_regs(c, patch).stats))) return rc;
     c->pm_resumable = false;                    // the single-step entry points overwrite the state of slot 0
     o.c = c; o.patch = patch; o.n_src = n_src; o.hw = (size_t)c->H * c->W;
-    o.a = base_args(c, patch, 1, pick_tile_rows(c, patch, n_src, 1, 0, 64, fast != 0));
+    const bool packed = usable_pairs(c) != nullptr;
+    o.a = base_args(c, patch, 1, amvs::plan::single_step_rows(plan_device(c, packed), plan_facts(patch, n_src, fast != 0, packed, 1u), patch));
     o.a.fast = fast;
     o.a.mode = amvs::MODE_EVAL;
     set_io(o.a, c, 0, false);                   // caller-supplied depth maps: no tag to strip
@@ -731,19 +529,25 @@ static int patchmatch_core(amvs_ctx *c, int n_ref, const int *ref_ids, const int
     c->pm_resumable = false;
     resolve_timing(c);
     c->timing = amvs_timing{};
-    const std::vector<SchedStep> sched = build_schedule(p);
-    const int cur0 = resume ? c->pm_cur : 0;
-    int cur = cur0;
-    for (const SchedStep &st : sched) cur ^= st.flip_d;                           // final depth buffer
     HIPCHK(c, hipEventRecord(c->ev[0].get(), c->stream));
+    // the launch plan (amvs_launch_plan.h): every decision of the call; the two schedules below only issue it
+    const bool packed = usable_pairs(c) != nullptr;
+    const PmPlan plan = amvs::plan::plan_patchmatch(
+        plan_device(c, packed), amvs::plan::Call{n_ref, n_src, fast, *p}, c->tuning,
+        plan_facts(p->patch_size, n_src, fast != 0, packed, amvs::plan::waves_entries_read(c->tuning, *p)));
+    c->last_tile_rows = plan.last_tile_rows;
+    const int cur0 = resume ? c->pm_cur : 0;
+    const int cur = cur0 ^ plan.final_parity;                                     // final depth buffer
     if (p->schedule == AMVS_SCHEDULE_SPLIT) {
-        if ((rc = run_split_schedule(c, n_ref, n_src, p, seed, sched, conf_dev))) return rc;
+        if ((rc = run_split_schedule(c, n_ref, n_src, p, seed, plan, conf_dev))) return rc;
     } else {
-        if ((rc = run_fused_schedule(c, n_ref, n_src, p, seed, fast, sched, conf_dev, cur0, !resume,
+        if ((rc = run_fused_schedule(c, n_src, p, seed, fast, plan, conf_dev, cur0, !resume,
                                      (p->flags & AMVS_PM_NO_CONFIDENCE) == 0))) return rc;
         c->pm_resumable = true; c->pm_cur = cur; c->pm_key = key;
         c->pm_next_iteration = p->first_iteration + p->num_iterations;
     }
+    c->timing.sweep_launches = plan.launches;
+    c->last_views_per_launch = plan.views_per_launch;
     // every group ran the same schedule, so the final depth buffer is the same for all
     HIPCHK(c, hipEventRecord(c->ev[3].get(), c->stream));
     *cur_out = cur;
@@ -797,7 +601,7 @@ int amvs_set_split_tuning(amvs_ctx *c, int groups, int sample_rows, int sample_l
     if (!c) return AMVS_EINVAL;
     if (groups < 0 || groups > 8 || sample_rows < 0 || sample_lds_bytes < 0 || sample_lds_bytes > 64 * 1024)
         return fail(c, AMVS_EINVAL, "split tuning out of range");
-    c->split_groups = groups; c->split_sample_rows = sample_rows; c->split_sample_lds = sample_lds_bytes;
+    c->tuning.split_groups = groups; c->tuning.split_sample_rows = sample_rows; c->tuning.split_sample_lds = sample_lds_bytes;
     return AMVS_OK;
 }
 
@@ -805,14 +609,14 @@ int amvs_set_step_tuning(amvs_ctx *c, int n_iterations, const int32_t *tile_rows
 {
     if (!c) return AMVS_EINVAL;
     if (n_iterations < 0 || (n_iterations > 0 && !tile_rows && !wgs_per_cu)) return fail(c, AMVS_EINVAL, "bad step tuning table");
-    c->tune_rows.clear(); c->tune_cap.clear();
+    c->tuning.tune_rows.clear(); c->tuning.tune_cap.clear();
     for (int i = 0; i < 2 * n_iterations; ++i) {
         const int r = tile_rows ? tile_rows[i] : 0, w = wgs_per_cu ? wgs_per_cu[i] : 0;
         if (r < 0 || r > (1 << 20) || w < 0 || w > 8) {
-            c->tune_rows.clear(); c->tune_cap.clear();
+            c->tuning.tune_rows.clear(); c->tuning.tune_cap.clear();
             return fail(c, AMVS_EINVAL, "step tuning: rows >= 0, workgroups per CU in 0..8");
         }
-        c->tune_rows.push_back(r); c->tune_cap.push_back(w);
+        c->tuning.tune_rows.push_back(r); c->tuning.tune_cap.push_back(w);
     }
     return AMVS_OK;
 }
@@ -822,8 +626,8 @@ int amvs_set_launch_order(amvs_ctx *c, int edge_first, int group_overlap)
     if (!c) return AMVS_EINVAL;
     if (edge_first < -1 || edge_first > 1 || group_overlap < -1 || group_overlap > 2)
         return fail(c, AMVS_EINVAL, "launch order: edge_first in -1..1, group_overlap in -1..2");
-    c->edge_first = edge_first < 0 ? AMVS_DEFAULT_EDGE_FIRST : edge_first;
-    c->group_overlap = group_overlap < 0 ? AMVS_DEFAULT_GROUP_OVERLAP : group_overlap;
+    c->tuning.edge_first = edge_first < 0 ? AMVS_DEFAULT_EDGE_FIRST : edge_first;
+    c->tuning.group_overlap = group_overlap < 0 ? AMVS_DEFAULT_GROUP_OVERLAP : group_overlap;
     return AMVS_OK;
 }
 
@@ -832,8 +636,8 @@ int amvs_set_step_sources(amvs_ctx *c, int ref_stats, int centre_depth)
     if (!c) return AMVS_EINVAL;
     if (ref_stats < -1 || ref_stats > 1 || centre_depth < -1 || centre_depth > 1)
         return fail(c, AMVS_EINVAL, "step sources: ref_stats and centre_depth in -1..1");
-    c->ref_stats_source = ref_stats < 0 ? AMVS_DEFAULT_REF_STATS_SOURCE : ref_stats;
-    c->depth_source = centre_depth < 0 ? AMVS_DEFAULT_DEPTH_SOURCE : centre_depth;
+    c->tuning.ref_stats_source = ref_stats < 0 ? AMVS_DEFAULT_REF_STATS_SOURCE : ref_stats;
+    c->tuning.depth_source = centre_depth < 0 ? AMVS_DEFAULT_DEPTH_SOURCE : centre_depth;
     return AMVS_OK;
 }
 
@@ -866,6 +670,32 @@ int amvs_sweep_order(int n_jobs, int tiles_x, int tiles_y, int band_major, int p
             out[o] = live ? sp.job : -1; out[o + 1] = live ? sp.ty : -1; out[o + 2] = live ? sp.tx : -1;
             out[o + 3] = live ? sp.up : -1; out[o + 4] = live ? sp.paired : -1;
         }
+    return AMVS_OK;
+}
+
+int amvs_plan_patchmatch(const amvs_plan_device *dev, const amvs_plan_call *call, const amvs_plan_tuning *tuning,
+                         const amvs_plan_facts *facts, amvs_pm_plan *out, amvs_plan_step *steps, int32_t capacity)
+{
+    if (!dev || !call || !tuning || !facts || !out || (capacity > 0 && !steps)) return AMVS_EINVAL;
+    const amvs_pm_params &p = call->p;
+    if (dev->H < 1 || dev->W < 1 || dev->n_cu < 1 || call->n_ref < 1 || facts->out_width < 1 || p.num_iterations < 0 ||
+        p.num_iterations > (1 << 16) || p.num_samples < 0 || p.num_samples > (1 << 10) || p.first_iteration < 0 || p.schedule < 0 ||
+        p.schedule > AMVS_SCHEDULE_PAIRED || tuning->n_tune < 0)
+        return AMVS_EINVAL;
+    for (int i = 0; i < tuning->n_tune; ++i)
+        if (tuning->tune_cap && (tuning->tune_cap[i] < 0 || tuning->tune_cap[i] > 8)) return AMVS_EINVAL;
+    const amvs::plan::SweepTuning t = plan_tuning(*tuning);
+    const unsigned read = amvs::plan::waves_entries_read(t, p);
+    for (int w = 0; w <= 8; ++w)
+        if ((read >> w & 1u) && facts->waves_per_cu[w] < 1) return AMVS_EINVAL;
+    const PmPlan plan = amvs::plan::plan_patchmatch(*dev, *call, t, *facts);
+    const amvs::plan::SplitPlan &sp = plan.split;
+    const StepRegs regs = amvs::plan::step_regs(t, facts->fast_regs_supported != 0, p.patch_size);
+    *out = amvs_pm_plan{plan.band_major, plan.paired, plan.views_per_launch, (int32_t)plan.groups.size(), plan.TH, plan.tiles_x, plan.tiles_y,
+                        plan.overlap, plan.edge_first, (int32_t)plan.steps.size(), plan.final_parity, plan.last_tile_rows, plan.launches,
+                        (int32_t)sp.groups.size(), sp.vpl, sp.TH, sp.s_TH, sp.s_lds, sp.s_tiles_x, sp.s_tiles_y, regs.stats, regs.hist,
+                        facts->waves_per_cu[0] >= 1 ? amvs::plan::single_step_rows(*dev, *facts, p.patch_size) : 0};
+    for (size_t i = 0; i < plan.steps.size() && (int64_t)i < capacity; ++i) steps[i] = plan.steps[i];
     return AMVS_OK;
 }
 

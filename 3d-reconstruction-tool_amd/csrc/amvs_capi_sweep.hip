@@ -13,7 +13,18 @@ int amvs_set_sweep_tuning(amvs_ctx *c, int tile_rows, int chunk)
     if (!c) return AMVS_EINVAL;
     if (tile_rows < 0 || tile_rows > AMVS_SWEEP_MAX_TH8 || chunk < 0)
         return fail(c, AMVS_EINVAL, "plane-sweep tuning out of range");
-    c->sweep_tile_rows = tile_rows; c->sweep_chunk = chunk;
+    c->tuning.sweep_tile_rows = tile_rows; c->tuning.sweep_chunk = chunk;
+    return AMVS_OK;
+}
+
+int amvs_plan_plane_sweep(const amvs_plan_device *dev, const amvs_plan_tuning *tuning, const amvs_plan_facts *facts, int n_ref,
+                          int D, amvs_sweep_plan *plan)
+{
+    if (!dev || !tuning || !facts || !plan || dev->H < 1 || dev->W < 1 || dev->n_cu < 1 || n_ref < 1 || D < 1 ||
+        facts->out_width < 1 || facts->sweep_max_th < 1 || facts->sweep_max_th8 < 1 || facts->sweep_max_chunk < 1)
+        return AMVS_EINVAL;
+    const amvs::plan::PlaneSweepPlan s = amvs::plan::plan_plane_sweep(*dev, plan_tuning(*tuning), *facts, n_ref, D);
+    *plan = amvs_sweep_plan{s.TH, s.tiles_x, s.tiles_y, s.chunk, s.n_chunks, s.key8};
     return AMVS_OK;
 }
 
@@ -35,41 +46,15 @@ int amvs_plane_sweep_device(amvs_ctx *c, int n_ref, const int *ref_ids, const in
     HIPCHK(c, c->d_keys.reserve(hw * n_ref, c->cache));
     amvs::SweepArgs a{};
     a.H = c->H; a.W = c->W;
-    // tall strips (little halo re-sampling); the planes are chunked so that the launch still has
-    // about four strips per resident wave slot.  A strip's running best lives in 4 KB of LDS: 16-bit keys for up
-    // to AMVS_SWEEP_MAX_TH = 32 rows, or -- compiled patch sizes, chunks of at most 32 planes -- 8-bit keys for up
-    // to 64 rows (SweepArgs::key8); the fewest bands of at most that many rows, evenly high.
-    a.tiles_x = (c->W + amvs::strip_out_width(patch_size) - 1) / amvs::strip_out_width(patch_size);
     a.n_jobs = n_ref; a.D = D;
-    auto shape = [&](int max_rows) {
-        const int bands = (c->H + max_rows - 1) / max_rows;
-        a.TH = (c->H + bands - 1) / bands;
-        if (c->sweep_tile_rows >= 1 && c->sweep_tile_rows <= max_rows && c->sweep_tile_rows < c->H) a.TH = c->sweep_tile_rows;
-        a.tiles_y = (c->H + a.TH - 1) / a.TH;
-        const long long strips = (long long)n_ref * a.tiles_x * a.tiles_y;
-        const long long slots = (long long)c->n_cu * 16;        // four waves per SIMD
-        // chunks for ~8 waves per slot, evenly sized (measured on MI355X, config 2, strips of 60 rows, planes per
-        // wave 2 / 3 / 4 / 5 / 6 / 8 / 13: exact 51.7 / 50.0 / 51.7 / 50.7 / 49.8 / 49.2 / 46.1, fast 73.7 / 73.8 / 76.8 /
-        // 74.5 / 74.0 / 72.5 / 67.8 G px-hyp/s: many short waves fill the tail of the launch, uneven last chunks lose)
-        long long want = (8 * slots + strips - 1) / strips;
-        if (want < 1) want = 1;
-        if (want > (D + 1) / 2) want = (D + 1) / 2;              // (at least two planes per wave: a wave's set-up)
-        a.chunk = (int)((D + want - 1) / want);
-        a.chunk = (int)((D + (D + a.chunk - 1) / a.chunk - 1) / ((D + a.chunk - 1) / a.chunk));   // even chunks
-        if (c->sweep_chunk >= 1) a.chunk = c->sweep_chunk < D ? c->sweep_chunk : D;
-        if (a.chunk > AMVS_SWEEP_MAX_CHUNK) a.chunk = AMVS_SWEEP_MAX_CHUNK;
-        a.n_chunks = (D + a.chunk - 1) / a.chunk;
-    };
-    a.key8 = 0;
-    if (amvs::patch_compiled(patch_size) && c->sweep_key8 != 0 && (c->sweep_tile_rows == 0 || c->sweep_tile_rows > AMVS_SWEEP_MAX_TH)) {
-        shape(AMVS_SWEEP_MAX_TH8);
-        a.key8 = a.chunk <= AMVS_SWEEP_MAX_CHUNK8 ? 1 : 0;
-    }
-    if (!a.key8) shape(AMVS_SWEEP_MAX_TH);
+    a.pairs = usable_pairs(c);
+    const amvs::plan::PlaneSweepPlan plan =
+        amvs::plan::plan_plane_sweep(plan_device(c, a.pairs != nullptr), c->tuning, plan_facts(patch_size, n_nbr, fast != 0, a.pairs != nullptr, 0u), n_ref, D);
+    a.TH = plan.TH; a.tiles_x = plan.tiles_x; a.tiles_y = plan.tiles_y;
+    a.chunk = plan.chunk; a.n_chunks = plan.n_chunks; a.key8 = plan.key8;
     c->last_tile_rows = a.TH;
     a.img_stride = c->stride;
     a.images = c->d_images.get();
-    a.pairs = usable_pairs(c);
     a.pair_stride = c->pstride;
     a.fast = fast;
     a.depths = c->d_planes.get();

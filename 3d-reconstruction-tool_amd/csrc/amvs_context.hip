@@ -176,26 +176,46 @@ int ensure_fast_stats(amvs_ctx *c, int patch)
     return AMVS_OK;
 }
 
-// Where the fast sweep steps of this context take the reference statistics and the centre depth from
-// (amvs_set_step_sources).  The automatic choice is a table by patch size, like the `paired` rule of
-// run_fused_schedule: the registers where they were measured faster by the rule of DESIGN.md section 5 (round 9; bench.py
-// main line at that patch size, ms per step, medians of five alternating runs, maps and loads / statistics in the kernel
-// / both): 3x3 51.24 / 47.08 / 45.64 (three runs), 5x5 54.25 / 51.35 / 49.96, 7x7 58.42 / 55.71 / 54.27 (a second
-// session 58.87 / 55.61 / 54.17), 9x9 68.18 / 66.02 / 64.72, 11x11 73.76 / 72.47 / 71.16 -- and 13x13 80.85 / 82.33 /
-// 80.64, 15x15 86.81 / 89.80 / 88.25: there the 2 (k - 1) more cross-lane adds cost more than the load saves.
-// The statistics entry meets that rule against the maps at every size up to 11x11.  The HISTORY entry does not meet
-// it as worded -- alone against the maps and loads it gains 1.2 - 1.7 %, below three parent spreads at 7x7 (2.6 -
-// 3.1 %) and 3x3 (1.3 %) --: it rests on the stacked comparison, "both" against "statistics" (7x7: 2.6 % in both
-// sessions against three spreads of 1.1 %, every run below every run).  Sizes other than 7x7: one session.
-// 13x13 and 15x15 stay compiled although the table never picks them: they are the measurements that place the
-// table's edge, and the switch lets that edge be measured again on another image size or source count with one build.
-// The run-time-k kernels and patches above step_fast_regs_max_patch() always read the maps.
+// where the fast sweep steps of this context take the reference statistics and the centre depth from (the rule and its
+// measurements: amvs_launch_plan.h)
 StepRegs step_regs(const amvs_ctx *c, int patch)
 {
-    if (!amvs::step_fast_regs_supported(patch)) return StepRegs{false, false};
-    const bool auto_stats = patch <= 11, auto_hist = patch <= 11;
-    return StepRegs{c->ref_stats_source < 0 ? auto_stats : c->ref_stats_source != 0,
-                    c->depth_source < 0 ? auto_hist : c->depth_source != 0};
+    return amvs::plan::step_regs(c->tuning, amvs::step_fast_regs_supported(patch), patch);
+}
+
+// The launch planner's inputs (amvs_launch_plan.h).  The kernel facts of (patch, n_src) in this arithmetic: the resident
+// waves per CU only for the workgroup caps named by `waves_entries` (bit w = cap w; an occupancy query each).
+amvs::plan::Device plan_device(const amvs_ctx *c, bool packed_maps) { return amvs::plan::Device{c->H, c->W, c->n_cu, packed_maps ? 1 : 0}; }
+
+amvs::plan::Facts plan_facts(int patch, int n_src, bool fast, bool packed_maps, unsigned waves_entries)
+{
+    amvs::plan::Facts f{};
+    f.out_width = amvs::strip_out_width(patch);
+    for (int w = 0; w <= 8; ++w)
+        if (waves_entries >> w & 1u)
+            f.waves_per_cu[w] = fast ? amvs::step_fast_waves_per_cu(patch, n_src, w) : amvs::step_waves_per_cu(patch, n_src, packed_maps, w);
+    f.patch_compiled = amvs::patch_compiled(patch);
+    f.pair_supported = amvs::step_pair_supported(patch, n_src);
+    f.fast_pair_supported = amvs::step_fast_pair_supported(patch, n_src);
+    f.fast_regs_supported = amvs::step_fast_regs_supported(patch);
+    f.sweep_max_th = AMVS_SWEEP_MAX_TH; f.sweep_max_th8 = AMVS_SWEEP_MAX_TH8;
+    f.sweep_max_chunk = AMVS_SWEEP_MAX_CHUNK; f.sweep_max_chunk8 = AMVS_SWEEP_MAX_CHUNK8;
+    return f;
+}
+
+amvs::plan::SweepTuning plan_tuning(const amvs_plan_tuning &t)
+{
+    amvs::plan::SweepTuning s;
+    s.default_band_major = t.default_band_major;
+    for (int i = 0; i < t.n_tune; ++i) {            // (as amvs_set_step_tuning stores them: two tables of one size)
+        s.tune_rows.push_back(t.tune_rows ? t.tune_rows[i] : 0);
+        s.tune_cap.push_back(t.tune_cap ? t.tune_cap[i] : 0);
+    }
+    s.split_groups = t.split_groups; s.split_sample_rows = t.split_sample_rows; s.split_sample_lds = t.split_sample_lds;
+    s.edge_first = t.edge_first; s.group_overlap = t.group_overlap;
+    s.sweep_tile_rows = t.sweep_tile_rows; s.sweep_chunk = t.sweep_chunk; s.sweep_key8 = t.sweep_key8;
+    s.ref_stats_source = t.ref_stats_source; s.depth_source = t.depth_source;
+    return s;
 }
 
 // `fast_patch` > 0: also fill the fast-mode records (precomposed projections, ref statistics of

@@ -5,6 +5,7 @@
 #include "amvs_kernels.h"
 #include "amvs_buffer.h"
 #include "amvs_handles.h"
+#include "amvs_launch_plan.h"
 #include "amvs_match_state.h"
 #include "amvs_sfm_state.h"
 #include "amvs_features_state.h"
@@ -15,25 +16,6 @@
 #include <memory>
 #include <string>
 #include <vector>
-
-// Defaults of amvs_set_launch_order (A/B builds: ALL=1 tools/build_variant.sh NAME -DAMVS_DEFAULT_GROUP_OVERLAP=0 ...).
-// Measured on MI355X, bench.py main line, ms per step, five alternating runs each:
-// one stream top-to-bottom 59.65, one stream edge-first 59.86, two equal streams edge-first 58.77, top-to-bottom
-// 58.95, a high / low pair 60.81.  Hence edge-first exactly where the groups overlap (-1), two equal streams.
-#ifndef AMVS_DEFAULT_EDGE_FIRST
-#define AMVS_DEFAULT_EDGE_FIRST -1
-#endif
-#ifndef AMVS_DEFAULT_GROUP_OVERLAP
-#define AMVS_DEFAULT_GROUP_OVERLAP 1
-#endif
-
-// Defaults of amvs_set_step_sources (-1 = the automatic table of step_regs, amvs_context.hip).
-#ifndef AMVS_DEFAULT_REF_STATS_SOURCE
-#define AMVS_DEFAULT_REF_STATS_SOURCE -1
-#endif
-#ifndef AMVS_DEFAULT_DEPTH_SOURCE
-#define AMVS_DEFAULT_DEPTH_SOURCE -1
-#endif
 
 // the communicator of amvs_comm.hip, the only file that sees RCCL (as rccl.h declares it)
 struct ncclComm;
@@ -92,9 +74,7 @@ struct amvs_ctx {
     mutable bool flags_dirty = false;
     bool force_f32 = false;             // amvs_set_sampling: A/B switch for tests
     int mode = AMVS_MODE_EXACT;         // arithmetic of the sweeps (amvs_set_mode)
-    int default_band_major = 0;         // schedule of amvs_pm_params.schedule == 0 (view-major measured faster)
-    int sweep_tile_rows = 0, sweep_chunk = 0;   // amvs_set_sweep_tuning (0 = automatic)
-    int sweep_key8 = 1;                         // strips above 32 rows with 8-bit keys where the plane chunks allow it
+    amvs::plan::SweepTuning tuning;     // the launch policy's knobs (amvs_set_*_tuning, amvs_set_launch_order, amvs_set_step_sources)
     std::map<int, amvs::host::Stats> stats;
     std::map<int, amvs::host::FastStats> fstats;    // fast mode: (mean1, var1) maps per patch size
     // PatchMatch state of the batch slots (ensure_slots); the cost is updated in place, so it has one buffer
@@ -119,7 +99,6 @@ struct amvs_ctx {
     // split schedule (amvs_pm_params.schedule == AMVS_SCHEDULE_SPLIT): sample maps (its streams and token events are
     // among the handles below)
     amvs::DeviceBuffer<float> d_samples;
-    int split_groups = 0, split_sample_rows = 0, split_sample_lds = 0;
     hipStream_t stream = nullptr;       // own_stream, or the caller's (amvs_set_stream: borrowed, never destroyed here)
     int last_tile_rows = 0, last_views_per_launch = 0;
     // state a continuation call (amvs_pm_params.first_iteration > 0) resumes: which depth buffer is
@@ -130,22 +109,12 @@ struct amvs_ctx {
     // native exchange (amvs_comm_*): RCCL resolved with dlopen, one communicator per context
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
-    // amvs_set_step_tuning: strip rows / resident workgroups per CU by [iteration][0 = propagation, 1 = refinement]
-    // (0 = automatic); iterations beyond the table use its last row
-    std::vector<int> tune_rows, tune_cap;
     // amvs_set_step_timing: an event behind every sweep launch of the last PatchMatch call (ev_steps)
     bool step_timing = false;
     int n_step_events = 0;
     int timing_groups = 0;
     bool timing_overlapped = false;      // the groups of the last call ran on two streams (resolve_timing)
     bool timing_pending = false;
-    // Sweep-step dispatch order (amvs_set_launch_order): edge_first -- every XCD walks each view's bands from the image
-    // edge to its centre (amvs_strip_order.h; -1: where the groups overlap, else top to bottom); group_overlap -- the view groups of a batch dealt to two streams of the
-    // context (run_fused_schedule): 0 one stream, 1 two streams of equal priority, 2 a high / low pair
-    int edge_first = AMVS_DEFAULT_EDGE_FIRST, group_overlap = AMVS_DEFAULT_GROUP_OVERLAP;
-    // Where the fast sweep step takes the reference window's statistics and the centre depth from (amvs_set_step_sources;
-    // resolved per call by step_regs): -1 the automatic table, 0 the (mean1, var1) maps / a second load, 1 the registers
-    int ref_stats_source = AMVS_DEFAULT_REF_STATS_SOURCE, depth_source = AMVS_DEFAULT_DEPTH_SOURCE;
     // -DAMVS_STEP_TRACE: [launch][trace_stride blocks][4] workgroup timeline of the last PatchMatch call
     amvs::DeviceBuffer<unsigned long long> d_trace;
     long long trace_stride = 0, trace_launches = 0;
@@ -185,8 +154,11 @@ int check_patch_src(amvs_ctx *c, int patch, int n_src);
 int ensure_slots(amvs_ctx *c, int n);
 int ensure_stats(amvs_ctx *c, int patch);
 int ensure_fast_stats(amvs_ctx *c, int patch);
-struct StepRegs { bool stats, hist; };      // StepArgs::ref_in_kernel / depth_hist of the fast sweep steps of `c`
+using StepRegs = amvs::plan::StepRegs;      // StepArgs::ref_in_kernel / depth_hist of the fast sweep steps of `c`
 StepRegs step_regs(const amvs_ctx *c, int patch);
+amvs::plan::Device plan_device(const amvs_ctx *c, bool packed_maps);
+amvs::plan::Facts plan_facts(int patch, int n_src, bool fast, bool packed_maps, unsigned waves_entries);
+amvs::plan::SweepTuning plan_tuning(const amvs_plan_tuning &t);
 int upload_jobs(amvs_ctx *c, int n_ref, const int *ref_ids, const int *src_ids, int n_src, int fast_patch = 0,
                 bool compose_only = false, bool ref_maps = true);
 const uint16_t *usable_pairs(const amvs_ctx *c);

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <utility>
 #include <vector>
 
 namespace amvs {
@@ -45,6 +46,21 @@ public:
 private:
     hipStream_t s_ = nullptr;
 };
+
+// A pair of streams, each of the device's most (`urgent`) or least urgent priority -- distinct priorities land on distinct
+// hardware queues -- created whole or not at all: a failure leaves `pair` as it was.
+inline hipError_t create_stream_pair(Stream (&pair)[2], bool urgent0, bool urgent1)
+{
+    int lo = 0, hi = 0;                 // (numerically: hi <= lo)
+    hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
+    Stream made[2];
+    if (e == hipSuccess) e = made[0].create(urgent0 ? hi : lo);
+    if (e == hipSuccess) e = made[1].create(urgent1 ? hi : lo);
+    if (e != hipSuccess) return e;
+    pair[0] = std::move(made[0]);
+    pair[1] = std::move(made[1]);
+    return hipSuccess;
+}
 
 // One event, with timing (hipEventElapsedTime) or without (ordering only), destroyed by the destructor.
 class Event {

@@ -200,6 +200,8 @@ int amvs_set_launch_order(amvs_ctx *ctx, int edge_first, int group_overlap);
  * values hold; *n_blocks is the grid of the launch.                                                           */
 int amvs_sweep_order(int n_jobs, int tiles_x, int tiles_y, int band_major, int paired, int edge_first,
                      int64_t capacity, int32_t *out, int32_t *n_blocks);
+/* (The same kind of view of the launch PLAN -- views per launch, strip rows, schedule, plane chunks; ctx-free, no GPU, test
+ * infrastructure -- is declared in amvs_plan.h: this header stays at its ninety-two entry points.)                      */
 /* Workgroup timeline of the sweep launches of the LAST PatchMatch call, from a library built with
  * -DAMVS_STEP_TRACE (amvs_version() then ends in "+step-trace"; tools/step_timeline.py): out is
  * [n_launches][blocks_per_launch][4] = (100 MHz wall clock at entry, before exit, XCC id,
